@@ -22,15 +22,26 @@ N > 1: one process per GPU.  Under torchrun (RANK / WORLD_SIZE in the environmen
 otherwise `--gpus N` SPAWNS the N ranks itself.  Genes shard across ranks in the contiguous ranges of
 R/parallel.R:10, no data-path collective; the only exchange is the all-gather of two n-vectors for the global
 dispersion trend, as in DESeqParallel.  Headline = STRONG scaling (the config's genes in total, as BASELINE
-quotes it: "50k x 500 x p=4 ... gene-sharded across 8 GPUs"); the same run also times WEAK scaling (the
+quotes it: "50k x 500 x p=4 ... gene-sharded across 8 GPUs"); with --full the same run also times WEAK scaling (the
 config's genes per GPU) and reports it under "weak".
 
 N = 1 on the fused chain: the K steps are pipelined two deep (--pipeline 2, the default) -- step k is enqueued, then
 step k - 1 is finished on the host (its result block waited for, its columns built) while the device runs step k; every
 step's results are consumed inside the timed region and all K steps are complete before the closing barrier.  The same
-steps one call at a time are timed right after ("one_call_at_a_time"); --pipeline 1 makes that the headline.
+steps one call at a time are timed right after with --full ("one_call_at_a_time"); --pipeline 1 makes that the headline.
 
 Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for the roofline accounting.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, step statistics, config).  Everything else -- the one-call-at-a-time region, the
+per-kernel passes and rooflines, result_digest, the oracle parity sample, the workload variants, weak scaling, the
+host-pointer passes, the other configs and the CPU baseline -- runs only with --full (the --no-* options thin that out).
+
+--dump-outputs DIR writes what the last timed step computed, as the caller receives it, to DIR/<name>.npy (float64):
+every per-gene result column (mcols_<name>), the trend's numbers (dispersionFunction_<name>), the prior variance
+(betaPriorVar, weights + betaPrior only) and a fixed sample of rows (assay_rows) of the n x m assays (assay_<name>).
+Every array is finite: NA / Inf entries are written as 0, and their kind goes to <name>_nonfinite.npy (1 NA, 2 +Inf,
+3 -Inf).  The inputs depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -92,6 +103,21 @@ def make_weights(n, m, seed):
     return w
 
 
+def synthetic_counts(cfg, n_req, x, seed, size_factors):
+    """the host side of a config's workload: counts (genes x samples, the all-zero rows dropped), size factors and the
+    optional weights -- a function of its arguments alone"""
+    from deseq2_amd import simulate
+    m = x.shape[0]
+    sf_in = None
+    if size_factors == "lognormal":
+        # SURVEY 8d: s_j ~ logN(0, 0.25^2), its own stream so that the per-gene draws are those of the s_j = 1 variant
+        sf_in = np.exp(np.random.Generator(np.random.PCG64(1000 + seed)).normal(0.0, 0.25, m))
+    d = simulate.make_counts(n_req, x, seed=seed, intercept_mean=cfg.get("intercept_mean", 4.0), size_factors=sf_in)
+    counts = d["counts"]
+    w = make_weights(counts.shape[0], m, seed + 77) if cfg.get("weights") else None
+    return counts, d["size_factors"], w
+
+
 def spawn_ranks(n_gpus, argv):
     """`python bench.py --gpus N` outside torchrun: start the N ranks (one process per GPU) and relay rank 0"""
     import socket
@@ -142,6 +168,12 @@ def main():
     ap.add_argument("--call-by-call", action="store_true",
                     help="time core.DESeq() (the R-side decision rules as host code between the native calls) instead "
                          "of the fused device-driven chain")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement and check (one call at a time, per-kernel "
+                         "passes, rooflines, result digest, parity, variants, weak scaling, host-pointer passes, other "
+                         "configs, CPU baseline; the --no-* options skip single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results as DIR/<name>.npy (float64, <= 64 MB)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -202,20 +234,13 @@ def main():
 
     def workload(seed, lo_hi=None, sf_mode=None):
         """synthetic counts (+ weights) of this config, resident in HBM in R layout; lo_hi = this rank's shard"""
-        sf_in = None
-        if (sf_mode or args.size_factors) == "lognormal":
-            # SURVEY 8d: s_j ~ logN(0, 0.25^2), its own stream so that the per-gene draws are those of the s_j = 1 variant
-            sf_in = np.exp(np.random.Generator(np.random.PCG64(1000 + seed)).normal(0.0, 0.25, m))
-        d = simulate.make_counts(n_req, x, seed=seed, intercept_mean=cfg.get("intercept_mean", 4.0), size_factors=sf_in)
-        counts = d["counts"]
-        w = make_weights(counts.shape[0], m, seed + 77) if use_w else None
+        counts, sf, w = synthetic_counts(cfg, n_req, x, seed, sf_mode or args.size_factors)
         n_all = counts.shape[0]
         if lo_hi is not None:
             lo, hi = lo_hi(n_all)
             counts = counts[lo:hi]
             w = None if w is None else w[lo:hi]
         n = counts.shape[0]
-        sf = d["size_factors"]
         sizes = [len(r) for r in parallel.shard_ranges(n_all, world)] if (lo_hi is not None and world > 1) else None
         counts_r = torch.as_tensor(np.ascontiguousarray(counts.T), device=dev)                 # (m, n) int32
         nf_r = torch.ones((m, n), dtype=torch.float64, device=dev) * torch.as_tensor(sf, device=dev)[:, None]
@@ -366,6 +391,40 @@ def main():
     depth = args.pipeline if (world == 1 and not args.call_by_call) else 1
     dt, n_total, dds, step_stats = timed(step, n, depth)
     fused_used = bool(dds[0].attrs.get("fused"))
+    if args.dump_outputs:
+        dump_outputs(dds[0], args.dump_outputs, rank, world)
+    head = {
+        "metric": "genes/sec for DESeq() disp+beta+%s fit, %s%s" % (
+            cfg["test"], {"C2": "20k x 100 x p=2", "C3": "50k x 500 x p=4", "C4": "60k x 2000 x p=10 (LRT)",
+                          "C4R": "60k x 2000 x p=10 (LRT vs 2-column reduced, minmu=1e-6)",
+                          "C5": "30k x 200, weights + betaPrior"}[args.config],
+            " (throughput of steps pipelined two deep; one call at a time: one_call_at_a_time)" if depth == 2 else ""),
+        "value": n_total * args.steps / dt,
+        "unit": "genes/s",
+        "config": {"workload": "%s; %d non-zero genes in total, sharded over %d GPU(s) in the contiguous ranges "
+                               "of R/parallel.R:10; inputs resident in HBM in R layout (int32 counts, f64 nf "
+                               "matrix%s; the fused chain reads the size factors as the m-vector the matrix was "
+                               "built from)" % (cfg["label"], n_total, world, ", f64 weights" if use_w else ""),
+                   "name": args.config, "genes_total": n_total, "genes_this_gpu": n, "samples": m, "p": p,
+                   "test": cfg["test"], "parallelism": "gene-shard x%d" % world,
+                   "chain": "fused device-driven (dsq_deseq_dev)" if fused_used else "call-by-call (core.py)",
+                   "steps_overlap": "step k enqueued while step k-1's results are copied and post-processed" if depth == 2 else "none"},
+    }
+    if not args.full:
+        # the plain run: the headline and nothing else (the other measurements and checks: --full)
+        if rank == 0:
+            print(json.dumps({"metric": head["metric"], "value": head["value"], "unit": head["unit"], "n_gpus": world,
+                              "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+                              "step_ms": step_stats["step_ms"], "gpu_span_ms": step_stats["gpu_span_ms"],
+                              "driver_allocs_in_timed_region": step_stats["driver_allocs_in_timed_region"],
+                              "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+                              "data": "synthetic", "config": head["config"],
+                              "workload": {"seed": args.seed, "size_factors": args.size_factors},
+                              "pipeline_depth": depth, "full": False}))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     sync_ms = None
     if depth == 2:
         # the same K steps, each waiting for its own results: what ONE DESeq() call costs end to end (reported beside the
@@ -504,13 +563,9 @@ def main():
                     "avg_launch_ms": avg_ms,
                     "note": "f64-VALU/transcendental bound, not HBM bound (DESIGN.md); see profiles/"}
         out = {
-            "metric": "genes/sec for DESeq() disp+beta+%s fit, %s%s" % (
-                cfg["test"], {"C2": "20k x 100 x p=2", "C3": "50k x 500 x p=4", "C4": "60k x 2000 x p=10 (LRT)",
-                              "C4R": "60k x 2000 x p=10 (LRT vs 2-column reduced, minmu=1e-6)",
-                              "C5": "30k x 200, weights + betaPrior"}[args.config],
-                " (throughput of steps pipelined two deep; one call at a time: one_call_at_a_time)" if depth == 2 else ""),
-            "value": n_total * args.steps / dt,
-            "unit": "genes/s",
+            "metric": head["metric"],
+            "value": head["value"],
+            "unit": head["unit"],
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
@@ -524,14 +579,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
-            "config": {"workload": "%s; %d non-zero genes in total, sharded over %d GPU(s) in the contiguous ranges "
-                                   "of R/parallel.R:10; inputs resident in HBM in R layout (int32 counts, f64 nf "
-                                   "matrix%s; the fused chain reads the size factors as the m-vector the matrix was "
-                                   "built from)" % (cfg["label"], n_total, world, ", f64 weights" if use_w else ""),
-                       "name": args.config, "genes_total": n_total, "genes_this_gpu": n, "samples": m, "p": p,
-                       "test": cfg["test"], "parallelism": "gene-shard x%d" % world,
-                       "chain": "fused device-driven (dsq_deseq_dev)" if fused_used else "call-by-call (core.py)",
-                       "steps_overlap": "step k enqueued while step k-1's results are copied and post-processed" if depth == 2 else "none"},
+            "config": head["config"],
             "roofline": roofline,
             "valu_roofline": valu,
             "f64_roofline": f64,
@@ -545,6 +593,7 @@ def main():
             # 2: step k is enqueued while step k - 1's result block is copied (side stream) and its columns are built on
             # the host -- every step's results are consumed inside the timed region; 1: each step waits for its own
             "pipeline_depth": depth,
+            "full": True,
         }
         if sync_ms is not None:
             out["one_call_at_a_time"] = sync_ms      # the same K steps without the overlap: one DESeq() call end to end
@@ -567,6 +616,99 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_ASSAY_ROWS = 256
+
+
+def _put_finite(out, name, v):
+    """store v as out[name] with its NA / Inf entries (R's NA: maxCooks when every sample is replaceable, p-values of
+    rows without a test, ...) as 0, and -- only where there are any -- their kind in out[name + "_nonfinite"]
+    (0 finite, 1 NA, 2 +Inf, 3 -Inf): every array written is finite and the NA pattern is part of the output"""
+    v = np.asarray(v, np.float64)
+    bad = ~np.isfinite(v)
+    if bad.any():
+        kind = np.zeros(v.shape)
+        kind[np.isnan(v)] = 1.0
+        kind[v == np.inf] = 2.0
+        kind[v == -np.inf] = 3.0
+        out[name + "_nonfinite"] = kind
+        v = np.where(bad, 0.0, v)
+    out[name] = v
+
+
+def dump_outputs(dds, outdir, rank, world):
+    """--dump-outputs: the last timed step's results as a caller of the chain receives them, as finite float64 .npy files
+    (NA / Inf entries: _put_finite).  Every per-gene column of mcols (all ranks' shards in gene order; booleans as 0 / 1),
+    the trend's numbers, betaPriorVar, and a fixed sample of up to DUMP_ASSAY_ROWS rows (assay_rows) of the n x m assays
+    (one process only: they stay on the device; an assay that is another's object, replaceCooks, is written once).  All
+    of it within DUMP_LIMIT_BYTES: the assays take at most a quarter, and should the per-gene columns not fit in the rest,
+    a fixed, seeded sample of genes (mcols_rows) is written instead."""
+    mc = {}
+    for k, v in dds.mcols.items():
+        v = np.asarray(v)
+        if v.dtype.kind in "biuf":
+            mc[k] = v.astype(np.float64)
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world
+        dist.all_gather_object(parts, mc)
+        if rank != 0:
+            return
+        keys = sorted({k for part in parts for k in part})
+        n_of = [len(next(iter(part.values()))) if part else 0 for part in parts]
+        mc = {}
+        for k in keys:
+            ref = next(part[k] for part in parts if k in part)
+            mc[k] = np.concatenate([part[k] if k in part else np.full((nr,) + ref.shape[1:], np.nan)
+                                    for part, nr in zip(parts, n_of)])
+    os.makedirs(outdir, exist_ok=True)
+    out = {}
+    fn = dds.dispersionFunction or {}
+    for k, v in fn.items():
+        v = np.asarray(v)
+        if v.dtype.kind in "biuf":
+            _put_finite(out, "dispersionFunction_" + k, v.reshape(-1))
+    if "betaPriorVar" in dds.attrs:
+        _put_finite(out, "betaPriorVar", np.asarray(dds.attrs["betaPriorVar"], np.float64).reshape(-1))
+    if world == 1 and dds.assays:
+        import torch
+        assays, seen = [], set()
+        for k, a in sorted(dds.assays.items()):
+            if id(a) not in seen:
+                seen.add(id(a))
+                assays.append((k, a))
+        # (value + NA kind per entry at worst: 2 x 8 bytes)
+        # the assays' own rows: on the call-by-call chain with all-zero rows set aside they cover only attrs["nz_rows"]
+        a_n = assays[0][1].n
+        assert all(a.n == a_n for _, a in assays), [(k, a.n) for k, a in assays]
+        per_row = 16 * dds.m * len(assays)
+        na = max(1, min(DUMP_ASSAY_ROWS, a_n, (DUMP_LIMIT_BYTES // 4) // per_row))
+        rows = np.sort(np.random.Generator(np.random.PCG64(20261016)).choice(a_n, na, replace=False))
+        genes_of_rows = rows if a_n == dds.n else np.asarray(dds.attrs["nz_rows"])[rows]
+        out["assay_rows"] = genes_of_rows.astype(np.float64)         # gene (mcols) index of each assay row written
+        for k, a in assays:
+            t = a.view()
+            _put_finite(out, "assay_" + k, t[torch.as_tensor(rows, device=t.device)].to(torch.float64).cpu().numpy())
+    budget = DUMP_LIMIT_BYTES - sum(v.nbytes for v in out.values())
+    n = len(next(iter(mc.values())))
+    genes = {}
+    for k, v in mc.items():
+        _put_finite(genes, "mcols_" + k, v)
+    per_gene = sum(v.nbytes for v in genes.values())
+    if per_gene > budget:
+        # a sample's arrays are at most keep / n of the full ones (a _nonfinite array only where the sample has NA)
+        keep = int(n * (budget - 8 * n) / per_gene)
+        rows = np.sort(np.random.Generator(np.random.PCG64(20261015)).choice(n, keep, replace=False))
+        genes = {"mcols_rows": rows.astype(np.float64)}
+        for k, v in mc.items():
+            _put_finite(genes, "mcols_" + k, v[rows])
+    out.update(genes)
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_LIMIT_BYTES, "dump of %d bytes" % total
+    for k, v in out.items():
+        np.save(os.path.join(outdir, k + ".npy"), np.ascontiguousarray(v))
 
 
 def parity_sample(dds, W, x, cfg, factors, reduced, rows=2048):
@@ -663,7 +805,7 @@ def other_configs(out, args):
     rows = [_config_row(out)]
     for name in ("C2", "C4", "C5"):
         cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", "5", "--warmup", "3", "--no-cpu-baseline",
-               "--no-hostpath", "--no-variants", "--no-configs", "--seed", str(args.seed), "--size-factors", args.size_factors,
+               "--no-hostpath", "--no-variants", "--no-configs", "--full", "--seed", str(args.seed), "--size-factors", args.size_factors,
                "--pipeline", str(args.pipeline)]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)

@@ -211,7 +211,7 @@ def test_bench_spawns_its_own_ranks():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DSQ_BENCH_ONE_DEVICE="1")
-    common = ["--steps", "1", "--warmup", "0", "--genes", "1500", "--no-cpu-baseline", "--no-hostpath"]
+    common = ["--steps", "1", "--warmup", "0", "--genes", "1500", "--no-cpu-baseline", "--no-hostpath", "--full"]
     r2 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"] + common, env=env,
                         capture_output=True, text=True, timeout=600)
     assert r2.returncode == 0, r2.stderr[-2000:]
@@ -227,14 +227,28 @@ def test_bench_spawns_its_own_ranks():
     assert j2["result_digest"] == j1["result_digest"]          # sharded == serial, every per-gene result column
 
 
+# How many processes may hold one GPU at once on the shared machines this suite runs on: a run that starts more is stopped
+# there as a whole.  The bench tests below that put N ranks on cuda:0 beside this process need N + 1; where a machine
+# admits more, DSQ_TEST_GPU_PROCS says so.
+GPU_PROCS = int(os.environ.get("DSQ_TEST_GPU_PROCS", "6"))
+
+
+def _need_gpu_procs(k):
+    """skip (before any work) a test that would hold k processes on one GPU where fewer are admitted"""
+    if k > GPU_PROCS:
+        pytest.skip("needs %d processes on one GPU (ranks + this one), this machine admits %d (DSQ_TEST_GPU_PROCS)"
+                    % (k, GPU_PROCS))
+
+
 def test_bench_eight_ranks_on_one_device_equal_serial():
     """the N = 8 path of bench.py (what the driver launches for SCALE): eight ranks (all on cuda:0 here, the n-vector
     exchanges over gloo), shards cut as R/parallel.R:10 -- the digest over every per-gene result column equals the serial
     run's (tests/testthat/test_parallel.R:27-37 at 8 workers), and the parity block reports the oracle's bits"""
     import json, os, subprocess, sys
+    _need_gpu_procs(9)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DSQ_BENCH_ONE_DEVICE="1")
-    common = ["--steps", "1", "--warmup", "0", "--genes", "4100", "--no-cpu-baseline", "--no-hostpath", "--no-weak"]
+    common = ["--steps", "1", "--warmup", "0", "--genes", "4100", "--no-cpu-baseline", "--no-hostpath", "--no-weak", "--full"]
     r8 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8"] + common, env=env,
                         capture_output=True, text=True, timeout=900)
     assert r8.returncode == 0, r8.stderr[-2000:]
@@ -249,6 +263,41 @@ def test_bench_eight_ranks_on_one_device_equal_serial():
     assert j8["result_digest"] == j1["result_digest"]
     for j in (j1, j8):
         assert j["parity"]["iter_equal"] == 1.0 and j["parity"]["max_rel"] == 0.0, j["parity"]
+
+
+def _load_dump(d):
+    return {f[:-4]: np.load(os.path.join(str(d), f)) for f in os.listdir(str(d))}
+
+
+def test_bench_four_ranks_on_one_device_equal_serial(tmp_path):
+    """the N > 1 path of bench.py at four ranks, all on cuda:0 (the n-vector exchanges over gloo), 4100 genes cut into four
+    ranges as R/parallel.R:10: the digest over every per-gene result column equals the serial run's
+    (tests/testthat/test_parallel.R:27-37 at 4 workers), the parity block reports the oracle's bits, and --dump-outputs of
+    the four ranks (their shards gathered in gene order) writes the serial run's per-gene columns bit for bit"""
+    import json, os, subprocess, sys
+    _need_gpu_procs(5)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, DSQ_BENCH_ONE_DEVICE="1")
+    common = ["--steps", "1", "--warmup", "0", "--genes", "4100", "--no-cpu-baseline", "--no-hostpath", "--no-weak", "--full"]
+    r4 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--dump-outputs", str(tmp_path / "d4")]
+                        + common, env=env, capture_output=True, text=True, timeout=900)
+    assert r4.returncode == 0, r4.stderr[-2000:]
+    j4 = json.loads(r4.stdout.strip().splitlines()[-1])
+    r1 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dump-outputs", str(tmp_path / "d1")]
+                        + common, env=env, capture_output=True, text=True, timeout=600)
+    assert r1.returncode == 0, r1.stderr[-2000:]
+    j1 = json.loads(r1.stdout.strip().splitlines()[-1])
+    assert j4["n_gpus"] == 4 and j4["config"]["genes_total"] == j1["config"]["genes_total"]
+    assert abs(j4["config"]["genes_this_gpu"] * 4 - j4["config"]["genes_total"]) < 4
+    assert j4["config"]["chain"].startswith("fused")
+    assert j4["result_digest"] == j1["result_digest"]
+    for j in (j1, j4):
+        assert j["parity"]["iter_equal"] == 1.0 and j["parity"]["max_rel"] == 0.0, j["parity"]
+    d4, d1 = _load_dump(tmp_path / "d4"), _load_dump(tmp_path / "d1")
+    cols = sorted(k for k in d1 if k.startswith("mcols_"))
+    assert "mcols_dispersion" in cols and sorted(k for k in d4 if k.startswith("mcols_")) == cols
+    for k in cols:
+        assert d4[k].shape == d1[k].shape and np.array_equal(d4[k], d1[k]), k
 
 
 def test_global_refit_count_over_rccl_single_rank():
@@ -370,9 +419,10 @@ def test_bench_two_ranks_over_rccl_when_two_devices_are_visible():
     import json, os, subprocess, sys
     import torch
     if torch.cuda.device_count() < 2:
-        pytest.skip("one visible device: the N > 1 path runs with ranks sharing it (tests above)")
+        pytest.skip("needs 2 GPUs (one rank per device), found %d; the N > 1 path with ranks sharing one device: tests above"
+                    % torch.cuda.device_count())
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--steps", "2", "--warmup", "1", "--genes", "3000", "--no-cpu-baseline", "--no-hostpath", "--no-weak"]
+    common = ["--steps", "2", "--warmup", "1", "--genes", "3000", "--no-cpu-baseline", "--no-hostpath", "--no-weak", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("DSQ_BENCH_ONE_DEVICE", None)
     r2 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"] + common, env=env, capture_output=True, text=True, timeout=600)
@@ -382,3 +432,82 @@ def test_bench_two_ranks_over_rccl_when_two_devices_are_visible():
     assert r1.returncode == 0, r1.stderr[-2000:]
     j2, j1 = json.loads(r2.stdout.strip().splitlines()[-1]), json.loads(r1.stdout.strip().splitlines()[-1])
     assert j2["n_gpus"] == 2 and j2["result_digest"] == j1["result_digest"]
+
+
+def _direct_chain(config, genes, seed=1, size_factors="lognormal"):
+    """the chain bench.py times, called once on the same inputs (bench.synthetic_counts, resident in HBM in R layout)"""
+    import torch
+    import bench
+    from deseq2_amd import fused
+    cfg = bench.CONFIGS[config]
+    x = bench.make_design(cfg["design"], cfg["samples"])
+    counts, sf, w = bench.synthetic_counts(cfg, genes, x, seed, size_factors)
+    dev = torch.device("cuda", 0)
+    m, n = x.shape[0], counts.shape[0]
+    counts_r = torch.as_tensor(np.ascontiguousarray(counts.T), device=dev)
+    nf_r = torch.ones((m, n), dtype=torch.float64, device=dev) * torch.as_tensor(sf, device=dev)[:, None]
+    w_r = None if w is None else torch.as_tensor(np.ascontiguousarray(w.T), device=dev)
+    dds = core.DESeqDataSet.from_device(DeviceEngine(dev), counts_r, nf_r, x, weights=w, sizeFactors=sf, weights_r=w_r)
+    kw = dict(test=cfg["test"], reduced=None)
+    if cfg.get("betaPrior"):
+        kw.update(betaPrior=True, factors={"condition": x[:, 1].astype(int)})
+    fused.DESeq(dds, comm_device=None, shard_sizes=None, wait=True, **kw)
+    return dds
+
+
+@pytest.mark.parametrize("config", ["C3", "C5"])
+def test_bench_plain_run_and_dump_outputs(tmp_path, config):
+    """a plain bench.py run (no --full) prints the headline line alone, and --dump-outputs writes the last timed step's
+    results as finite float64 .npy files within 64 MB -- the per-gene columns of every gene, the trend, betaPriorVar
+    (C5), a fixed sample of assay rows -- equal, array for array and bit for bit, to what one direct call of the same
+    chain on the same inputs returns (C3: the fused chain; C5: weights + betaPrior, the call-by-call chain)"""
+    import json, os, subprocess, sys
+    import torch
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--config", config, "--genes", "1500", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["full"] is False and j["ms_per_step"] > 0
+    assert abs(j["value"] - j["config"]["genes_total"] / (j["ms_per_step"] * 1e-3)) <= 1e-6 * j["value"]
+    for k in ("parity", "kernels", "roofline", "result_digest", "variants", "configs", "cpu_baseline", "one_call_at_a_time"):
+        assert k not in j, k
+    files = _load_dump(out)
+    assert sum(v.nbytes for v in files.values()) <= 64 << 20
+    assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in files.values())
+    for k, v in files.items():          # NA / Inf entries: 0 in the array, their kind (1 NA, 2 +Inf, 3 -Inf) beside it
+        if k.endswith("_nonfinite"):
+            base = files[k[: -len("_nonfinite")]]
+            assert v.shape == base.shape and set(np.unique(v)) <= {0.0, 1.0, 2.0, 3.0} and (base[v != 0] == 0).all(), k
+    n = j["config"]["genes_total"]
+    assert files["mcols_dispersion"].shape == (n,) and files["assay_mu"].shape == (files["assay_rows"].size, j["config"]["samples"])
+    assert ("betaPriorVar" in files) == (config == "C5")
+    # the same values, in gene order, as the chain returns them to its caller
+    dds = _direct_chain(config, 1500)
+    assert dds.n == n
+    want = {}
+    for k, v in dds.mcols.items():
+        if np.asarray(v).dtype.kind in "biuf":
+            bench._put_finite(want, "mcols_" + k, np.asarray(v, np.float64))
+    for k, v in (dds.dispersionFunction or {}).items():
+        if np.asarray(v).dtype.kind in "biuf":
+            bench._put_finite(want, "dispersionFunction_" + k, np.asarray(v, np.float64).reshape(-1))
+    if "betaPriorVar" in dds.attrs:
+        bench._put_finite(want, "betaPriorVar", np.asarray(dds.attrs["betaPriorVar"], np.float64).reshape(-1))
+    rows = files["assay_rows"].astype(np.int64)
+    seen = set()
+    for k, a in sorted(dds.assays.items()):          # (an assay that is another's object, replaceCooks: written once)
+        if id(a) in seen:
+            continue
+        seen.add(id(a))
+        assert a.n == dds.n, k
+        bench._put_finite(want, "assay_" + k, a.view()[torch.as_tensor(rows, device=a.t.device)].double().cpu().numpy())
+    want["assay_rows"] = files["assay_rows"]
+    assert sorted(files) == sorted(want)
+    for k in want:
+        assert np.array_equal(files[k], want[k]), k

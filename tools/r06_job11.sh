@@ -7,7 +7,7 @@ run() { # name, env..., -- args
 }
 for spec in "6250_key2_0:DSQ_LPT_KEY2=0:--genes=6250" "6250_key2_1:DSQ_LPT_KEY2=1:--genes=6250" "12500_k1:DSQ_LPT_KEY2=1:--genes=12500" "12500_off:DSQ_LPT=0:--genes=12500" "C2_k1_max:DSQ_LPT_KEY2=1,DSQ_LPT_MAXN=100000:--config=C2" "C2_off:DSQ_LPT=0:--config=C2" "C3_k1_max:DSQ_LPT_KEY2=1,DSQ_LPT_MAXN=100000:--config=C3" "C3_off:DSQ_LPT=0:--config=C3" "C5_k1_max:DSQ_LPT_KEY2=1,DSQ_LPT_MAXN=100000:--config=C5" "C5_off:DSQ_LPT=0:--config=C5"; do
   IFS=':' read -r name envs arg <<< "$spec"
-  (export ${envs//,/ }; timeout 300 python bench.py $arg --pipeline 1 --no-cpu-baseline --no-hostpath --no-variants --no-parity --no-configs > $O/b_$name.json 2> $O/b_$name.err)
+  (export ${envs//,/ }; timeout 300 python bench.py --full $arg --pipeline 1 --no-cpu-baseline --no-hostpath --no-variants --no-parity --no-configs > $O/b_$name.json 2> $O/b_$name.err)
   python - <<PY
 import json
 try:

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${1:-r06q}; mkdir -p $O; cd $R; ex
 timeout 1200 python -m pytest tests/test_gpu_fused.py tests/test_gpu_pipeline.py tests/test_gpu_deseq_host.py tests/test_gpu_testthat.py -m gpu --maxfail=5 -q -x > $O/tests.log 2>&1; echo "tests rc=$? $(tail -1 $O/tests.log)"
 for spec in "6250:--genes=6250" "C3:--config=C3" "C2:--config=C2" "C5:--config=C5" "C4:--config=C4"; do
   IFS=':' read -r name arg <<< "$spec"
-  timeout 300 python bench.py $arg --pipeline 1 --no-cpu-baseline --no-hostpath --no-variants --no-configs > $O/b_$name.json 2> $O/b_$name.err
+  timeout 300 python bench.py --full $arg --pipeline 1 --no-cpu-baseline --no-hostpath --no-variants --no-configs > $O/b_$name.json 2> $O/b_$name.err
   python - <<PY
 import json
 try:
