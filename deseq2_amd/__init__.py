@@ -4,5 +4,6 @@ fitDispGrid boundary.  The compute lives in libdeseq2_mi355x.so
 callers of that boundary."""
 from . import _lib  # noqa: F401
 from .native import fitBeta, fitDisp, fitDispGrid  # noqa: F401
+from .core import estimateSizeFactors, estimateSizeFactorsForMatrix  # noqa: F401
 
-__all__ = ["fitBeta", "fitDisp", "fitDispGrid"]
+__all__ = ["fitBeta", "fitDisp", "fitDispGrid", "estimateSizeFactors", "estimateSizeFactorsForMatrix"]

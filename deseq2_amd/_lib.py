@@ -222,6 +222,20 @@ class DsqDeseqHostOut(C.Structure):
         ("mle_beta", C.c_void_p)]
 
 
+class DsqSizeFactorArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("m", C.c_int32), ("layout", C.c_int32), ("ld", C.c_int64), ("y", C.c_void_p),
+        ("y_type", C.c_int32), ("type", C.c_int32), ("geoMeans", C.c_void_p), ("control", C.c_void_p),
+        ("normMatrix", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
+class DsqSizeFactorOut(C.Structure):
+    _fields_ = [("sizeFactors", C.c_void_p), ("loggeomeans", C.c_void_p), ("normalizationFactors", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
+DSQ_SF = {"ratio": 0, "poscounts": 1}
 DSQ_PH_GENE_EST, DSQ_PH_TREND, DSQ_PH_MAP_TEST, DSQ_PH_OUTLIERS, DSQ_PH_FINISH, DSQ_PH_PRIOR = 1, 2, 4, 8, 16, 32
 DSQ_PH_OUTLIERS_DETECT, DSQ_PH_OUTLIERS_REFIT = 64, 128
 DSQ_ST = {k: i for i, k in enumerate((
@@ -246,6 +260,7 @@ EXPORTED_SYMBOLS = [
     "dsq_profile_count", "dsq_profile_get",
     "dsq_deseq", "dsq_beta_prior_var", "dsq_weights_prep_dev", "dsq_xim_dev",
     "dsq_linear_mu", "dsq_linear_mu_dev", "dsq_cooks_distance", "dsq_cooks_distance_dev", "dsq_replace_outliers", "dsq_replace_outliers_dev",
+    "dsq_size_factors", "dsq_size_factors_dev", "dsq_size_factors_workspace_bytes",
 ]
 
 _lib = None
@@ -308,6 +323,10 @@ def lib():
     L.dsq_xim_dev.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dsq_deseq.argtypes = [C.POINTER(DsqDeseqHostArgs), C.POINTER(DsqDeseqHostOut)]
     L.dsq_beta_prior_var.argtypes = [C.POINTER(DsqBetaPriorArgs), C.c_void_p]
+    L.dsq_size_factors.argtypes = [C.POINTER(DsqSizeFactorArgs), C.POINTER(DsqSizeFactorOut)]
+    L.dsq_size_factors_dev.argtypes = [C.POINTER(DsqSizeFactorArgs), C.POINTER(DsqSizeFactorOut), C.c_void_p]
+    L.dsq_size_factors_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.dsq_size_factors_workspace_bytes.restype = C.c_int64
     L.dsq_deseq_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.dsq_deseq_workspace_bytes.restype = C.c_int64
     L.dsq_profile_get.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double)]

@@ -1742,3 +1742,120 @@ int dsq_test_math(int op, const double *a, const double *b, const double *c, dou
 }
 
 }  // extern "C"
+
+// ---- estimateSizeFactors (size_factors.hip) -------------------------------------------------------------------------
+namespace dsq {
+
+static int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o) {
+    if (!a || !o) return fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->n < 1 || a->m < 1) return fail(DSQ_ERR_ARG, "bad dimensions");
+    if (!a->y || !o->sizeFactors || !o->status) return fail(DSQ_ERR_ARG, "NULL counts, sizeFactors or status");
+    if (a->y_type != DSQ_Y_INT32 && a->y_type != DSQ_Y_FLOAT64) return fail(DSQ_ERR_ARG, "unknown y_type %d", a->y_type);
+    if (a->type != DSQ_SF_RATIO && a->type != DSQ_SF_POSCOUNTS)
+        return fail(DSQ_ERR_ARG, "type %d: DSQ_SF_RATIO or DSQ_SF_POSCOUNTS (\"iterate\" is not served)", a->type);
+    if ((a->normMatrix != nullptr) != (o->normalizationFactors != nullptr))
+        return fail(DSQ_ERR_ARG, "normalizationFactors is required if and only if normMatrix is given");
+    return DSQ_OK;
+}
+
+static int size_factors_dev_locked(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o, hipStream_t st) {
+    if (int rc = size_factors_check(a, o)) return rc;
+    if (a->layout != DSQ_LAYOUT_R && a->layout != DSQ_LAYOUT_GENE_MAJOR) return fail(DSQ_ERR_ARG, "unknown layout %d", a->layout);
+    if (a->layout == DSQ_LAYOUT_GENE_MAJOR && a->ld < a->m) return fail(DSQ_ERR_ARG, "ld < m");
+    const size_t need = size_factors_workspace_bytes(a->n, a->m);
+    if (!a->workspace || a->workspace_bytes < (int64_t)need)
+        return fail(DSQ_ERR_ARG, "workspace of %lld bytes: dsq_size_factors_workspace_bytes(n, m) = %zu", (long long)a->workspace_bytes, need);
+    if (int rc = check_device()) return rc;
+    SizeFactorKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.m = a->m;
+    kp.y = a->y;
+    const bool gm = a->layout == DSQ_LAYOUT_GENE_MAJOR;
+    kp.y_si = gm ? (long)a->ld : 1L;  kp.y_sj = gm ? 1L : (long)a->n;
+    kp.nm = a->normMatrix; kp.nm_si = kp.y_si; kp.nm_sj = kp.y_sj;
+    kp.type = a->type;
+    kp.geoMeans = a->type == DSQ_SF_POSCOUNTS ? nullptr : a->geoMeans;
+    kp.stabilize = a->type == DSQ_SF_POSCOUNTS || a->geoMeans != nullptr;
+    kp.control = a->control;
+    kp.sf = o->sizeFactors; kp.lgm_out = o->loggeomeans; kp.nf_out = o->normalizationFactors; kp.status = o->status;
+    capi_prof_begin("size_factors", a->n, st);
+    DSQ_HIP(launch_size_factors(kp, a->y_type == DSQ_Y_FLOAT64, a->workspace, st));
+    capi_prof_end(st);
+    return DSQ_OK;
+}
+
+}  // namespace dsq
+
+extern "C" {
+
+int64_t dsq_size_factors_workspace_bytes(int32_t n, int32_t m) {
+    if (n < 0 || m < 0) return 0;
+    return (int64_t)size_factors_workspace_bytes(n, m);
+}
+
+int dsq_size_factors_dev(const DsqSizeFactorArgs *args, const DsqSizeFactorOut *out, void *stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    WsScope ws((hipStream_t)stream);
+    return size_factors_dev_locked(args, out, (hipStream_t)stream);
+}
+
+int dsq_size_factors(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    WsScope ws(nullptr);
+    if (int rc = size_factors_check(a, o)) return rc;
+    if (a->layout != DSQ_LAYOUT_R) return fail(DSQ_ERR_ARG, "host entry points take R layout only");
+    if (int rc = check_device()) return rc;
+    hipStream_t st = nullptr;
+    const size_t n = a->n, m = a->m;
+    const long ld = round_ld(a->m);
+    const size_t ye = a->y_type == DSQ_Y_INT32 ? 4 : 8;
+    DsqSizeFactorArgs d = *a;
+    DsqSizeFactorOut od = *o;
+    void *v, *g;
+    int rc;
+    // counts and normMatrix: up in R layout, turned gene-major on the device (rows of 64 consecutive samples)
+    if ((rc = up(WS_H_Y, a->y, n * m * ye, st, &v))) return rc;
+    if ((rc = ws_get(WS_Y, n * ld * ye, &g))) return rc;
+    if (ye == 4) DSQ_HIP(launch_transpose_r_to_gm_i32((const int32_t *)v, (int32_t *)g, a->n, a->m, ld, st));
+    else DSQ_HIP(launch_transpose_r_to_gm_f64((const double *)v, (double *)g, a->n, a->m, ld, st));
+    d.y = g; d.layout = DSQ_LAYOUT_GENE_MAJOR; d.ld = ld;
+    double *nf_gm = nullptr;
+    if (a->normMatrix) {
+        if ((rc = up(WS_H_NF, a->normMatrix, n * m * 8, st, &v))) return rc;
+        if ((rc = ws_get(WS_NF, n * ld * 8, &g))) return rc;
+        DSQ_HIP(launch_transpose_r_to_gm_f64((const double *)v, (double *)g, a->n, a->m, ld, st));
+        d.normMatrix = (const double *)g;
+        if ((rc = ws_get(WS_MUOUT, n * ld * 8, &g))) return rc;
+        nf_gm = (double *)g;
+        od.normalizationFactors = nf_gm;
+    }
+    // geoMeans (n f64) | control (n i32)
+    if ((rc = ws_get(WS_H_VEC, n * 12 + 8, &v))) return rc;
+    if (a->geoMeans) { DSQ_HIP(hipMemcpyAsync(v, a->geoMeans, n * 8, hipMemcpyHostToDevice, st)); d.geoMeans = (const double *)v; }
+    if (a->control) {
+        DSQ_HIP(hipMemcpyAsync((char *)v + n * 8, a->control, n * 4, hipMemcpyHostToDevice, st));
+        d.control = (const int32_t *)((char *)v + n * 8);
+    }
+    const size_t wsb = size_factors_workspace_bytes(a->n, a->m);
+    if ((rc = ws_get(WS_SCRATCH, wsb, &v))) return rc;
+    d.workspace = v; d.workspace_bytes = (int64_t)wsb;
+    // sizeFactors (m f64) | loggeomeans (n f64) | status
+    if ((rc = ws_get(WS_H_OUTVEC, (m + n + 1) * 8, &v))) return rc;
+    double *ov = (double *)v;
+    od.sizeFactors = ov; od.loggeomeans = ov + m; od.status = (int32_t *)(ov + m + n);
+    if ((rc = size_factors_dev_locked(&d, &od, st))) return rc;
+    DSQ_HIP(hipMemcpyAsync(o->sizeFactors, od.sizeFactors, m * 8, hipMemcpyDeviceToHost, st));
+    if (o->loggeomeans) DSQ_HIP(hipMemcpyAsync(o->loggeomeans, od.loggeomeans, n * 8, hipMemcpyDeviceToHost, st));
+    DSQ_HIP(hipMemcpyAsync(o->status, od.status, 4, hipMemcpyDeviceToHost, st));
+    if (nf_gm) {
+        if ((rc = ws_get(WS_H_OUTMAT, n * m * 8, &v))) return rc;
+        DSQ_HIP(launch_transpose_gm_to_r_f64(nf_gm, (double *)v, a->n, a->m, ld, st));
+        if ((rc = down(o->normalizationFactors, v, n * m * 8, st))) return rc;
+    }
+    DSQ_HIP(hipStreamSynchronize(st));
+    if (*o->status == 1)
+        return fail(DSQ_ERR_FIT, "every gene contains at least one zero, cannot compute log geometric means");
+    return DSQ_OK;
+}
+
+}  // extern "C"

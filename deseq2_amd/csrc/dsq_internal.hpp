@@ -192,6 +192,31 @@ struct ReplaceKernelParams {
     const int32_t *n_dev;
 };
 
+// estimateSizeFactors (size_factors.hip).  Element (i, j) of the counts sits at y[i * y_si + j * y_sj] (either layout), of
+// normMatrix / the normalization factors at [i * nm_si + j * nm_sj].  The second block is carved from the caller's
+// workspace by launch_size_factors.
+struct SizeFactorKernelParams {
+    int n, m;
+    const void *y;
+    long y_si, y_sj;
+    const double *nm;            // normMatrix or nullptr
+    long nm_si, nm_sj;
+    const double *geoMeans;      // n or nullptr
+    const int32_t *control;      // n flags or nullptr
+    int type;                    // 0 ratio, 1 poscounts
+    int stabilize;               // divide by exp(mean(log sf)) (R/core.R:573-576)
+    double *sf;                  // m
+    double *lgm_out;             // n or nullptr
+    double *nf_out;              // normalization factors or nullptr
+    int32_t *status;
+    double *lgm, *logsf;
+    unsigned long long *prefix, *hikey, *hiprefix;
+    unsigned int *hist, *cnt, *rank, *histate, *hishift;
+    int *any_not_inf;
+};
+hipError_t launch_size_factors(SizeFactorKernelParams kp, int y_f64, void *workspace, hipStream_t st);
+size_t size_factors_workspace_bytes(long n, long m);
+
 // gene index of work item i, and the number of work items, of a (possibly row-listed) launch
 #define DSQ_NWORK(kp) ((kp).n_dev ? *(kp).n_dev : (kp).n)
 #define DSQ_GENE(kp, i) ((kp).rows ? (kp).rows[i] : (i))

@@ -116,6 +116,32 @@ def _weights_ok_host(w, x, thr, full_rank):
     return ok
 
 
+SF_ALL_ZERO = "every gene contains at least one zero, cannot compute log geometric means"       # R/core.R:558
+
+
+def control_flags(controlGenes, n):
+    """controlGenes (R/core.R:564-568: an index vector -- 0-based here -- or a logical vector over the genes) as n int32
+    flags, the form the engine takes; None = every gene.  R's `counts[controlGenes, ]` would repeat a row listed twice:
+    a repeated index is refused instead of silently counted once."""
+    if controlGenes is None:
+        return None
+    c = np.asarray(controlGenes)
+    if c.dtype == np.bool_:
+        if c.shape != (n,):
+            raise ValueError("a logical controlGenes must have one entry per gene")
+        return np.ascontiguousarray(c, dtype=np.int32)
+    if c.dtype.kind not in "iuf":
+        raise ValueError("controlGenes should be either a numeric or logical vector")
+    idx = c.astype(np.int64).reshape(-1)
+    if (idx != c.reshape(-1)).any() or (idx < 0).any() or (idx >= n).any():
+        raise IndexError("controlGenes: indices must be integers in [0, n)")
+    if np.unique(idx).size != idx.size:
+        raise ValueError("controlGenes: an index is listed twice")
+    f = np.zeros(n, dtype=np.int32)
+    f[idx] = 1
+    return f
+
+
 class HostEngine:
     name = "host"
 
@@ -195,6 +221,42 @@ class HostEngine:
         for j0 in range(0, m, 64):
             rec[j0:j0 + 64] = 1.0 / (np.cumsum(nf[:, j0:j0 + 64], axis=0)[-1] / n)
         return float(np.cumsum(rec)[-1] / m)
+
+    def size_factors(self, y, type="ratio", geoMeans=None, control=None, normMatrix=None):
+        """estimateSizeFactorsForMatrix / estimateNormFactors (R/core.R:535-578, 2159-2163; "poscounts" as
+        estimateSizeFactors.DESeqDataSet runs it, R/methods.R:377-382) in plain numpy: the host statement of what
+        csrc/size_factors.hip computes on the device (libm log / exp and numpy's sums here, so equal to rounding, not
+        to the bit).  control: int32 flags (control_flags) or None.  Returns sizeFactors (m), loggeomeans (n) and, with
+        normMatrix, normalizationFactors (n x m)."""
+        K = np.asarray(y, np.float64)
+        n, m = K.shape
+        V = K if normMatrix is None else K / np.asarray(normMatrix, np.float64)
+        with np.errstate(all="ignore"):
+            if type == "poscounts":
+                pos = K > 0
+                s = np.where(pos, np.log(np.where(pos, K, 1.0)), 0.0).sum(axis=1)
+                lgm = np.log(np.where(pos.any(axis=1), np.exp(s / m), 0.0))
+            elif geoMeans is not None:
+                lgm = np.log(np.asarray(geoMeans, np.float64))
+            else:
+                lgm = np.log(V).sum(axis=1) / m
+            if np.isinf(lgm).all():
+                raise ValueError(SF_ALL_ZERO)
+            use = np.isfinite(lgm)
+            if control is not None:
+                use &= np.asarray(control) != 0
+            sf = np.full(m, np.nan)
+            for j in range(m):
+                sel = use & (V[:, j] > 0)
+                if sel.any():
+                    sf[j] = np.exp(np.median(np.log(V[sel, j]) - lgm[sel]))
+            if type == "poscounts" or geoMeans is not None:
+                sf = sf / np.exp(np.mean(np.log(sf)))                                   # R/core.R:573-576
+            out = {"sizeFactors": sf, "loggeomeans": lgm}
+            if normMatrix is not None:
+                nf = np.asarray(normMatrix, np.float64) * sf[None, :]
+                out["normalizationFactors"] = np.asfortranarray(nf / np.exp(np.log(nf).sum(axis=1) / m)[:, None])
+        return out
 
     def linear_mu(self, y, nf, x):
         """linearModelMuNormalized, R/core.R:2465-2471 (engine kernel: a BLAS product on the host would make
@@ -476,6 +538,21 @@ class DeviceEngine:
         _lib.check(_lib.lib().dsq_xim_dev(C.c_void_p(nf.t.data_ptr()), nf.n, nf.m, nf.ld, C.c_void_p(buf.data_ptr()),
                                           C.c_void_p(buf[nf.m:].data_ptr()), st))
         return float(self._host(buf[nf.m:])[0])
+
+    def size_factors(self, y, type="ratio", geoMeans=None, control=None, normMatrix=None):
+        """estimateSizeFactors on the resident counts (csrc/size_factors.hip): the loggeomeans, the per-sample medians by
+        radix selection and, with a normMatrix handle, the normalization-factor matrix, all on the current stream.  The ONE
+        host look is the m size factors with the status word (the caller needs them for xim, and R's error for a matrix
+        whose every gene has a zero has to surface).  sizeFactors_dev / normalizationFactors stay resident."""
+        r = self.native.sizeFactors_dev(y, type=type, geoMeans=None if geoMeans is None else self._vec(geoMeans),
+                                        control=control, normMatrix=normMatrix)
+        h = self._host(r["_pack"])
+        if int(h[y.m:].view(self.torch.int32)[0]) == 1:
+            raise ValueError(SF_ALL_ZERO)
+        out = {"sizeFactors": h[: y.m].numpy().copy(), "sizeFactors_dev": r["sizeFactors"], "loggeomeans_dev": r["loggeomeans"]}
+        if normMatrix is not None:
+            out["normalizationFactors"] = r["normalizationFactors"]
+        return out
 
     def weights_prep(self, w, x, thr=1e-2):
         """getAndCheckWeights (R/core.R:2697-2751) in ONE kernel on the resident weights: (w / rowmax, its 1e-6 floor,

@@ -434,7 +434,7 @@ def finish(dds):
 
 
 def DESeq(dds, test="Wald", fitType="parametric", reduced=None, minReplicatesForReplace=7, comm_device=None,
-          shard_sizes=None, wait=True, **kw):
+          shard_sizes=None, wait=True, sfType=None, **kw):
     """core.DESeq() / parallel.DESeqParallel() semantics (R/core.R:280-432, R/parallel.R:6-74) on the fused device
     chain.  With torch.distributed initialised, `dds` is this rank's gene shard and the dispersion trend is fitted
     over the gathered (baseMean, dispGeneEst) of all ranks.
@@ -443,7 +443,16 @@ def DESeq(dds, test="Wald", fitType="parametric", reduced=None, minReplicatesFor
     fused.finish(dds), which enqueues the copy of the result block (side stream), waits for it and builds the columns --
     input errors the device detects (negative weights, all-zero counts, a trend that does not fit) surface THERE.  A loop over analyses then keeps the device busy while the host
     prepares the next one and post-processes the previous one, and the result copy (a side stream) runs beside the
-    next chain's kernels -- bench.py's pipelined steps."""
+    next chain's kernels -- bench.py's pipelined steps.
+
+    sfType = "ratio" / "poscounts": estimateSizeFactors first (R/core.R:304,378-389), on the resident counts; the chain then
+    reads the resident m-vector.  The host sees the m size factors (xim is their mean reciprocal): one small copy.  (A
+    gene shard would estimate from its own rows only: as in R/parallel.R, estimate on the whole matrix before the split.)"""
+    if sfType is not None:
+        from . import parallel as _par
+        if _par.world_size() > 1:
+            raise ValueError("sfType: size factors are estimated on the whole matrix, before the genes are split")
+        core.estimateSizeFactors(dds, type=sfType)
     if not supported(dds, test=test, reduced=reduced, fitType=fitType, minReplicatesForReplace=minReplicatesForReplace, **kw):
         from . import parallel
         if parallel.world_size() > 1:

@@ -551,9 +551,50 @@ typedef struct {
 int dsq_deseq_dev(const DsqDeseqArgs *args, const DsqDeseqOut *out, void *stream);
 int64_t dsq_deseq_workspace_bytes(int32_t n, int32_t m, int32_t p, int32_t n_trend);
 
+/* ---- dsq_size_factors: estimateSizeFactors on the device --------------------------------------
+ * estimateSizeFactorsForMatrix (R/core.R:535-578), estimateNormFactors (R/core.R:2159-2163) and the dispatch of
+ * estimateSizeFactors.DESeqDataSet (R/methods.R:363-406): sf_j = exp(median over {i : loggeomeans_i finite, k_ij > 0
+ * [, control_i]} of (log k_ij - loggeomeans_i)), the median an EXACT order statistic found by radix selection over
+ * order-preserving 64-bit keys (no sort).
+ *   DSQ_SF_RATIO      loggeomeans_i = mean_j log k_ij (-Inf when the gene has a zero)
+ *   DSQ_SF_POSCOUNTS  geoMeans_i = exp(sum of log over the positive counts / m), 0 for an all-zero row (R/methods.R:377-382),
+ *                     then as a caller's geoMeans
+ *   geoMeans given    loggeomeans = log(geoMeans); the result is divided by exp(mean(log sf)) (R/core.R:573-576)
+ * normMatrix: the size factors of counts / normMatrix, then normalizationFactors = normMatrix * sf per column, each row
+ * divided by its geometric mean.  A sample with an empty selection gets NaN (R: NA).
+ * _dev: device pointers, asynchronous on `stream`, no host synchronisation and no allocation: the workspace
+ * (dsq_size_factors_workspace_bytes) is the caller's.  Counts may be int32 or float64 in either layout (gene-major is
+ * the fast one: a wavefront reads 64 consecutive samples of a gene).                                                  */
+enum { DSQ_SF_RATIO = 0, DSQ_SF_POSCOUNTS = 1 };
+typedef struct {
+    int32_t n, m;
+    int32_t layout;            /* DSQ_LAYOUT_* of y / normMatrix / normalizationFactors                             */
+    int64_t ld;                /* leading dimension for DSQ_LAYOUT_GENE_MAJOR (>= m)                                */
+    const void *y;             /* n x m counts                                                                      */
+    int32_t y_type;            /* DSQ_Y_INT32 or DSQ_Y_FLOAT64                                                      */
+    int32_t type;              /* DSQ_SF_RATIO or DSQ_SF_POSCOUNTS                                                  */
+    const double *geoMeans;    /* n, or NULL (ignored by DSQ_SF_POSCOUNTS, which computes its own, R/methods.R:381) */
+    const int32_t *control;    /* n flags (controlGenes as a logical vector), or NULL = every gene                  */
+    const double *normMatrix;  /* n x m in `layout`, or NULL                                                        */
+    void *workspace;           /* device; dsq_size_factors: ignored                                                 */
+    int64_t workspace_bytes;
+} DsqSizeFactorArgs;
+
+typedef struct {
+    double *sizeFactors;           /* m                                                                             */
+    double *loggeomeans;           /* n, or NULL                                                                    */
+    double *normalizationFactors;  /* n x m in `layout`: required if and only if normMatrix is given                */
+    int32_t *status;               /* 1 value: 0 ok, 1 = every gene contains at least one zero (R/core.R:557-559)   */
+} DsqSizeFactorOut;
+
+int dsq_size_factors_dev(const DsqSizeFactorArgs *args, const DsqSizeFactorOut *out, void *stream);
+/* host pointers in R layout, one device, synchronous; DSQ_ERR_FIT when *status comes back 1 */
+int dsq_size_factors(const DsqSizeFactorArgs *args, const DsqSizeFactorOut *out);
+int64_t dsq_size_factors_workspace_bytes(int32_t n, int32_t m);
+
 /* ---- dsq_deseq: DESeq() behind ONE host-pointer call ------------------------------------------------------------
  * What an R session binds as .Call("_DESeq2_mi355x_DESeq", ...) in place of the body of DESeq() between
- * estimateSizeFactors and the final bookkeeping (R/core.R:388-426: estimateDispersions -> nbinomWaldTest / nbinomLRT
+ * estimateSizeFactors (dsq_size_factors above) and the final bookkeeping (R/core.R:388-426: estimateDispersions -> nbinomWaldTest / nbinomLRT
  * -> refitWithoutOutliers): every array is a HOST pointer in R's layout (what INTEGER() / REAL() give), the call
  * uploads the count matrix ONCE through pinned staging, runs the device-driven chain of dsq_deseq_dev (all four
  * phases, the optim-fallback rows included, no host decision in between), and downloads the per-gene columns; the
