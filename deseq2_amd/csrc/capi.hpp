@@ -1,0 +1,43 @@
+// capi.hpp -- what the two halves of the C ABI (capi.hip: device pointers, capi_host.hip: host pointers) share.
+#pragma once
+#include "../../include/deseq2_mi355x.h"
+#include "dsq_internal.hpp"
+
+namespace dsq {
+
+static inline void prof_begin(hipStream_t st) { capi_prof_begin("call", 0, st); }
+static inline void prof_end(hipStream_t st) { capi_prof_end(st); }
+
+enum {  // workspace slots
+    WS_Y = 0, WS_NF, WS_W, WS_MU, WS_HAT, WS_MUOUT, WS_SCRATCH, WS_BAD, WS_CELLS, WS_COOKS_IN, WS_COUNTER, WS_TREND, WS_PAD_X, WS_PAD_VEC, WS_PAD_BETA,
+    WS_CELLS_BETA,
+    // host-entry staging
+    WS_H_Y, WS_H_X, WS_H_NF, WS_H_W, WS_H_MU, WS_H_VEC, WS_H_OUTMAT, WS_H_OUTMAT2, WS_H_OUTVEC,
+    WS_COUNT
+};
+static_assert(WS_COUNT <= DSQ_WS_PIPE_PADXR, "pipeline workspace slots follow the call slots");
+
+static inline long round_ld(int m) { return ((long)m + 7) & ~7L; }
+static inline bool is_wide(int p) { return p > DSQ_P_REG && p <= DSQ_P_WIDE; }
+static inline int wide_width(int p) { return dsq_wide_width(p); }   // padded width for a wide p
+
+// capi.hip: layout conversion into the workspace, and the device-pointer bodies behind the entry points (the caller
+// holds the call lock and has latched the stream's context)
+int prep_counts(const void *y, int y_type, int layout, long ld_in, int n, int m, hipStream_t st,
+                const int32_t **out, long *ld_out, bool *checked_async);
+int prep_matrix(const double *src, int layout, long ld_in, int n, int m, int slot, hipStream_t st,
+                const double **out, long ld_expected);
+int finish_ycheck(bool ycheck, hipStream_t st);
+int fit_beta_dev_locked(const DsqFitBetaArgs *a, const DsqFitBetaOut *o, hipStream_t st);
+int fit_disp_dev_locked(const DsqFitDispArgs *a, const DsqFitDispOut *o, hipStream_t st);
+int fit_disp_grid_dev_locked(const DsqFitDispGridArgs *a, const DsqFitDispGridOut *o, hipStream_t st);
+int prefit_dev_locked(const DsqPrefitArgs *a, const DsqPrefitOut *o, hipStream_t st);
+int linear_mu_dev_locked(const DsqPrefitArgs *a, double mu_floor, double *mu, hipStream_t st);
+int loglike_dev_locked(const DsqLogLikeArgs *a, double *out, hipStream_t st);
+int intercept_dev_locked(const DsqInterceptArgs *a, const DsqInterceptOut *o, hipStream_t st);
+int cooks_dev_locked(const DsqCooksArgs *a, const DsqCooksOut *o, hipStream_t st);
+int replace_dev_locked(const DsqReplaceArgs *a, const DsqReplaceOut *o, hipStream_t st);
+int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o);
+int size_factors_dev_locked(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o, hipStream_t st);
+
+}  // namespace dsq

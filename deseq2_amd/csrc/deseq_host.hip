@@ -6,7 +6,7 @@
 //     :2101, "one group per column" :735-742, mean(1 / sizeFactors) :2440-2444, the dispersion grid R/wrappers.R:70-72)
 //     are derived on the host -- O(m p) work;
 //   * the genes are cut into the contiguous ranges of R/parallel.R:10, one per visible device, each driven by a
-//     persistent worker thread with its own stream (capi.hip: host_sharded);
+//     persistent worker thread with its own stream (capi_host.hip: host_sharded);
 //   * a range uploads its rows of the count matrix ONCE (pinned staging, stage.hip), converts them to the gene-major
 //     layout on the device, enqueues the device-driven chain of pipeline.hip (every phase, no host decision), and
 //     downloads the per-gene columns; n x m assays only on request;
@@ -31,21 +31,11 @@
 namespace dsq {
 
 int pipeline_run(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st);      // pipeline.hip
-int capi_host_sharded(size_t n, const std::function<int(size_t, size_t, hipStream_t, int, int)> &f, int max_shards);   // capi.hip
-int capi_host_shards(size_t n);
 int beta_prior_var(const DsqBetaPriorArgs *a, double *out);                        // beta_prior.hip
 
 // DSQ_TIMING=1: wall-clock marks of one dsq_deseq call on stderr (where does a PCIe-inclusive call spend its time)
 static bool timing_on() { static int on = getenv("DSQ_TIMING") ? atoi(getenv("DSQ_TIMING")) : 0; return on != 0; }
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-#define HD_HIP(expr)                                                                                     \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess)                                                                            \
-            return capi_fail(e_ == hipErrorOutOfMemory ? DSQ_ERR_NOMEM : DSQ_ERR_DEVICE, "%s: %s", #expr, \
-                             hipGetErrorString(e_));                                                     \
-    } while (0)
 
 namespace {
 
@@ -236,9 +226,9 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
     if ((rc = capi_ws_get(HD_STAT, (DSQ_ST_COUNT + 4) * 4 + DSQ_SC_COUNT * 8 + 64, &v))) return rc;
     double *scalars = (double *)v;
     int32_t *status = (int32_t *)(scalars + DSQ_SC_COUNT), *bad = status + DSQ_ST_COUNT, *neg = bad + 1, *refit_total = bad + 2;
-    HD_HIP(hipMemsetAsync(v, 0, (DSQ_ST_COUNT + 4) * 4 + DSQ_SC_COUNT * 8, st));
-    if (a->y_type == DSQ_Y_INT32) HD_HIP(launch_transpose_r_to_gm_i32((const int32_t *)y_r, y, (int)cnt, (int)m, ld, st));
-    else HD_HIP(launch_counts_f64_to_gm_i32((const double *)y_r, y, (int)cnt, (int)m, ld, bad, st));
+    DSQ_HIP(hipMemsetAsync(v, 0, (DSQ_ST_COUNT + 4) * 4 + DSQ_SC_COUNT * 8, st));
+    if (a->y_type == DSQ_Y_INT32) DSQ_HIP(launch_transpose_r_to_gm_i32((const int32_t *)y_r, y, (int)cnt, (int)m, ld, st));
+    else DSQ_HIP(launch_counts_f64_to_gm_i32((const double *)y_r, y, (int)cnt, (int)m, ld, bad, st));
     // ---- normalization-factor matrix / observation weights: rows up, gene-major on the device
     const double *nf_gm = nullptr, *w_raw = nullptr;
     double *w_norm = nullptr, *w_floor = nullptr;
@@ -247,7 +237,7 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
         if ((rc = capi_ws_get(HD_NFR, cnt * m * 8, &r_))) return rc;
         if ((rc = stage_h2d(r_, a->normalizationFactors, 8, n, lo, cnt, m, st))) return rc;
         if ((rc = capi_ws_get(HD_NF, cnt * (size_t)ld * 8, &g_))) return rc;
-        HD_HIP(launch_transpose_r_to_gm_f64((const double *)r_, (double *)g_, (int)cnt, (int)m, ld, st));
+        DSQ_HIP(launch_transpose_r_to_gm_f64((const double *)r_, (double *)g_, (int)cnt, (int)m, ld, st));
         nf_gm = (const double *)g_;
     }
     if (a->weights) {
@@ -255,7 +245,7 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
         if ((rc = capi_ws_get(HD_NFR, cnt * m * 8, &r_))) return rc;      // (the staging slot is free again: same stream)
         if ((rc = stage_h2d(r_, a->weights, 8, n, lo, cnt, m, st))) return rc;
         if ((rc = capi_ws_get(HD_WRAW, cnt * (size_t)ld * 8, &g_))) return rc;
-        HD_HIP(launch_transpose_r_to_gm_f64((const double *)r_, (double *)g_, (int)cnt, (int)m, ld, st));
+        DSQ_HIP(launch_transpose_r_to_gm_f64((const double *)r_, (double *)g_, (int)cnt, (int)m, ld, st));
         w_raw = (const double *)g_;
         if ((rc = capi_ws_get(HD_WNORM, cnt * (size_t)ld * 8, &g_))) return rc;
         w_norm = (double *)g_;
@@ -282,7 +272,7 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
             memcpy(hb.data() + off_ar, F.a_red.data(), m * pr * 8); memcpy(hb.data() + off_rr, a->r_reduced, pr * pr * 8);
         }
         if (pxp) memcpy(hb.data() + off_xp, a->x_prior, m * pxp * 8);
-        HD_HIP(hipMemcpyAsync(dd, hb.data(), dtot * 8, hipMemcpyHostToDevice, st));      // (pageable: staged at once)
+        DSQ_HIP(hipMemcpyAsync(dd, hb.data(), dtot * 8, hipMemcpyHostToDevice, st));      // (pageable: staged at once)
     }
     // ---- outputs
     if ((rc = capi_ws_get(HD_VEC, V_COUNT * cnt * 8, &v))) return rc;
@@ -344,7 +334,7 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
     od.optim_geneest = ivec + I_OPT1 * cnt; od.optim_test = ivec + I_OPT2 * cnt;
     if (a->weights) {
         // getAndCheckWeights (R/core.R:2697-2751): w / rowmax, its 1e-6 floor for the gene-wise search, the weightsFail rows
-        HD_HIP(launch_weights_prep(w_raw, d.x, (int)cnt, (int)m, (int)p, ld, 1e-2, w_norm, w_floor, ivec + I_FORCEZERO * cnt, neg, st));
+        DSQ_HIP(launch_weights_prep(w_raw, d.x, (int)cnt, (int)m, (int)p, ld, 1e-2, w_norm, w_floor, ivec + I_FORCEZERO * cnt, neg, st));
         d.weights_raw = w_raw; d.weights_norm = w_norm; d.weights_floor = w_floor; d.force_zero = ivec + I_FORCEZERO * cnt;
     }
     od.mu_hat = mats[0]; od.mu = mats[1]; od.H = mats[2]; od.cooks = mats[3]; od.replaceCounts = repc;
@@ -355,13 +345,13 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
     // the all-zero flags) to the host, the first range through computes the prior variance over ALL rows (R/core.R:1601-1689,
     // beta_prior.hip) -- DESeqParallel's exchange for this branch, R/parallel.R:34-48
     auto prior_exchange = [&]() -> int {
-        HD_HIP(hipMemcpy2DAsync(X.mle.data() + lo, n * 8, mle, cnt * 8, cnt * 8, p, hipMemcpyDeviceToHost, st));
-        HD_HIP(hipMemcpyAsync(X.bm.data() + lo, od.baseMean, cnt * 8, hipMemcpyDeviceToHost, st));
-        HD_HIP(hipMemcpyAsync(X.dfit.data() + lo, od.dispFit, cnt * 8, hipMemcpyDeviceToHost, st));
-        HD_HIP(hipMemcpyAsync(X.allzero.data() + lo, od.allZero, cnt * 4, hipMemcpyDeviceToHost, st));
+        DSQ_HIP(hipMemcpy2DAsync(X.mle.data() + lo, n * 8, mle, cnt * 8, cnt * 8, p, hipMemcpyDeviceToHost, st));
+        DSQ_HIP(hipMemcpyAsync(X.bm.data() + lo, od.baseMean, cnt * 8, hipMemcpyDeviceToHost, st));
+        DSQ_HIP(hipMemcpyAsync(X.dfit.data() + lo, od.dispFit, cnt * 8, hipMemcpyDeviceToHost, st));
+        DSQ_HIP(hipMemcpyAsync(X.allzero.data() + lo, od.allZero, cnt * 4, hipMemcpyDeviceToHost, st));
         int32_t hst[DSQ_ST_COUNT];
-        HD_HIP(hipMemcpyAsync(hst, status, sizeof hst, hipMemcpyDeviceToHost, st));
-        HD_HIP(hipStreamSynchronize(st));
+        DSQ_HIP(hipMemcpyAsync(hst, status, sizeof hst, hipMemcpyDeviceToHost, st));
+        DSQ_HIP(hipStreamSynchronize(st));
         if (shard == 0 && (hst[DSQ_ST_N_TREND] == 0 || hst[DSQ_ST_TREND_STATUS] != 0 || hst[DSQ_ST_N_ABOVE_MIN] == 0)) X.trend_ok = false;
         if (!X.wait(2)) return capi_fail(DSQ_ERR_DEVICE, "another gene range of this call failed");
         std::lock_guard<std::mutex> lk(X.prior_mu);
@@ -393,17 +383,17 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
         // the caller's trend: this range's values beside the gathered vectors (behind them: all n, for the residuals)
         if ((rc = capi_ws_get(HD_TREND, 3 * n * 8, &v))) return rc;
         double *tv = (double *)v;
-        HD_HIP(hipMemcpyAsync(tv + 2 * n, a->dispFit, n * 8, hipMemcpyHostToDevice, st));
+        DSQ_HIP(hipMemcpyAsync(tv + 2 * n, a->dispFit, n * 8, hipMemcpyHostToDevice, st));
         d.dispFit_in = tv + 2 * n + lo;
         d.trend_fit_in = tv + 2 * n;
     }
     if (a->geneEstOnly) {
         // estimateDispersionsGeneEst alone (the caller fits its own trend next): every other column NA
-        HD_HIP(hipMemsetAsync(vec, 0xFF, V_COUNT * cnt * 8, st));
-        HD_HIP(hipMemsetAsync(mat, 0xFF, 4 * pcol * cnt * 8, st));
-        HD_HIP(hipMemsetAsync(ivec, 0xFF, I_COUNT * cnt * 4, st));
-        HD_HIP(hipMemsetAsync(scalars, 0xFF, DSQ_SC_COUNT * 8, st));
-        HD_HIP(hipMemsetAsync(status, 0, DSQ_ST_COUNT * 4, st));
+        DSQ_HIP(hipMemsetAsync(vec, 0xFF, V_COUNT * cnt * 8, st));
+        DSQ_HIP(hipMemsetAsync(mat, 0xFF, 4 * pcol * cnt * 8, st));
+        DSQ_HIP(hipMemsetAsync(ivec, 0xFF, I_COUNT * cnt * 4, st));
+        DSQ_HIP(hipMemsetAsync(scalars, 0xFF, DSQ_SC_COUNT * 8, st));
+        DSQ_HIP(hipMemsetAsync(status, 0, DSQ_ST_COUNT * 4, st));
         d.phases = DSQ_PH_GENE_EST;
         if ((rc = pipeline_run(&d, &od, st))) return rc;
     } else if (nshards == 1 && a->betaPrior) {
@@ -421,14 +411,14 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
         d.phases = DSQ_PH_GENE_EST;
         if ((rc = pipeline_run(&d, &od, st))) return rc;
         // the trend's input vectors of all ranges, through host memory (R/parallel.R:27-28)
-        HD_HIP(hipMemcpyAsync(X.bm.data() + lo, od.baseMean, cnt * 8, hipMemcpyDeviceToHost, st));
-        HD_HIP(hipMemcpyAsync(X.dge.data() + lo, od.dispGeneEst, cnt * 8, hipMemcpyDeviceToHost, st));
-        HD_HIP(hipStreamSynchronize(st));
+        DSQ_HIP(hipMemcpyAsync(X.bm.data() + lo, od.baseMean, cnt * 8, hipMemcpyDeviceToHost, st));
+        DSQ_HIP(hipMemcpyAsync(X.dge.data() + lo, od.dispGeneEst, cnt * 8, hipMemcpyDeviceToHost, st));
+        DSQ_HIP(hipStreamSynchronize(st));
         if (!X.wait(0)) return capi_fail(DSQ_ERR_DEVICE, "another gene range of this call failed");
         if ((rc = capi_ws_get(HD_TREND, 3 * n * 8, &v))) return rc;
         double *tv = (double *)v;
-        HD_HIP(hipMemcpyAsync(tv, X.bm.data(), n * 8, hipMemcpyHostToDevice, st));
-        HD_HIP(hipMemcpyAsync(tv + n, X.dge.data(), n * 8, hipMemcpyHostToDevice, st));
+        DSQ_HIP(hipMemcpyAsync(tv, X.bm.data(), n * 8, hipMemcpyHostToDevice, st));
+        DSQ_HIP(hipMemcpyAsync(tv + n, X.dge.data(), n * 8, hipMemcpyHostToDevice, st));
         d.trend_mean = tv; d.trend_disp = tv + n;
         d.defer_finish = 1;
         if (a->betaPrior) {
@@ -447,13 +437,13 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
             // refitWithoutOutliers' closing steps ask whether ANY row of the whole object was refitted (R/core.R:2496):
             // the ranges add up their counts, then each finishes its own rows
             int32_t mine = 0;
-            HD_HIP(hipMemcpyAsync(&mine, status + DSQ_ST_N_REFIT, 4, hipMemcpyDeviceToHost, st));
-            HD_HIP(hipStreamSynchronize(st));
+            DSQ_HIP(hipMemcpyAsync(&mine, status + DSQ_ST_N_REFIT, 4, hipMemcpyDeviceToHost, st));
+            DSQ_HIP(hipStreamSynchronize(st));
             if (!X.wait(1, mine)) return capi_fail(DSQ_ERR_DEVICE, "another gene range of this call failed");
             const int32_t total = (int32_t)(X.n_refit > 0x7fffffffL ? 0x7fffffffL : X.n_refit);
             static thread_local int32_t total_h;
             total_h = total;
-            HD_HIP(hipMemcpyAsync(refit_total, &total_h, 4, hipMemcpyHostToDevice, st));  // (pageable: staged at once)
+            DSQ_HIP(hipMemcpyAsync(refit_total, &total_h, 4, hipMemcpyHostToDevice, st));  // (pageable: staged at once)
             d.n_refit_global = refit_total;
             d.phases = DSQ_PH_FINISH;
             if ((rc = pipeline_run(&d, &od, st))) return rc;
@@ -468,14 +458,14 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
     hi.resize(I_COUNT * cnt);
     double *hvec = hv.data(), *hmat = hvec + V_COUNT * cnt, *hsc = hmat + 4 * pcol * cnt;
     int32_t *hst = (int32_t *)(hsc + DSQ_SC_COUNT);
-    HD_HIP(hipMemcpyAsync(hsc, scalars, DSQ_SC_COUNT * 8 + (DSQ_ST_COUNT + 4) * 4, hipMemcpyDeviceToHost, st));
+    DSQ_HIP(hipMemcpyAsync(hsc, scalars, DSQ_SC_COUNT * 8 + (DSQ_ST_COUNT + 4) * 4, hipMemcpyDeviceToHost, st));
     // (the MLE coefficients as the chain leaves them: the refit has rewritten the rows it refitted, R/core.R:2533-2534)
     if (a->betaPrior && o->mle_beta)
-        HD_HIP(hipMemcpy2DAsync(o->mle_beta + lo, n * 8, mle, cnt * 8, cnt * 8, p, hipMemcpyDeviceToHost, st));
+        DSQ_HIP(hipMemcpy2DAsync(o->mle_beta + lo, n * 8, mle, cnt * 8, cnt * 8, p, hipMemcpyDeviceToHost, st));
     if ((rc = stage_d2h(hvec, vec, 1, V_COUNT * cnt * 8, 0, V_COUNT * cnt * 8, 1, st))) return rc;
     if ((rc = stage_d2h(hmat, mat, 1, 4 * pcol * cnt * 8, 0, 4 * pcol * cnt * 8, 1, st))) return rc;
     if ((rc = stage_d2h(hi.data(), ivec, 1, I_COUNT * cnt * 4, 0, I_COUNT * cnt * 4, 1, st))) return rc;
-    HD_HIP(hipStreamSynchronize(st));
+    DSQ_HIP(hipStreamSynchronize(st));
     if (hst[DSQ_ST_COUNT] != 0) return capi_fail(DSQ_ERR_VALUE, "count matrix holds negative, non-finite or non-integer values");
     if (hst[DSQ_ST_COUNT + 1] != 0) return capi_fail(DSQ_ERR_VALUE, "all(weights >= 0) is not TRUE");
     memcpy(X.status.data() + (size_t)shard * DSQ_ST_COUNT, hst, DSQ_ST_COUNT * 4);
@@ -506,7 +496,7 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
     for (int k = 0; k < 3; k++) {
         if (!want[k] || a->geneEstOnly) continue;        // (geneEstOnly: no test has run, nothing to bring down)
         if ((rc = capi_ws_get(HD_OUTR, cnt * m * 8, &v))) return rc;
-        HD_HIP(launch_transpose_gm_to_r_f64(mats[k + 1], (double *)v, (int)cnt, (int)m, ld, st));
+        DSQ_HIP(launch_transpose_gm_to_r_f64(mats[k + 1], (double *)v, (int)cnt, (int)m, ld, st));
         if ((rc = stage_d2h(want[k], v, 8, n, lo, cnt, m, st))) return rc;
         t_assay[k] = now_ms();
     }
@@ -516,7 +506,7 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
                 t_assay[2] ? t_assay[2] - t_assay[1] : 0.0);
     if (o->replaceCounts) {
         if ((rc = capi_ws_get(HD_OUTR, cnt * m * 8, &v))) return rc;
-        HD_HIP(launch_transpose_gm_to_r_i32(repc, (int32_t *)v, (int)cnt, (int)m, ld, st));
+        DSQ_HIP(launch_transpose_gm_to_r_i32(repc, (int32_t *)v, (int)cnt, (int)m, ld, st));
         if ((rc = stage_d2h(o->replaceCounts, v, 4, n, lo, cnt, m, st))) return rc;
     }
     return DSQ_OK;
@@ -528,7 +518,7 @@ static int deseq_range(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o, const Fact
 using namespace dsq;
 
 extern "C" int dsq_deseq(const DsqDeseqHostArgs *a, DsqDeseqHostOut *o) {
-    std::lock_guard<std::mutex> lk(capi_mutex());
+    std::lock_guard<std::mutex> lk(g_mu);
     capi_latch_stream(nullptr);
     int rc = check_args(a, o);
     if (rc) return rc;

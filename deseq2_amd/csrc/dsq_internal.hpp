@@ -286,6 +286,7 @@ hipError_t launch_transpose_gm_to_r_f64(const double *src, double *dst, int n, i
 hipError_t launch_transpose_gm_to_r_i32(const int32_t *src, int32_t *dst, int n, int m, long ld, hipStream_t st);
 hipError_t launch_test_math(int op, const double *a, const double *b, const double *c, double *out, long n, hipStream_t st);
 
+constexpr int kMaxDevices = 64;      // device indices the per-device tables take (device_cu_count, stage.hip)
 int device_cu_count();
 // launch-geometry caches are per host thread (the multi-device host entry points drive one device per worker thread)
 // and are dropped when that thread moves to another device: the MaxDynamicSharedMemorySize attribute and the occupancy
@@ -298,15 +299,30 @@ int device_cu_count();
         if (dev_now_ != cache_dev_) { memset(a, 0, sizeof a); memset(b, 0, sizeof b); cache_dev_ = dev_now_; } \
     } while (0)
 
-// ---- shared by capi.hip and pipeline.hip (the fused DESeq() chain) ------------------------------------------
-int capi_fail(int code, const char *fmt, ...);
+// ---- host side: shared by the C ABI files (ctx.hip, capi.hip, capi_host.hip) and the chain (pipeline.hip, deseq_host.hip) ----
+int capi_fail(int code, const char *fmt, ...);                   // sets this thread's dsq_last_error() text, returns code
+extern thread_local char g_err[512];                             // that text
+#define DSQ_HIP(expr)                                                                            \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return capi_fail(e_ == hipErrorOutOfMemory ? DSQ_ERR_NOMEM : DSQ_ERR_DEVICE, "%s: %s", #expr, \
+                             hipGetErrorString(e_));                                             \
+    } while (0)
+int env_int(const char *name, int dflt);
+// ctx.hip: everything that belongs to "the stream this call runs on" -- the workspace slots (table cache included), the
+// pinned upload ring with its events, the side stream -- sits in one StreamCtx per (device, stream).  An entry point
+// (WsScope / capi_latch_stream, under the call lock) and a worker thread of a host call (at the start of every job)
+// resolve the context ONCE and latch a pointer to it for their thread; the functions below work on the latched
+// context without a lock: a context is only ever used by the thread that latched it.  dsq_release_workspace() destroys
+// the contexts, so a latch is never kept across calls.
+extern std::mutex g_mu;                                          // the library's call lock
+void capi_latch_stream(hipStream_t s);
+int capi_ws_get(int slot, size_t bytes, void **out);             // grow-only workspace slot of the latched context
 int capi_upload_table(int slot, const void *src, size_t bytes, hipStream_t st, void **dev_out);   // small host table -> slot (pinned ring, skipped when unchanged)
-int capi_ws_get(int slot, size_t bytes, void **out);             // grow-only workspace of the current (device, stream)
 int capi_check_device();
 int capi_upload_cells(const int32_t *labels, int m, int slot, hipStream_t st, const int32_t **perm_dev,
                       const int32_t **start_dev);
-std::mutex &capi_mutex();                                        // the library's call lock
-void capi_latch_stream(hipStream_t s);                           // workspace key of the current call (under the lock)
 // the rolled kernel of the wide designs without design cells (fit_beta_wide.hip): any kp.p in 11 .. 64
 hipError_t launch_fit_beta_rolled(const BetaKernelParams &kp, hipStream_t st);
 void fit_beta_rolled_scratch_doubles(int n, int m, int p, int useW, size_t *slab, size_t *cscr);
@@ -318,9 +334,12 @@ hipError_t dispatch_optim_rows(int p, const OptimKernelParams &kp, hipStream_t s
 void capi_prof_begin(const char *name, int n, hipStream_t st);   // no-ops unless dsq_profile_enable(1)
 void capi_prof_end(hipStream_t st);
 bool capi_prof_on();
-// a second stream (with two events) next to `main` on the current device: the chain runs work that nothing downstream
-// waits for beside its serial tail (pipeline.hip); created once per (device, main stream), under the call lock
-int capi_side_stream(hipStream_t main, hipStream_t *side, hipEvent_t *fork_ev, hipEvent_t *join_ev);
+// a second stream (with two events) next to the latched context's: the chain runs work that nothing downstream waits for
+// beside its serial tail (pipeline.hip); created on first use
+int capi_side_stream(hipStream_t *side, hipEvent_t *fork_ev, hipEvent_t *join_ev);
+// the gene ranges of a host-pointer call (capi_host.hip); the caller holds the call lock
+int capi_host_sharded(size_t n, const std::function<int(size_t, size_t, hipStream_t, int, int)> &f, int max_shards);
+int capi_host_shards(size_t n);
 // stage.hip: pageable host memory <-> device through pinned chunks packed by a small thread pool; rows [lo, lo + cnt) of
 // a column-major n_total x cols host matrix <-> a contiguous column-major cnt x cols device matrix.  stage_d2h returns
 // when the host rows are complete.
@@ -331,6 +350,9 @@ int stage_d2h(void *host, const void *dev, size_t e, size_t n_total, size_t lo, 
 void stage_prefault(void *host, size_t bytes);
 void stage_prefault_finish();
 struct PrefaultScope { ~PrefaultScope() { stage_prefault_finish(); } };
+// an entry point's scope: latches the context of its stream (under g_mu); on the way out it waits for the first-touch
+// threads of stage.hip -- no entry point returns while they are at work
+struct WsScope { explicit WsScope(hipStream_t s) { capi_latch_stream(s); } ~WsScope() { stage_prefault_finish(); } };
 // (three slots between the call slots of capi.hip and the chain's: the padded reduced / prior design, the padded design, the
 //  prior-variance selection workspace)
 enum { DSQ_WS_PIPE_PADXR = 37, DSQ_WS_PIPE_PADX = 38, DSQ_WS_PIPE_SEL = 39 };

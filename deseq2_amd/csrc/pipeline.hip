@@ -913,14 +913,6 @@ __global__ void __launch_bounds__(256) chain_init_kernel(InitParams q) {
 }
 
 // ---- orchestration -----------------------------------------------------------------------------------------------
-#define PIPE_HIP(expr)                                                                                   \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess)                                                                            \
-            return capi_fail(e_ == hipErrorOutOfMemory ? DSQ_ERR_NOMEM : DSQ_ERR_DEVICE, "%s: %s", #expr, \
-                             hipGetErrorString(e_));                                                     \
-    } while (0)
-
 static inline int kern_width(int p) { return p > DSQ_P_REG ? dsq_wide_width(p) : p; }
 
 struct Pipe {
@@ -1068,7 +1060,7 @@ static int launch_fit_beta(Pipe &P, const Rows &rw, const int32_t *y, const doub
     char nm[32];
     snprintf(nm, sizeof nm, "%s%s", name, P.tag);
     capi_prof_begin(nm, P.n, P.st);
-    PIPE_HIP(dispatch_fit_beta(kp.p, kp, P.st, &ok));
+    DSQ_HIP(dispatch_fit_beta(kp.p, kp, P.st, &ok));
     capi_prof_end(P.st);
     if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "dsq_deseq_dev: no register kernel for p=%d", P.p);
     return DSQ_OK;
@@ -1103,7 +1095,7 @@ static int launch_fit_disp(Pipe &P, const Rows &rw, const int32_t *y, const doub
     char nm[32];
     snprintf(nm, sizeof nm, "%s%s", name, P.tag);
     capi_prof_begin(nm, P.n, P.st);
-    PIPE_HIP(dispatch_fit_disp(P.pk, kp, P.st, grid, &ok));
+    DSQ_HIP(dispatch_fit_disp(P.pk, kp, P.st, grid, &ok));
     capi_prof_end(P.st);
     if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "dsq_deseq_dev: no register kernel for p=%d", P.p);
     return DSQ_OK;
@@ -1122,7 +1114,7 @@ static int launch_prefit_rows(Pipe &P, const Rows &rw, const int32_t *y) {
     kp.rows = rw.rows; kp.n_dev = rw.n_dev;
     bool ok = false;
     capi_prof_begin(rw.rows ? "prefit_moments:refit" : "prefit_moments", P.n, P.st);
-    PIPE_HIP(launch_prefit(kp, P.st, &ok));
+    DSQ_HIP(launch_prefit(kp, P.st, &ok));
     capi_prof_end(P.st);
     if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "dsq_deseq_dev: p=%d", P.p);
     return DSQ_OK;
@@ -1164,14 +1156,14 @@ static int launch_optim(Pipe &P, int cnt_optim, const int32_t *y, const double *
     char nm[32];
     snprintf(nm, sizeof nm, "optim_rows%s", P.tag);
     capi_prof_begin(nm, P.n, P.st);
-    PIPE_HIP(dispatch_optim_rows(kp.p, kp, P.st, &ok));
+    DSQ_HIP(dispatch_optim_rows(kp.p, kp, P.st, &ok));
     capi_prof_end(P.st);
     if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "dsq_deseq_dev: no optim kernel for p=%d", P.p);
     if (via_work) {
         const Rows orw = {P.rows_opt, P.counters + cnt_optim, P.n};
         hipLaunchKernelGGL(copy_rows_cols_kernel, dim3(16), dim3(256), 0, P.st, orw, P.n, ds.p_true, (const double *)P.opt_beta,
                            (const double *)P.opt_se, beta, betaSE);
-        PIPE_HIP(hipGetLastError());
+        DSQ_HIP(hipGetLastError());
     }
     return DSQ_OK;
 }
@@ -1202,7 +1194,7 @@ static int gene_est(Pipe &P, const Rows &rw, const int32_t *y, double *mu_hat, i
         kp.rows = rw.rows; kp.n_dev = rw.n_dev;
         bool ok = false;
         capi_prof_begin("linear_mu", P.n, P.st);
-        PIPE_HIP(launch_linear_mu(kp, P.ge_floor, mu_hat, P.st, &ok));     // minmu of estimateDispersionsGeneEst (:763)
+        DSQ_HIP(launch_linear_mu(kp, P.ge_floor, mu_hat, P.st, &ok));     // minmu of estimateDispersionsGeneEst (:763)
         capi_prof_end(P.st);
         if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "dsq_deseq_dev: p=%d", P.p);
     } else {
@@ -1230,7 +1222,7 @@ static int gene_est(Pipe &P, const Rows &rw, const int32_t *y, double *mu_hat, i
     rc = launch_fit_disp(P, gr, y, mu_hat, P.la0, P.la0, false, a->weights_floor, a->useCR != 0, true, "fit_disp_grid");
     if (rc) return rc;
     hipLaunchKernelGGL(gene_est_final_kernel, ew_grid(P.n), dim3(256), 0, P.st, q);
-    PIPE_HIP(hipGetLastError());
+    DSQ_HIP(hipGetLastError());
     return DSQ_OK;
 }
 
@@ -1249,7 +1241,7 @@ static int map_est(Pipe &P, const Rows &rw, const int32_t *y, const double *mu_h
     rc = launch_fit_disp(P, gr, y, mu_hat, P.la_init, P.log_dfit, true, a->weights_norm, true, true, "fit_disp_grid");   // useCR = TRUE, :1061
     if (rc) return rc;
     hipLaunchKernelGGL(map_final_kernel, ew_grid(P.n), dim3(256), 0, P.st, q);
-    PIPE_HIP(hipGetLastError());
+    DSQ_HIP(hipGetLastError());
     return DSQ_OK;
 }
 
@@ -1278,7 +1270,7 @@ static int mle_fit(Pipe &P, const Rows &rw, const int32_t *y, double *mu_out, do
     hipLaunchKernelGGL(beta_post_kernel, ew_grid(P.n), dim3(256), 0, P.st, b);
     rc = launch_optim(P, cnt3, y, o->dispersion, a->weights_norm, P.t_minmu, 0.0, o->mle_beta, P.red_se, P.opt_ll, mu_out);
     if (rc) return rc;
-    PIPE_HIP(hipGetLastError());
+    DSQ_HIP(hipGetLastError());
     return DSQ_OK;
 }
 
@@ -1296,12 +1288,12 @@ static int prior_fit(Pipe &P, const Rows &rw, const int32_t *y, int cnt_optim) {
         pk.baseMean = P.cnum; pk.baseVar = P.cden; pk.roughDisp = P.dev; pk.allZero = P.opt_conv; pk.beta_init = P.opt_ll;
         pk.rows = rw.rows; pk.n_dev = rw.n_dev;
         bool ok = false;
-        PIPE_HIP(launch_prefit(pk, P.st, &ok));
+        DSQ_HIP(launch_prefit(pk, P.st, &ok));
         if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "dsq_deseq_dev: prefit p=1");
         hipLaunchKernelGGL(prior_start_kernel, ew_grid(P.n), dim3(256), 0, P.st, rw, P.n, a->p_prior, a->prior_intercept,
                            (const double *)P.cnum, P.red_binit);
         if (P.pri_pk > a->p_prior)        // (start values 0 on the padding of a wide expanded design)
-            PIPE_HIP(hipMemsetAsync(P.red_binit + (size_t)P.n * a->p_prior, 0, (size_t)P.n * (P.pri_pk - a->p_prior) * sizeof(double), P.st));
+            DSQ_HIP(hipMemsetAsync(P.red_binit + (size_t)P.n * a->p_prior, 0, (size_t)P.n * (P.pri_pk - a->p_prior) * sizeof(double), P.st));
     }
     rc = launch_fit_beta(P, rw, y, o->dispersion, a->weights_norm, P.red_mu, 0.0, nullptr, P.t_tol, P.t_maxit, P.t_useQR,
                          P.t_minmu, "fit_beta_prior", DES_PRIOR);
@@ -1312,7 +1304,7 @@ static int prior_fit(Pipe &P, const Rows &rw, const int32_t *y, int cnt_optim) {
     lk.weights = a->useWeights ? a->weights_norm : nullptr; lk.useWeights = a->useWeights ? 1 : 0;
     lk.loglike = o->logLike; lk.rows = rw.rows; lk.n_dev = rw.n_dev; lk.kconst = P.kconst;
     capi_prof_begin(P.tag[0] ? "nbinom_loglike:refit" : "nbinom_loglike", P.n, P.st);
-    PIPE_HIP(launch_loglike(lk, P.st));
+    DSQ_HIP(launch_loglike(lk, P.st));
     capi_prof_end(P.st);
     const DesignSel ds = design_of(P, DES_PRIOR);
     RuleParams b = rule_params(P, rw);
@@ -1322,7 +1314,7 @@ static int prior_fit(Pipe &P, const Rows &rw, const int32_t *y, int cnt_optim) {
     b.optim_flag = o->optim_test; b.optim_count = P.counters + cnt_optim;
     hipLaunchKernelGGL(beta_post_kernel, ew_grid(P.n), dim3(256), 0, P.st, b);
     if (P.pri_pk > ds.p_true)             // (columns p_prior .. of the optim start values may hold another fit's: zero on the padding)
-        PIPE_HIP(hipMemsetAsync(P.opt_start + (size_t)P.n * ds.p_true, 0, (size_t)P.n * (P.pri_pk - ds.p_true) * sizeof(double), P.st));
+        DSQ_HIP(hipMemsetAsync(P.opt_start + (size_t)P.n * ds.p_true, 0, (size_t)P.n * (P.pri_pk - ds.p_true) * sizeof(double), P.st));
     rc = launch_optim(P, cnt_optim, y, o->dispersion, a->weights_norm, P.t_minmu, 0.0, o->beta, o->betaSE, o->logLike, P.red_mu,
                       DES_PRIOR);
     if (rc) return rc;
@@ -1331,7 +1323,7 @@ static int prior_fit(Pipe &P, const Rows &rw, const int32_t *y, int cnt_optim) {
     ob.p = ds.p_true;
     ob.beta = o->beta; ob.betaSE = o->betaSE; ob.stat = o->stat; ob.pvalue = o->pvalue; ob.wald = 1; ob.betaConv = o->betaConv;
     hipLaunchKernelGGL(optim_post_kernel, dim3(16), dim3(256), 0, P.st, ob);
-    PIPE_HIP(hipGetLastError());
+    DSQ_HIP(hipGetLastError());
     return DSQ_OK;
 }
 
@@ -1342,8 +1334,8 @@ hipError_t launch_xim_flagged(const double *nf, int n, int m, long ld, const int
 static int join_side(Pipe &P) {
     if (!P.forked) return DSQ_OK;
     P.forked = false;
-    PIPE_HIP(hipEventRecord(P.ev_join, P.side));
-    PIPE_HIP(hipStreamWaitEvent(P.st, P.ev_join, 0));
+    DSQ_HIP(hipEventRecord(P.ev_join, P.side));
+    DSQ_HIP(hipStreamWaitEvent(P.st, P.ev_join, 0));
     return DSQ_OK;
 }
 
@@ -1352,12 +1344,12 @@ static int launch_pending_ll(Pipe &P, bool beside) {
     if (!P.ll_pending) return DSQ_OK;
     P.ll_pending = false;
     if (beside) {
-        PIPE_HIP(hipEventRecord(P.ev_fork, P.st));
-        PIPE_HIP(hipStreamWaitEvent(P.side, P.ev_fork, 0));
-        PIPE_HIP(launch_loglike_side(P.ll, P.side));
+        DSQ_HIP(hipEventRecord(P.ev_fork, P.st));
+        DSQ_HIP(hipStreamWaitEvent(P.side, P.ev_fork, 0));
+        DSQ_HIP(launch_loglike_side(P.ll, P.side));
         P.forked = true;
     } else {
-        PIPE_HIP(launch_loglike(P.ll, P.st));
+        DSQ_HIP(launch_loglike(P.ll, P.st));
     }
     return DSQ_OK;
 }
@@ -1394,7 +1386,7 @@ static int test_fit(Pipe &P, const Rows &rw, const int32_t *y, double *mu_out, d
     const bool overlap = P.overlap && !P.tag[0];
     if (!overlap) {
         capi_prof_begin(P.tag[0] ? "nbinom_loglike:refit" : "nbinom_loglike", P.n, P.st);
-        PIPE_HIP(launch_loglike(lk, P.st));
+        DSQ_HIP(launch_loglike(lk, P.st));
         capi_prof_end(P.st);
     }
     hipLaunchKernelGGL(beta_post_kernel, ew_grid(P.n), dim3(256), 0, P.st, b);
@@ -1427,7 +1419,7 @@ static int test_fit(Pipe &P, const Rows &rw, const int32_t *y, double *mu_out, d
         pk.rows = rw.rows; pk.n_dev = rw.n_dev;
         bool ok = false;
         capi_prof_begin(P.tag[0] ? "prefit_reduced:refit" : "prefit_reduced", P.n, P.st);
-        PIPE_HIP(launch_prefit(pk, P.st, &ok));
+        DSQ_HIP(launch_prefit(pk, P.st, &ok));
         capi_prof_end(P.st);
         if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "dsq_deseq_dev: reduced design with p=%d", a->p_red);
         rc = launch_fit_beta(P, rw, y, o->dispersion, a->weights_norm, P.red_mu, 0.0, nullptr, P.t_tol, P.t_maxit, P.t_useQR,
@@ -1435,7 +1427,7 @@ static int test_fit(Pipe &P, const Rows &rw, const int32_t *y, double *mu_out, d
         if (rc) return rc;
         lk.mu = P.red_mu; lk.loglike = o->logLikeReduced;
         capi_prof_begin(P.tag[0] ? "nbinom_loglike_red:refit" : "nbinom_loglike_red", P.n, P.st);
-        PIPE_HIP(launch_loglike(lk, P.st));
+        DSQ_HIP(launch_loglike(lk, P.st));
         capi_prof_end(P.st);
         const int cnt3 = P.tag[0] ? CNT_OPT3R : CNT_OPT3;
         RuleParams rb = rule_params(P, rw);
@@ -1443,7 +1435,7 @@ static int test_fit(Pipe &P, const Rows &rw, const int32_t *y, double *mu_out, d
         rb.optim_flag = P.grid_flag; rb.optim_count = P.counters + cnt3;      // (the grid flags are free between the searches)
         hipLaunchKernelGGL(beta_post_kernel, ew_grid(P.n), dim3(256), 0, P.st, rb);
         if (P.red_pk > a->p_red)         // (columns p_red .. of the start values may hold the full fit's: zero on the padding)
-            PIPE_HIP(hipMemsetAsync(P.opt_start + (size_t)P.n * a->p_red, 0, (size_t)P.n * (P.red_pk - a->p_red) * sizeof(double), P.st));
+            DSQ_HIP(hipMemsetAsync(P.opt_start + (size_t)P.n * a->p_red, 0, (size_t)P.n * (P.red_pk - a->p_red) * sizeof(double), P.st));
         rc = launch_optim(P, cnt3, y, o->dispersion, a->weights_norm, P.t_minmu, 0.0, P.red_beta, P.red_se, o->logLikeReduced,
                           P.red_mu, DES_REDUCED);
         if (rc) return rc;
@@ -1456,10 +1448,10 @@ static int test_fit(Pipe &P, const Rows &rw, const int32_t *y, double *mu_out, d
         ik.loglike = o->logLikeReduced; ik.rows = rw.rows; ik.n_dev = rw.n_dev;
         ik.kconst = P.kconst;            // (the full model's fit of the same rows: same counts, dispersions, weights)
         capi_prof_begin("intercept_fit", P.n, P.st);
-        PIPE_HIP(launch_intercept_fit(ik, P.st));
+        DSQ_HIP(launch_intercept_fit(ik, P.st));
         capi_prof_end(P.st);
     }
-    PIPE_HIP(hipGetLastError());
+    DSQ_HIP(hipGetLastError());
     return DSQ_OK;
 }
 
@@ -1519,7 +1511,7 @@ static int outlier_finish(Pipe &P, const Rows &nz, const Rows &rep, const Outlie
     hipLaunchKernelGGL(masked_max_kernel, dim3(grid), dim3(256), 0, P.st, nz, m, P.ld, (const double *)o->cooks,
                        (const int32_t *)M.duse3, (const int32_t *)M.drepl, M.all_rep, (m > p && M.any3) ? 1 : 0, n_refit,
                        o->maxCooks);
-    PIPE_HIP(hipGetLastError());
+    DSQ_HIP(hipGetLastError());
     return DSQ_OK;
 }
 
@@ -1615,7 +1607,7 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
         // time every launch on one stream; DSQ_OVERLAP=0 switches it off
         static const bool env_on = !(getenv("DSQ_OVERLAP") && atoi(getenv("DSQ_OVERLAP")) == 0);
         P.overlap = env_on && !capi_prof_on() && !a->betaPrior && (a->phases & DSQ_PH_MAP_TEST) && (a->phases & DSQ_PH_OUTLIERS);
-        if (P.overlap && capi_side_stream(st, &P.side, &P.ev_fork, &P.ev_join) != DSQ_OK) P.overlap = false;
+        if (P.overlap && capi_side_stream(&P.side, &P.ev_fork, &P.ev_join) != DSQ_OK) P.overlap = false;
     }
     const int n = P.n = a->n, m = P.m = a->m, p = P.p = a->p;
     P.ld = a->ld;
@@ -1726,7 +1718,7 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
         if (blocks < 1) blocks = 1;
         if (blocks > 2048) blocks = 2048;
         hipLaunchKernelGGL(chain_init_kernel, dim3(blocks), dim3(256), 0, st, ip);
-        PIPE_HIP(hipGetLastError());
+        DSQ_HIP(hipGetLastError());
     }
     P.x_k = a->x; P.padmask = 0;
     if (pk > p) {
@@ -1735,12 +1727,12 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
         void *b;
         rc = capi_ws_get(DSQ_WS_PIPE_PADX, (size_t)m * pk * sizeof(double), &b);
         if (rc) return rc;
-        PIPE_HIP(hipMemsetAsync(b, 0, (size_t)m * pk * sizeof(double), st));
-        PIPE_HIP(hipMemcpyAsync(b, a->x, (size_t)m * p * sizeof(double), hipMemcpyDeviceToDevice, st));
+        DSQ_HIP(hipMemsetAsync(b, 0, (size_t)m * pk * sizeof(double), st));
+        DSQ_HIP(hipMemcpyAsync(b, a->x, (size_t)m * p * sizeof(double), hipMemcpyDeviceToDevice, st));
         P.x_k = (const double *)b;
         P.padmask = dsq_low_bits(pk) & ~dsq_low_bits(p);
-        PIPE_HIP(hipMemsetAsync(P.beta_init + (size_t)n * p, 0, (size_t)n * (pk - p) * sizeof(double), st));
-        PIPE_HIP(hipMemsetAsync(P.opt_start + (size_t)n * p, 0, (size_t)n * (pk - p) * sizeof(double), st));
+        DSQ_HIP(hipMemsetAsync(P.beta_init + (size_t)n * p, 0, (size_t)n * (pk - p) * sizeof(double), st));
+        DSQ_HIP(hipMemsetAsync(P.opt_start + (size_t)n * p, 0, (size_t)n * (pk - p) * sizeof(double), st));
     }
     P.red_x_k = a->x_red; P.red_pk = a->x_red ? a->p_red : 0; P.red_lam = a->x_red ? P.lam_prior : P.lam;
     if (a->x_red && kern_width(a->p_red) > a->p_red) {
@@ -1750,18 +1742,18 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
         void *b;
         rc = capi_ws_get(DSQ_WS_PIPE_PADXR, (size_t)m * pkr * sizeof(double), &b);
         if (rc) return rc;
-        PIPE_HIP(hipMemsetAsync(b, 0, (size_t)m * pkr * sizeof(double), st));
-        PIPE_HIP(hipMemcpyAsync(b, a->x_red, (size_t)m * a->p_red * sizeof(double), hipMemcpyDeviceToDevice, st));
+        DSQ_HIP(hipMemsetAsync(b, 0, (size_t)m * pkr * sizeof(double), st));
+        DSQ_HIP(hipMemcpyAsync(b, a->x_red, (size_t)m * a->p_red * sizeof(double), hipMemcpyDeviceToDevice, st));
         P.red_x_k = (const double *)b; P.red_pk = pkr;
-        PIPE_HIP(hipMemsetAsync(P.red_binit + (size_t)n * a->p_red, 0, (size_t)n * (pkr - a->p_red) * sizeof(double), st));
+        DSQ_HIP(hipMemsetAsync(P.red_binit + (size_t)n * a->p_red, 0, (size_t)n * (pkr - a->p_red) * sizeof(double), st));
     }
     P.pri_x_k = a->x_prior; P.pri_pk = a->betaPrior ? a->p_prior : 0;
     if (a->betaPrior && pkp > a->p_prior) {
         void *b;
         rc = capi_ws_get(DSQ_WS_PIPE_PADXR, (size_t)m * pkp * sizeof(double), &b);      // (never beside a reduced model: Wald only)
         if (rc) return rc;
-        PIPE_HIP(hipMemsetAsync(b, 0, (size_t)m * pkp * sizeof(double), st));
-        PIPE_HIP(hipMemcpyAsync(b, a->x_prior, (size_t)m * a->p_prior * sizeof(double), hipMemcpyDeviceToDevice, st));
+        DSQ_HIP(hipMemsetAsync(b, 0, (size_t)m * pkp * sizeof(double), st));
+        DSQ_HIP(hipMemcpyAsync(b, a->x_prior, (size_t)m * a->p_prior * sizeof(double), hipMemcpyDeviceToDevice, st));
         P.pri_x_k = (const double *)b; P.pri_pk = pkp;
     }
     const Rows nz = {P.rows_nz, P.counters + CNT_NZ, n};
@@ -1790,7 +1782,7 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
             void *b;
             rc = capi_ws_get(DSQ_WS_PIPE_META + 5, ((size_t)m + 8) * sizeof(double), &b);
             if (rc) return rc;
-            PIPE_HIP(launch_xim_rows(a->nf, P.rows_nz, P.counters + CNT_NZ, m, P.ld, (double *)b, P.xim_dev, st));
+            DSQ_HIP(launch_xim_rows(a->nf, P.rows_nz, P.counters + CNT_NZ, m, P.ld, (double *)b, P.xim_dev, st));
         }
         rc = gene_est(P, nz, a->y, o->mu_hat, CNT_GRID1, CNT_OPT1, o->optim_geneest);
         if (rc) return rc;
@@ -1800,7 +1792,7 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
         const double *tm = a->trend_mean ? a->trend_mean : o->baseMean;
         const double *td = a->trend_mean ? a->trend_disp : o->dispGeneEst;
         const int nt = a->trend_mean ? a->n_trend : n;
-        if (!with_gene_est) PIPE_HIP(hipMemsetAsync(P.counters + CNT_TREND, 0, sizeof(int32_t), st));      // (else: the status fill)
+        if (!with_gene_est) DSQ_HIP(hipMemsetAsync(P.counters + CNT_TREND, 0, sizeof(int32_t), st));      // (else: the status fill)
         hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, st, 1, nt, (int32_t *)nullptr, (const int32_t *)nullptr,
                            tm, td, 100.0 * a->minDisp, (int32_t *)nullptr, P.trend_mean_c, P.trend_disp_c,
                            P.counters + CNT_TREND);
@@ -1813,7 +1805,7 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
             hipLaunchKernelGGL(trend_given_kernel, dim3(1), dim3(1), 0, st, o->scalars, o->status);
         } else {
             if (a->fitType != DSQ_FIT_MEAN)
-                PIPE_HIP(launch_trend_fit_dev_zeroed(P.trend_mean_c, P.trend_disp_c, P.counters + CNT_TREND, o->scalars + DSQ_SC_COEF0,
+                DSQ_HIP(launch_trend_fit_dev_zeroed(P.trend_mean_c, P.trend_disp_c, P.counters + CNT_TREND, o->scalars + DSQ_SC_COEF0,
                                                      o->status + DSQ_ST_TREND_STATUS, tws_zeroed, st));
             if (a->fitType != DSQ_FIT_PARAMETRIC)            // R/core.R:894-899 over the same vector, uncompacted
                 hipLaunchKernelGGL(trend_mean_kernel, dim3(1), dim3(1024), 0, st, td, nt, a->minDisp, (int)a->fitType, o->scalars, o->status);
@@ -1830,15 +1822,15 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
                                    (m > p) ? 1 : 0, P.resbuf, o->scalars, o->status, fin, a->dispPriorVar_in, (SelWs *)sws_zeroed);
         }
         capi_prof_end(st);
-        PIPE_HIP(hipGetLastError());
+        DSQ_HIP(hipGetLastError());
     }
     // ================================================================ MAP dispersions + test
     bool counters_zeroed = false;
     if (a->phases & DSQ_PH_MAP_TEST) {
         if (!with_gene_est) {            // (else still zero from the status fill: nothing in between counts into them)
-            PIPE_HIP(hipMemsetAsync(P.counters + CNT_GRID2, 0, sizeof(int32_t), st));
-            PIPE_HIP(hipMemsetAsync(P.counters + CNT_OPT2, 0, sizeof(int32_t), st));
-            PIPE_HIP(hipMemsetAsync(P.counters + CNT_OPT3, 0, sizeof(int32_t), st));
+            DSQ_HIP(hipMemsetAsync(P.counters + CNT_GRID2, 0, sizeof(int32_t), st));
+            DSQ_HIP(hipMemsetAsync(P.counters + CNT_OPT2, 0, sizeof(int32_t), st));
+            DSQ_HIP(hipMemsetAsync(P.counters + CNT_OPT3, 0, sizeof(int32_t), st));
         }
         rc = map_est(P, nz, a->y, o->mu_hat, CNT_GRID2);
         if (rc) return rc;
@@ -1852,7 +1844,7 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
     }
     // ================================================================ betaPrior: the pass with lambda = 1 / betaPriorVar
     if ((a->phases & DSQ_PH_PRIOR) && a->betaPrior) {
-        PIPE_HIP(hipMemsetAsync(P.counters + CNT_OPT2, 0, sizeof(int32_t), st));
+        DSQ_HIP(hipMemsetAsync(P.counters + CNT_OPT2, 0, sizeof(int32_t), st));
         rc = prior_fit(P, nz, a->y, CNT_OPT2);
         if (rc) return rc;
     }
@@ -1868,7 +1860,7 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
         int32_t *dperm = M.dperm, *din3 = M.din3, *drepl = M.drepl, *dstart = M.dstart;
         const int any3 = M.any3, maxcell = M.maxcell;
       if (ph_detect) {
-        if (!counters_zeroed) PIPE_HIP(hipMemsetAsync(P.counters + CNT_REP, 0, (CNT_N - CNT_REP) * sizeof(int32_t), st));      // REP .. OPT3R
+        if (!counters_zeroed) DSQ_HIP(hipMemsetAsync(P.counters + CNT_REP, 0, (CNT_N - CNT_REP) * sizeof(int32_t), st));      // REP .. OPT3R
 
         CooksKernelParams ck;
         memset(&ck, 0, sizeof ck);
@@ -1880,7 +1872,7 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
         ck.rows = nz.rows; ck.n_dev = nz.n_dev;
         bool ok = true;
         capi_prof_begin("cooks_distance", n, st);
-        PIPE_HIP(launch_cooks(ck, st, &ok));
+        DSQ_HIP(launch_cooks(ck, st, &ok));
         capi_prof_end(st);
         if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "m=%d samples: a gene row plus its sort buffer exceeds the 160 KiB LDS", m);
         // (before the replacement: allZero still says which rows had no fit -- a row that only BECOMES all zero keeps its assays)
@@ -1896,7 +1888,7 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
             rk.newCounts = o->replaceCounts; rk.replace = o->replace;
             rk.rows = nz.rows; rk.n_dev = nz.n_dev;
             capi_prof_begin("replace_outliers", n, st);
-            PIPE_HIP(launch_replace(rk, st, &ok));
+            DSQ_HIP(launch_replace(rk, st, &ok));
             capi_prof_end(st);
             if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "m=%d samples: the sort buffer exceeds the 160 KiB LDS", m);
             // rows with a replacement (R/core.R:2488-2490) -> their moments on the new counts (:2491) -> the ones
@@ -1924,7 +1916,7 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
                 void *b;
                 rc = capi_ws_get(DSQ_WS_PIPE_META + 5, ((size_t)m + 8) * sizeof(double), &b);
                 if (rc) return rc;
-                PIPE_HIP(launch_xim_flagged(a->nf, n, m, P.ld, o->replace, o->allZero, (double *)b, P.xim_dev + 1, st));
+                DSQ_HIP(launch_xim_flagged(a->nf, n, m, P.ld, o->replace, o->allZero, (double *)b, P.xim_dev + 1, st));
                 P.xim_cur = P.xim_dev + 1;
             }
             rc = gene_est(P, rf, o->replaceCounts, o->mu_hat, CNT_GRID1R, CNT_OPT1R, o->optim_geneest);
@@ -1969,7 +1961,7 @@ extern "C" int64_t dsq_deseq_workspace_bytes(int32_t n, int32_t m, int32_t p, in
 }
 
 extern "C" int dsq_deseq_dev(const DsqDeseqArgs *args, const DsqDeseqOut *out, void *stream) {
-    std::lock_guard<std::mutex> lk(dsq::capi_mutex());
+    std::lock_guard<std::mutex> lk(dsq::g_mu);
     dsq::capi_latch_stream((hipStream_t)stream);
     return dsq::run(args, out, (hipStream_t)stream);
 }

@@ -188,7 +188,7 @@ struct Stager {
     bool busy[NB] = {false, false, false};
     size_t cap = 0;
 };
-static thread_local Stager g_stagers[64];
+static thread_local Stager g_stagers[kMaxDevices];
 
 static size_t chunk_bytes() {
     // (16 MiB: tools/d2h_probe.hip, three chunks in flight, 8 copy threads -> 47 GB/s into touched pages; 8 MiB: 31)
@@ -202,7 +202,7 @@ static bool staging_on() {
 
 static int stager_get(Stager **out) {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return capi_fail(DSQ_ERR_DEVICE, "hipGetDevice failed");
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return capi_fail(DSQ_ERR_DEVICE, "hipGetDevice failed");
     Stager &s = g_stagers[dev];
     if (s.cap == 0) {
         const size_t c = chunk_bytes();
@@ -244,14 +244,6 @@ static void build_pieces(std::vector<Piece> *out, char *buf, const char *host, s
     }
 }
 
-#define ST_HIP(expr)                                                                                     \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess)                                                                            \
-            return capi_fail(e_ == hipErrorOutOfMemory ? DSQ_ERR_NOMEM : DSQ_ERR_DEVICE, "%s: %s", #expr, \
-                             hipGetErrorString(e_));                                                     \
-    } while (0)
-
 }  // namespace
 
 static std::atomic<bool> g_prefault_live{false};      // (entry points that never announce anything never start the threads)
@@ -272,8 +264,8 @@ int stage_h2d(void *dev, const void *host, size_t e, size_t n_total, size_t lo, 
     const size_t seg = cnt * e, stride = n_total * e, total = seg * cols;
     const char *h = (const char *)host + lo * e;
     if (!staging_on() || total < (1u << 20)) {
-        if (cnt == n_total) ST_HIP(hipMemcpyAsync(dev, host, total, hipMemcpyHostToDevice, st));
-        else ST_HIP(hipMemcpy2DAsync(dev, seg, h, stride, seg, cols, hipMemcpyHostToDevice, st));
+        if (cnt == n_total) DSQ_HIP(hipMemcpyAsync(dev, host, total, hipMemcpyHostToDevice, st));
+        else DSQ_HIP(hipMemcpy2DAsync(dev, seg, h, stride, seg, cols, hipMemcpyHostToDevice, st));
         return DSQ_OK;
     }
     Stager *s;
@@ -285,11 +277,11 @@ int stage_h2d(void *dev, const void *host, size_t e, size_t n_total, size_t lo, 
     for (size_t off = 0; off < total; off += s->cap, k++) {
         const int b = k % Stager::NB;
         const size_t len = (total - off < s->cap) ? total - off : s->cap;
-        if (s->busy[b]) { ST_HIP(hipEventSynchronize(s->ev[b])); s->busy[b] = false; }
+        if (s->busy[b]) { DSQ_HIP(hipEventSynchronize(s->ev[b])); s->busy[b] = false; }
         build_pieces(&pieces, s->buf[b], h, seg_eff, stride, off, off + len, true);
         CopyPool::get().run(pieces);
-        ST_HIP(hipMemcpyAsync((char *)dev + off, s->buf[b], len, hipMemcpyHostToDevice, st));
-        ST_HIP(hipEventRecord(s->ev[b], st));
+        DSQ_HIP(hipMemcpyAsync((char *)dev + off, s->buf[b], len, hipMemcpyHostToDevice, st));
+        DSQ_HIP(hipEventRecord(s->ev[b], st));
         s->busy[b] = true;
     }
     return DSQ_OK;
@@ -302,9 +294,9 @@ int stage_d2h(void *host, const void *dev, size_t e, size_t n_total, size_t lo, 
     const size_t seg = cnt * e, stride = n_total * e, total = seg * cols;
     char *h = (char *)host + lo * e;
     if (!staging_on() || total < (1u << 20)) {
-        if (cnt == n_total) ST_HIP(hipMemcpyAsync(host, dev, total, hipMemcpyDeviceToHost, st));
-        else ST_HIP(hipMemcpy2DAsync(h, stride, dev, seg, seg, cols, hipMemcpyDeviceToHost, st));
-        ST_HIP(hipStreamSynchronize(st));
+        if (cnt == n_total) DSQ_HIP(hipMemcpyAsync(host, dev, total, hipMemcpyDeviceToHost, st));
+        else DSQ_HIP(hipMemcpy2DAsync(h, stride, dev, seg, seg, cols, hipMemcpyDeviceToHost, st));
+        DSQ_HIP(hipStreamSynchronize(st));
         return DSQ_OK;
     }
     Stager *s;
@@ -312,7 +304,7 @@ int stage_d2h(void *host, const void *dev, size_t e, size_t n_total, size_t lo, 
     // (the whole matrix the rows belong to: a no-op when the entry point has announced it)
     stage_prefault((char *)host, (cnt == n_total) ? total : stride * cols);
     for (int b = 0; b < Stager::NB; b++)
-        if (s->busy[b]) { ST_HIP(hipEventSynchronize(s->ev[b])); s->busy[b] = false; }
+        if (s->busy[b]) { DSQ_HIP(hipEventSynchronize(s->ev[b])); s->busy[b] = false; }
     const size_t seg_eff = (cnt == n_total) ? total : seg;
     const size_t nchunk = (total + s->cap - 1) / s->cap;
     auto issue = [&](size_t k) -> hipError_t {
@@ -324,12 +316,12 @@ int stage_d2h(void *host, const void *dev, size_t e, size_t n_total, size_t lo, 
     };
     static thread_local std::vector<Piece> pieces;
     const size_t ahead = Stager::NB - 1;
-    for (size_t k = 0; k < ahead && k < nchunk; k++) ST_HIP(issue(k));
+    for (size_t k = 0; k < ahead && k < nchunk; k++) DSQ_HIP(issue(k));
     for (size_t k = 0; k < nchunk; k++) {
-        if (k + ahead < nchunk) ST_HIP(issue(k + ahead));     // its buffer was scattered in the previous round
+        if (k + ahead < nchunk) DSQ_HIP(issue(k + ahead));     // its buffer was scattered in the previous round
         const int b = (int)(k % Stager::NB);
         const size_t off = k * s->cap, len = (total - off < s->cap) ? total - off : s->cap;
-        ST_HIP(hipEventSynchronize(s->ev[b]));
+        DSQ_HIP(hipEventSynchronize(s->ev[b]));
         build_pieces(&pieces, s->buf[b], h, seg_eff, stride, off, off + len, false);
         CopyPool::get().run(pieces);
     }
