@@ -5,5 +5,9 @@ callers of that boundary."""
 from . import _lib  # noqa: F401
 from .native import fitBeta, fitDisp, fitDispGrid  # noqa: F401
 from .core import estimateSizeFactors, estimateSizeFactorsForMatrix  # noqa: F401
+from .core import (vst, varianceStabilizingTransformation, getVarianceStabilizedData, normTransform,  # noqa: F401
+                   normalized_counts, DESeqTransform)
 
-__all__ = ["fitBeta", "fitDisp", "fitDispGrid", "estimateSizeFactors", "estimateSizeFactorsForMatrix"]
+__all__ = ["fitBeta", "fitDisp", "fitDispGrid", "estimateSizeFactors", "estimateSizeFactorsForMatrix", "vst",
+           "varianceStabilizingTransformation", "getVarianceStabilizedData", "normTransform", "normalized_counts",
+           "DESeqTransform"]

@@ -235,6 +235,21 @@ class DsqSizeFactorOut(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class DsqVstArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("m", C.c_int32), ("layout", C.c_int32), ("ld", C.c_int64), ("y", C.c_void_p),
+        ("y_type", C.c_int32), ("nf", C.c_void_p), ("nf_is_vector", C.c_int32), ("kind", C.c_int32),
+        ("asymptDisp", C.c_double), ("extraPois", C.c_double), ("alpha", C.c_double), ("pc", C.c_double),
+        ("spline", C.c_void_p), ("nknots", C.c_int32), ("eta", C.c_double), ("xi", C.c_double),
+    ]
+
+
+class DsqVstOut(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("rowMean", C.c_void_p), ("rowMax", C.c_void_p), ("bad", C.c_void_p)]
+
+
+DSQ_VST = {"parametric": 0, "mean": 1, "spline": 2, "log2": 3, "normalized": 4}
+DSQ_VST_MAX_KNOTS = 1600
 DSQ_SF = {"ratio": 0, "poscounts": 1}
 DSQ_PH_GENE_EST, DSQ_PH_TREND, DSQ_PH_MAP_TEST, DSQ_PH_OUTLIERS, DSQ_PH_FINISH, DSQ_PH_PRIOR = 1, 2, 4, 8, 16, 32
 DSQ_PH_OUTLIERS_DETECT, DSQ_PH_OUTLIERS_REFIT = 64, 128
@@ -261,6 +276,7 @@ EXPORTED_SYMBOLS = [
     "dsq_deseq", "dsq_beta_prior_var", "dsq_weights_prep_dev", "dsq_xim_dev",
     "dsq_linear_mu", "dsq_linear_mu_dev", "dsq_cooks_distance", "dsq_cooks_distance_dev", "dsq_replace_outliers", "dsq_replace_outliers_dev",
     "dsq_size_factors", "dsq_size_factors_dev", "dsq_size_factors_workspace_bytes",
+    "dsq_vst", "dsq_vst_dev", "dsq_vst_rowstats_dev",
 ]
 
 _lib = None
@@ -327,6 +343,9 @@ def lib():
     L.dsq_size_factors_dev.argtypes = [C.POINTER(DsqSizeFactorArgs), C.POINTER(DsqSizeFactorOut), C.c_void_p]
     L.dsq_size_factors_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
     L.dsq_size_factors_workspace_bytes.restype = C.c_int64
+    L.dsq_vst.argtypes = [C.POINTER(DsqVstArgs), C.POINTER(DsqVstOut)]
+    L.dsq_vst_dev.argtypes = [C.POINTER(DsqVstArgs), C.POINTER(DsqVstOut), C.c_void_p]
+    L.dsq_vst_rowstats_dev.argtypes = [C.POINTER(DsqVstArgs), C.POINTER(DsqVstOut), C.c_void_p]
     L.dsq_deseq_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.dsq_deseq_workspace_bytes.restype = C.c_int64
     L.dsq_profile_get.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double)]

@@ -11,6 +11,9 @@ O(n m) parts run in the engine.
 Size factors: estimateSizeFactors / estimateSizeFactorsForMatrix ("ratio", "poscounts", geoMeans, controlGenes,
 normMatrix) run in the engine too (csrc/size_factors.hip); type = "iterate" is not mirrored.
 
+Transformations: vst / varianceStabilizingTransformation / getVarianceStabilizedData (R/vst.R), normTransform and
+counts(normalized = TRUE) run in the engine as well (csrc/vst.hip); rlog is not mirrored.
+
 Not mirrored (out of the hot-path scope): local/glmGamPoi dispersion fits, results(), lfcShrink().
 """
 import numpy as np
@@ -71,6 +74,7 @@ class DESeqDataSet:
             nf = np.broadcast_to(sf[None, :], counts.shape)                          # getSizeOrNormFactors :2221
             self.sizeFactors = sf
         self.counts_host = counts.astype(np.int32)
+        self._sf_given = sizeFactors is not None or normalizationFactors is not None
         E = self.engine
         self.y = E.counts(self.counts_host)
         self.nf = E.matrix(nf)
@@ -137,6 +141,9 @@ class DESeqDataSet:
     def p(self):
         return self.x.shape[1]
 
+    # False: the object was built without size or normalization factors and none were estimated since (is.null(sizeFactors)
+    # & is.null(normalizationFactors), R/vst.R:122,236); the factors of one it carries are a placeholder
+    _sf_given = True
     # normalization factors in the engine's gene-major layout; from_device() defers the conversion (see there)
     _nf = None
     _nf_src = None
@@ -270,6 +277,7 @@ def estimateSizeFactors(dds, type="ratio", geoMeans=None, controlGenes=None, nor
     r = E.size_factors(dds.y, type=type, geoMeans=geoMeans, control=ctl, normMatrix=nmh)
     for k in ("prefit", "prefit_for"):                     # baseMean / baseVar belong to the old factors
         dds.attrs.pop(k, None)
+    dds._sf_given = True
     if normMatrix is not None:
         dds.sizeFactors = None
         dds.nf = r["normalizationFactors"] if E.name == "device" else E.matrix(r["normalizationFactors"])
@@ -1174,3 +1182,225 @@ def DESeq(dds, test="Wald", fitType="parametric", reduced=None, minReplicatesFor
     dds.assays, dds.attrs = sub.assays, dict(sub.attrs, nz_rows=nz)
     dds.dispersionFunction = sub.dispersionFunction
     return dds
+
+
+# ------------------------------------------------------------------ R/vst.R, R/helper.R:421-436
+class DESeqTransform:
+    """What the transformations return: the n x m engine handle of the transformed values (resident in HBM on the device
+    engine) next to the object it was computed from.  assay() brings the matrix to the host on request."""
+
+    def __init__(self, dds, handle, kind):
+        self.dds, self.handle, self.kind, self.engine = dds, handle, kind, dds.engine
+
+    def assay(self):
+        return np.asarray(self.engine.to_numpy(self.handle))
+
+
+def _norm_source(dds):
+    """what the engine divides by: the m size factors when the object has them, else the normalization-factor handle"""
+    if dds.sizeFactors is not None:
+        return None, dds.sizeFactors
+    return dds.nf, None
+
+
+def normalized_counts(dds):
+    """counts(object, normalized = TRUE) (R/methods.R:58-69)"""
+    nf, sf = _norm_source(dds)
+    return DESeqTransform(dds, dds.engine.vst_transform(dds.y, nf, "normalized", sizeFactors=sf), "normalized")
+
+
+def normTransform(dds, pc=1):
+    """R/helper.R:421-436 with its default f = log2: log2(counts(object, normalized = TRUE) + pc)"""
+    nf, sf = _norm_source(dds)
+    return DESeqTransform(dds, dds.engine.vst_transform(dds.y, nf, "log2", sizeFactors=sf, pc=pc), "log2")
+
+
+def fmm_spline(x, y):
+    """The coefficients of splinefun(x, y)'s default method "fmm" (Forsythe, Malcolm & Moler's SPLINE): the cubic spline
+    whose third derivative at either end is that of the cubic through the first / the last four points.  Returns the
+    5 x K table x | y | b | c | d with S(u) = y_i + dx (b_i + dx (c_i + dx d_i)), dx = u - x_i."""
+    x = np.asarray(x, np.float64)
+    y = np.asarray(y, np.float64)
+    n = x.size
+    if n < 2 or not (np.diff(x) > 0).all():
+        raise ValueError("fmm_spline needs at least two strictly ascending knots")
+    b, c, d = np.zeros(n), np.zeros(n), np.zeros(n)
+    if n < 3:
+        b[:] = (y[1] - y[0]) / (x[1] - x[0])
+        return np.vstack([x, y, b, c, d])
+    last = n - 1
+    # tridiagonal system: b = diagonal, d = off-diagonal, c = right-hand side
+    d[0] = x[1] - x[0]
+    c[1] = (y[1] - y[0]) / d[0]
+    for i in range(1, last):
+        d[i] = x[i + 1] - x[i]
+        b[i] = 2.0 * (d[i - 1] + d[i])
+        c[i + 1] = (y[i + 1] - y[i]) / d[i]
+        c[i] = c[i + 1] - c[i]
+    # end conditions: third derivatives from divided differences
+    b[0], b[last] = -d[0], -d[n - 2]
+    c[0] = c[last] = 0.0
+    if n > 3:
+        c[0] = c[2] / (x[3] - x[1]) - c[1] / (x[2] - x[0])
+        c[last] = c[n - 2] / (x[last] - x[n - 3]) - c[n - 3] / (x[n - 2] - x[n - 4])
+        c[0] = c[0] * d[0] * d[0] / (x[3] - x[0])
+        c[last] = -c[last] * d[n - 2] * d[n - 2] / (x[last] - x[n - 4])
+    for i in range(1, n):                                  # elimination
+        t = d[i - 1] / b[i - 1]
+        b[i] = b[i] - t * d[i - 1]
+        c[i] = c[i] - t * c[i - 1]
+    c[last] = c[last] / b[last]                            # back substitution
+    for i in range(n - 2, -1, -1):
+        c[i] = (c[i] - d[i] * c[i + 1]) / b[i]
+    b[last] = (y[last] - y[n - 2]) / d[n - 2] + d[n - 2] * (c[n - 2] + 2.0 * c[last])
+    for i in range(last):
+        b[i] = (y[i + 1] - y[i]) / d[i] - d[i] * (c[i + 1] + 2.0 * c[i])
+        d[i] = (c[i + 1] - c[i]) / d[i]
+        c[i] = 3.0 * c[i]
+    c[last] = 3.0 * c[last]
+    d[last] = d[n - 2]
+    return np.vstack([x, y, b, c, d])
+
+
+def quantile7(v, p):
+    """stats::quantile's default (type 7): (1 - g) x[lo] + g x[hi] at h = (n - 1) p"""
+    s = np.sort(np.asarray(v, np.float64))
+    h = (s.size - 1) * p
+    lo, hi = int(np.floor(h)), int(np.ceil(h))
+    g = h - lo
+    if g == 0 or s[hi] == s[lo]:
+        return float(s[lo])
+    return float((1 - g) * s[lo] + g * s[hi])
+
+
+def vst_spline_table(dispFunction, max_q, xim, ngrid=1000):
+    """The numerically integrated transformation of a non-parametric trend (R/vst.R:166-174): the grid
+    sinh(seq(0, asinh(max q), length = 1000))[-1], the integrand 1 / sqrt(f(x) x^2 + xim x), its cumulative trapezoid sums,
+    and splinefun() through them at asinh of the interval midpoints.  Returns the 5 x 998 table."""
+    xg = np.sinh(np.linspace(0.0, np.arcsinh(max_q), ngrid))[1:]
+    with np.errstate(all="ignore"):
+        base = np.asarray(dispFunction(xg), dtype=np.float64) * xg ** 2 + xim * xg
+        integrand = 1.0 / np.sqrt(base)
+    knots = np.arcsinh((xg[1:] + xg[:-1]) / 2)
+    vals = np.cumsum((xg[1:] - xg[:-1]) * (integrand[1:] + integrand[:-1]) / 2)
+    if not np.isfinite(vals).all():
+        raise ValueError("the dispersion function gives no finite variance on the integration grid")
+    return fmm_spline(knots, vals)
+
+
+def vst_subset_rows(baseMean, nsub):
+    """the rows vst() estimates the trend on (R/vst.R:240-250): among the rows with mean normalized count > 5, ordered by it
+    (order(): stable), the nsub positions round(seq(1, L, length = nsub)) (round half to even); 0-based row indices"""
+    bm = np.asarray(baseMean, np.float64)
+    with np.errstate(invalid="ignore"):
+        keep = np.where(bm > 5)[0]
+    if keep.size < nsub:
+        raise ValueError("less than 'nsub' rows with mean normalized count > 5, \n"
+                         "  it is recommended to use varianceStabilizingTransformation directly")
+    o = np.argsort(bm[keep], kind="stable")
+    L = keep.size
+    if nsub == 1:
+        pos = np.array([1.0])
+    else:
+        pos = 1.0 + np.arange(nsub) * ((L - 1) / (nsub - 1))
+        pos[-1] = L
+    return keep[o[np.rint(pos).astype(np.int64) - 1]]
+
+
+def getVarianceStabilizedData(dds):
+    """R/vst.R:146-193: the transformation that belongs to the object's dispersion function, applied to the normalized
+    counts by the engine in one pass.  fitType "custom" (the caller's trend: what R reaches as "local") takes the spline
+    path.  Returns the n x m engine handle."""
+    fn = dds.dispersionFunction
+    if fn is None or fn.get("fitType") is None:
+        raise ValueError("call estimateDispersions before calling getVarianceStabilizedData")
+    E = dds.engine
+    nf, sf = _norm_source(dds)
+    if fn["fitType"] == "parametric":
+        a, e = (float(v) for v in fn["coefficients"])                            # asymptDisp, extraPois
+        return E.vst_transform(dds.y, nf, "parametric", sizeFactors=sf, asymptDisp=a, extraPois=e)
+    if fn["fitType"] == "mean":
+        return E.vst_transform(dds.y, nf, "mean", sizeFactors=sf, alpha=float(fn["coefficients"]))
+    if fn["fitType"] == "custom":
+        sfa = sf if sf is not None else E.nf_col_geomeans(nf)                    # :159-165
+        xim = float(np.mean(1.0 / np.asarray(sfa, np.float64)))
+        rmean, rmax = E.row_stats(dds.y, nf, sizeFactors=sf)
+        table = vst_spline_table(fn["coefficients"], float(np.max(rmax)), xim)
+        from .engine import spline_eval
+        h1, h2 = quantile7(rmean, .95), quantile7(rmean, .999)                   # :175-176
+        s1, s2 = (float(spline_eval(table, np.arcsinh(h))) for h in (h1, h2))
+        eta = (np.log2(h2) - np.log2(h1)) / (s2 - s1)                            # :177
+        xi = np.log2(h1) - eta * s1                                              # :178
+        dds.attrs["vst_spline"] = {"table": table, "eta": float(eta), "xi": float(xi), "h1": h1, "h2": h2}
+        return E.vst_transform(dds.y, nf, "spline", sizeFactors=sf, table=table, eta=float(eta), xi=float(xi))
+    raise ValueError("fitType is not parametric, local or mean")
+
+
+def _shallow(dds, x=None):
+    """the same object (same handles) with fresh mcols / assays / attrs and, optionally, another design"""
+    c = DESeqDataSet.__new__(DESeqDataSet)
+    c.__dict__.update(dds.__dict__)
+    c.mcols, c.assays, c.attrs = {}, {}, {}
+    if x is not None:
+        c.x = np.asarray(x, np.float64)
+        c.xh = dds.engine.design(c.x)
+    return c
+
+
+def _vst_object(obj, engine):
+    """a count matrix becomes the `~ 1` object (R/vst.R:116-118, 227-229); an object is copied (same handles, own mcols /
+    assays / attrs), so that -- as in R -- the caller's object keeps its factors and its dispersion function"""
+    if isinstance(obj, DESeqDataSet):
+        c = _shallow(obj)
+        c.mcols, c.assays, c.attrs = dict(obj.mcols), dict(obj.assays), dict(obj.attrs)
+        if obj.dispersionFunction is not None:
+            c.dispersionFunction = dict(obj.dispersionFunction)
+        return c, False
+    counts = np.asarray(obj)
+    return DESeqDataSet(counts, np.ones((counts.shape[1], 1)), engine=engine), True
+
+
+def _fit_trend(sub, fitType):
+    getBaseMeansAndVariances(sub)
+    estimateDispersionsGeneEst(sub)
+    estimateDispersionsFit(sub, fitType=fitType)
+    return sub.dispersionFunction
+
+
+def varianceStabilizingTransformation(obj, blind=True, fitType="parametric", engine=None, sfType="ratio"):
+    """R/vst.R:112-142.  obj: a DESeqDataSet or a count matrix (then `engine` says where it lives).  Size factors are
+    estimated (sfType) when the object has neither factors nor a matrix; blind swaps the design for the intercept; with
+    blind = False and a dispersion function on the object nothing is fitted (the "frozen" VST).  The dispersion steps run
+    on the rows that are not all zero.  Returns a DESeqTransform (for a matrix too: assay() is what R returns) whose `.dds`
+    is a copy of the object carrying the factors and the dispersion function used; the argument is left as it was."""
+    dds, _ = _vst_object(obj, engine)
+    if not dds._sf_given:
+        estimateSizeFactors(dds, type=sfType)                                       # :122-124
+    fn = dds.dispersionFunction
+    if blind or fn is None or fn.get("fitType") is None:                            # :128
+        work = _shallow(dds, np.ones((dds.m, 1)) if blind else None)                # :125-127
+        getBaseMeansAndVariances(work)
+        allZero = work.mcols["allZero"]
+        if allZero.all():
+            raise ValueError("all genes have zero counts in every sample")
+        sub = work if not allZero.any() else work.subset(np.where(~allZero)[0])
+        dds.dispersionFunction = _fit_trend(sub, fitType)                           # :129-130
+    return DESeqTransform(dds, getVarianceStabilizedData(dds), "vst")
+
+
+def vst(obj, blind=True, nsub=1000, fitType="parametric", engine=None, sfType="ratio"):
+    """R/vst.R:219-267: the trend is estimated on nsub rows spanning the range of the mean normalized count, then the
+    transformation is applied to every row.  The argument is left as it was; the DESeqTransform's `.dds` is the copy that
+    carries the estimated factors, the dispersion function and attrs["vst_rows"]."""
+    dds, matrixIn = _vst_object(obj, engine)
+    if dds.n < nsub:
+        raise ValueError("less than 'nsub' rows,\n  it is recommended to use varianceStabilizingTransformation directly")
+    if not dds._sf_given:
+        estimateSizeFactors(dds, type=sfType)                                       # :236-238
+    work = _shallow(dds, np.ones((dds.m, 1)) if (blind or matrixIn) else None)      # :231-233
+    nf, sf = _norm_source(dds)
+    baseMean, _ = dds.engine.row_stats(dds.y, nf, sizeFactors=sf)                   # :239 (unweighted rowMeans)
+    idx = vst_subset_rows(baseMean, nsub)                                           # :240-250
+    dds.dispersionFunction = _fit_trend(work.subset(idx), fitType)                  # :253-257
+    dds.attrs["vst_rows"] = idx
+    return DESeqTransform(dds, getVarianceStabilizedData(dds), "vst")               # :261

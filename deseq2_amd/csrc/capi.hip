@@ -689,11 +689,96 @@ int size_factors_dev_locked(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *
     return DSQ_OK;
 }
 
+// the variance stabilizing transformation (vst.hip): what both entries check before anything is launched
+int vst_check(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->n < 1 || a->m < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
+    if (!a->y || !a->nf) return capi_fail(DSQ_ERR_ARG, "NULL counts or size / normalization factors");
+    if (a->y_type != DSQ_Y_INT32 && a->y_type != DSQ_Y_FLOAT64) return capi_fail(DSQ_ERR_ARG, "unknown y_type %d", a->y_type);
+    if (stats && (!o->rowMean || !o->rowMax)) return capi_fail(DSQ_ERR_ARG, "NULL rowMean or rowMax");
+    if (!transform) return DSQ_OK;
+    if (!o->out) return capi_fail(DSQ_ERR_ARG, "NULL output matrix");
+    const auto finite = [](double v) { return v - v == 0.0; };
+    switch (a->kind) {
+    case DSQ_VST_PARAMETRIC:
+        if (!(a->asymptDisp > 0.0) || !finite(a->asymptDisp) || !finite(a->extraPois))
+            return capi_fail(DSQ_ERR_ARG, "parametric: asymptDisp = %g must be positive, extraPois = %g finite", a->asymptDisp, a->extraPois);
+        break;
+    case DSQ_VST_MEAN:
+        if (!(a->alpha > 0.0) || !finite(a->alpha)) return capi_fail(DSQ_ERR_ARG, "mean: alpha = %g must be positive", a->alpha);
+        break;
+    case DSQ_VST_SPLINE:
+        if (!a->spline || a->nknots < 2) return capi_fail(DSQ_ERR_ARG, "spline: a table of at least two knots is needed");
+        if (a->nknots > DSQ_VST_MAX_KNOTS)
+            return capi_fail(DSQ_ERR_UNSUPPORTED, "spline: %d knots (at most %d: the table is held in LDS)", a->nknots, DSQ_VST_MAX_KNOTS);
+        for (int k = 0; k + 1 < a->nknots; k++)
+            if (!(a->spline[k] < a->spline[k + 1])) return capi_fail(DSQ_ERR_ARG, "spline: knots must be strictly ascending (knot %d)", k + 1);
+        if (!finite(a->spline[0]) || !finite(a->spline[a->nknots - 1])) return capi_fail(DSQ_ERR_ARG, "spline: knots must be finite");
+        break;
+    case DSQ_VST_LOG2:
+        if (a->pc != a->pc) return capi_fail(DSQ_ERR_ARG, "log2: the pseudocount is NaN");
+        break;
+    case DSQ_VST_NORMALIZED:
+        break;
+    default:
+        return capi_fail(DSQ_ERR_ARG, "unknown kind %d", a->kind);
+    }
+    return DSQ_OK;
+}
+
+int vst_dev_locked(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats, hipStream_t st) {
+    if (int rc = vst_check(a, o, transform, stats)) return rc;
+    if (a->layout != DSQ_LAYOUT_R && a->layout != DSQ_LAYOUT_GENE_MAJOR) return capi_fail(DSQ_ERR_ARG, "unknown layout %d", a->layout);
+    if (a->layout == DSQ_LAYOUT_GENE_MAJOR && a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld < m");
+    if (int rc = capi_check_device()) return rc;
+    VstKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.m = a->m;
+    kp.y = a->y;
+    const bool gm = a->layout == DSQ_LAYOUT_GENE_MAJOR;
+    kp.si = gm ? (long)a->ld : 1L;  kp.sj = gm ? 1L : (long)a->n;
+    kp.nf = a->nf; kp.nf_is_vector = a->nf_is_vector ? 1 : 0;
+    kp.kind = a->kind;
+    kp.a = a->asymptDisp; kp.e = a->extraPois; kp.alpha = a->alpha; kp.pc = a->pc;
+    kp.nknots = a->nknots; kp.eta = a->eta; kp.xi = a->xi;
+    kp.out = o->out; kp.rowMean = o->rowMean; kp.rowMax = o->rowMax;
+    kp.bad = a->y_type == DSQ_Y_FLOAT64 ? o->bad : nullptr;
+    if (transform && a->kind == DSQ_VST_SPLINE) {
+        // the slot is sized for the largest table at once: a later, longer table never takes the grow path (which synchronises)
+        void *tab;
+        if (int rc = capi_ws_get(WS_VST_TABLE, (size_t)DSQ_VST_MAX_KNOTS * 5 * sizeof(double), &tab)) return rc;
+        if (int rc = capi_upload_table(WS_VST_TABLE, a->spline, (size_t)a->nknots * 5 * sizeof(double), st, &tab)) return rc;
+        kp.table = (const double *)tab;
+    }
+    if (stats) {
+        capi_prof_begin("vst_rowstats", a->n, st);
+        DSQ_HIP(launch_vst_rowstats(kp, a->y_type == DSQ_Y_FLOAT64, st));
+        capi_prof_end(st);
+    }
+    if (transform) {
+        capi_prof_begin("vst_transform", a->n, st);
+        DSQ_HIP(launch_vst_transform(kp, a->y_type == DSQ_Y_FLOAT64, st));
+        capi_prof_end(st);
+    }
+    return DSQ_OK;
+}
+
 }  // namespace dsq
 
 using namespace dsq;
 
 extern "C" {
+
+int dsq_vst_dev(const DsqVstArgs *args, const DsqVstOut *out, void *stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    WsScope ws((hipStream_t)stream);
+    return vst_dev_locked(args, out, true, false, (hipStream_t)stream);
+}
+int dsq_vst_rowstats_dev(const DsqVstArgs *args, const DsqVstOut *out, void *stream) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    WsScope ws((hipStream_t)stream);
+    return vst_dev_locked(args, out, false, true, (hipStream_t)stream);
+}
 
 int dsq_fit_beta_dev(const DsqFitBetaArgs *args, const DsqFitBetaOut *out, void *stream) {
     std::lock_guard<std::mutex> lk(g_mu);

@@ -10,7 +10,7 @@ static inline void prof_end(hipStream_t st) { capi_prof_end(st); }
 
 enum {  // workspace slots
     WS_Y = 0, WS_NF, WS_W, WS_MU, WS_HAT, WS_MUOUT, WS_SCRATCH, WS_BAD, WS_CELLS, WS_COOKS_IN, WS_COUNTER, WS_TREND, WS_PAD_X, WS_PAD_VEC, WS_PAD_BETA,
-    WS_CELLS_BETA,
+    WS_CELLS_BETA, WS_VST_TABLE,
     // host-entry staging
     WS_H_Y, WS_H_X, WS_H_NF, WS_H_W, WS_H_MU, WS_H_VEC, WS_H_OUTMAT, WS_H_OUTMAT2, WS_H_OUTVEC,
     WS_COUNT
@@ -39,5 +39,7 @@ int cooks_dev_locked(const DsqCooksArgs *a, const DsqCooksOut *o, hipStream_t st
 int replace_dev_locked(const DsqReplaceArgs *a, const DsqReplaceOut *o, hipStream_t st);
 int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o);
 int size_factors_dev_locked(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o, hipStream_t st);
+int vst_check(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats);
+int vst_dev_locked(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats, hipStream_t st);
 
 }  // namespace dsq

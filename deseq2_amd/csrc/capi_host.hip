@@ -752,4 +752,61 @@ int dsq_size_factors(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o) {
     return DSQ_OK;
 }
 
+int dsq_vst(const DsqVstArgs *a, const DsqVstOut *o) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    WsScope ws(nullptr);
+    const bool transform = o && o->out, stats = o && (o->rowMean || o->rowMax);
+    if (o && !transform && !stats) return capi_fail(DSQ_ERR_ARG, "neither an output matrix nor row statistics asked for");
+    if (int rc = vst_check(a, o, transform, stats)) return rc;
+    if (a->layout != DSQ_LAYOUT_R) return capi_fail(DSQ_ERR_ARG, "host entry points take R layout only");
+    if (int rc = capi_check_device()) return rc;
+    hipStream_t st = nullptr;
+    const size_t n = a->n, m = a->m;
+    const long ld = round_ld(a->m);
+    const size_t ye = a->y_type == DSQ_Y_INT32 ? 4 : 8;
+    DsqVstArgs d = *a;
+    DsqVstOut od = *o;
+    void *v, *g;
+    int rc;
+    if (transform) stage_prefault(o->out, n * m * 8);
+    // counts and a normalization-factor matrix: up in R layout, turned gene-major on the device
+    if ((rc = up(WS_H_Y, a->y, n * m * ye, st, &v))) return rc;
+    if ((rc = capi_ws_get(WS_Y, n * ld * ye, &g))) return rc;
+    if (ye == 4) DSQ_HIP(launch_transpose_r_to_gm_i32((const int32_t *)v, (int32_t *)g, a->n, a->m, ld, st));
+    else DSQ_HIP(launch_transpose_r_to_gm_f64((const double *)v, (double *)g, a->n, a->m, ld, st));
+    d.y = g; d.layout = DSQ_LAYOUT_GENE_MAJOR; d.ld = ld;
+    if (a->nf_is_vector) {
+        if ((rc = up(WS_H_NF, a->nf, m * 8, st, &v))) return rc;
+        d.nf = (const double *)v;
+    } else {
+        if ((rc = up(WS_H_NF, a->nf, n * m * 8, st, &v))) return rc;
+        if ((rc = capi_ws_get(WS_NF, n * ld * 8, &g))) return rc;
+        DSQ_HIP(launch_transpose_r_to_gm_f64((const double *)v, (double *)g, a->n, a->m, ld, st));
+        d.nf = (const double *)g;
+    }
+    // rowMean (n f64) | rowMax (n f64) | the bad-count flag
+    if ((rc = capi_ws_get(WS_H_OUTVEC, (2 * n + 1) * 8, &v))) return rc;
+    double *ov = (double *)v;
+    od.rowMean = ov; od.rowMax = ov + n; od.bad = (int32_t *)(ov + 2 * n);
+    DSQ_HIP(hipMemsetAsync(od.bad, 0, 8, st));
+    double *out_gm = nullptr;
+    if (transform) {
+        if ((rc = capi_ws_get(WS_MUOUT, n * ld * 8, &g))) return rc;
+        od.out = out_gm = (double *)g;
+    }
+    if ((rc = vst_dev_locked(&d, &od, transform, stats, st))) return rc;
+    int32_t bad = 0;
+    DSQ_HIP(hipMemcpyAsync(&bad, od.bad, 4, hipMemcpyDeviceToHost, st));
+    if (o->rowMean) DSQ_HIP(hipMemcpyAsync(o->rowMean, od.rowMean, n * 8, hipMemcpyDeviceToHost, st));
+    if (o->rowMax) DSQ_HIP(hipMemcpyAsync(o->rowMax, od.rowMax, n * 8, hipMemcpyDeviceToHost, st));
+    if (out_gm) {
+        if ((rc = capi_ws_get(WS_H_OUTMAT, n * m * 8, &v))) return rc;
+        DSQ_HIP(launch_transpose_gm_to_r_f64(out_gm, (double *)v, a->n, a->m, ld, st));
+        if ((rc = down(o->out, v, n * m * 8, st))) return rc;
+    }
+    DSQ_HIP(hipStreamSynchronize(st));
+    if (bad) return capi_fail(DSQ_ERR_VALUE, "count matrix holds negative, non-finite or non-integer values");
+    return DSQ_OK;
+}
+
 }  // extern "C"

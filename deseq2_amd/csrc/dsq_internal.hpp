@@ -217,6 +217,28 @@ struct SizeFactorKernelParams {
 hipError_t launch_size_factors(SizeFactorKernelParams kp, int y_f64, void *workspace, hipStream_t st);
 size_t size_factors_workspace_bytes(long n, long m);
 
+// the variance stabilizing transformation (vst.hip).  Element (i, j) of counts / nf matrix / output sits at
+// [i * si + j * sj] (either layout; all three share the strides).  kind = DSQ_VST_* of the public header.
+struct VstKernelParams {
+    int n, m;
+    const void *y;
+    long si, sj;
+    const double *nf;            // m-vector (nf_is_vector) or matrix
+    int nf_is_vector;
+    int kind;
+    double a, e;                 // parametric: asymptDisp, extraPois
+    double alpha;                // mean
+    double pc;                   // log2
+    const double *table;         // spline: DEVICE copy of x | y | b | c | d
+    int nknots;
+    double eta, xi;
+    double *out;
+    double *rowMean, *rowMax;
+    int32_t *bad;                // float64 counts: set to 1 on a negative / non-finite / non-integer value; may be nullptr
+};
+hipError_t launch_vst_transform(const VstKernelParams &kp, int y_f64, hipStream_t st);
+hipError_t launch_vst_rowstats(const VstKernelParams &kp, int y_f64, hipStream_t st);
+
 // gene index of work item i, and the number of work items, of a (possibly row-listed) launch
 #define DSQ_NWORK(kp) ((kp).n_dev ? *(kp).n_dev : (kp).n)
 #define DSQ_GENE(kp, i) ((kp).rows ? (kp).rows[i] : (i))

@@ -142,6 +142,16 @@ def control_flags(controlGenes, n):
     return f
 
 
+def spline_eval(table, u):
+    """the piecewise cubic of a table x | y | b | c | d (5 x K) as R's splinefun() evaluates its "fmm" fit: interval = the
+    largest i with x_i <= u (the first knot left of all), y + dx (b + dx (c + dx d)), cubic extrapolation on both sides"""
+    x, y, b, c, d = np.asarray(table, np.float64).reshape(5, -1)
+    u = np.asarray(u, np.float64)
+    i = np.clip(np.searchsorted(x, u, side="right") - 1, 0, x.size - 1)
+    dx = u - x[i]
+    return y[i] + dx * (b[i] + dx * (c[i] + dx * d[i]))
+
+
 class HostEngine:
     name = "host"
 
@@ -257,6 +267,41 @@ class HostEngine:
                 nf = np.asarray(normMatrix, np.float64) * sf[None, :]
                 out["normalizationFactors"] = np.asfortranarray(nf / np.exp(np.log(nf).sum(axis=1) / m)[:, None])
         return out
+
+    def vst_transform(self, y, nf, kind, sizeFactors=None, asymptDisp=None, extraPois=None, alpha=None, pc=1.0,
+                      table=None, eta=None, xi=None):
+        """getVarianceStabilizedData's formulas (R/vst.R:151-189), normTransform (R/helper.R:421-436) and
+        counts(normalized = TRUE) in plain numpy + libm: the host statement of what csrc/vst.hip computes on the device
+        (equal to rounding, not to the bit).  sizeFactors (m) take precedence over the nf handle.  Returns an n x m handle."""
+        K = np.asarray(y, np.float64)
+        with np.errstate(all="ignore"):
+            q = K / (np.asarray(sizeFactors, np.float64)[None, :] if sizeFactors is not None else np.asarray(nf, np.float64))
+            if kind == "parametric":
+                a, e = float(asymptDisp), float(extraPois)
+                r = np.log((1 + e + 2 * a * q + 2 * np.sqrt(a * q * (1 + e + a * q))) / (4 * a)) / np.log(2)
+            elif kind == "mean":
+                al = float(alpha)
+                r = (2 * np.arcsinh(np.sqrt(al * q)) - np.log(al) - np.log(4)) / np.log(2)
+            elif kind == "spline":
+                r = float(eta) * spline_eval(table, np.arcsinh(q)) + float(xi)
+            elif kind == "log2":
+                r = np.log2(q + float(pc))
+            elif kind == "normalized":
+                r = q
+            else:
+                raise ValueError("kind should be parametric, mean, spline, log2 or normalized")
+        return np.asfortranarray(r)
+
+    def row_stats(self, y, nf, sizeFactors=None):
+        """(rowMeans, row maxima) of the normalized counts (R/vst.R:166,175-176,239), host n-vectors"""
+        K = np.asarray(y, np.float64)
+        with np.errstate(all="ignore"):
+            q = K / (np.asarray(sizeFactors, np.float64)[None, :] if sizeFactors is not None else np.asarray(nf, np.float64))
+            return q.mean(axis=1), q.max(axis=1)
+
+    def nf_col_geomeans(self, nf):
+        """exp(colMeans(log(normalizationFactors))): the approximate size factors of R/vst.R:162"""
+        return np.exp(np.log(np.asarray(nf, np.float64)).mean(axis=0))
 
     def linear_mu(self, y, nf, x):
         """linearModelMuNormalized, R/core.R:2465-2471 (engine kernel: a BLAS product on the host would make
@@ -553,6 +598,33 @@ class DeviceEngine:
         if normMatrix is not None:
             out["normalizationFactors"] = r["normalizationFactors"]
         return out
+
+    def _sf_dev(self, sizeFactors):
+        """the m size factors as a device vector (the one estimateSizeFactors left resident, if these are its bytes)"""
+        sf = np.ascontiguousarray(sizeFactors, dtype=np.float64)
+        v = self._cache.get(("sf", sf.tobytes()))
+        return v if v is not None else self._vec(sf)
+
+    def vst_transform(self, y, nf, kind, sizeFactors=None, asymptDisp=None, extraPois=None, alpha=None, pc=1.0,
+                      table=None, eta=None, xi=None):
+        """the transformation of the resident counts in one pass (csrc/vst.hip, dsq_vst_dev) on the current stream; the
+        n x m result is a handle and stays in HBM.  What goes up: the scalars of the formula (kernel arguments) and, for
+        the spline formula, the 40 KB table.  Nothing comes down."""
+        f = self._sf_dev(sizeFactors) if sizeFactors is not None else nf
+        return self._timed("vst_transform", y.n, lambda: self.native.vst_dev(
+            y, f, kind, asymptDisp=asymptDisp, extraPois=extraPois, alpha=alpha, pc=pc, table=table, eta=eta, xi=xi))
+
+    def row_stats(self, y, nf, sizeFactors=None):
+        """(rowMeans, row maxima) of the normalized counts by dsq_vst_rowstats_dev; the two n-vectors come to the host in one
+        copy (vst()'s subset rule and the spline path's quantiles are host decisions over n-vectors)"""
+        f = self._sf_dev(sizeFactors) if sizeFactors is not None else nf
+        pack = self._timed("vst_rowstats", y.n, lambda: self.native.vstRowStats_dev(y, f))
+        h = self._host(pack).numpy()
+        return h[0], h[1]
+
+    def nf_col_geomeans(self, nf):
+        t = self.torch
+        return self._host(t.exp(t.log(nf.view()).mean(dim=0))).numpy()
 
     def weights_prep(self, w, x, thr=1e-2):
         """getAndCheckWeights (R/core.R:2697-2751) in ONE kernel on the resident weights: (w / rowmax, its 1e-6 floor,

@@ -490,6 +490,48 @@ def estimateSizeFactorsForMatrix(counts, type="ratio", geoMeans=None, controlGen
     return (res, lgm) if want_loggeomeans else res
 
 
+def _vst_args(kind, asymptDisp, extraPois, alpha, pc, table, eta, xi):
+    """the formula part of DsqVstArgs; the spline table (5 x K: x | y | b | c | d) stays a host array"""
+    if kind not in L.DSQ_VST:
+        raise ValueError("kind should be one of %s" % ", ".join(L.DSQ_VST))
+    tab = None
+    if table is not None:
+        tab = np.ascontiguousarray(table, dtype=np.float64)
+        if tab.ndim != 2 or tab.shape[0] != 5:
+            raise ValueError("the spline table is 5 x K: x | y | b | c | d")
+    kw = dict(kind=L.DSQ_VST[kind], asymptDisp=float(0.0 if asymptDisp is None else asymptDisp),
+              extraPois=float(0.0 if extraPois is None else extraPois), alpha=float(0.0 if alpha is None else alpha),
+              pc=float(pc), spline=_ptr(tab), nknots=0 if tab is None else int(tab.shape[1]),
+              eta=float(0.0 if eta is None else eta), xi=float(0.0 if xi is None else xi))
+    return kw, tab
+
+
+def vst(counts, nf, kind="parametric", asymptDisp=None, extraPois=None, alpha=None, pc=1.0, table=None, eta=None, xi=None,
+        want_out=True, want_stats=False):
+    """getVarianceStabilizedData / normTransform / counts(normalized = TRUE) (R/vst.R:146-193, R/helper.R:421-436) through
+    dsq_vst: host arrays in R layout in, the n x m matrix out.  nf: the m size factors or an n x m matrix.  want_stats:
+    also (rowMeans, row maxima) of the normalized counts."""
+    y, ytype = _counts(counts)
+    if y.ndim != 2:
+        raise ValueError("counts must be a matrix")
+    n, m = y.shape
+    nf = np.asarray(nf, np.float64)
+    vec = nf.ndim == 1
+    nf = np.ascontiguousarray(nf) if vec else _fcol(nf)
+    if nf.shape != ((m,) if vec else (n, m)):
+        raise ValueError("nf must be the m size factors or an n x m matrix")
+    kw, tab = _vst_args(kind, asymptDisp, extraPois, alpha, pc, table, eta, xi)
+    out = np.zeros((n, m), order="F") if want_out else None
+    rmean = np.zeros(n) if want_stats else None
+    rmax = np.zeros(n) if want_stats else None
+    a = L.DsqVstArgs(n=n, m=m, layout=L.DSQ_LAYOUT_R, ld=0, y=_ptr(y), y_type=ytype, nf=_ptr(nf), nf_is_vector=int(vec), **kw)
+    o = L.DsqVstOut(out=_ptr(out), rowMean=_ptr(rmean), rowMax=_ptr(rmax), bad=None)
+    L.check(L.lib().dsq_vst(C.byref(a), C.byref(o)))
+    if want_out and want_stats:
+        return out, rmean, rmax
+    return out if want_out else (rmean, rmax)
+
+
 _FIT_ERRORS = {1: "parametric dispersion fit failed", 2: "dispersion fit did not converge"}
 
 
@@ -706,6 +748,48 @@ def sizeFactors_dev(y, type="ratio", geoMeans=None, control=None, normMatrix=Non
     L.check(L.lib().dsq_size_factors_dev(C.byref(a), C.byref(o), _stream()))
     # (the workspace is stream-ordered scratch: torch's caching allocator hands it out again only to work enqueued later)
     return {"sizeFactors": pack[:m], "loggeomeans": lgm, "normalizationFactors": nf, "_pack": pack}
+
+
+def _vst_dev_args(y, nf):
+    import torch
+    assert isinstance(y, GeneMajor)
+    vec = torch.is_tensor(nf)
+    if not vec:
+        assert isinstance(nf, GeneMajor) and nf.ld == y.ld and nf.n == y.n
+    else:
+        assert nf.dtype == torch.float64 and nf.numel() == y.m and nf.is_contiguous()
+    return dict(n=y.n, m=y.m, layout=L.DSQ_LAYOUT_GENE_MAJOR, ld=y.ld, y=_t_ptr(y.t),
+                y_type=L.DSQ_Y_FLOAT64 if y.t.dtype == torch.float64 else L.DSQ_Y_INT32,
+                nf=_t_ptr(nf if vec else nf.t), nf_is_vector=int(vec))
+
+
+def vst_dev(y, nf, kind="parametric", asymptDisp=None, extraPois=None, alpha=None, pc=1.0, table=None, eta=None, xi=None,
+            bad=None, out=None):
+    """dsq_vst_dev on resident counts: y GeneMajor (int32 or float64), nf the m size factors (a device tensor) or a
+    GeneMajor matrix with y's ld; the spline table is a host array (5 x K).  Returns the transformed matrix as a GeneMajor
+    handle (padding columns zero; `out`: a GeneMajor of y's shape to write into); nothing is read back."""
+    import torch
+    kw, tab = _vst_args(kind, asymptDisp, extraPois, alpha, pc, table, eta, xi)
+    if out is None:
+        # (the kernel writes every sample column exactly once: only the padding, which it leaves alone, is cleared)
+        out = GeneMajor(torch.empty((y.n, y.ld), dtype=torch.float64, device=y.t.device), y.m)
+        if y.ld > y.m:
+            out.t[:, y.m:] = 0.0
+    assert out.n == y.n and out.ld == y.ld and out.m == y.m
+    a = L.DsqVstArgs(**_vst_dev_args(y, nf), **kw)
+    o = L.DsqVstOut(out=_t_ptr(out.t), rowMean=None, rowMax=None, bad=_t_ptr(bad))
+    L.check(L.lib().dsq_vst_dev(C.byref(a), C.byref(o), _stream()))
+    return out
+
+
+def vstRowStats_dev(y, nf):
+    """dsq_vst_rowstats_dev: a (2, n) device tensor, row 0 = rowMeans, row 1 = row maxima of counts / nf"""
+    import torch
+    pack = torch.empty((2, y.n), dtype=torch.float64, device=y.t.device)
+    a = L.DsqVstArgs(**_vst_dev_args(y, nf), kind=L.DSQ_VST["normalized"])
+    o = L.DsqVstOut(out=None, rowMean=_t_ptr(pack[0]), rowMax=_t_ptr(pack[1]), bad=None)
+    L.check(L.lib().dsq_vst_rowstats_dev(C.byref(a), C.byref(o), _stream()))
+    return pack
 
 
 def prefitMoments_dev(y, nf, q, a, r, weights=None, useWeights=False, nf_is_vector=False):

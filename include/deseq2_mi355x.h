@@ -592,6 +592,57 @@ int dsq_size_factors_dev(const DsqSizeFactorArgs *args, const DsqSizeFactorOut *
 int dsq_size_factors(const DsqSizeFactorArgs *args, const DsqSizeFactorOut *out);
 int64_t dsq_size_factors_workspace_bytes(int32_t n, int32_t m);
 
+/* ---- dsq_vst: the variance stabilizing transformation and its relatives ------------------------
+ * getVarianceStabilizedData (R/vst.R:146-193), normTransform (R/helper.R:421-436) and counts(normalized = TRUE): ONE pass
+ * over the counts, q_ij = k_ij / nf_ij (one IEEE division; nf = the m size factors or an n x m matrix), then by `kind`
+ *   DSQ_VST_PARAMETRIC  log((1 + e + 2 a q + 2 sqrt(a q (1 + e + a q))) / (4 a)) / log(2)     a = asymptDisp, e = extraPois
+ *                       (R/vst.R:151-156)
+ *   DSQ_VST_MEAN        (2 asinh(sqrt(alpha q)) - log(alpha) - log(4)) / log(2)                 (R/vst.R:184-189)
+ *   DSQ_VST_SPLINE      eta * S(asinh(q)) + xi, S the piecewise cubic of the caller's table: what splinefun() returned
+ *                       for the numerically integrated trend of fitType "local" (R/vst.R:157-183)
+ *   DSQ_VST_LOG2        log2(q + pc)                                                            (R/helper.R:421-436)
+ *   DSQ_VST_NORMALIZED  q                                                                       (counts(normalized = TRUE))
+ * every operation rounded once in the order the R expression evaluates it; log / log1p are the library's (dsq_math.hpp),
+ * asinh is built from them.  The spline table is a HOST array of 5 * nknots doubles, x | y | b | c | d
+ * (knots ascending, value and the three polynomial coefficients of each knot): S(u) = y + dx (b + dx (c + dx d)) with
+ * dx = u - x_i, i the largest index with x_i <= u, the first knot left of all of them (cubic extrapolation on both sides).
+ * dsq_vst_rowstats_dev (host pointers: dsq_vst with rowMean / rowMax given, out NULL or not): rowMeans and row maxima of q (vst()'s gene subset, R/vst.R:239, and max / quantiles of the spline
+ * path, :166,175-176): the mean is the wave-order sum over the samples divided by m, the maximum is exact (NaN if the row
+ * holds one).
+ * _dev: device pointers (the table excepted), asynchronous on `stream`, no host synchronisation; a float64 count that is
+ * negative, non-finite or non-integer sets *bad (when given) to 1 and is transformed as it stands.  The host entry
+ * returns DSQ_ERR_VALUE for such a matrix.  Padding columns m .. ld-1 of a gene-major output are not written.          */
+enum { DSQ_VST_PARAMETRIC = 0, DSQ_VST_MEAN = 1, DSQ_VST_SPLINE = 2, DSQ_VST_LOG2 = 3, DSQ_VST_NORMALIZED = 4 };
+#define DSQ_VST_MAX_KNOTS 1600 /* the table lives in LDS: 40 bytes per knot, 64 000 bytes (62.5 KiB) per workgroup at most */
+typedef struct {
+    int32_t n, m;
+    int32_t layout;            /* DSQ_LAYOUT_* of y / nf (matrix) / out                                             */
+    int64_t ld;                /* leading dimension for DSQ_LAYOUT_GENE_MAJOR (>= m)                                */
+    const void *y;             /* n x m counts                                                                      */
+    int32_t y_type;            /* DSQ_Y_INT32 or DSQ_Y_FLOAT64                                                      */
+    const double *nf;          /* m size factors (nf_is_vector) or n x m normalization factors in `layout`          */
+    int32_t nf_is_vector;
+    int32_t kind;              /* DSQ_VST_*                                                                         */
+    double asymptDisp, extraPois;  /* DSQ_VST_PARAMETRIC: both finite, asymptDisp > 0                               */
+    double alpha;              /* DSQ_VST_MEAN: finite, > 0                                                         */
+    double pc;                 /* DSQ_VST_LOG2: the pseudocount                                                     */
+    const double *spline;      /* DSQ_VST_SPLINE: HOST pointer, 5 * nknots doubles x | y | b | c | d                */
+    int32_t nknots;            /* 2 .. DSQ_VST_MAX_KNOTS                                                            */
+    double eta, xi;            /* DSQ_VST_SPLINE: the affine rescaling (R/vst.R:177-178)                            */
+} DsqVstArgs;
+
+typedef struct {
+    double *out;               /* n x m in `layout` (dsq_vst[_dev]); dsq_vst: may be NULL when only the row statistics are wanted */
+    double *rowMean;           /* n (dsq_vst_rowstats_dev; dsq_vst: optional, both or neither)                      */
+    double *rowMax;            /* n (dsq_vst_rowstats_dev; dsq_vst: optional, both or neither)                      */
+    int32_t *bad;              /* _dev: one device int32 the CALLER has zeroed, or NULL; host entries: ignored      */
+} DsqVstOut;
+
+int dsq_vst_dev(const DsqVstArgs *args, const DsqVstOut *out, void *stream);
+int dsq_vst_rowstats_dev(const DsqVstArgs *args, const DsqVstOut *out, void *stream);   /* kind and its scalars are ignored */
+/* host pointers in R layout, one device, synchronous: the transform into out (if non-NULL) and the row statistics (if non-NULL) */
+int dsq_vst(const DsqVstArgs *args, const DsqVstOut *out);
+
 /* ---- dsq_deseq: DESeq() behind ONE host-pointer call ------------------------------------------------------------
  * What an R session binds as .Call("_DESeq2_mi355x_DESeq", ...) in place of the body of DESeq() between
  * estimateSizeFactors (dsq_size_factors above) and the final bookkeeping (R/core.R:388-426: estimateDispersions -> nbinomWaldTest / nbinomLRT
