@@ -136,24 +136,14 @@ hipError_t dispatch_optim_rows(int p, const OptimKernelParams &kp, hipStream_t s
 // Gram / QR / LU arithmetic of the real coefficients sees only extra exact zeros (x + 0 = x, 0 * y = 0), so their
 // results keep their bits (tests/test_gpu_wide.py compares with the oracle run at the true p).
 
-static int wide_pad_matrix(int slot, const double *src, size_t rows, int p, hipStream_t st, double **out) {
-    // column-major rows x p  ->  rows x wide_width(p), new columns zero
-    const size_t pw = wide_width(p);
+int capi_pad_design(int slot, const double *src, size_t rows, int p, int pw, hipStream_t st, const double **out) {
+    // column-major rows x p  ->  rows x pw in the slot, new columns zero
     void *b;
-    int rc = capi_ws_get(slot, rows * pw * sizeof(double), &b);
+    int rc = capi_ws_get(slot, rows * (size_t)pw * sizeof(double), &b);
     if (rc) return rc;
-    DSQ_HIP(hipMemsetAsync(b, 0, rows * pw * sizeof(double), st));
+    DSQ_HIP(hipMemsetAsync(b, 0, rows * (size_t)pw * sizeof(double), st));
     DSQ_HIP(hipMemcpyAsync(b, src, rows * (size_t)p * sizeof(double), hipMemcpyDeviceToDevice, st));
-    *out = (double *)b;
-    return DSQ_OK;
-}
-
-static int wide_pad_x(int m, int p, const double *x, hipStream_t st, const double **xout, unsigned long long *padmask) {
-    double *b;
-    int rc = wide_pad_matrix(WS_PAD_X, x, (size_t)m, p, st, &b);
-    if (rc) return rc;
-    *xout = b;
-    *padmask = dsq_low_bits(wide_width(p)) & ~dsq_low_bits(p);
+    *out = (const double *)b;
     return DSQ_OK;
 }
 
@@ -239,8 +229,7 @@ int fit_beta_dev_locked(const DsqFitBetaArgs *a, const DsqFitBetaOut *o, hipStre
     const int pk = wide ? wide_width(a->p) : a->p;       // the kernel's design width
     double *wide_out = nullptr;
     if (wide) {
-        unsigned long long padmask;
-        rc = wide_pad_x(a->m, a->p, a->x, st, &kp.x, &padmask); if (rc) return rc;
+        rc = capi_pad_design(WS_PAD_X, a->x, (size_t)a->m, a->p, pk, st, &kp.x); if (rc) return rc;
         static thread_local double ones[DSQ_P_WIDE];
         for (int c = 0; c < DSQ_P_WIDE; c++) ones[c] = 1.0;
         void *v;
@@ -337,9 +326,10 @@ static int disp_common(int n, int m, int p, int layout, long ld_in, const void *
     if (cell_of && ncell > 0 && p >= tuning().disp_cell_minp)
         kp->ncell = capi_upload_cells(cell_of, m, WS_CELLS_BETA, st, &kp->cell_perm, &kp->cell_start);
     if (is_wide(p)) {           // zero-padded design, unit diagonal on the padding in the Cox-Reid matrix
-        rc = wide_pad_x(m, p, x, st, &kp->x, &kp->padmask);
-        if (rc) return rc;
         kp->p = wide_width(p);
+        rc = capi_pad_design(WS_PAD_X, x, (size_t)m, p, kp->p, st, &kp->x);
+        if (rc) return rc;
+        kp->padmask = dsq_low_bits(kp->p) & ~dsq_low_bits(p);
     }
     return DSQ_OK;
 }

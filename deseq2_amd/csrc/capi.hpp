@@ -28,6 +28,9 @@ int prep_counts(const void *y, int y_type, int layout, long ld_in, int n, int m,
 int prep_matrix(const double *src, int layout, long ld_in, int n, int m, int slot, hipStream_t st,
                 const double **out, long ld_expected);
 int finish_ycheck(bool ycheck, hipStream_t st);
+// a zero-padded copy of a design in a workspace slot of the latched context: column-major rows x p -> rows x pw (memset,
+// then a device-to-device copy of the true columns, on `st`); the calls' wide designs and the chain's three use it
+int capi_pad_design(int slot, const double *src, size_t rows, int p, int pw, hipStream_t st, const double **out);
 int fit_beta_dev_locked(const DsqFitBetaArgs *a, const DsqFitBetaOut *o, hipStream_t st);
 int fit_disp_dev_locked(const DsqFitDispArgs *a, const DsqFitDispOut *o, hipStream_t st);
 int fit_disp_grid_dev_locked(const DsqFitDispGridArgs *a, const DsqFitDispGridOut *o, hipStream_t st);

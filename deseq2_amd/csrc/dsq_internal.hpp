@@ -298,6 +298,11 @@ struct Tuning {
     int dynamic;             // DSQ_DYNAMIC (default 1): dynamic gene scheduling in the fit kernels
     int beta_cells;          // DSQ_BETA_CELLS (default 1): cell-collapsed fitBeta for designs with <= DSQ_CMAX cells
     int disp_cell_minp;      // DSQ_DISP_CELL_MINP (profiling; default = the macro): fitDisp cell mode from this width up
+    // the chain (pipeline.hip)
+    int overlap;             // DSQ_OVERLAP (default 1): the test's full-row nbinomLogLike on a side stream beside the refit
+    int prior_var_one_block; // DSQ_PRIOR_VAR_ONE_BLOCK (default 0): the one-workgroup prior variance at every size
+    int lpt, lpt_maxn;       // DSQ_LPT (default 1), DSQ_LPT_MAXN (16384): longest-expected-first order of the fit_beta rows, up to n
+    int lpt_key2;            // DSQ_LPT_KEY2 (default 0) = 1: the test's fit is ordered by baseMean like the gene-wise one
 };
 const Tuning &tuning();
 
@@ -378,6 +383,9 @@ struct WsScope { explicit WsScope(hipStream_t s) { capi_latch_stream(s); } ~WsSc
 // (three slots between the call slots of capi.hip and the chain's: the padded reduced / prior design, the padded design, the
 //  prior-variance selection workspace)
 enum { DSQ_WS_PIPE_PADXR = 37, DSQ_WS_PIPE_PADX = 38, DSQ_WS_PIPE_SEL = 39 };
-enum { DSQ_WS_PIPE = 40, DSQ_WS_PIPE_SCRATCH = 41, DSQ_WS_PIPE_META = 42, DSQ_WS_HOSTDESEQ = 48, DSQ_WS_COUNT = 72 };
+// (DSQ_WS_PIPE_META: the trend fit's workspace; behind it the outlier tables, the design cells of the full and the reduced
+//  model, the reduced / prior fit's fitted means, the column sums behind xim)
+enum { DSQ_WS_PIPE = 40, DSQ_WS_PIPE_SCRATCH = 41, DSQ_WS_PIPE_META = 42, DSQ_WS_PIPE_OUTLIER_META = 43, DSQ_WS_PIPE_CELLS = 44,
+       DSQ_WS_PIPE_CELLS_RED = 45, DSQ_WS_PIPE_RED_MU = 46, DSQ_WS_PIPE_XIM_SCRATCH = 47, DSQ_WS_HOSTDESEQ = 48, DSQ_WS_COUNT = 72 };
 
 }  // namespace dsq

@@ -10,8 +10,7 @@
 // launches: no host decision, no device-to-host copy.  Every formula is evaluated with the operations of the
 // host mirror (deseq2_amd/core.py: IEEE + - * / sqrt, the engine's dlog / dexp, numpy's NaN-propagating
 // minimum / maximum), so the results equal the call-by-call chain bit for bit (tests/test_gpu_fused.py).
-#include "../../include/deseq2_mi355x.h"
-#include "dsq_internal.hpp"
+#include "capi.hpp"
 #include "dsq_math.hpp"
 #include "dsq_wave.hpp"
 
@@ -894,14 +893,28 @@ __global__ void __launch_bounds__(1024) lpt_order_kernel(Rows rw, const int32_t 
 // dynamic-scheduling counters, the ridge / contrast block): ~ 5 us of dependent dispatch each -- 0.11 ms of a 2.7 ms step
 // at one rank's share of C3.  The segments (4-byte aligned, word patterns) and the small block (by value) ride in the
 // kernel's arguments: no host buffer is read after the launch returns.
+// The result columns the gene-wise phase pre-fills, by pattern (rows that turn out all-zero keep it: 0xFF bytes are a NaN /
+// -1).  kInitSegMax counts the regions ONE call can ask for when no two of them are neighbours, so a column added to a
+// list below grows InitParams::seg with it.
+typedef double *DsqDeseqOut::*OutF64;
+typedef int32_t *DsqDeseqOut::*OutI32;
+static constexpr OutF64 kNaVectors[] = {&DsqDeseqOut::dispGeneEst, &DsqDeseqOut::dispFit, &DsqDeseqOut::dispMAP, &DsqDeseqOut::dispersion,
+                                        &DsqDeseqOut::betaIter, &DsqDeseqOut::logLike, &DsqDeseqOut::maxCooks, &DsqDeseqOut::logLikeReduced};
+static constexpr OutF64 kNaMatrices[] = {&DsqDeseqOut::beta, &DsqDeseqOut::betaSE, &DsqDeseqOut::stat, &DsqDeseqOut::pvalue};
+static constexpr OutI32 kNaInts[] = {&DsqDeseqOut::dispGeneIter, &DsqDeseqOut::dispIter, &DsqDeseqOut::dispOutlier, &DsqDeseqOut::betaConv};
+static constexpr OutI32 kZeroInts[] = {&DsqDeseqOut::replace, &DsqDeseqOut::optim_geneest, &DsqDeseqOut::optim_test};
+template <class T, size_t N> constexpr int count_of(T (&)[N]) { return (int)N; }
+static constexpr int kInitSegMax = 1 /* work counters */ + 1 /* status */ + count_of(kNaVectors) + count_of(kNaMatrices) + 1 /* mle_beta */ +
+                                   count_of(kNaInts) + count_of(kZeroInts) + 1 /* grid flags */ + 3 /* FIT_USED, trend fit, selection */;
 struct InitSeg { uint32_t *p; uint32_t words; uint32_t val; };
 struct InitParams {
     int nseg;
-    InitSeg seg[24];
+    InitSeg seg[kInitSegMax];
     double *blk_dst;
     int nblk;
     double blk[3 * DSQ_P_WIDE + 8];
 };
+static_assert(sizeof(InitParams) <= 4096, "InitParams rides in the kernel arguments");
 __global__ void __launch_bounds__(256) chain_init_kernel(InitParams q) {
     const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
     for (int s = 0; s < q.nseg; s++) {
@@ -954,7 +967,9 @@ struct Pipe {
     const int32_t *red_cell_perm, *red_cell_start;
     int red_ncell;
     int32_t *cells_dev;            // perm | in3 | cell_start | use3 | replaceable
-    void *trend_ws;
+    void *trend_ws, *sel_ws;       // the trend fit's barrier / partial-sum block and the selection workspace of the sixteen-
+                                   // workgroup prior variance, both zeroed by the init launch (nullptr: not used by this call)
+    int pkp, pmax;                 // the padded width of the beta-prior pass (0: none); the columns of the n x . work matrices
     int next_counter;
     const int32_t *cell_perm, *cell_start;   // design cells for the cell-collapsed fitBeta kernel (ncell = 0: general)
     int ncell;
@@ -990,6 +1005,22 @@ static int *next_work_counter(Pipe &P) {
 }
 
 static inline dim3 ew_grid(int n) { return dim3((unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1)); }
+
+// a row list that is expected to be short (stragglers, refits): neither the non-zero rows nor their longest-first order
+static inline int rows_few(const Pipe &P, const Rows &rw) { return (rw.rows && rw.rows != P.rows_nz && rw.rows != P.rows_lpt) ? 1 : 0; }
+
+// the fields the parameter blocks of the fit kernels share (everything else zero): shape, counts, normalization factors,
+// the weights of this launch when the analysis has any, the rows
+template <class KP>
+static KP fit_head(const Pipe &P, const Rows &rw, const int32_t *y, const double *weights) {
+    KP kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = P.n; kp.m = P.m; kp.ld = P.ld;
+    kp.y = y; kp.nf = P.a->nf; kp.nf_is_vector = P.a->nf_is_vector;
+    kp.weights = P.a->useWeights ? weights : nullptr; kp.useWeights = kp.weights ? 1 : 0;
+    kp.rows = rw.rows; kp.n_dev = rw.n_dev;
+    return kp;
+}
 
 static RuleParams rule_params(const Pipe &P, const Rows &rw) {
     RuleParams q;
@@ -1037,14 +1068,9 @@ static DesignSel design_of(const Pipe &P, int which) {
 static int launch_fit_beta(Pipe &P, const Rows &rw, const int32_t *y, const double *alpha, const double *weights,
                            double *mu_out, double mu_floor, double *hat, double tol, int maxit, int useQR, double minmu,
                            const char *name, int which = DES_FULL) {
-    const DsqDeseqArgs *a = P.a;
     const DesignSel ds = design_of(P, which);
-    BetaKernelParams kp;
-    memset(&kp, 0, sizeof kp);
-    kp.n = P.n; kp.m = P.m; kp.p = ds.p; kp.ld = P.ld;
-    kp.y = y; kp.nf = a->nf; kp.nf_is_vector = a->nf_is_vector;
-    kp.weights = a->useWeights ? weights : nullptr; kp.useWeights = a->useWeights ? 1 : 0;
-    kp.x = ds.x; kp.alpha_hat = alpha; kp.contrast = P.contrast;
+    BetaKernelParams kp = fit_head<BetaKernelParams>(P, rw, y, weights);
+    kp.p = ds.p; kp.x = ds.x; kp.alpha_hat = alpha; kp.contrast = P.contrast;
     kp.beta_init = ds.beta_init; kp.lambda = ds.lam;
     kp.tol = tol; kp.minmu = minmu; kp.mu_floor = mu_floor; kp.maxit = maxit; kp.useQR = useQR ? 1 : 0;
     kp.beta_mat = P.beta_nat; kp.beta_var_mat = P.beta_var; kp.iter = P.beta_iter;
@@ -1053,7 +1079,7 @@ static int launch_fit_beta(Pipe &P, const Rows &rw, const int32_t *y, const doub
     kp.kconst_out = P.kconst;            // K' of the rows this launch fits: the nbinomLogLike launch behind it reads it
     kp.scratch = P.scratch; kp.cscratch = P.cscratch;
     kp.work_counter = next_work_counter(P);
-    kp.rows = rw.rows; kp.n_dev = rw.n_dev; kp.rows_few = (rw.rows && rw.rows != P.rows_nz && rw.rows != P.rows_lpt) ? 1 : 0;
+    kp.rows_few = rows_few(P, rw);
     kp.cell_perm = ds.cperm; kp.cell_start = ds.cstart; kp.ncell = ds.ncell;
     kp.p_true = ds.p_true;
     bool ok = false;
@@ -1082,7 +1108,7 @@ static int launch_fit_disp(Pipe &P, const Rows &rw, const int32_t *y, const doub
     kp.weightThreshold = a->weightThreshold; kp.maxit = a->maxit;
     kp.usePrior = usePrior ? 1 : 0; kp.useCR = useCR ? 1 : 0;
     kp.work_counter = next_work_counter(P);
-    kp.rows = rw.rows; kp.n_dev = rw.n_dev; kp.rows_few = (rw.rows && rw.rows != P.rows_nz && rw.rows != P.rows_lpt) ? 1 : 0;
+    kp.rows = rw.rows; kp.n_dev = rw.n_dev; kp.rows_few = rows_few(P, rw);
     if (P.p >= tuning().disp_cell_minp) { kp.cell_perm = P.cell_perm; kp.cell_start = P.cell_start; kp.ncell = P.ncell; }
     if (grid) {
         kp.grid = a->disp_grid; kp.ngrid = a->ngrid; kp.log_alpha = P.la_grid;
@@ -1101,17 +1127,36 @@ static int launch_fit_disp(Pipe &P, const Rows &rw, const int32_t *y, const doub
     return DSQ_OK;
 }
 
+// the pre-fit kernels on the design itself: Q and X R^-1 of its QR factors, no outputs yet
+static PrefitKernelParams prefit_params(const Pipe &P, const Rows &rw, const int32_t *y, const double *weights = nullptr) {
+    PrefitKernelParams kp = fit_head<PrefitKernelParams>(P, rw, y, weights);
+    kp.p = P.p; kp.q = P.a->q; kp.a = P.a->a;
+    return kp;
+}
+// ... and, unweighted, on ANOTHER model matrix (nbinomLRT's reduced one, the intercept of the expanded prior design): the
+// start values go to beta_init, the moments to work vectors that nobody reads (but baseMean = P.cnum, prior_fit)
+static PrefitKernelParams prefit_other(const Pipe &P, const Rows &rw, const int32_t *y, int p, const double *q, const double *xr,
+                                       const double *r, double *beta_init) {
+    PrefitKernelParams kp = fit_head<PrefitKernelParams>(P, rw, y, nullptr);
+    kp.p = p; kp.q = q; kp.a = xr; kp.r = r;
+    kp.baseMean = P.cnum; kp.baseVar = P.cden; kp.roughDisp = P.dev; kp.allZero = P.opt_conv; kp.beta_init = beta_init;
+    return kp;
+}
+// nbinomLogLike of the rows at the fitted means `mu` and the final dispersions, K' from the fitBeta launch in front of it
+static LogLikeKernelParams loglike_params(const Pipe &P, const Rows &rw, const int32_t *y, const double *mu, double *out) {
+    LogLikeKernelParams lk;
+    memset(&lk, 0, sizeof lk);
+    lk.n = P.n; lk.m = P.m; lk.ld = P.ld; lk.y = y; lk.mu = mu; lk.disp = P.o->dispersion;
+    lk.weights = P.a->useWeights ? P.a->weights_norm : nullptr; lk.useWeights = P.a->useWeights ? 1 : 0;
+    lk.loglike = out; lk.rows = rw.rows; lk.n_dev = rw.n_dev; lk.kconst = P.kconst;
+    return lk;
+}
+
 static int launch_prefit_rows(Pipe &P, const Rows &rw, const int32_t *y) {
-    const DsqDeseqArgs *a = P.a;
-    PrefitKernelParams kp;
-    memset(&kp, 0, sizeof kp);
-    kp.n = P.n; kp.m = P.m; kp.p = P.p; kp.ld = P.ld;
-    kp.y = y; kp.nf = a->nf; kp.nf_is_vector = a->nf_is_vector;
-    kp.weights = a->useWeights ? a->weights_raw : nullptr; kp.useWeights = a->useWeights ? 1 : 0;
-    kp.q = a->q; kp.a = a->a; kp.r = a->r;
+    PrefitKernelParams kp = prefit_params(P, rw, y, P.a->weights_raw);
+    kp.r = P.a->r;
     kp.baseMean = P.o->baseMean; kp.baseVar = P.o->baseVar; kp.roughDisp = P.roughDisp; kp.beta_init = P.beta_init;
     kp.allZero = P.o->allZero;
-    kp.rows = rw.rows; kp.n_dev = rw.n_dev;
     bool ok = false;
     capi_prof_begin(rw.rows ? "prefit_moments:refit" : "prefit_moments", P.n, P.st);
     DSQ_HIP(launch_prefit(kp, P.st, &ok));
@@ -1137,21 +1182,16 @@ __global__ void copy_rows_cols_kernel(Rows rw, int n, int p, const double *src_a
 // logLike / fitted means written at the rows' own positions
 static int launch_optim(Pipe &P, int cnt_optim, const int32_t *y, const double *alpha, const double *weights, double minmu,
                         double mu_floor, double *beta, double *betaSE, double *loglike, double *mu_out, int which = DES_FULL) {
-    const DsqDeseqArgs *a = P.a;
     const DesignSel ds = design_of(P, which);
-    OptimKernelParams kp;
-    memset(&kp, 0, sizeof kp);
-    kp.n = P.n; kp.m = P.m; kp.p = ds.p; kp.ld = P.ld;
-    kp.y = y; kp.nf = a->nf; kp.nf_is_vector = a->nf_is_vector;
-    kp.weights = a->useWeights ? weights : nullptr; kp.useWeights = a->useWeights ? 1 : 0;
-    kp.x = ds.x; kp.alpha_hat = alpha; kp.lamnat = ds.lam; kp.beta_start = P.opt_start;
+    const Rows orw = {P.rows_opt, P.counters + cnt_optim, P.n};
+    OptimKernelParams kp = fit_head<OptimKernelParams>(P, orw, y, weights);
+    kp.p = ds.p; kp.x = ds.x; kp.alpha_hat = alpha; kp.lamnat = ds.lam; kp.beta_start = P.opt_start;
     kp.minmu = minmu; kp.mu_floor = mu_floor;
     // (a padded design: the kernel writes ds.p columns -- into the work matrices; the listed rows' true columns are copied
     //  to the caller's n x p matrices behind the launch)
     const bool via_work = ds.p != ds.p_true && which != DES_REDUCED && beta != P.opt_beta;     // (the reduced fit's coefficients are work matrices already)
     kp.beta = via_work ? P.opt_beta : beta; kp.betaSE = via_work ? P.opt_se : betaSE;
     kp.conv = P.opt_conv; kp.mu_out = mu_out; kp.loglike = loglike;
-    kp.rows = P.rows_opt; kp.n_dev = P.counters + cnt_optim;
     bool ok = false;
     char nm[32];
     snprintf(nm, sizeof nm, "optim_rows%s", P.tag);
@@ -1160,7 +1200,6 @@ static int launch_optim(Pipe &P, int cnt_optim, const int32_t *y, const double *
     capi_prof_end(P.st);
     if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "dsq_deseq_dev: no optim kernel for p=%d", P.p);
     if (via_work) {
-        const Rows orw = {P.rows_opt, P.counters + cnt_optim, P.n};
         hipLaunchKernelGGL(copy_rows_cols_kernel, dim3(16), dim3(256), 0, P.st, orw, P.n, ds.p_true, (const double *)P.opt_beta,
                            (const double *)P.opt_se, beta, betaSE);
         DSQ_HIP(hipGetLastError());
@@ -1172,9 +1211,7 @@ static int launch_optim(Pipe &P, int cnt_optim, const int32_t *y, const double *
 static Rows lpt_rows(Pipe &P, const Rows &rw, const int32_t *key_i, const double *key_d, int small_first = 0) {
     // only where it pays: below ~ 5 genes per resident wave slot (measured, C3 shapes: 6 250 genes fit_beta 0.305 -> 0.256 ms;
     // 50 000 genes: the launch gains 0.03 ms and the one-workgroup sort in front of it costs 0.1)
-    static const bool on = !(getenv("DSQ_LPT") && atoi(getenv("DSQ_LPT")) == 0);
-    static const int maxn = getenv("DSQ_LPT_MAXN") ? atoi(getenv("DSQ_LPT_MAXN")) : 16384;
-    if (!on || rw.rows != P.rows_nz || P.n > maxn) return rw;
+    if (!tuning().lpt || rw.rows != P.rows_nz || P.n > tuning().lpt_maxn) return rw;
     hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, P.st, rw, key_i, key_d, small_first, P.rows_lpt);
     return Rows{P.rows_lpt, rw.n_dev, rw.n};
 }
@@ -1187,14 +1224,9 @@ static int gene_est(Pipe &P, const Rows &rw, const int32_t *y, double *mu_hat, i
     hipLaunchKernelGGL(alpha_init_kernel, ew_grid(P.n), dim3(256), 0, P.st, q);
     int rc;
     if (a->linearMu) {
-        PrefitKernelParams kp;
-        memset(&kp, 0, sizeof kp);
-        kp.n = P.n; kp.m = P.m; kp.p = P.p; kp.ld = P.ld; kp.y = y; kp.nf = a->nf; kp.nf_is_vector = a->nf_is_vector;
-        kp.q = a->q; kp.a = a->a;
-        kp.rows = rw.rows; kp.n_dev = rw.n_dev;
         bool ok = false;
         capi_prof_begin("linear_mu", P.n, P.st);
-        DSQ_HIP(launch_linear_mu(kp, P.ge_floor, mu_hat, P.st, &ok));     // minmu of estimateDispersionsGeneEst (:763)
+        DSQ_HIP(launch_linear_mu(prefit_params(P, rw, y), P.ge_floor, mu_hat, P.st, &ok));     // minmu of estimateDispersionsGeneEst (:763)
         capi_prof_end(P.st);
         if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "dsq_deseq_dev: p=%d", P.p);
     } else {
@@ -1274,55 +1306,53 @@ static int mle_fit(Pipe &P, const Rows &rw, const int32_t *y, double *mu_out, do
     return DSQ_OK;
 }
 
+// what follows the IRLS of a test's GLM fit on the design `which`: beta_post (log2 scale, Wald columns, betaConv, the rows for
+// the optim fallback, R/fitNbinomGLMs.R:185-227) -> the fallback on those rows: coefficients, standard errors, logLike
+// (:398-399) and fitted means (:386) in place -> optim_post: betaConv and the Wald columns from them
+static int beta_post_optim(Pipe &P, const Rows &rw, const int32_t *y, int which, int wald, int cnt_optim, double *mu_out) {
+    const DsqDeseqOut *o = P.o;
+    const DesignSel ds = design_of(P, which);
+    RuleParams b = rule_params(P, rw);
+    b.p = ds.p_true; b.beta_init = ds.beta_init;
+    b.beta = o->beta; b.betaSE = o->betaSE; b.stat = o->stat; b.pvalue = o->pvalue; b.wald = wald;
+    b.betaConv = o->betaConv; b.betaIter_out = o->betaIter;
+    b.optim_flag = o->optim_test; b.optim_count = P.counters + cnt_optim;
+    hipLaunchKernelGGL(beta_post_kernel, ew_grid(P.n), dim3(256), 0, P.st, b);
+    if (which != DES_FULL && ds.p > ds.p_true)   // (columns p_true .. of the optim start values may hold another fit's: zero on the padding)
+        DSQ_HIP(hipMemsetAsync(P.opt_start + (size_t)P.n * ds.p_true, 0, (size_t)P.n * (ds.p - ds.p_true) * sizeof(double), P.st));
+    int rc = launch_optim(P, cnt_optim, y, o->dispersion, P.a->weights_norm, P.t_minmu, 0.0, o->beta, o->betaSE, o->logLike, mu_out, which);
+    if (rc) return rc;
+    const Rows orw = {P.rows_opt, P.counters + cnt_optim, P.n};
+    RuleParams ob = rule_params(P, orw);
+    ob.p = ds.p_true;
+    ob.beta = o->beta; ob.betaSE = o->betaSE; ob.stat = o->stat; ob.pvalue = o->pvalue; ob.wald = wald; ob.betaConv = o->betaConv;
+    hipLaunchKernelGGL(optim_post_kernel, dim3(16), dim3(256), 0, P.st, ob);
+    return DSQ_OK;
+}
+
 // ... and its second pass (:311-325): the fit with lambda = 1 / betaPriorVar on the standard or the expanded model
 // matrix; coefficients, standard errors, Wald statistics, betaConv, betaIter and logLike are this fit's
 static int prior_fit(Pipe &P, const Rows &rw, const int32_t *y, int cnt_optim) {
     const DsqDeseqArgs *a = P.a;
-    const DsqDeseqOut *o = P.o;
     int rc;
     if (a->prior_expanded) {
-        PrefitKernelParams pk;            // getBaseMeansAndVariances without weights on the intercept-only design
-        memset(&pk, 0, sizeof pk);
-        pk.n = P.n; pk.m = P.m; pk.p = 1; pk.ld = P.ld; pk.y = y; pk.nf = a->nf; pk.nf_is_vector = a->nf_is_vector;
-        pk.q = a->x_prior; pk.a = a->x_prior; pk.r = P.lam;                      // (only baseMean is read)
-        pk.baseMean = P.cnum; pk.baseVar = P.cden; pk.roughDisp = P.dev; pk.allZero = P.opt_conv; pk.beta_init = P.opt_ll;
-        pk.rows = rw.rows; pk.n_dev = rw.n_dev;
+        // getBaseMeansAndVariances without weights on the intercept-only design (only baseMean is read)
         bool ok = false;
-        DSQ_HIP(launch_prefit(pk, P.st, &ok));
+        DSQ_HIP(launch_prefit(prefit_other(P, rw, y, 1, a->x_prior, a->x_prior, P.lam, P.opt_ll), P.st, &ok));
         if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "dsq_deseq_dev: prefit p=1");
         hipLaunchKernelGGL(prior_start_kernel, ew_grid(P.n), dim3(256), 0, P.st, rw, P.n, a->p_prior, a->prior_intercept,
                            (const double *)P.cnum, P.red_binit);
         if (P.pri_pk > a->p_prior)        // (start values 0 on the padding of a wide expanded design)
             DSQ_HIP(hipMemsetAsync(P.red_binit + (size_t)P.n * a->p_prior, 0, (size_t)P.n * (P.pri_pk - a->p_prior) * sizeof(double), P.st));
     }
-    rc = launch_fit_beta(P, rw, y, o->dispersion, a->weights_norm, P.red_mu, 0.0, nullptr, P.t_tol, P.t_maxit, P.t_useQR,
+    rc = launch_fit_beta(P, rw, y, P.o->dispersion, a->weights_norm, P.red_mu, 0.0, nullptr, P.t_tol, P.t_maxit, P.t_useQR,
                          P.t_minmu, "fit_beta_prior", DES_PRIOR);
     if (rc) return rc;
-    LogLikeKernelParams lk;
-    memset(&lk, 0, sizeof lk);
-    lk.n = P.n; lk.m = P.m; lk.ld = P.ld; lk.y = y; lk.mu = P.red_mu; lk.disp = o->dispersion;
-    lk.weights = a->useWeights ? a->weights_norm : nullptr; lk.useWeights = a->useWeights ? 1 : 0;
-    lk.loglike = o->logLike; lk.rows = rw.rows; lk.n_dev = rw.n_dev; lk.kconst = P.kconst;
     capi_prof_begin(P.tag[0] ? "nbinom_loglike:refit" : "nbinom_loglike", P.n, P.st);
-    DSQ_HIP(launch_loglike(lk, P.st));
+    DSQ_HIP(launch_loglike(loglike_params(P, rw, y, P.red_mu, P.o->logLike), P.st));
     capi_prof_end(P.st);
-    const DesignSel ds = design_of(P, DES_PRIOR);
-    RuleParams b = rule_params(P, rw);
-    b.p = ds.p_true; b.beta_init = ds.beta_init;
-    b.beta = o->beta; b.betaSE = o->betaSE; b.stat = o->stat; b.pvalue = o->pvalue; b.wald = 1;
-    b.betaConv = o->betaConv; b.betaIter_out = o->betaIter;
-    b.optim_flag = o->optim_test; b.optim_count = P.counters + cnt_optim;
-    hipLaunchKernelGGL(beta_post_kernel, ew_grid(P.n), dim3(256), 0, P.st, b);
-    if (P.pri_pk > ds.p_true)             // (columns p_prior .. of the optim start values may hold another fit's: zero on the padding)
-        DSQ_HIP(hipMemsetAsync(P.opt_start + (size_t)P.n * ds.p_true, 0, (size_t)P.n * (P.pri_pk - ds.p_true) * sizeof(double), P.st));
-    rc = launch_optim(P, cnt_optim, y, o->dispersion, a->weights_norm, P.t_minmu, 0.0, o->beta, o->betaSE, o->logLike, P.red_mu,
-                      DES_PRIOR);
+    rc = beta_post_optim(P, rw, y, DES_PRIOR, 1, cnt_optim, P.red_mu);
     if (rc) return rc;
-    const Rows orw = {P.rows_opt, P.counters + cnt_optim, P.n};
-    RuleParams ob = rule_params(P, orw);
-    ob.p = ds.p_true;
-    ob.beta = o->beta; ob.betaSE = o->betaSE; ob.stat = o->stat; ob.pvalue = o->pvalue; ob.wald = 1; ob.betaConv = o->betaConv;
-    hipLaunchKernelGGL(optim_post_kernel, dim3(16), dim3(256), 0, P.st, ob);
     DSQ_HIP(hipGetLastError());
     return DSQ_OK;
 }
@@ -1360,66 +1390,38 @@ static int test_fit(Pipe &P, const Rows &rw, const int32_t *y, double *mu_out, d
     const DsqDeseqOut *o = P.o;
     if (a->betaPrior) return mle_fit(P, rw, y, mu_out, hat);         // (the prior fit follows once lambda is known)
     // (P.beta_iter: the iteration counts of the gene-wise estimate's IRLS on the same rows, when that fit ran)
-    static const bool by_mean = getenv("DSQ_LPT_KEY2") && atoi(getenv("DSQ_LPT_KEY2")) == 1;
+    const bool by_mean = tuning().lpt_key2 == 1;
     int rc = launch_fit_beta(P, by_mean ? lpt_rows(P, rw, nullptr, o->baseMean, 1) : (a->linearMu ? rw : lpt_rows(P, rw, nullptr, P.beta_iter)),
                              y, o->dispersion, a->weights_norm, mu_out, 0.0, hat,
                              P.t_tol, P.t_maxit, P.t_useQR, P.t_minmu, "fit_beta");
     if (rc) return rc;
-    LogLikeKernelParams lk;
-    memset(&lk, 0, sizeof lk);
-    lk.n = P.n; lk.m = P.m; lk.ld = P.ld; lk.y = y; lk.mu = mu_out; lk.disp = o->dispersion;
-    lk.weights = a->useWeights ? a->weights_norm : nullptr; lk.useWeights = a->useWeights ? 1 : 0;
-    lk.loglike = o->logLike; lk.rows = rw.rows; lk.n_dev = rw.n_dev; lk.kconst = P.kconst;
-    RuleParams b = rule_params(P, rw);
-    b.beta = o->beta; b.betaSE = o->betaSE; b.stat = o->stat; b.pvalue = o->pvalue; b.wald = (a->test == 0) ? 1 : 0;
-    b.betaConv = o->betaConv; b.betaIter_out = o->betaIter;
-    b.optim_flag = o->optim_test; b.optim_count = P.counters + cnt_optim;
+    LogLikeKernelParams lk = loglike_params(P, rw, y, mu_out, o->logLike);
     // OVERLAP (the main chain, when this call also runs the outlier phase): nothing on the way to the refit of the replaced
     // rows reads the log likelihoods -- beta_post / the optim fallback / Cook's distances / replaceOutliers / the refit's
     // own dispersion searches -- and the refit is latency, not throughput: a handful of rows, each one gene's serial search
-    // (~0.45 ms of a 12.8 ms step at C3 on an otherwise idle device).  So the full-row nbinomLogLike is DEFERRED: run_chain
+    // (~0.45 ms of a 12.8 ms step at C3 on an otherwise idle device).  So the full-row nbinomLogLike is DEFERRED: phase_refit
     // launches it on a side stream when the refit starts (beside Cook's distances, another full-size launch, it would only
-    // share the device: measured).  It leaves the rows flagged for the optim fallback alone (`skip`): the fallback
-    // writes their logLike (and rewrites their fitted means) itself, R/fitNbinomGLMs.R:386,398-399.  What it may read
-    // half-updated -- the dispersion of a row the refit is re-estimating -- only feeds that row's logLike, which the
-    // refit's own test fit writes after the join (run(): join_side before the refit's test_fit).
-    const bool overlap = P.overlap && !P.tag[0];
-    if (!overlap) {
+    // share the device: measured), run() behind everything else when there is no refit.  It leaves the rows flagged for the
+    // optim fallback alone (`skip`): the fallback writes their logLike (and rewrites their fitted means) itself,
+    // R/fitNbinomGLMs.R:386,398-399.  What it may read half-updated -- the dispersion of a row the refit is re-estimating --
+    // only feeds that row's logLike, which the refit's own test fit writes after the join (join_side before its test_fit).
+    if (P.overlap && !P.tag[0]) {
+        P.ll = lk;
+        P.ll.skip = o->optim_test;
+        P.ll_pending = true;
+    } else {
         capi_prof_begin(P.tag[0] ? "nbinom_loglike:refit" : "nbinom_loglike", P.n, P.st);
         DSQ_HIP(launch_loglike(lk, P.st));
         capi_prof_end(P.st);
     }
-    hipLaunchKernelGGL(beta_post_kernel, ew_grid(P.n), dim3(256), 0, P.st, b);
-    if (overlap) {
-        // (launched by run_chain: beside the refit of the replaced rows when there is one, else right behind this fit)
-        P.ll = lk;
-        P.ll.skip = o->optim_test;
-        P.ll_pending = true;
-    }
-    // rows for the optim fallback (R/fitNbinomGLMs.R:203-227): coefficients, standard errors, logLike (:398-399) and
-    // fitted means (:386) of those rows in place, then betaConv and the Wald columns from them
-    rc = launch_optim(P, cnt_optim, y, o->dispersion, a->weights_norm, P.t_minmu, 0.0, o->beta, o->betaSE, o->logLike, mu_out);
+    rc = beta_post_optim(P, rw, y, DES_FULL, (a->test == 0) ? 1 : 0, cnt_optim, mu_out);
     if (rc) return rc;
-    {
-        const Rows orw = {P.rows_opt, P.counters + cnt_optim, P.n};
-        RuleParams ob = rule_params(P, orw);
-        ob.beta = o->beta; ob.betaSE = o->betaSE; ob.stat = o->stat; ob.pvalue = o->pvalue; ob.wald = b.wald;
-        ob.betaConv = o->betaConv;
-        hipLaunchKernelGGL(optim_post_kernel, dim3(16), dim3(256), 0, P.st, ob);
-    }
     if (a->test == 1 && a->x_red) {
         // nbinomLRT's reduced fit (R/core.R:1856-1868): fitNbinomGLMs on the reduced model matrix at the same
         // dispersions -- QR start values, IRLS, logLik at its fitted means, its own optim-fallback rows
-        PrefitKernelParams pk;
-        memset(&pk, 0, sizeof pk);
-        pk.n = P.n; pk.m = P.m; pk.p = a->p_red; pk.ld = P.ld; pk.y = y; pk.nf = a->nf; pk.nf_is_vector = a->nf_is_vector;
-        pk.q = a->q_red; pk.a = a->a_red; pk.r = a->r_red;
-        pk.baseMean = P.cnum; pk.baseVar = P.cden; pk.roughDisp = P.dev; pk.allZero = P.opt_conv;      // (not read)
-        pk.beta_init = P.red_binit;
-        pk.rows = rw.rows; pk.n_dev = rw.n_dev;
         bool ok = false;
         capi_prof_begin(P.tag[0] ? "prefit_reduced:refit" : "prefit_reduced", P.n, P.st);
-        DSQ_HIP(launch_prefit(pk, P.st, &ok));
+        DSQ_HIP(launch_prefit(prefit_other(P, rw, y, a->p_red, a->q_red, a->a_red, a->r_red, P.red_binit), P.st, &ok));
         capi_prof_end(P.st);
         if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "dsq_deseq_dev: reduced design with p=%d", a->p_red);
         rc = launch_fit_beta(P, rw, y, o->dispersion, a->weights_norm, P.red_mu, 0.0, nullptr, P.t_tol, P.t_maxit, P.t_useQR,
@@ -1440,12 +1442,9 @@ static int test_fit(Pipe &P, const Rows &rw, const int32_t *y, double *mu_out, d
                           P.red_mu, DES_REDUCED);
         if (rc) return rc;
     } else if (a->test == 1) {
-        InterceptKernelParams ik;
-        memset(&ik, 0, sizeof ik);
-        ik.n = P.n; ik.m = P.m; ik.ld = P.ld; ik.y = y; ik.nf = a->nf; ik.nf_is_vector = a->nf_is_vector;
-        ik.weights = a->useWeights ? a->weights_norm : nullptr; ik.useWeights = a->useWeights ? 1 : 0;
+        InterceptKernelParams ik = fit_head<InterceptKernelParams>(P, rw, y, a->weights_norm);
         ik.alpha = o->dispersion; ik.beta_log2 = P.cnum; ik.betaSE = P.cden;      // not read by nbinomLRT
-        ik.loglike = o->logLikeReduced; ik.rows = rw.rows; ik.n_dev = rw.n_dev;
+        ik.loglike = o->logLikeReduced;
         ik.kconst = P.kconst;            // (the full model's fit of the same rows: same counts, dispersions, weights)
         capi_prof_begin("intercept_fit", P.n, P.st);
         DSQ_HIP(launch_intercept_fit(ik, P.st));
@@ -1488,7 +1487,7 @@ static int outlier_meta(const DsqDeseqArgs *a, int m, hipStream_t st, OutlierMet
         if (!repl[j]) all_rep = 0;
     }
     void *mv;
-    int rc = capi_upload_table(DSQ_WS_PIPE_META + 1, meta.data(), meta.size() * sizeof(int32_t), st, &mv);
+    int rc = capi_upload_table(DSQ_WS_PIPE_OUTLIER_META, meta.data(), meta.size() * sizeof(int32_t), st, &mv);
     if (rc) return rc;
     M->dperm = (int32_t *)mv; M->din3 = M->dperm + m; M->drepl = M->din3 + m; M->duse3 = M->drepl + m; M->dstart = M->duse3 + m;
     M->maxcell = maxcell; M->any3 = any3; M->all_rep = all_rep;
@@ -1517,48 +1516,38 @@ static int outlier_finish(Pipe &P, const Rows &nz, const Rows &rep, const Outlie
 
 static size_t align8(size_t v) { return (v + 7) & ~(size_t)7; }
 
-struct Carve {
-    size_t o_rough, o_binit, o_ainit, o_la0, o_laout, o_lchg, o_ilp, o_idlp, o_llp, o_ldlp, o_lagrid, o_ldfit, o_lainit,
-        o_bnat, o_bvar, o_biter, o_cnum, o_cden, o_dev, o_lam, o_res, o_tm, o_td, o_robust, o_ostart, o_obeta, o_ose, o_oll, o_rbinit, o_rbeta, o_rse, o_kc, dbl;
-    size_t i_iter, i_itacc, i_gflag, i_nz, i_grid, i_rep, i_refit, i_cnt, i_wc, i_opt, i_oconv, i_lpt, ints;
-    size_t bytes;
+// ---- the caller's workspace, stated ONCE: every vector of it, in layout order, with its length ----------------------
+// The walker below visits the table twice: without a base to size the workspace (dsq_deseq_workspace_bytes, ABI) and with
+// one to bind the Pipe's pointers.  Every entry starts on a multiple of 8 elements; all doubles come first, the int32
+// entries follow them (so the int base is known when the first of them is visited); 256 spare bytes close it.  The row
+// lists and counters persist between the phases of one analysis.  p: the columns of the n x . work matrices.
+struct WsWalk {
+    double *D;                     // nullptr: size only
+    size_t d = 0, i = 0;           // doubles / int32s taken so far
+    void operator()(double *&f, size_t k) { if (D) f = D + d; d += align8(k); }
+    void operator()(int32_t *&f, size_t k) { if (D) f = (int32_t *)(D + d) + i; i += align8(k); }
+    size_t bytes() const { return d * sizeof(double) + i * sizeof(int32_t) + 256; }
 };
-
-static Carve carve(int n, int p, int nt) {
-    Carve c;
+static size_t workspace_table(Pipe &P, int n, int p, int nt, double *base) {
     const size_t nd = align8((size_t)n), np_ = align8((size_t)n * p), ntd = align8((size_t)nt);
-    size_t d = 0;
-    auto takeD = [&](size_t k) { size_t off = d; d += align8(k); return off; };
-    c.o_rough = takeD(nd); c.o_binit = takeD(np_); c.o_ainit = takeD(nd); c.o_la0 = takeD(nd); c.o_laout = takeD(nd);
-    c.o_lchg = takeD(nd); c.o_ilp = takeD(nd); c.o_idlp = takeD(nd); c.o_llp = takeD(nd); c.o_ldlp = takeD(nd);
-    c.o_lagrid = takeD(nd); c.o_ldfit = takeD(nd); c.o_lainit = takeD(nd); c.o_bnat = takeD(np_); c.o_bvar = takeD(np_);
-    c.o_biter = takeD(nd); c.o_cnum = takeD(nd); c.o_cden = takeD(nd); c.o_dev = takeD(nd); c.o_lam = takeD(3 * (size_t)p + 8);
-    c.o_res = takeD(ntd); c.o_tm = takeD(ntd); c.o_td = takeD(ntd); c.o_robust = takeD(nd);
-    c.o_ostart = takeD(np_); c.o_obeta = takeD(np_); c.o_ose = takeD(np_); c.o_oll = takeD(nd);
-    c.o_rbinit = takeD(np_); c.o_rbeta = takeD(np_); c.o_rse = takeD(np_);
-    c.o_kc = takeD(nd);
-    c.dbl = d;
-    size_t i = 0;
-    auto takeI = [&](size_t k) { size_t off = i; i += align8(k); return off; };
-    c.i_iter = takeI(nd); c.i_itacc = takeI(nd); c.i_gflag = takeI(nd); c.i_nz = takeI(nd); c.i_grid = takeI(nd);
-    c.i_rep = takeI(nd); c.i_refit = takeI(nd); c.i_cnt = takeI(16); c.i_wc = takeI(64);
-    c.i_opt = takeI(nd); c.i_oconv = takeI(nd);
-    c.i_lpt = takeI(nd);
-    c.ints = i;
-    c.bytes = d * sizeof(double) + i * sizeof(int32_t) + 256;
-    return c;
+    WsWalk v{base};
+    v(P.roughDisp, nd); v(P.beta_init, np_); v(P.alpha_init, nd); v(P.la0, nd); v(P.la_out, nd);
+    v(P.last_change, nd); v(P.initial_lp, nd); v(P.initial_dlp, nd); v(P.last_lp, nd); v(P.last_dlp, nd);
+    v(P.la_grid, nd); v(P.log_dfit, nd); v(P.la_init, nd); v(P.beta_nat, np_); v(P.beta_var, np_);
+    v(P.beta_iter, nd); v(P.cnum, nd); v(P.cden, nd); v(P.dev, nd);
+    v(P.lam, 3 * (size_t)p + 8);   // lam | contrast | lam_prior, p each, and the two xim scalars behind them
+    v(P.resbuf, ntd); v(P.trend_mean_c, ntd); v(P.trend_disp_c, ntd); v(P.robustDisp, nd);
+    v(P.opt_start, np_); v(P.opt_beta, np_); v(P.opt_se, np_); v(P.opt_ll, nd);
+    v(P.red_binit, np_); v(P.red_beta, np_); v(P.red_se, np_); v(P.kconst, nd);
+    int32_t *spare;                // (16 ints: the row-list counters lived here before they became the caller's status block)
+    v(P.iter, nd); v(P.iter_accept, nd); v(P.grid_flag, nd); v(P.rows_nz, nd); v(P.rows_grid, nd);
+    v(P.rows_rep, nd); v(P.rows_refit, nd); v(spare, 16); v(P.work_counters, 64);
+    v(P.rows_opt, nd); v(P.opt_conv, nd); v(P.rows_lpt, nd);
+    return v.bytes();
 }
 
-static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st, Pipe &P);
-static int run(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st) {
-    Pipe P;
-    memset(&P, 0, sizeof P);
-    const int rc = run_chain(a, o, st, P);
-    const int rl = rc ? DSQ_OK : launch_pending_ll(P, false);      // (no refit in this analysis: behind everything else)
-    const int rj = join_side(P);             // (whatever path the chain left by: nothing stays in flight beside `st`)
-    return rc ? rc : (rl ? rl : rj);
-}
-static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st, Pipe &P) {
+// every validation in front of the first look at the device
+static int check_args(const DsqDeseqArgs *a, const DsqDeseqOut *o) {
     if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
     if (a->n < 1 || a->m < 2 || a->p < 1 || a->m <= a->p) return capi_fail(DSQ_ERR_ARG, "bad dimensions n=%d m=%d p=%d", a->n, a->m, a->p);
     if (a->p > DSQ_P_WIDE) return capi_fail(DSQ_ERR_UNSUPPORTED, "dsq_deseq_dev: p=%d > %d design columns", a->p, DSQ_P_WIDE);
@@ -1597,356 +1586,358 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
     if (a->test == 0 && (!o->stat || !o->pvalue)) return capi_fail(DSQ_ERR_ARG, "Wald test needs stat / pvalue outputs");
     if (a->test == 1 && !o->logLikeReduced) return capi_fail(DSQ_ERR_ARG, "LRT needs logLikeReduced");
     if ((a->phases & (DSQ_PH_OUTLIERS | DSQ_PH_OUTLIERS_DETECT | DSQ_PH_OUTLIERS_REFIT | DSQ_PH_FINISH)) && (!a->cell_of || !a->replaceable || a->ncell < 1)) return capi_fail(DSQ_ERR_ARG, "outlier phase needs cell_of / replaceable");
-    int rc = capi_check_device();
-    if (rc) return rc;
+    return DSQ_OK;
+}
 
+// the call's settings, the caller's workspace (workspace_table) and the fit kernels' scratch slot -> P
+static int bind(Pipe &P, const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st) {
     P.a = a; P.o = o; P.st = st; P.tag = "";
     P.t_tol = a->betaTol; P.t_maxit = a->betaMaxit; P.t_useQR = a->useQR; P.t_minmu = a->minmu; P.ge_floor = a->minmu;
-    {
-        // (see test_fit) only when the test's fit and the outlier phase are enqueued by this one call; the profiling passes
-        // time every launch on one stream; DSQ_OVERLAP=0 switches it off
-        static const bool env_on = !(getenv("DSQ_OVERLAP") && atoi(getenv("DSQ_OVERLAP")) == 0);
-        P.overlap = env_on && !capi_prof_on() && !a->betaPrior && (a->phases & DSQ_PH_MAP_TEST) && (a->phases & DSQ_PH_OUTLIERS);
-        if (P.overlap && capi_side_stream(&P.side, &P.ev_fork, &P.ev_join) != DSQ_OK) P.overlap = false;
-    }
-    const int n = P.n = a->n, m = P.m = a->m, p = P.p = a->p;
-    P.ld = a->ld;
+    // (see test_fit) only when the test's fit and the outlier phase are enqueued by this one call; the profiling passes
+    // time every launch on one stream; DSQ_OVERLAP=0 switches it off
+    P.overlap = tuning().overlap && !capi_prof_on() && !a->betaPrior && (a->phases & DSQ_PH_MAP_TEST) && (a->phases & DSQ_PH_OUTLIERS);
+    if (P.overlap && capi_side_stream(&P.side, &P.ev_fork, &P.ev_join) != DSQ_OK) P.overlap = false;
+    const int n = P.n = a->n, m = P.m = a->m;
+    P.p = a->p; P.ld = a->ld;
     P.maxDisp = m > 10 ? (double)m : 10.0;
     P.min_log_alpha = a->min_log_alpha;
-    // ---- workspace carve (caller-owned: the row lists and counters persist between the phases of an analysis)
+    P.pk = kern_width(a->p);
+    P.pkp = a->betaPrior ? kern_width(a->p_prior) : 0;
+    P.pmax = P.pkp > P.pk ? P.pkp : P.pk;
     const int nt_cap = a->n_trend > n ? a->n_trend : n;      // (n_trend is the capacity even in the phases without a trend)
-    const int pk = P.pk = kern_width(p);
-    const int pkp = a->betaPrior ? kern_width(a->p_prior) : 0;
-    const int pmax = pkp > pk ? pkp : pk;                                     // columns of the n x . work matrices
-    Carve cv = carve(n, pmax, nt_cap);
-    if (!a->workspace || a->workspace_bytes < (int64_t)cv.bytes)
-        return capi_fail(DSQ_ERR_ARG, "workspace of %lld bytes, dsq_deseq_workspace_bytes() asks for %zu",
-                         (long long)a->workspace_bytes, cv.bytes);
-    double *D = (double *)a->workspace;
-    int32_t *I = (int32_t *)(D + cv.dbl);
-    P.roughDisp = D + cv.o_rough; P.beta_init = D + cv.o_binit; P.alpha_init = D + cv.o_ainit; P.la0 = D + cv.o_la0;
-    P.la_out = D + cv.o_laout; P.last_change = D + cv.o_lchg; P.initial_lp = D + cv.o_ilp; P.initial_dlp = D + cv.o_idlp;
-    P.last_lp = D + cv.o_llp; P.last_dlp = D + cv.o_ldlp; P.la_grid = D + cv.o_lagrid; P.log_dfit = D + cv.o_ldfit;
-    P.la_init = D + cv.o_lainit; P.beta_nat = D + cv.o_bnat; P.beta_var = D + cv.o_bvar; P.beta_iter = D + cv.o_biter;
-    P.cnum = D + cv.o_cnum; P.cden = D + cv.o_cden; P.dev = D + cv.o_dev;
-    P.lam = D + cv.o_lam; P.contrast = P.lam + pmax; P.lam_prior = P.contrast + pmax; P.xim_dev = P.lam + 3 * (size_t)pmax; P.xim_cur = P.xim_dev;
-    P.resbuf = D + cv.o_res; P.trend_mean_c = D + cv.o_tm; P.trend_disp_c = D + cv.o_td; P.robustDisp = D + cv.o_robust;
-    P.iter = I + cv.i_iter; P.iter_accept = I + cv.i_itacc; P.grid_flag = I + cv.i_gflag; P.rows_nz = I + cv.i_nz;
-    P.rows_grid = I + cv.i_grid; P.rows_rep = I + cv.i_rep; P.rows_refit = I + cv.i_refit; P.counters = o->status;
-    P.work_counters = I + cv.i_wc;
-    P.opt_start = D + cv.o_ostart; P.opt_beta = D + cv.o_obeta; P.opt_se = D + cv.o_ose; P.opt_ll = D + cv.o_oll;
-    P.rows_opt = I + cv.i_opt; P.opt_conv = I + cv.i_oconv;
-    P.rows_lpt = I + cv.i_lpt;
-    P.red_binit = D + cv.o_rbinit; P.red_beta = D + cv.o_rbeta; P.red_se = D + cv.o_rse;
-    P.kconst = D + cv.o_kc;
-    {
-        size_t slab_d = 0, cscr_d = 0;
-        dispatch_beta_scratch(pk, n, m, a->useWeights, &slab_d, &cscr_d);
-        if (a->x_red || a->betaPrior) {
-            size_t s2 = 0, c2 = 0;
-            dispatch_beta_scratch(a->betaPrior ? pkp : kern_width(a->p_red), n, m, a->useWeights, &s2, &c2);
-            if (s2 > slab_d) slab_d = s2;
-            if (c2 > cscr_d) cscr_d = c2;
-        }
-        void *b;
-        rc = capi_ws_get(DSQ_WS_PIPE_SCRATCH, (slab_d + cscr_d) * sizeof(double) + 64, &b);
-        if (rc) return rc;
-        P.scratch = (double *)b; P.cscratch = (double *)b + slab_d;
+    const size_t need = workspace_table(P, n, P.pmax, nt_cap, nullptr);
+    if (!a->workspace || a->workspace_bytes < (int64_t)need)
+        return capi_fail(DSQ_ERR_ARG, "workspace of %lld bytes, dsq_deseq_workspace_bytes() asks for %zu", (long long)a->workspace_bytes, need);
+    workspace_table(P, n, P.pmax, nt_cap, (double *)a->workspace);
+    P.contrast = P.lam + P.pmax; P.lam_prior = P.contrast + P.pmax; P.xim_dev = P.lam + 3 * (size_t)P.pmax; P.xim_cur = P.xim_dev;
+    P.counters = o->status;
+    size_t slab_d = 0, cscr_d = 0;
+    dispatch_beta_scratch(P.pk, n, m, a->useWeights, &slab_d, &cscr_d);
+    if (a->x_red || a->betaPrior) {
+        size_t s2 = 0, c2 = 0;
+        dispatch_beta_scratch(a->betaPrior ? P.pkp : kern_width(a->p_red), n, m, a->useWeights, &s2, &c2);
+        if (s2 > slab_d) slab_d = s2;
+        if (c2 > cscr_d) cscr_d = c2;
     }
-    // ONE launch for every fill this call needs in front of its first kernel (chain_init_kernel): the dynamic-scheduling
-    // counters of the fit launches of THIS call, the ridge (R/fitNbinomGLMs.R:73,162) / default contrast (R/wrappers.R:105-108)
-    // / prior block, and -- gene-wise phase -- the NA patterns of the result columns and the status block
-    static thread_local InitParams ip;
-    ip.nseg = 0; ip.nblk = 0;
-    auto fill_words = [&](void *p_, size_t bytes, uint32_t val) {
+    void *b;
+    int rc = capi_ws_get(DSQ_WS_PIPE_SCRATCH, (slab_d + cscr_d) * sizeof(double) + 64, &b);
+    if (rc) return rc;
+    P.scratch = (double *)b; P.cscratch = (double *)b + slab_d;
+    return DSQ_OK;
+}
+
+// one more region for chain_init_kernel; neighbouring regions with the same pattern are one segment.  kInitSegMax is
+// every region a call can ask for, so the bound cannot be met (`full` would say so at the launch)
+struct InitFills {
+    InitParams ip;
+    bool full;
+    void add(void *p_, size_t bytes, uint32_t val) {
         if (!p_ || !bytes) return;
-        // neighbouring regions with the same pattern are one segment
-        if (ip.nseg && ip.seg[ip.nseg - 1].val == val && (char *)ip.seg[ip.nseg - 1].p + 4 * (size_t)ip.seg[ip.nseg - 1].words == (char *)p_ &&
-            (size_t)ip.seg[ip.nseg - 1].words + bytes / 4 < 0xFFFFFFFFull) { ip.seg[ip.nseg - 1].words += (uint32_t)(bytes / 4); return; }
-        ip.seg[ip.nseg++] = {(uint32_t *)p_, (uint32_t)(bytes / 4), val};
-    };
-    fill_words(P.work_counters, 64 * sizeof(int32_t), 0u);
+        InitSeg *last = ip.nseg ? &ip.seg[ip.nseg - 1] : nullptr;
+        if (last && last->val == val && (char *)last->p + 4 * (size_t)last->words == (char *)p_ && (size_t)last->words + bytes / 4 < 0xFFFFFFFFull)
+            last->words += (uint32_t)(bytes / 4);
+        else if (ip.nseg < kInitSegMax) ip.seg[ip.nseg++] = {(uint32_t *)p_, (uint32_t)(bytes / 4), val};
+        else full = true;
+    }
+};
+
+// ONE launch for every fill this call needs in front of its first kernel (chain_init_kernel): the dynamic-scheduling
+// counters of the fit launches of THIS call, the ridge (R/fitNbinomGLMs.R:73,162) / default contrast (R/wrappers.R:105-108)
+// / prior block, -- gene-wise phase -- the NA patterns of the result columns and the status block, -- trend phase -- the
+// workspaces of the trend fit and of the sixteen-workgroup prior variance (fetched here, and only here)
+static int launch_init_fills(Pipe &P) {
+    const DsqDeseqArgs *a = P.a;
+    const DsqDeseqOut *o = P.o;
+    const int n = P.n, p = P.p, pmax = P.pmax;
+    static thread_local InitFills f;
+    InitParams &ip = f.ip;
+    ip.nseg = 0; f.full = false;
+    f.add(P.work_counters, 64 * sizeof(int32_t), 0u);
     for (int c = 0; c < pmax; c++) {
-        ip.blk[c] = c < p ? a->lambda[c] : (c < pk ? 1.0 : 0.0);          // (ridge 1 on the padding of a wide design)
+        ip.blk[c] = c < p ? a->lambda[c] : (c < P.pk ? 1.0 : 0.0);          // (ridge 1 on the padding of a wide design)
         ip.blk[pmax + c] = (c == 0) ? 1.0 : 0.0;
-        ip.blk[2 * pmax + c] = (a->betaPrior && a->lambda_prior) ? (c < a->p_prior ? a->lambda_prior[c] : (c < pkp ? 1.0 : 0.0)) : 0.0;
+        ip.blk[2 * pmax + c] = (a->betaPrior && a->lambda_prior) ? (c < a->p_prior ? a->lambda_prior[c] : (c < P.pkp ? 1.0 : 0.0)) : 0.0;
         if (a->x_red) ip.blk[2 * pmax + c] = c < a->p_red ? a->lambda[c] : (c < kern_width(a->p_red) ? 1.0 : 0.0);
     }
     ip.blk_dst = P.lam; ip.nblk = 3 * pmax;
-    const bool with_gene_est = (a->phases & DSQ_PH_GENE_EST) != 0;
-    if (with_gene_est) {
-        // results of rows that turn out all-zero stay NA: 0xFF bytes are a NaN / -1.  The outputs of a caller usually sit
-        // side by side (packed blocks): sorted by address, neighbours with the same pattern merge
+    if (a->phases & DSQ_PH_GENE_EST) {
+        // the outputs of a caller usually sit side by side (packed blocks): sorted by address, neighbours with the same
+        // pattern merge
         struct Fill { char *p; size_t bytes; uint32_t val; };
         std::vector<Fill> fills;
         auto fill = [&](void *p_, size_t bytes, uint32_t val) { if (p_ && bytes) fills.push_back({(char *)p_, bytes, val}); };
         fill(o->status, DSQ_ST_COUNT * sizeof(int32_t), 0u);
-        for (double *v : {o->dispGeneEst, o->dispFit, o->dispMAP, o->dispersion, o->betaIter, o->logLike, o->maxCooks, o->logLikeReduced})
-            fill(v, (size_t)n * sizeof(double), 0xFFFFFFFFu);
-        for (double *v : {o->beta, o->betaSE, o->stat, o->pvalue})
-            fill(v, (size_t)n * (a->betaPrior ? a->p_prior : p) * sizeof(double), 0xFFFFFFFFu);
+        for (OutF64 v : kNaVectors) fill(o->*v, (size_t)n * sizeof(double), 0xFFFFFFFFu);
+        for (OutF64 v : kNaMatrices) fill(o->*v, (size_t)n * (a->betaPrior ? a->p_prior : p) * sizeof(double), 0xFFFFFFFFu);
         if (a->betaPrior) fill(o->mle_beta, (size_t)n * p * sizeof(double), 0xFFFFFFFFu);
-        for (int32_t *v : {o->dispGeneIter, o->dispIter, o->dispOutlier, o->betaConv}) fill(v, (size_t)n * sizeof(int32_t), 0xFFFFFFFFu);
-        for (int32_t *v : {o->replace, o->optim_geneest, o->optim_test, P.grid_flag}) fill(v, (size_t)n * sizeof(int32_t), 0u);
+        for (OutI32 v : kNaInts) fill(o->*v, (size_t)n * sizeof(int32_t), 0xFFFFFFFFu);
+        for (OutI32 v : kZeroInts) fill(o->*v, (size_t)n * sizeof(int32_t), 0u);
+        fill(P.grid_flag, (size_t)n * sizeof(int32_t), 0u);
         std::sort(fills.begin(), fills.end(), [](const Fill &x, const Fill &y) { return x.p < y.p; });
-        for (const Fill &f : fills) {
-            if (ip.nseg >= 23) return capi_fail(DSQ_ERR_ARG, "dsq_deseq_dev: the result columns lie in more than 23 separate regions");
-            fill_words(f.p, f.bytes, f.val);
-        }
+        for (const Fill &fl : fills) f.add(fl.p, fl.bytes, fl.val);
     }
-    if (a->phases & DSQ_PH_TREND) fill_words(o->scalars + DSQ_SC_FIT_USED, sizeof(double), 0u);     // 0.0 = DSQ_FIT_PARAMETRIC
-    void *tws_zeroed = nullptr;          // the trend fit's barrier / partial-sum block, zeroed by the same launch
-    if ((a->phases & DSQ_PH_TREND) && !a->dispFit_in && a->fitType != DSQ_FIT_MEAN) {
-        rc = capi_ws_get(DSQ_WS_PIPE_META, trend_fit_workspace_bytes() + 64, &tws_zeroed);
-        if (rc) return rc;
-        fill_words(tws_zeroed, (trend_fit_workspace_bytes() + 3) / 4 * 4, 0u);
-    }
-    void *sws_zeroed = nullptr;          // ... and the selection workspace of the sixteen-workgroup prior variance
     if (a->phases & DSQ_PH_TREND) {
-        static const int one_block = getenv("DSQ_PRIOR_VAR_ONE_BLOCK") ? atoi(getenv("DSQ_PRIOR_VAR_ONE_BLOCK")) : 0;
-        const int nt_ = a->trend_mean ? a->n_trend : n;
-        if (!(one_block || nt_ < 16384)) {     // (6 250 genes: 0.116 ms on one workgroup, 0.146 on sixteen; 50 000: 0.243 / 0.124)
-            rc = capi_ws_get(DSQ_WS_PIPE_SEL, prior_var_workspace_bytes() + 64, &sws_zeroed);
-            if (rc) return rc;
-            fill_words(sws_zeroed, (prior_var_workspace_bytes() + 3) / 4 * 4, 0u);
+        f.add(o->scalars + DSQ_SC_FIT_USED, sizeof(double), 0u);     // 0.0 = DSQ_FIT_PARAMETRIC
+        int rc;
+        if (!a->dispFit_in && a->fitType != DSQ_FIT_MEAN) {
+            if ((rc = capi_ws_get(DSQ_WS_PIPE_META, trend_fit_workspace_bytes() + 64, &P.trend_ws))) return rc;
+            f.add(P.trend_ws, (trend_fit_workspace_bytes() + 3) / 4 * 4, 0u);
+        }
+        const int nt = a->trend_mean ? a->n_trend : n;
+        if (!(tuning().prior_var_one_block || nt < 16384)) {     // (6 250 genes: 0.116 ms on one workgroup, 0.146 on sixteen; 50 000: 0.243 / 0.124)
+            if ((rc = capi_ws_get(DSQ_WS_PIPE_SEL, prior_var_workspace_bytes() + 64, &P.sel_ws))) return rc;
+            f.add(P.sel_ws, (prior_var_workspace_bytes() + 3) / 4 * 4, 0u);
         }
     }
-    {
-        size_t words = 0;
-        for (int sgi = 0; sgi < ip.nseg; sgi++) words += ip.seg[sgi].words;
-        unsigned blocks = (unsigned)((words + 256 * 8 - 1) / (256 * 8));
-        if (blocks < 1) blocks = 1;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(chain_init_kernel, dim3(blocks), dim3(256), 0, st, ip);
-        DSQ_HIP(hipGetLastError());
-    }
-    P.x_k = a->x; P.padmask = 0;
+    if (f.full) return capi_fail(DSQ_ERR_DEVICE, "dsq_deseq_dev: more than %d init segments", kInitSegMax);
+    size_t words = 0;
+    for (int sgi = 0; sgi < ip.nseg; sgi++) words += ip.seg[sgi].words;
+    unsigned blocks = (unsigned)((words + 256 * 8 - 1) / (256 * 8));
+    if (blocks < 1) blocks = 1;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(chain_init_kernel, dim3(blocks), dim3(256), 0, P.st, ip);
+    DSQ_HIP(hipGetLastError());
+    return DSQ_OK;
+}
+
+// the three designs at their kernels' widths (wide ones: zero-padded copies), the design cells, the reduced / prior fit's
+// fitted means
+static int prepare_designs(Pipe &P) {
+    const DsqDeseqArgs *a = P.a;
+    const int n = P.n, m = P.m, p = P.p, pk = P.pk;
+    hipStream_t st = P.st;
+    int rc;
+    P.x_k = a->x;
     if (pk > p) {
-        // the design zero-padded to the kernels' width; the padded columns of the start values (the moments kernel writes
-        // the true p columns) and of the optim start values are zero
-        void *b;
-        rc = capi_ws_get(DSQ_WS_PIPE_PADX, (size_t)m * pk * sizeof(double), &b);
-        if (rc) return rc;
-        DSQ_HIP(hipMemsetAsync(b, 0, (size_t)m * pk * sizeof(double), st));
-        DSQ_HIP(hipMemcpyAsync(b, a->x, (size_t)m * p * sizeof(double), hipMemcpyDeviceToDevice, st));
-        P.x_k = (const double *)b;
+        // the padded columns of the start values (the moments kernel writes the true p columns) and of the optim start
+        // values are zero
+        if ((rc = capi_pad_design(DSQ_WS_PIPE_PADX, a->x, m, p, pk, st, &P.x_k))) return rc;
         P.padmask = dsq_low_bits(pk) & ~dsq_low_bits(p);
         DSQ_HIP(hipMemsetAsync(P.beta_init + (size_t)n * p, 0, (size_t)n * (pk - p) * sizeof(double), st));
         DSQ_HIP(hipMemsetAsync(P.opt_start + (size_t)n * p, 0, (size_t)n * (pk - p) * sizeof(double), st));
     }
-    P.red_x_k = a->x_red; P.red_pk = a->x_red ? a->p_red : 0; P.red_lam = a->x_red ? P.lam_prior : P.lam;
-    if (a->x_red && kern_width(a->p_red) > a->p_red) {
+    P.red_x_k = a->x_red; P.red_pk = a->x_red ? kern_width(a->p_red) : 0; P.red_lam = a->x_red ? P.lam_prior : P.lam;
+    if (P.red_pk > a->p_red) {
         // the reduced design at its own padded width; the padded columns of its start values are zero (the moments kernel
         // writes the true p_red columns; those of the optim start values are cleared in front of the reduced fit)
-        const int pkr = kern_width(a->p_red);
-        void *b;
-        rc = capi_ws_get(DSQ_WS_PIPE_PADXR, (size_t)m * pkr * sizeof(double), &b);
-        if (rc) return rc;
-        DSQ_HIP(hipMemsetAsync(b, 0, (size_t)m * pkr * sizeof(double), st));
-        DSQ_HIP(hipMemcpyAsync(b, a->x_red, (size_t)m * a->p_red * sizeof(double), hipMemcpyDeviceToDevice, st));
-        P.red_x_k = (const double *)b; P.red_pk = pkr;
-        DSQ_HIP(hipMemsetAsync(P.red_binit + (size_t)n * a->p_red, 0, (size_t)n * (pkr - a->p_red) * sizeof(double), st));
+        if ((rc = capi_pad_design(DSQ_WS_PIPE_PADXR, a->x_red, m, a->p_red, P.red_pk, st, &P.red_x_k))) return rc;
+        DSQ_HIP(hipMemsetAsync(P.red_binit + (size_t)n * a->p_red, 0, (size_t)n * (P.red_pk - a->p_red) * sizeof(double), st));
     }
-    P.pri_x_k = a->x_prior; P.pri_pk = a->betaPrior ? a->p_prior : 0;
-    if (a->betaPrior && pkp > a->p_prior) {
-        void *b;
-        rc = capi_ws_get(DSQ_WS_PIPE_PADXR, (size_t)m * pkp * sizeof(double), &b);      // (never beside a reduced model: Wald only)
-        if (rc) return rc;
-        DSQ_HIP(hipMemsetAsync(b, 0, (size_t)m * pkp * sizeof(double), st));
-        DSQ_HIP(hipMemcpyAsync(b, a->x_prior, (size_t)m * a->p_prior * sizeof(double), hipMemcpyDeviceToDevice, st));
-        P.pri_x_k = (const double *)b; P.pri_pk = pkp;
-    }
-    const Rows nz = {P.rows_nz, P.counters + CNT_NZ, n};
+    P.pri_x_k = a->x_prior; P.pri_pk = P.pkp;
+    if (a->betaPrior && P.pkp > a->p_prior)      // (the slot: never beside a reduced model, the prior is Wald only)
+        if ((rc = capi_pad_design(DSQ_WS_PIPE_PADXR, a->x_prior, m, a->p_prior, P.pkp, st, &P.pri_x_k))) return rc;
     if (a->cell_of && a->ncell > 0)
-        P.ncell = capi_upload_cells(a->cell_of, m, DSQ_WS_PIPE_META + 2, st, &P.cell_perm, &P.cell_start);
+        P.ncell = capi_upload_cells(a->cell_of, m, DSQ_WS_PIPE_CELLS, st, &P.cell_perm, &P.cell_start);
     if (a->x_red || a->betaPrior) {
         if (a->x_red && a->cell_of_red && a->ncell_red > 0)
-            P.red_ncell = capi_upload_cells(a->cell_of_red, m, DSQ_WS_PIPE_META + 3, st, &P.red_cell_perm, &P.red_cell_start);
+            P.red_ncell = capi_upload_cells(a->cell_of_red, m, DSQ_WS_PIPE_CELLS_RED, st, &P.red_cell_perm, &P.red_cell_start);
         void *b;        // the reduced / prior fit's fitted means: read once by its logLik
-        rc = capi_ws_get(DSQ_WS_PIPE_META + 4, (size_t)n * P.ld * sizeof(double), &b);
-        if (rc) return rc;
+        if ((rc = capi_ws_get(DSQ_WS_PIPE_RED_MU, (size_t)n * P.ld * sizeof(double), &b))) return rc;
         P.red_mu = (double *)b;
     }
+    return DSQ_OK;
+}
 
-    // ================================================================ gene-wise estimates
-    if (a->phases & DSQ_PH_GENE_EST) {
-        const Rows all = {nullptr, nullptr, n};
-        rc = launch_prefit_rows(P, all, a->y);                                   // getBaseMeansAndVariances + moments
-        if (rc) return rc;
-        hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, st, 0, n, o->allZero, a->force_zero,
-                           (const double *)nullptr, (const double *)nullptr, 0.0, P.rows_nz, (double *)nullptr,
-                           (double *)nullptr, P.counters + CNT_NZ);
-        if (!a->nf_is_vector) {
-            // momentsDispEstimate's mean(1 / colMeans(normalizationFactors)) over the rows that are not all zero
-            // (R/core.R:2440-2444 on objectNZ): columns summed down the listed genes in gene order
-            void *b;
-            rc = capi_ws_get(DSQ_WS_PIPE_META + 5, ((size_t)m + 8) * sizeof(double), &b);
-            if (rc) return rc;
-            DSQ_HIP(launch_xim_rows(a->nf, P.rows_nz, P.counters + CNT_NZ, m, P.ld, (double *)b, P.xim_dev, st));
-        }
-        rc = gene_est(P, nz, a->y, o->mu_hat, CNT_GRID1, CNT_OPT1, o->optim_geneest);
-        if (rc) return rc;
+// m + 8 doubles of scratch for the column sums behind xim (the one place that fetches the slot)
+static int xim_scratch(const Pipe &P, double **out) {
+    void *b;
+    const int rc = capi_ws_get(DSQ_WS_PIPE_XIM_SCRATCH, ((size_t)P.m + 8) * sizeof(double), &b);
+    *out = (double *)b;
+    return rc;
+}
+
+// ---- the phases of DSQ_PH_*, in the chain's order ---------------------------------------------
+// gene-wise estimates
+static int phase_gene_est(Pipe &P, const Rows &nz) {
+    const DsqDeseqArgs *a = P.a;
+    const DsqDeseqOut *o = P.o;
+    const Rows all = {nullptr, nullptr, P.n};
+    int rc = launch_prefit_rows(P, all, a->y);                                   // getBaseMeansAndVariances + moments
+    if (rc) return rc;
+    hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, P.st, 0, P.n, o->allZero, a->force_zero,
+                       (const double *)nullptr, (const double *)nullptr, 0.0, P.rows_nz, (double *)nullptr,
+                       (double *)nullptr, P.counters + CNT_NZ);
+    if (!a->nf_is_vector) {
+        // momentsDispEstimate's mean(1 / colMeans(normalizationFactors)) over the rows that are not all zero
+        // (R/core.R:2440-2444 on objectNZ): columns summed down the listed genes in gene order
+        double *b;
+        if ((rc = xim_scratch(P, &b))) return rc;
+        DSQ_HIP(launch_xim_rows(a->nf, P.rows_nz, P.counters + CNT_NZ, P.m, P.ld, b, P.xim_dev, P.st));
     }
-    // ================================================================ dispersion trend + prior variance
-    if (a->phases & DSQ_PH_TREND) {
-        const double *tm = a->trend_mean ? a->trend_mean : o->baseMean;
-        const double *td = a->trend_mean ? a->trend_disp : o->dispGeneEst;
-        const int nt = a->trend_mean ? a->n_trend : n;
-        if (!with_gene_est) DSQ_HIP(hipMemsetAsync(P.counters + CNT_TREND, 0, sizeof(int32_t), st));      // (else: the status fill)
-        hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, st, 1, nt, (int32_t *)nullptr, (const int32_t *)nullptr,
-                           tm, td, 100.0 * a->minDisp, (int32_t *)nullptr, P.trend_mean_c, P.trend_disp_c,
-                           P.counters + CNT_TREND);
-        void *tws;
-        rc = capi_ws_get(DSQ_WS_PIPE_META, trend_fit_workspace_bytes() + 64, &tws);
-        if (rc) return rc;
-        capi_prof_begin("trend_fit", nt, st);
-        if (a->dispFit_in) {
-            // the caller's trend (fitType "local" evaluated by R, dispersionFunction<-): nothing to fit; the coefficients are NA
-            hipLaunchKernelGGL(trend_given_kernel, dim3(1), dim3(1), 0, st, o->scalars, o->status);
-        } else {
-            if (a->fitType != DSQ_FIT_MEAN)
-                DSQ_HIP(launch_trend_fit_dev_zeroed(P.trend_mean_c, P.trend_disp_c, P.counters + CNT_TREND, o->scalars + DSQ_SC_COEF0,
-                                                     o->status + DSQ_ST_TREND_STATUS, tws_zeroed, st));
-            if (a->fitType != DSQ_FIT_PARAMETRIC)            // R/core.R:894-899 over the same vector, uncompacted
-                hipLaunchKernelGGL(trend_mean_kernel, dim3(1), dim3(1024), 0, st, td, nt, a->minDisp, (int)a->fitType, o->scalars, o->status);
-        }
-        capi_prof_end(st);
-        capi_prof_begin("prior_var", nt, st);
-        {
-            const double *fin = a->dispFit_in ? (a->trend_mean ? a->trend_fit_in : a->dispFit_in) : (const double *)nullptr;
-            if (!sws_zeroed)
-                hipLaunchKernelGGL(prior_var_kernel, dim3(1), dim3(1024), 0, st, tm, td, nt, a->minDisp, a->expVarLogDisp,
-                                   (m > p) ? 1 : 0, P.resbuf, o->scalars, o->status, fin, a->dispPriorVar_in);
-            else
-                hipLaunchKernelGGL(prior_var_grid_kernel, dim3(kSelBlocks), dim3(1024), 0, st, tm, td, nt, a->minDisp, a->expVarLogDisp,
-                                   (m > p) ? 1 : 0, P.resbuf, o->scalars, o->status, fin, a->dispPriorVar_in, (SelWs *)sws_zeroed);
-        }
-        capi_prof_end(st);
-        DSQ_HIP(hipGetLastError());
+    return gene_est(P, nz, a->y, o->mu_hat, CNT_GRID1, CNT_OPT1, o->optim_geneest);
+}
+
+// dispersion trend + prior variance
+static int phase_trend(Pipe &P) {
+    const DsqDeseqArgs *a = P.a;
+    const DsqDeseqOut *o = P.o;
+    hipStream_t st = P.st;
+    const double *tm = a->trend_mean ? a->trend_mean : o->baseMean;
+    const double *td = a->trend_mean ? a->trend_disp : o->dispGeneEst;
+    const int nt = a->trend_mean ? a->n_trend : P.n;
+    if (!(a->phases & DSQ_PH_GENE_EST)) DSQ_HIP(hipMemsetAsync(P.counters + CNT_TREND, 0, sizeof(int32_t), st));      // (else: the status fill)
+    hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, st, 1, nt, (int32_t *)nullptr, (const int32_t *)nullptr,
+                       tm, td, 100.0 * a->minDisp, (int32_t *)nullptr, P.trend_mean_c, P.trend_disp_c,
+                       P.counters + CNT_TREND);
+    capi_prof_begin("trend_fit", nt, st);
+    if (a->dispFit_in) {
+        // the caller's trend (fitType "local" evaluated by R, dispersionFunction<-): nothing to fit; the coefficients are NA
+        hipLaunchKernelGGL(trend_given_kernel, dim3(1), dim3(1), 0, st, o->scalars, o->status);
+    } else {
+        if (a->fitType != DSQ_FIT_MEAN)
+            DSQ_HIP(launch_trend_fit_dev_zeroed(P.trend_mean_c, P.trend_disp_c, P.counters + CNT_TREND, o->scalars + DSQ_SC_COEF0,
+                                                 o->status + DSQ_ST_TREND_STATUS, P.trend_ws, st));
+        if (a->fitType != DSQ_FIT_PARAMETRIC)            // R/core.R:894-899 over the same vector, uncompacted
+            hipLaunchKernelGGL(trend_mean_kernel, dim3(1), dim3(1024), 0, st, td, nt, a->minDisp, (int)a->fitType, o->scalars, o->status);
     }
-    // ================================================================ MAP dispersions + test
-    bool counters_zeroed = false;
-    if (a->phases & DSQ_PH_MAP_TEST) {
-        if (!with_gene_est) {            // (else still zero from the status fill: nothing in between counts into them)
-            DSQ_HIP(hipMemsetAsync(P.counters + CNT_GRID2, 0, sizeof(int32_t), st));
-            DSQ_HIP(hipMemsetAsync(P.counters + CNT_OPT2, 0, sizeof(int32_t), st));
-            DSQ_HIP(hipMemsetAsync(P.counters + CNT_OPT3, 0, sizeof(int32_t), st));
-        }
-        rc = map_est(P, nz, a->y, o->mu_hat, CNT_GRID2);
-        if (rc) return rc;
-        rc = test_fit(P, nz, a->y, o->mu, o->H, CNT_OPT2);
-        if (rc) return rc;
-        // (the counters of the outlier phase -- REP .. OPT3R -- are zeroed here when that phase follows in this call and no
-        //  beta-prior pass, which counts into OPT3, comes in between)
-        counters_zeroed = (a->phases & (DSQ_PH_OUTLIERS | DSQ_PH_OUTLIERS_DETECT)) && !((a->phases & DSQ_PH_PRIOR) && a->betaPrior);
-        hipLaunchKernelGGL(na_assay_rows_kernel, ew_grid(n), dim3(256), 0, st, n, m, P.ld, (const int32_t *)o->allZero, o->mu, o->H,
-                           counters_zeroed ? P.counters + CNT_REP : (int32_t *)nullptr, counters_zeroed ? (int)(CNT_N - CNT_REP) : 0);
+    capi_prof_end(st);
+    capi_prof_begin("prior_var", nt, st);
+    const double *fin = a->dispFit_in ? (a->trend_mean ? a->trend_fit_in : a->dispFit_in) : (const double *)nullptr;
+    if (!P.sel_ws)
+        hipLaunchKernelGGL(prior_var_kernel, dim3(1), dim3(1024), 0, st, tm, td, nt, a->minDisp, a->expVarLogDisp,
+                           (P.m > P.p) ? 1 : 0, P.resbuf, o->scalars, o->status, fin, a->dispPriorVar_in);
+    else
+        hipLaunchKernelGGL(prior_var_grid_kernel, dim3(kSelBlocks), dim3(1024), 0, st, tm, td, nt, a->minDisp, a->expVarLogDisp,
+                           (P.m > P.p) ? 1 : 0, P.resbuf, o->scalars, o->status, fin, a->dispPriorVar_in, (SelWs *)P.sel_ws);
+    capi_prof_end(st);
+    DSQ_HIP(hipGetLastError());
+    return DSQ_OK;
+}
+
+// MAP dispersions + test.  *counters_zeroed: this phase's last kernel has zeroed the counters of the outlier phase (REP ..
+// OPT3R) -- when that phase follows in this call and no beta-prior pass, which counts into OPT3, comes in between
+static int phase_map_test(Pipe &P, const Rows &nz, bool *counters_zeroed) {
+    const DsqDeseqArgs *a = P.a;
+    const DsqDeseqOut *o = P.o;
+    if (!(a->phases & DSQ_PH_GENE_EST)) {            // (else still zero from the status fill: nothing in between counts into them)
+        DSQ_HIP(hipMemsetAsync(P.counters + CNT_GRID2, 0, sizeof(int32_t), P.st));
+        DSQ_HIP(hipMemsetAsync(P.counters + CNT_OPT2, 0, sizeof(int32_t), P.st));
+        DSQ_HIP(hipMemsetAsync(P.counters + CNT_OPT3, 0, sizeof(int32_t), P.st));
     }
-    // ================================================================ betaPrior: the pass with lambda = 1 / betaPriorVar
-    if ((a->phases & DSQ_PH_PRIOR) && a->betaPrior) {
-        DSQ_HIP(hipMemsetAsync(P.counters + CNT_OPT2, 0, sizeof(int32_t), st));
-        rc = prior_fit(P, nz, a->y, CNT_OPT2);
-        if (rc) return rc;
+    int rc = map_est(P, nz, a->y, o->mu_hat, CNT_GRID2);
+    if (rc) return rc;
+    if ((rc = test_fit(P, nz, a->y, o->mu, o->H, CNT_OPT2))) return rc;
+    const bool z = *counters_zeroed = (a->phases & (DSQ_PH_OUTLIERS | DSQ_PH_OUTLIERS_DETECT)) && !((a->phases & DSQ_PH_PRIOR) && a->betaPrior);
+    hipLaunchKernelGGL(na_assay_rows_kernel, ew_grid(P.n), dim3(256), 0, P.st, P.n, P.m, P.ld, (const int32_t *)o->allZero, o->mu, o->H,
+                       z ? P.counters + CNT_REP : (int32_t *)nullptr, z ? (int)(CNT_N - CNT_REP) : 0);
+    return DSQ_OK;
+}
+
+// betaPrior: the pass with lambda = 1 / betaPriorVar
+static int phase_prior(Pipe &P, const Rows &nz) {
+    DSQ_HIP(hipMemsetAsync(P.counters + CNT_OPT2, 0, sizeof(int32_t), P.st));
+    return prior_fit(P, nz, P.a->y, CNT_OPT2);
+}
+
+// count outliers, first half: Cook's distances, replaceOutliers, the lists of the replaced rows and of the ones to refit
+static int phase_outlier_detect(Pipe &P, const Rows &nz, const OutlierMeta &M, bool counters_zeroed) {
+    const DsqDeseqArgs *a = P.a;
+    const DsqDeseqOut *o = P.o;
+    const int n = P.n, m = P.m;
+    hipStream_t st = P.st;
+    if (!counters_zeroed) DSQ_HIP(hipMemsetAsync(P.counters + CNT_REP, 0, (CNT_N - CNT_REP) * sizeof(int32_t), st));      // REP .. OPT3R
+    CooksKernelParams ck;
+    memset(&ck, 0, sizeof ck);
+    ck.n = n; ck.m = m; ck.p = P.p; ck.ld = P.ld; ck.y = a->y; ck.nf = a->nf; ck.nf_is_vector = a->nf_is_vector;
+    ck.mu = o->mu; ck.H = o->H; ck.perm = M.dperm; ck.cell_start = M.dstart; ck.in3 = M.din3; ck.ncell = a->ncell; ck.any3 = M.any3;
+    int cap = 2; while (cap < (M.any3 ? M.maxcell : m)) cap <<= 1;
+    ck.sortcap = cap;
+    ck.cooks = o->cooks; ck.maxCooks = o->maxCooks; ck.robustDisp = P.robustDisp;
+    ck.rows = nz.rows; ck.n_dev = nz.n_dev;
+    bool ok = true;
+    capi_prof_begin("cooks_distance", n, st);
+    DSQ_HIP(launch_cooks(ck, st, &ok));
+    capi_prof_end(st);
+    if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "m=%d samples: a gene row plus its sort buffer exceeds the 160 KiB LDS", m);
+    // (before the replacement: allZero still says which rows had no fit -- a row that only BECOMES all zero keeps its assays)
+    hipLaunchKernelGGL(na_assay_rows_kernel, ew_grid(n), dim3(256), 0, st, n, m, P.ld, (const int32_t *)o->allZero, o->cooks,
+                       (double *)nullptr);
+    if (!a->do_replace) return DSQ_OK;
+    ReplaceKernelParams rk;
+    memset(&rk, 0, sizeof rk);
+    rk.n = n; rk.m = m; rk.ld = P.ld; rk.y = a->y; rk.nf = a->nf; rk.nf_is_vector = a->nf_is_vector;
+    rk.cooks = o->cooks; rk.cutoff = a->cooksCutoff; rk.trim = a->trim; rk.replaceable = M.drepl;
+    int cap2 = 2; while (cap2 < m) cap2 <<= 1;
+    rk.sortcap = cap2;
+    rk.newCounts = o->replaceCounts; rk.replace = o->replace;
+    rk.rows = nz.rows; rk.n_dev = nz.n_dev;
+    capi_prof_begin("replace_outliers", n, st);
+    DSQ_HIP(launch_replace(rk, st, &ok));
+    capi_prof_end(st);
+    if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "m=%d samples: the sort buffer exceeds the 160 KiB LDS", m);
+    // rows with a replacement (R/core.R:2488-2490) -> their moments on the new counts (:2491) -> the ones that are still
+    // non-zero are refitted (:2496-2500)
+    hipLaunchKernelGGL(list_kernel, ew_grid(n), dim3(256), 0, st, nz, (const int32_t *)o->replace, 1, P.rows_rep, P.counters + CNT_REP);
+    const Rows rep = {P.rows_rep, P.counters + CNT_REP, n};
+    const int rc = launch_prefit_rows(P, rep, o->replaceCounts);
+    if (rc) return rc;
+    hipLaunchKernelGGL(list_kernel, ew_grid(n), dim3(256), 0, st, rep, (const int32_t *)o->allZero, 0, P.rows_refit, P.counters + CNT_REFIT);
+    return DSQ_OK;
+}
+
+// the refit of the replaced rows runs every step on its DEFAULTS: refitWithoutOutliers passes none of the caller's betaTol /
+// maxit / useQR / minmu on to estimateDispersions / nbinomWaldTest / nbinomLRT (R/core.R:2509-2531)
+static void refit_defaults(Pipe &P) {
+    P.tag = ":refit";
+    P.t_tol = 1e-8; P.t_maxit = 100; P.t_useQR = 1; P.t_minmu = 0.5; P.ge_floor = 0.5;
+}
+
+// count outliers, second half: the same chain on the replaced rows that are still non-zero; their mu-hat and fitted means go
+// to the (now dead) mu_hat matrix, assays mu / H keep the original fit as in R (the refit runs on a subset object, :2500-2531)
+static int phase_outlier_refit(Pipe &P, const Rows &nz, const OutlierMeta &M) {
+    const DsqDeseqArgs *a = P.a;
+    const DsqDeseqOut *o = P.o;
+    const Rows rep = {P.rows_rep, P.counters + CNT_REP, P.n};
+    const Rows rf = {P.rows_refit, P.counters + CNT_REFIT, P.n};
+    int rc;
+    if ((rc = launch_pending_ll(P, true))) return rc;      // the full-row log likelihoods, beside the refit
+    refit_defaults(P);
+    if (!a->nf_is_vector) {
+        // momentsDispEstimate of the refitted subset averages the normalization factors over ITS rows
+        // (R/core.R:2440-2444 on objectSub, :2500-2509): the second scalar behind the lambda block
+        double *b;
+        if ((rc = xim_scratch(P, &b))) return rc;
+        DSQ_HIP(launch_xim_flagged(a->nf, P.n, P.m, P.ld, o->replace, o->allZero, b, P.xim_dev + 1, P.st));
+        P.xim_cur = P.xim_dev + 1;
     }
-    // ================================================================ count outliers
+    if ((rc = gene_est(P, rf, o->replaceCounts, o->mu_hat, CNT_GRID1R, CNT_OPT1R, o->optim_geneest))) return rc;
+    if ((rc = map_est(P, rf, o->replaceCounts, o->mu_hat, CNT_GRID2R))) return rc;
+    if ((rc = join_side(P))) return rc;          // the full-row log likelihoods are down before the refit writes its rows'
+    if ((rc = test_fit(P, rf, o->replaceCounts, o->mu_hat, nullptr, CNT_OPT2R))) return rc;
+    if (a->betaPrior && (rc = prior_fit(P, rf, o->replaceCounts, CNT_OPT2R))) return rc;
+    return a->defer_finish ? DSQ_OK : outlier_finish(P, nz, rep, M, P.counters + CNT_REFIT);
+}
+
+static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st, Pipe &P) {
+    int rc = check_args(a, o);
+    if (rc || (rc = capi_check_device()) || (rc = bind(P, a, o, st)) || (rc = launch_init_fills(P)) || (rc = prepare_designs(P))) return rc;
+    const Rows nz = {P.rows_nz, P.counters + CNT_NZ, P.n};
+    const int ph = a->phases;
+    if ((ph & DSQ_PH_GENE_EST) && (rc = phase_gene_est(P, nz))) return rc;
+    if ((ph & DSQ_PH_TREND) && (rc = phase_trend(P))) return rc;
+    bool counters_zeroed = false;          // handed from the MAP / test phase to the outlier phase
+    if ((ph & DSQ_PH_MAP_TEST) && (rc = phase_map_test(P, nz, &counters_zeroed))) return rc;
+    if ((ph & DSQ_PH_PRIOR) && a->betaPrior && (rc = phase_prior(P, nz))) return rc;
     // (one call: DSQ_PH_OUTLIERS; a caller with its own dispersion trend splits it -- DSQ_PH_OUTLIERS_DETECT up to the moments
     //  of the replaced rows, then, with dispFit_in updated at those rows' new means, DSQ_PH_OUTLIERS_REFIT)
-    const bool ph_detect = (a->phases & (DSQ_PH_OUTLIERS | DSQ_PH_OUTLIERS_DETECT)) != 0;
-    const bool ph_refit = (a->phases & (DSQ_PH_OUTLIERS | DSQ_PH_OUTLIERS_REFIT)) != 0;
-    if (ph_detect || ph_refit) {
-        OutlierMeta M;
-        rc = outlier_meta(a, m, st, &M);
-        if (rc) return rc;
-        int32_t *dperm = M.dperm, *din3 = M.din3, *drepl = M.drepl, *dstart = M.dstart;
-        const int any3 = M.any3, maxcell = M.maxcell;
-      if (ph_detect) {
-        if (!counters_zeroed) DSQ_HIP(hipMemsetAsync(P.counters + CNT_REP, 0, (CNT_N - CNT_REP) * sizeof(int32_t), st));      // REP .. OPT3R
-
-        CooksKernelParams ck;
-        memset(&ck, 0, sizeof ck);
-        ck.n = n; ck.m = m; ck.p = p; ck.ld = P.ld; ck.y = a->y; ck.nf = a->nf; ck.nf_is_vector = a->nf_is_vector;
-        ck.mu = o->mu; ck.H = o->H; ck.perm = dperm; ck.cell_start = dstart; ck.in3 = din3; ck.ncell = a->ncell; ck.any3 = any3;
-        int cap = 2; while (cap < (any3 ? maxcell : m)) cap <<= 1;
-        ck.sortcap = cap;
-        ck.cooks = o->cooks; ck.maxCooks = o->maxCooks; ck.robustDisp = P.robustDisp;
-        ck.rows = nz.rows; ck.n_dev = nz.n_dev;
-        bool ok = true;
-        capi_prof_begin("cooks_distance", n, st);
-        DSQ_HIP(launch_cooks(ck, st, &ok));
-        capi_prof_end(st);
-        if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "m=%d samples: a gene row plus its sort buffer exceeds the 160 KiB LDS", m);
-        // (before the replacement: allZero still says which rows had no fit -- a row that only BECOMES all zero keeps its assays)
-        hipLaunchKernelGGL(na_assay_rows_kernel, ew_grid(n), dim3(256), 0, st, n, m, P.ld, (const int32_t *)o->allZero, o->cooks,
-                           (double *)nullptr);
-        if (a->do_replace) {
-            ReplaceKernelParams rk;
-            memset(&rk, 0, sizeof rk);
-            rk.n = n; rk.m = m; rk.ld = P.ld; rk.y = a->y; rk.nf = a->nf; rk.nf_is_vector = a->nf_is_vector;
-            rk.cooks = o->cooks; rk.cutoff = a->cooksCutoff; rk.trim = a->trim; rk.replaceable = drepl;
-            int cap2 = 2; while (cap2 < m) cap2 <<= 1;
-            rk.sortcap = cap2;
-            rk.newCounts = o->replaceCounts; rk.replace = o->replace;
-            rk.rows = nz.rows; rk.n_dev = nz.n_dev;
-            capi_prof_begin("replace_outliers", n, st);
-            DSQ_HIP(launch_replace(rk, st, &ok));
-            capi_prof_end(st);
-            if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "m=%d samples: the sort buffer exceeds the 160 KiB LDS", m);
-            // rows with a replacement (R/core.R:2488-2490) -> their moments on the new counts (:2491) -> the ones
-            // that are still non-zero are refitted (:2496-2500)
-            hipLaunchKernelGGL(list_kernel, ew_grid(n), dim3(256), 0, st, nz, (const int32_t *)o->replace, 1, P.rows_rep,
-                               P.counters + CNT_REP);
-            const Rows rep = {P.rows_rep, P.counters + CNT_REP, n};
-            rc = launch_prefit_rows(P, rep, o->replaceCounts);
-            if (rc) return rc;
-            hipLaunchKernelGGL(list_kernel, ew_grid(n), dim3(256), 0, st, rep, (const int32_t *)o->allZero, 0, P.rows_refit,
-                               P.counters + CNT_REFIT);
-        }
-      }
-        if (ph_refit && a->do_replace) {
-            const Rows rep = {P.rows_rep, P.counters + CNT_REP, n};
-            const Rows rf = {P.rows_refit, P.counters + CNT_REFIT, n};
-            // the same chain on the replaced rows; their mu-hat and fitted means go to the (now dead) mu_hat matrix,
-            // assays mu / H keep the original fit as in R (the refit runs on a subset object, :2500-2531)
-            if ((rc = launch_pending_ll(P, true))) return rc;      // the full-row log likelihoods, beside the refit
-            P.tag = ":refit";
-            P.t_tol = 1e-8; P.t_maxit = 100; P.t_useQR = 1; P.t_minmu = 0.5; P.ge_floor = 0.5;
-            if (!a->nf_is_vector) {
-                // momentsDispEstimate of the refitted subset averages the normalization factors over ITS rows
-                // (R/core.R:2440-2444 on objectSub, :2500-2509): the second scalar behind the lambda block
-                void *b;
-                rc = capi_ws_get(DSQ_WS_PIPE_META + 5, ((size_t)m + 8) * sizeof(double), &b);
-                if (rc) return rc;
-                DSQ_HIP(launch_xim_flagged(a->nf, n, m, P.ld, o->replace, o->allZero, (double *)b, P.xim_dev + 1, st));
-                P.xim_cur = P.xim_dev + 1;
-            }
-            rc = gene_est(P, rf, o->replaceCounts, o->mu_hat, CNT_GRID1R, CNT_OPT1R, o->optim_geneest);
-            if (rc) return rc;
-            rc = map_est(P, rf, o->replaceCounts, o->mu_hat, CNT_GRID2R);
-            if (rc) return rc;
-            if ((rc = join_side(P))) return rc;          // the full-row log likelihoods are down before the refit writes its rows'
-            rc = test_fit(P, rf, o->replaceCounts, o->mu_hat, nullptr, CNT_OPT2R);
-            if (rc) return rc;
-            if (a->betaPrior) {
-                rc = prior_fit(P, rf, o->replaceCounts, CNT_OPT2R);
-                if (rc) return rc;
-            }
-            if (!a->defer_finish) {
-                rc = outlier_finish(P, nz, rep, M, P.counters + CNT_REFIT);
-                if (rc) return rc;
-            }
-        }
-    }
-    // ================================================================ (sharding callers) the closing steps, with the
-    // number of refitted rows over all shards
-    if ((a->phases & DSQ_PH_FINISH) && a->do_replace) {
-        OutlierMeta M;
-        rc = outlier_meta(a, m, st, &M);
-        if (rc) return rc;
-        const Rows rep = {P.rows_rep, P.counters + CNT_REP, n};
-        rc = outlier_finish(P, nz, rep, M, a->n_refit_global ? a->n_refit_global : P.counters + CNT_REFIT);
-        if (rc) return rc;
-    }
+    const bool detect = (ph & (DSQ_PH_OUTLIERS | DSQ_PH_OUTLIERS_DETECT)) != 0, refit = (ph & (DSQ_PH_OUTLIERS | DSQ_PH_OUTLIERS_REFIT)) != 0;
+    OutlierMeta M;
+    if ((detect || refit || ((ph & DSQ_PH_FINISH) && a->do_replace)) && (rc = outlier_meta(a, P.m, st, &M))) return rc;
+    if (detect && (rc = phase_outlier_detect(P, nz, M, counters_zeroed))) return rc;
+    if (refit && a->do_replace && (rc = phase_outlier_refit(P, nz, M))) return rc;
+    // (sharding callers) the closing steps, with the number of refitted rows over all shards
+    if ((ph & DSQ_PH_FINISH) && a->do_replace)
+        return outlier_finish(P, nz, Rows{P.rows_rep, P.counters + CNT_REP, P.n}, M, a->n_refit_global ? a->n_refit_global : P.counters + CNT_REFIT);
     return DSQ_OK;
+}
+
+static int run(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st) {
+    Pipe P;
+    memset(&P, 0, sizeof P);
+    const int rc = run_chain(a, o, st, P);
+    const int rl = rc ? DSQ_OK : launch_pending_ll(P, false);      // (no refit in this analysis: behind everything else)
+    const int rj = join_side(P);             // (whatever path the chain left by: nothing stays in flight beside `st`)
+    return rc ? rc : (rl ? rl : rj);
 }
 
 // (deseq_host.hip: the host-pointer entry drives the same chain from its per-device worker threads, under the call lock)
@@ -1957,7 +1948,8 @@ int pipeline_run(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st) { 
 extern "C" int64_t dsq_deseq_workspace_bytes(int32_t n, int32_t m, int32_t p, int32_t n_trend) {
     (void)m;
     if (n < 1 || p < 1) return 0;
-    return (int64_t)dsq::carve(n, dsq::kern_width(p), n_trend > n ? n_trend : n).bytes;
+    dsq::Pipe P;
+    return (int64_t)dsq::workspace_table(P, n, dsq::kern_width(p), n_trend > n ? n_trend : n, nullptr);
 }
 
 extern "C" int dsq_deseq_dev(const DsqDeseqArgs *args, const DsqDeseqOut *out, void *stream) {

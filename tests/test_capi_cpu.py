@@ -81,6 +81,30 @@ def test_argument_validation():
                        np.ones((4, 6)), False, 1e-8, 100, True, 0.5)
 
 
+# dsq_deseq_workspace_bytes(n, 12, p, n_trend) as the library of commit b05cb59 (the one before the workspace layout became
+# one table in pipeline.hip) returns it: per p, the pairs (n_trend = n // 2, n_trend = 2 n + 3) for n = 1, 7, 6 250, 50 000
+_WORKSPACE_BYTES = {
+    1: (3008, 3008, 3008, 3392, 1802432, 1952384, 14400704, 15600896),
+    4: (3072, 3072, 4800, 5184, 3152064, 3302016, 25200768, 26400960),
+    10: (3776, 3776, 7808, 8192, 5852480, 6002432, 46800896, 48001088),
+    11: (3904, 3904, 10816, 11200, 8552320, 8702272, 68401024, 69601216),
+    31: (5440, 5440, 19264, 19648, 15752704, 15902656, 126001408, 127201600),
+    48: (6976, 6976, 27712, 28096, 22953088, 23103040, 183601792, 184801984),
+    64: (8512, 8512, 36160, 36544, 30153472, 30303424, 241202176, 242402368),
+}
+
+
+@pytest.mark.parametrize("p", sorted(_WORKSPACE_BYTES))
+def test_deseq_workspace_bytes_is_pinned(p):
+    """the caller-owned workspace of dsq_deseq_dev persists between the phases of an analysis: its size is ABI (pure host
+    code -- the library loads without a device)"""
+    from deseq2_amd import _lib
+    L = _lib.lib()
+    got = tuple(int(L.dsq_deseq_workspace_bytes(n, 12, p, nt)) for n in (1, 7, 6250, 50000) for nt in (n // 2, 2 * n + 3))
+    assert got == _WORKSPACE_BYTES[p]
+    assert L.dsq_deseq_workspace_bytes(0, 12, p, 0) == 0 and L.dsq_deseq_workspace_bytes(7, 12, 0, 0) == 0
+
+
 def test_product_never_imports_oracle():
     """the oracle is test infrastructure: nothing under deseq2_amd/ may reference it"""
     for dp, _, files in os.walk(os.path.join(ROOT, "deseq2_amd")):

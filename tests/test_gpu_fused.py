@@ -307,6 +307,67 @@ def test_all_gene_kernels_above_their_size_thresholds(E):
     assert_same(np.asarray(a2.mcols["dispersion"], float), np.asarray(b2.mcols["dispersion"], float), "custom trend, 20 000 genes")
 
 
+def test_result_columns_in_separate_regions(E):
+    """the result columns of a C caller need not be one packed block: with every DsqDeseqOut column in a region of its own
+    (a gap between neighbours, so that no two fills merge) the chain's init launch has its largest number of segments --
+    work counters, status, 19 columns, grid flags, FIT_USED, the trend fit's workspace and (from 16 384 genes) the selection
+    workspace of the prior variance: 25, one more than InitParams::seg held before kInitSegMax counted them.  Every column
+    equals the packed layout's bit for bit.  (16 384 genes: the smallest analysis on the sixteen-workgroup path.)"""
+    from deseq2_amd import _lib as L
+    t = E.torch
+    x = simulate.design_two_group(16)                       # cells of 8 >= 7: replaceOutliers + refit
+    d = simulate.make_counts(16384, x, seed=62, drop_all_zero=False)
+    counts = d["counts"].copy()
+    counts[::29] = 0
+    counts = _spike_outliers(counts, np.random.default_rng(8), k=6)
+    phases = L.DSQ_PH_GENE_EST | L.DSQ_PH_TREND | L.DSQ_PH_MAP_TEST | L.DSQ_PH_OUTLIERS
+    cols = ["baseMean", "baseVar", "allZero", "dispGeneEst", "dispGeneIter", "dispFit", "dispMAP", "dispersion", "dispIter",
+            "dispOutlier", "beta", "betaSE", "stat", "pvalue", "betaConv", "betaIter", "logLike", "logLikeReduced", "maxCooks",
+            "replace", "optim_geneest", "optim_test", "status", "scalars"]
+    runs = []
+    for separate in (False, True):
+        dds = core.DESeqDataSet(counts, x, sizeFactors=d["size_factors"], engine=E)
+        assert fused.supported(dds) and dds.n >= 16384
+        run = fused._Run(dds, "Wald", 7, 0, {})
+        run.args.fitType = L.DSQ_FIT["parametric"]
+        n, p = run.n, run.p
+        size = dict({c: 8 * n for c in cols}, beta=8 * n * p, betaSE=8 * n * p, stat=8 * n * p, pvalue=8 * n * p,
+                    status=4 * L.DSQ_ST_COUNT, scalars=8 * L.DSQ_SC_COUNT)
+        for c in ("allZero", "dispGeneIter", "dispIter", "dispOutlier", "betaConv", "replace", "optim_geneest", "optim_test"):
+            size[c] = 4 * n
+        if separate:
+            gap = 256
+            buf = t.zeros(sum(size[c] + gap for c in cols), dtype=t.uint8, device=E.device)
+            off = 0
+            run.regions = {}
+            for c in cols:
+                run.regions[c] = buf[off: off + size[c]]
+                setattr(run.out, c, fused._ptr(run.regions[c]))
+                off += size[c] + gap
+        else:
+            flat = dict(beta=run.mat[0], betaSE=run.mat[1], stat=run.mat[2], pvalue=run.mat[3])
+            run.regions = {c: flat.get(c, getattr(run, c, None)).reshape(-1).view(t.uint8) for c in cols}
+        run.launch(phases)
+        t.cuda.synchronize()
+        runs.append(run)
+    a, b = runs
+    st = {k: int(a.status[i]) for k, i in L.DSQ_ST.items()}
+    assert st["TREND_STATUS"] == 0 and st["N_NONZERO"] > 15000 and st["N_REFIT"] >= 1
+    # (scalars: DSQ_SC_COEF0 .. DSQ_SC_FIT_USED are the entries the chain defines; the spare ones behind them are never
+    #  written, so they hold whatever the allocation held)
+    written = dict(size, scalars=8 * (L.DSQ_SC_FIT_USED + 1))
+    for c in cols:
+        assert a.regions[c].numel() == b.regions[c].numel() == size[c], c
+        assert t.equal(a.regions[c][: written[c]], b.regions[c][: written[c]]), \
+            "column %s differs between the packed and the separated layout" % c
+    m = run.m
+    for c in ("mu", "H", "cooks"):                          # (NA in the all-zero rows; the padding m .. ld-1 is not written)
+        assert t.equal(getattr(a, c)[:, :m].contiguous().view(t.uint8), getattr(b, c)[:, :m].contiguous().view(t.uint8)), c
+    nz, rp = a.allZero == 0, a.replace != 0
+    assert t.equal(a.mu_hat[nz][:, :m].contiguous().view(t.uint8), b.mu_hat[nz][:, :m].contiguous().view(t.uint8)), "mu_hat"
+    assert t.equal(a.replaceCounts[rp][:, :m], b.replaceCounts[rp][:, :m]), "replaceCounts"
+
+
 def test_unsupported_settings_fall_back(E):
     x = simulate.design_two_group(12)
     d = simulate.make_counts(200, x, seed=11)
