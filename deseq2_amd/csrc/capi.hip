@@ -3,9 +3,11 @@
 // Host side of the engine, in three files:
 //   ctx.hip        the per-(device, stream) context (workspace slots, pinned upload ring, side stream), the error text,
 //                  the tuning knobs, the profile list and the entry points that manage them;
-//   capi.hip       (this file) argument validation, layout conversion (R column-major <-> gene-major), kernel dispatch on
-//                  the design width p, and the device-pointer entry points dsq_*_dev;
-//   capi_host.hip  the host-pointer entry points the R .Call shim binds: staging, gene ranges, worker threads.
+//   capi.hip       (this file) each call's argument checks (check_<call>: stated once, used by both halves), layout
+//                  conversion (R column-major <-> gene-major: GmIn for the inputs, GmOut for the n x m outputs), kernel
+//                  dispatch on the design width p, and the device-pointer entry points dsq_*_dev (dev_entry);
+//   capi_host.hip  the host-pointer entry points the R .Call shim binds: staging (struct Stage), gene ranges, worker threads.
+// A body here reads: check_<call>, the device, an empty call returns DSQ_OK, inputs, outputs, launch, finish.
 // No CPU fallback: if HIP cannot give us a device, every entry point fails with DSQ_ERR_DEVICE.
 #include "capi.hpp"
 
@@ -180,45 +182,187 @@ int capi_upload_cells(const int32_t *labels, int m, int slot, hipStream_t st, co
     return C;
 }
 
+// =============================================================== each call's checks, stated once
+// check_<call>(args, out): everything that can be decided from the argument block alone.  Both halves of the ABI call it
+// first; a host entry adds only what is its own (R layout, the row range).  One skeleton: the call's own conditions, sizes,
+// NULL pointers, weights, ld / layout -- all DSQ_ERR_ARG -- and, when nothing else is wrong, a design wider than the
+// kernels (DSQ_ERR_UNSUPPORTED; p = 0: the call has no such limit of its own).
+#define DSQ_NEED(cond, what) do { if (!(cond)) return capi_fail(DSQ_ERR_ARG, what); } while (0)
+static int too_wide(int p) {
+    return capi_fail(DSQ_ERR_UNSUPPORTED, "p=%d design columns: kernels are compiled for 1..%d", p, DSQ_P_WIDE);
+}
+static int check_layout(int layout, long ld, int m, bool known_only) {
+    if (layout == DSQ_LAYOUT_GENE_MAJOR && ld < m) return capi_fail(DSQ_ERR_ARG, "ld = %ld < m = %d", ld, m);
+    if (known_only && layout != DSQ_LAYOUT_R && layout != DSQ_LAYOUT_GENE_MAJOR) return capi_fail(DSQ_ERR_ARG, "unknown layout %d", layout);
+    return DSQ_OK;
+}
+template <class A>
+static int check_block(const A *a, bool dims_ok, int p, bool inputs, const double *weights, int useWeights, bool outputs,
+                       bool known_layout_only) {
+    if (a->n < 0 || a->m < 1 || !dims_ok) return capi_fail(DSQ_ERR_ARG, "bad dimensions n=%d m=%d p=%d", a->n, a->m, p);
+    DSQ_NEED(inputs, "NULL input array");
+    DSQ_NEED(!useWeights || weights, "useWeights set but weights is NULL");
+    DSQ_NEED(outputs, "NULL output array");
+    if (int rc = check_layout(a->layout, a->ld, a->m, known_layout_only)) return rc;
+    return p > DSQ_P_WIDE ? too_wide(p) : DSQ_OK;
+}
+
+int check_host_layout(int layout) {
+    DSQ_NEED(layout == DSQ_LAYOUT_R, "host entry points take R layout only");
+    return DSQ_OK;
+}
+int check_fit_beta(const DsqFitBetaArgs *a, const DsqFitBetaOut *o) {
+    DSQ_NEED(a && o, "NULL args/out");
+    DSQ_NEED(a->maxit >= 0, "maxit < 0");
+    return check_block(a, a->p >= 1, a->p, a->y && a->x && a->nf && a->alpha_hat && a->contrast && a->beta_mat && a->lambda,
+                       a->weights, a->useWeights,
+                       o->beta_mat && o->beta_var_mat && o->iter && o->contrast_num && o->contrast_denom && o->deviance, true);
+}
+int check_fit_disp(const DsqFitDispArgs *a, const DsqFitDispOut *o) {
+    DSQ_NEED(a && o, "NULL args/out");
+    DSQ_NEED(a->maxit >= 0, "maxit < 0");
+    return check_block(a, a->p >= 1, a->p, a->y && a->x && a->mu_hat && a->log_alpha && a->log_alpha_prior_mean, a->weights,
+                       a->useWeights,          // (last_d2lp may be NULL in the device entry: its kernel is then skipped)
+                       o->log_alpha && o->iter && o->iter_accept && o->last_change && o->initial_lp && o->initial_dlp &&
+                           o->last_lp && o->last_dlp, true);
+}
+int check_fit_disp_grid(const DsqFitDispGridArgs *a, const DsqFitDispGridOut *o) {
+    DSQ_NEED(a && o, "NULL args/out");
+    DSQ_NEED(a->ngrid >= 2, "disp_grid needs at least 2 points");
+    return check_block(a, a->p >= 1, a->p, a->y && a->x && a->mu_hat && a->disp_grid && a->log_alpha_prior_mean, a->weights,
+                       a->useWeights, o->log_alpha != nullptr, true);
+}
+int check_trend_fit(const double *means, const double *disps, int64_t n, const double *coefs, const int32_t *status) {
+    DSQ_NEED(means && disps && coefs && status && n >= 1, "bad arguments");
+    return DSQ_OK;
+}
+int check_prefit(const DsqPrefitArgs *a, const DsqPrefitOut *o) {
+    DSQ_NEED(a && o, "NULL args/out");
+    return check_block(a, a->m >= 2 && a->p >= 1 && a->m > a->p, 0, a->y && a->nf && a->q && a->a && a->r, a->weights, a->useWeights,
+                       o->baseMean && o->baseVar && o->allZero && o->roughDisp && o->beta_init, false);
+}
+int check_linear_mu(const DsqPrefitArgs *a, const double *mu) {
+    DSQ_NEED(a && mu, "NULL args/out");
+    return check_block(a, a->p >= 1, 0, a->y && a->nf && a->q && a->a, nullptr, 0, true, false);
+}
+int check_loglike(const DsqLogLikeArgs *a, const double *out) {
+    DSQ_NEED(a && out, "NULL args/out");
+    return check_block(a, true, 0, a->y && a->mu && a->disp, a->weights, a->useWeights, true, false);
+}
+int check_intercept(const DsqInterceptArgs *a, const DsqInterceptOut *o) {
+    DSQ_NEED(a && o, "NULL args/out");
+    return check_block(a, true, 0, a->y && a->nf && a->alpha, a->weights, a->useWeights, o->beta_log2 && o->betaSE, false);
+}
+int check_optim(const DsqOptimArgs *a, const DsqOptimOut *o) {
+    DSQ_NEED(a && o, "NULL args/out");
+    return check_block(a, a->p >= 1, a->p, a->y && a->x && a->nf && a->alpha_hat && a->lambda && a->beta_start, a->weights,
+                       a->useWeights, o->beta && o->betaSE && o->conv && o->mu && o->logLike, false);
+}
+int check_cooks(const DsqCooksArgs *a, const DsqCooksOut *o) {
+    DSQ_NEED(a && o, "NULL args/out");
+    if (int rc = check_block(a, a->p >= 1 && a->ncell >= 1, 0, a->y && a->nf && a->mu && a->H && a->cell_of, nullptr, 0,
+                             o->cooks && o->maxCooks, false)) return rc;
+    for (int j = 0; j < a->m; j++)          // (cell_of is a host array in both halves)
+        if (a->cell_of[j] < 0 || a->cell_of[j] >= a->ncell) return capi_fail(DSQ_ERR_VALUE, "cell_of[%d] out of range", j);
+    return DSQ_OK;
+}
+int check_replace(const DsqReplaceArgs *a, const DsqReplaceOut *o) {
+    DSQ_NEED(a && o, "NULL args/out");
+    DSQ_NEED(a->trim >= 0.0 && a->trim < 0.5, "trim must be in [0, 0.5)");
+    return check_block(a, true, 0, a->y && a->nf && a->cooks && a->replaceable, nullptr, 0, o->newCounts && o->replace, false);
+}
+// a body's opening after its check: the device; *empty: the call has no genes and returns DSQ_OK
+static int dev_ready(int check_rc, int n, bool *empty) {
+    *empty = n == 0;
+    return check_rc ? check_rc : capi_check_device();
+}
+
+// =============================================================== the n x m arrays of a call, into and out of gene-major
+// Inputs: the counts first (they fix ld), then each matrix into its slot (prep_matrix: as it is when gene-major).
+struct GmIn {
+    int layout, n, m;
+    long ld_in;
+    hipStream_t st;
+    long ld = 0;
+    bool ycheck = false;        // float64 counts: their validity flag is read back by finish_ycheck
+    GmIn(int layout_, int n_, int m_, long ld_, hipStream_t st_) : layout(layout_), n(n_), m(m_), ld_in(ld_), st(st_) {}
+    template <class A>
+    GmIn(const A *a, hipStream_t st_) : GmIn(a->layout, a->n, a->m, a->ld, st_) {}
+    int counts(const void *y, int y_type, const int32_t **out, long *ld_out) {
+        int rc = prep_counts(y, y_type, layout, ld_in, n, m, st, out, &ld, &ycheck);
+        *ld_out = ld;
+        return rc;
+    }
+    int matrix(const double *src, int slot, const double **out) const { return prep_matrix(src, layout, ld_in, n, m, slot, st, out, ld); }
+    // size factors (m of them, used as they are) or an n x m matrix of normalization factors
+    int nf(const double *src, int is_vector, const double **out, int *flag) const {
+        *flag = is_vector ? 1 : 0;
+        if (is_vector) { *out = src; return DSQ_OK; }
+        return matrix(src, WS_NF, out);
+    }
+    int weights(const double *src, int use, const double **out, int *flag) const {
+        *flag = use ? 1 : 0;
+        return use ? matrix(src, WS_W, out) : DSQ_OK;
+    }
+    bool gene_major() const { return layout == DSQ_LAYOUT_GENE_MAJOR; }
+};
+
+static hipError_t transpose_back(const double *gm, double *r, int n, int m, long ld, hipStream_t st) {
+    return launch_transpose_gm_to_r_f64(gm, r, n, m, ld, st);
+}
+static hipError_t transpose_back(const int32_t *gm, int32_t *r, int n, int m, long ld, hipStream_t st) {
+    return launch_transpose_gm_to_r_i32(gm, r, n, m, ld, st);
+}
+
+// An n x m output: the kernel writes the caller's buffer when that is gene-major, else a workspace slot that finish()
+// transposes back into it after the launch.  A NULL buffer (an output not asked for) stays NULL.
+template <class T>
+struct GmOut {
+    T *user = nullptr, *ws = nullptr;
+    int bind(const GmIn &g, T *dst, int slot, T **kernel_ptr) {
+        user = dst;
+        *kernel_ptr = dst;
+        if (!dst || g.gene_major()) return DSQ_OK;
+        void *b;
+        if (int rc = capi_ws_get(slot, (size_t)g.n * g.ld * sizeof(T), &b)) return rc;
+        *kernel_ptr = ws = (T *)b;
+        return DSQ_OK;
+    }
+    int finish(const GmIn &g) {
+        if (ws) DSQ_HIP(transpose_back(ws, user, g.n, g.m, g.ld, g.st));
+        return DSQ_OK;
+    }
+};
+
+int finish_ycheck(bool ycheck, hipStream_t st) {
+    if (!ycheck) return DSQ_OK;
+    int32_t bad = 0;
+    void *badp;
+    int rc = capi_ws_get(WS_BAD, sizeof(int32_t), &badp);
+    if (rc) return rc;
+    DSQ_HIP(hipMemcpyAsync(&bad, badp, sizeof bad, hipMemcpyDeviceToHost, st));
+    DSQ_HIP(hipStreamSynchronize(st));
+    if (bad) return capi_fail(DSQ_ERR_VALUE, "count matrix holds negative, non-finite or non-integer values");
+    return DSQ_OK;
+}
+
 // =============================================================== fitBeta (device)
 int fit_beta_dev_locked(const DsqFitBetaArgs *a, const DsqFitBetaOut *o, hipStream_t st) {
-    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
-    if (a->n < 0 || a->m < 1 || a->p < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions n=%d m=%d p=%d", a->n, a->m, a->p);
-    if (a->p > DSQ_P_WIDE)
-        return capi_fail(DSQ_ERR_UNSUPPORTED, "p=%d design columns: kernels are compiled for 1..%d", a->p, DSQ_P_WIDE);
-    if (!a->y || !a->x || !a->nf || !a->alpha_hat || !a->contrast || !a->beta_mat || !a->lambda)
-        return capi_fail(DSQ_ERR_ARG, "NULL input array");
-    if (a->useWeights && !a->weights) return capi_fail(DSQ_ERR_ARG, "useWeights set but weights is NULL");
-    if (!o->beta_mat || !o->beta_var_mat || !o->iter || !o->contrast_num || !o->contrast_denom || !o->deviance)
-        return capi_fail(DSQ_ERR_ARG, "NULL output array");
-    if (a->maxit < 0) return capi_fail(DSQ_ERR_ARG, "maxit < 0");
-    if (a->layout == DSQ_LAYOUT_GENE_MAJOR && a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld < m");
-    if (a->layout != DSQ_LAYOUT_R && a->layout != DSQ_LAYOUT_GENE_MAJOR) return capi_fail(DSQ_ERR_ARG, "bad layout");
-    int rc = capi_check_device();
-    if (rc) return rc;
-    if (a->n == 0) return DSQ_OK;
+    bool empty;
+    int rc = dev_ready(check_fit_beta(a, o), a ? a->n : 0, &empty);
+    if (rc || empty) return rc;
 
     BetaKernelParams kp;
     memset(&kp, 0, sizeof kp);
     kp.n = a->n; kp.m = a->m; kp.p = a->p;
-    bool ycheck = false;
-    long ld = 0;
-    rc = prep_counts(a->y, a->y_type, a->layout, a->ld, a->n, a->m, st, &kp.y, &ld, &ycheck);
-    if (rc) return rc;
-    kp.ld = ld;
-    if (a->nf_is_vector) { kp.nf = a->nf; kp.nf_is_vector = 1; }
-    else {
-        rc = prep_matrix(a->nf, a->layout, a->ld, a->n, a->m, WS_NF, st, &kp.nf, ld);
-        if (rc) return rc;
-    }
-    if (a->useWeights) {
-        rc = prep_matrix(a->weights, a->layout, a->ld, a->n, a->m, WS_W, st, &kp.weights, ld);
-        if (rc) return rc;
-    }
+    GmIn in(a, st);
+    if ((rc = in.counts(a->y, a->y_type, &kp.y, &kp.ld))) return rc;
+    if ((rc = in.nf(a->nf, a->nf_is_vector, &kp.nf, &kp.nf_is_vector))) return rc;
+    if ((rc = in.weights(a->weights, a->useWeights, &kp.weights, &kp.useWeights))) return rc;
     kp.x = a->x; kp.alpha_hat = a->alpha_hat; kp.contrast = a->contrast; kp.beta_init = a->beta_mat;
     kp.lambda = a->lambda;
     kp.tol = a->tol; kp.minmu = a->minmu; kp.mu_floor = o->mu_floor;
-    kp.maxit = a->maxit; kp.useQR = a->useQR ? 1 : 0; kp.useWeights = a->useWeights ? 1 : 0;
+    kp.maxit = a->maxit; kp.useQR = a->useQR ? 1 : 0;
     kp.ablate = tuning().ablate; kp.force_iters = tuning().force_iters;
     rc = work_counter(st, &kp.work_counter); if (rc) return rc;
     if (a->cell_of && a->ncell > 0)
@@ -250,22 +394,9 @@ int fit_beta_dev_locked(const DsqFitBetaArgs *a, const DsqFitBetaOut *o, hipStre
         wide_out = bb + npw;
         kp.p = pk;
     }
-    // n x m outputs: directly when gene-major, through a workspace when R layout
-    double *hat_ws = nullptr, *mu_ws = nullptr;
-    if (o->hat_diagonals) {
-        if (a->layout == DSQ_LAYOUT_GENE_MAJOR) kp.hat_diagonals = o->hat_diagonals;
-        else {
-            void *b; rc = capi_ws_get(WS_HAT, (size_t)a->n * ld * sizeof(double), &b); if (rc) return rc;
-            hat_ws = (double *)b; kp.hat_diagonals = hat_ws;
-        }
-    }
-    if (o->mu) {
-        if (a->layout == DSQ_LAYOUT_GENE_MAJOR) kp.mu_out = o->mu;
-        else {
-            void *b; rc = capi_ws_get(WS_MUOUT, (size_t)a->n * ld * sizeof(double), &b); if (rc) return rc;
-            mu_ws = (double *)b; kp.mu_out = mu_ws;
-        }
-    }
+    GmOut<double> hat, mu;
+    if ((rc = hat.bind(in, o->hat_diagonals, WS_HAT, &kp.hat_diagonals))) return rc;
+    if ((rc = mu.bind(in, o->mu, WS_MUOUT, &kp.mu_out))) return rc;
     size_t slab_d = 0, cscr_d = 0;
     dispatch_beta_scratch(pk, a->n, a->m, a->useWeights, &slab_d, &cscr_d);
     {
@@ -283,46 +414,25 @@ int fit_beta_dev_locked(const DsqFitBetaArgs *a, const DsqFitBetaOut *o, hipStre
         DSQ_HIP(hipMemcpyAsync(o->beta_mat, wide_out, npp, hipMemcpyDeviceToDevice, st));
         DSQ_HIP(hipMemcpyAsync(o->beta_var_mat, wide_out + npw, npp, hipMemcpyDeviceToDevice, st));
     }
-    if (hat_ws) DSQ_HIP(launch_transpose_gm_to_r_f64(hat_ws, o->hat_diagonals, a->n, a->m, ld, st));
-    if (mu_ws) DSQ_HIP(launch_transpose_gm_to_r_f64(mu_ws, o->mu, a->n, a->m, ld, st));
-    if (ycheck) {
-        int32_t bad = 0;
-        void *badp; rc = capi_ws_get(WS_BAD, sizeof(int32_t), &badp); if (rc) return rc;
-        DSQ_HIP(hipMemcpyAsync(&bad, badp, sizeof bad, hipMemcpyDeviceToHost, st));
-        DSQ_HIP(hipStreamSynchronize(st));
-        if (bad) return capi_fail(DSQ_ERR_VALUE, "count matrix holds negative, non-finite or non-integer values");
-    }
-    return DSQ_OK;
+    if ((rc = hat.finish(in))) return rc;
+    if ((rc = mu.finish(in))) return rc;
+    return finish_ycheck(in.ycheck, st);
 }
 
 // =============================================================== fitDisp (device)
+// the part of the kernel parameters fitDisp and fitDispGrid share (the caller has run its check and found n > 0)
 static int disp_common(int n, int m, int p, int layout, long ld_in, const void *y, int y_type, const double *x,
                        const double *mu_hat, const double *weights, int useWeights, hipStream_t st,
-                       DispKernelParams *kp, bool *ycheck, const int32_t *cell_of = nullptr, int ncell = 0) {
-    if (n < 0 || m < 1 || p < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions n=%d m=%d p=%d", n, m, p);
-    if (p > DSQ_P_WIDE)
-        return capi_fail(DSQ_ERR_UNSUPPORTED, "p=%d design columns: kernels are compiled for 1..%d", p, DSQ_P_WIDE);
-    if (!y || !x || !mu_hat) return capi_fail(DSQ_ERR_ARG, "NULL input array");
-    if (useWeights && !weights) return capi_fail(DSQ_ERR_ARG, "useWeights set but weights is NULL");
-    if (layout == DSQ_LAYOUT_GENE_MAJOR && ld_in < m) return capi_fail(DSQ_ERR_ARG, "ld < m");
-    if (layout != DSQ_LAYOUT_R && layout != DSQ_LAYOUT_GENE_MAJOR) return capi_fail(DSQ_ERR_ARG, "bad layout");
-    int rc = capi_check_device();
-    if (rc) return rc;
+                       DispKernelParams *kp, bool *ycheck, const int32_t *cell_of, int ncell) {
     memset(kp, 0, sizeof *kp);
     kp->n = n; kp->m = m; kp->p = p;
-    if (n == 0) return DSQ_OK;
-    long ld = 0;
-    rc = prep_counts(y, y_type, layout, ld_in, n, m, st, &kp->y, &ld, ycheck);
+    GmIn in(layout, n, m, ld_in, st);
+    int rc = in.counts(y, y_type, &kp->y, &kp->ld);
+    *ycheck = in.ycheck;
     if (rc) return rc;
-    kp->ld = ld;
-    rc = prep_matrix(mu_hat, layout, ld_in, n, m, WS_MU, st, &kp->mu_hat, ld);
-    if (rc) return rc;
-    if (useWeights) {
-        rc = prep_matrix(weights, layout, ld_in, n, m, WS_W, st, &kp->weights, ld);
-        if (rc) return rc;
-    }
+    if ((rc = in.matrix(mu_hat, WS_MU, &kp->mu_hat))) return rc;
+    if ((rc = in.weights(weights, useWeights, &kp->weights, &kp->useWeights))) return rc;
     kp->x = x;
-    kp->useWeights = useWeights ? 1 : 0;
     if (cell_of && ncell > 0 && p >= tuning().disp_cell_minp)
         kp->ncell = capi_upload_cells(cell_of, m, WS_CELLS_BETA, st, &kp->cell_perm, &kp->cell_start);
     if (is_wide(p)) {           // zero-padded design, unit diagonal on the padding in the Cox-Reid matrix
@@ -334,31 +444,15 @@ static int disp_common(int n, int m, int p, int layout, long ld_in, const void *
     return DSQ_OK;
 }
 
-int finish_ycheck(bool ycheck, hipStream_t st) {
-    if (!ycheck) return DSQ_OK;
-    int32_t bad = 0;
-    void *badp;
-    int rc = capi_ws_get(WS_BAD, sizeof(int32_t), &badp);
-    if (rc) return rc;
-    DSQ_HIP(hipMemcpyAsync(&bad, badp, sizeof bad, hipMemcpyDeviceToHost, st));
-    DSQ_HIP(hipStreamSynchronize(st));
-    if (bad) return capi_fail(DSQ_ERR_VALUE, "count matrix holds negative, non-finite or non-integer values");
-    return DSQ_OK;
-}
-
 int fit_disp_dev_locked(const DsqFitDispArgs *a, const DsqFitDispOut *o, hipStream_t st) {
-    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
-    if (!a->log_alpha || !a->log_alpha_prior_mean) return capi_fail(DSQ_ERR_ARG, "NULL input vector");
-    if (!o->log_alpha || !o->iter || !o->iter_accept || !o->last_change || !o->initial_lp || !o->initial_dlp ||
-        !o->last_lp || !o->last_dlp)
-        return capi_fail(DSQ_ERR_ARG, "NULL output array");   // last_d2lp may be NULL: its kernel is then skipped
-    if (a->maxit < 0) return capi_fail(DSQ_ERR_ARG, "maxit < 0");
+    bool empty;
+    int rc = dev_ready(check_fit_disp(a, o), a ? a->n : 0, &empty);
+    if (rc || empty) return rc;
     DispKernelParams kp;
     bool ycheck = false;
-    int rc = disp_common(a->n, a->m, a->p, a->layout, a->ld, a->y, a->y_type, a->x, a->mu_hat, a->weights,
-                         a->useWeights, st, &kp, &ycheck, a->cell_of, a->ncell);
+    rc = disp_common(a->n, a->m, a->p, a->layout, a->ld, a->y, a->y_type, a->x, a->mu_hat, a->weights,
+                     a->useWeights, st, &kp, &ycheck, a->cell_of, a->ncell);
     if (rc) return rc;
-    if (a->n == 0) return DSQ_OK;
     kp.log_alpha_in = a->log_alpha; kp.prior_mean = a->log_alpha_prior_mean;
     kp.prior_sigmasq = a->log_alpha_prior_sigmasq; kp.min_log_alpha = a->min_log_alpha;
     kp.kappa_0 = a->kappa_0; kp.tol = a->tol; kp.weightThreshold = a->weightThreshold;
@@ -377,15 +471,14 @@ int fit_disp_dev_locked(const DsqFitDispArgs *a, const DsqFitDispOut *o, hipStre
 }
 
 int fit_disp_grid_dev_locked(const DsqFitDispGridArgs *a, const DsqFitDispGridOut *o, hipStream_t st) {
-    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
-    if (!a->disp_grid || !a->log_alpha_prior_mean || !o->log_alpha) return capi_fail(DSQ_ERR_ARG, "NULL array");
-    if (a->ngrid < 2) return capi_fail(DSQ_ERR_ARG, "disp_grid needs at least 2 points");
+    bool empty;
+    int rc = dev_ready(check_fit_disp_grid(a, o), a ? a->n : 0, &empty);
+    if (rc || empty) return rc;
     DispKernelParams kp;
     bool ycheck = false;
-    int rc = disp_common(a->n, a->m, a->p, a->layout, a->ld, a->y, a->y_type, a->x, a->mu_hat, a->weights,
-                         a->useWeights, st, &kp, &ycheck, a->cell_of, a->ncell);
+    rc = disp_common(a->n, a->m, a->p, a->layout, a->ld, a->y, a->y_type, a->x, a->mu_hat, a->weights,
+                     a->useWeights, st, &kp, &ycheck, a->cell_of, a->ncell);
     if (rc) return rc;
-    if (a->n == 0) return DSQ_OK;
     kp.prior_mean = a->log_alpha_prior_mean; kp.prior_sigmasq = a->log_alpha_prior_sigmasq;
     kp.weightThreshold = a->weightThreshold;
     kp.usePrior = a->usePrior ? 1 : 0; kp.useCR = a->useCR ? 1 : 0;
@@ -401,27 +494,16 @@ int fit_disp_grid_dev_locked(const DsqFitDispGridArgs *a, const DsqFitDispGridOu
 
 // =============================================================== extensions (device)
 int prefit_dev_locked(const DsqPrefitArgs *a, const DsqPrefitOut *o, hipStream_t st) {
-    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
-    if (a->n < 0 || a->m < 2 || a->p < 1 || a->m <= a->p) return capi_fail(DSQ_ERR_ARG, "bad dimensions n=%d m=%d p=%d", a->n, a->m, a->p);
-    if (!a->y || !a->nf || !a->q || !a->a || !a->r) return capi_fail(DSQ_ERR_ARG, "NULL input array");
-    if (a->useWeights && !a->weights) return capi_fail(DSQ_ERR_ARG, "useWeights set but weights is NULL");
-    if (!o->baseMean || !o->baseVar || !o->allZero || !o->roughDisp || !o->beta_init) return capi_fail(DSQ_ERR_ARG, "NULL output array");
-    if (a->layout == DSQ_LAYOUT_GENE_MAJOR && a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld < m");
-    int rc = capi_check_device();
-    if (rc) return rc;
-    if (a->n == 0) return DSQ_OK;
+    bool empty;
+    int rc = dev_ready(check_prefit(a, o), a ? a->n : 0, &empty);
+    if (rc || empty) return rc;
     PrefitKernelParams kp;
     memset(&kp, 0, sizeof kp);
     kp.n = a->n; kp.m = a->m; kp.p = a->p;
-    bool ycheck = false;
-    long ld = 0;
-    rc = prep_counts(a->y, a->y_type, a->layout, a->ld, a->n, a->m, st, &kp.y, &ld, &ycheck);
-    if (rc) return rc;
-    kp.ld = ld;
-    if (a->nf_is_vector) { kp.nf = a->nf; kp.nf_is_vector = 1; }
-    else { rc = prep_matrix(a->nf, a->layout, a->ld, a->n, a->m, WS_NF, st, &kp.nf, ld); if (rc) return rc; }
-    if (a->useWeights) { rc = prep_matrix(a->weights, a->layout, a->ld, a->n, a->m, WS_W, st, &kp.weights, ld); if (rc) return rc; }
-    kp.useWeights = a->useWeights ? 1 : 0;
+    GmIn in(a, st);
+    if ((rc = in.counts(a->y, a->y_type, &kp.y, &kp.ld))) return rc;
+    if ((rc = in.nf(a->nf, a->nf_is_vector, &kp.nf, &kp.nf_is_vector))) return rc;
+    if ((rc = in.weights(a->weights, a->useWeights, &kp.weights, &kp.useWeights))) return rc;
     kp.q = a->q; kp.a = a->a; kp.r = a->r;
     kp.baseMean = o->baseMean; kp.baseVar = o->baseVar; kp.allZero = o->allZero; kp.roughDisp = o->roughDisp;
     kp.beta_init = o->beta_init;
@@ -429,130 +511,88 @@ int prefit_dev_locked(const DsqPrefitArgs *a, const DsqPrefitOut *o, hipStream_t
     prof_begin(st);
     DSQ_HIP(launch_prefit(kp, st, &ok));
     prof_end(st);
-    if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "p=%d design columns: kernels are compiled for 1..%d", a->p, DSQ_P_WIDE);
-    return finish_ycheck(ycheck, st);
+    if (!ok) return too_wide(a->p);
+    return finish_ycheck(in.ycheck, st);
 }
 
 int linear_mu_dev_locked(const DsqPrefitArgs *a, double mu_floor, double *mu, hipStream_t st) {
-    if (!a || !mu) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
-    if (a->n < 0 || a->m < 1 || a->p < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
-    if (!a->y || !a->nf || !a->q || !a->a) return capi_fail(DSQ_ERR_ARG, "NULL input array");
-    if (a->layout == DSQ_LAYOUT_GENE_MAJOR && a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld < m");
-    int rc = capi_check_device();
-    if (rc) return rc;
-    if (a->n == 0) return DSQ_OK;
+    bool empty;
+    int rc = dev_ready(check_linear_mu(a, mu), a ? a->n : 0, &empty);
+    if (rc || empty) return rc;
     PrefitKernelParams kp;
     memset(&kp, 0, sizeof kp);
     kp.n = a->n; kp.m = a->m; kp.p = a->p;
-    bool ycheck = false;
-    long ld = 0;
-    rc = prep_counts(a->y, a->y_type, a->layout, a->ld, a->n, a->m, st, &kp.y, &ld, &ycheck);
-    if (rc) return rc;
-    kp.ld = ld;
-    if (a->nf_is_vector) { kp.nf = a->nf; kp.nf_is_vector = 1; }
-    else { rc = prep_matrix(a->nf, a->layout, a->ld, a->n, a->m, WS_NF, st, &kp.nf, ld); if (rc) return rc; }
+    GmIn in(a, st);
+    if ((rc = in.counts(a->y, a->y_type, &kp.y, &kp.ld))) return rc;
+    if ((rc = in.nf(a->nf, a->nf_is_vector, &kp.nf, &kp.nf_is_vector))) return rc;
     kp.q = a->q; kp.a = a->a;
-    double *dst = mu;
-    if (a->layout != DSQ_LAYOUT_GENE_MAJOR) {
-        void *b; rc = capi_ws_get(WS_MUOUT, (size_t)a->n * ld * sizeof(double), &b); if (rc) return rc;
-        dst = (double *)b;
-    }
+    GmOut<double> out;
+    double *dst;
+    if ((rc = out.bind(in, mu, WS_MUOUT, &dst))) return rc;
     bool ok = false;
     prof_begin(st);
     DSQ_HIP(launch_linear_mu(kp, mu_floor, dst, st, &ok));
     prof_end(st);
-    if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "p=%d design columns: kernels are compiled for 1..%d", a->p, DSQ_P_WIDE);
-    if (a->layout != DSQ_LAYOUT_GENE_MAJOR) DSQ_HIP(launch_transpose_gm_to_r_f64(dst, mu, a->n, a->m, ld, st));
-    return finish_ycheck(ycheck, st);
+    if (!ok) return too_wide(a->p);
+    if ((rc = out.finish(in))) return rc;
+    return finish_ycheck(in.ycheck, st);
 }
 
 int loglike_dev_locked(const DsqLogLikeArgs *a, double *out, hipStream_t st) {
-    if (!a || !out) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
-    if (a->n < 0 || a->m < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
-    if (!a->y || !a->mu || !a->disp) return capi_fail(DSQ_ERR_ARG, "NULL input array");
-    if (a->useWeights && !a->weights) return capi_fail(DSQ_ERR_ARG, "useWeights set but weights is NULL");
-    if (a->layout == DSQ_LAYOUT_GENE_MAJOR && a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld < m");
-    int rc = capi_check_device();
-    if (rc) return rc;
-    if (a->n == 0) return DSQ_OK;
+    bool empty;
+    int rc = dev_ready(check_loglike(a, out), a ? a->n : 0, &empty);
+    if (rc || empty) return rc;
     LogLikeKernelParams kp;
     memset(&kp, 0, sizeof kp);
     kp.n = a->n; kp.m = a->m;
-    bool ycheck = false;
-    long ld = 0;
-    rc = prep_counts(a->y, a->y_type, a->layout, a->ld, a->n, a->m, st, &kp.y, &ld, &ycheck);
-    if (rc) return rc;
-    kp.ld = ld;
-    rc = prep_matrix(a->mu, a->layout, a->ld, a->n, a->m, WS_MU, st, &kp.mu, ld);
-    if (rc) return rc;
-    if (a->useWeights) { rc = prep_matrix(a->weights, a->layout, a->ld, a->n, a->m, WS_W, st, &kp.weights, ld); if (rc) return rc; }
-    kp.useWeights = a->useWeights ? 1 : 0;
+    GmIn in(a, st);
+    if ((rc = in.counts(a->y, a->y_type, &kp.y, &kp.ld))) return rc;
+    if ((rc = in.matrix(a->mu, WS_MU, &kp.mu))) return rc;
+    if ((rc = in.weights(a->weights, a->useWeights, &kp.weights, &kp.useWeights))) return rc;
     kp.disp = a->disp; kp.loglike = out;
     prof_begin(st);
     DSQ_HIP(launch_loglike(kp, st));
     prof_end(st);
-    return finish_ycheck(ycheck, st);
+    return finish_ycheck(in.ycheck, st);
 }
 
 int intercept_dev_locked(const DsqInterceptArgs *a, const DsqInterceptOut *o, hipStream_t st) {
-    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
-    if (a->n < 0 || a->m < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
-    if (!a->y || !a->nf || !a->alpha) return capi_fail(DSQ_ERR_ARG, "NULL input array");
-    if (a->useWeights && !a->weights) return capi_fail(DSQ_ERR_ARG, "useWeights set but weights is NULL");
-    if (!o->beta_log2 || !o->betaSE) return capi_fail(DSQ_ERR_ARG, "NULL output array");
-    if (a->layout == DSQ_LAYOUT_GENE_MAJOR && a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld < m");
-    int rc = capi_check_device();
-    if (rc) return rc;
-    if (a->n == 0) return DSQ_OK;
+    bool empty;
+    int rc = dev_ready(check_intercept(a, o), a ? a->n : 0, &empty);
+    if (rc || empty) return rc;
     InterceptKernelParams kp;
     memset(&kp, 0, sizeof kp);
     kp.n = a->n; kp.m = a->m;
-    bool ycheck = false;
-    long ld = 0;
-    rc = prep_counts(a->y, a->y_type, a->layout, a->ld, a->n, a->m, st, &kp.y, &ld, &ycheck);
-    if (rc) return rc;
-    kp.ld = ld;
-    if (a->nf_is_vector) { kp.nf = a->nf; kp.nf_is_vector = 1; }
-    else { rc = prep_matrix(a->nf, a->layout, a->ld, a->n, a->m, WS_NF, st, &kp.nf, ld); if (rc) return rc; }
-    if (a->useWeights) { rc = prep_matrix(a->weights, a->layout, a->ld, a->n, a->m, WS_W, st, &kp.weights, ld); if (rc) return rc; }
-    kp.useWeights = a->useWeights ? 1 : 0;
+    GmIn in(a, st);
+    if ((rc = in.counts(a->y, a->y_type, &kp.y, &kp.ld))) return rc;
+    if ((rc = in.nf(a->nf, a->nf_is_vector, &kp.nf, &kp.nf_is_vector))) return rc;
+    if ((rc = in.weights(a->weights, a->useWeights, &kp.weights, &kp.useWeights))) return rc;
     kp.alpha = a->alpha; kp.mu_floor = a->mu_floor;
     kp.beta_log2 = o->beta_log2; kp.betaSE = o->betaSE;
-    double *mu_ws = nullptr, *hat_ws = nullptr;
-    if (o->mu) {
-        if (a->layout == DSQ_LAYOUT_GENE_MAJOR) kp.mu_out = o->mu;
-        else { void *b; rc = capi_ws_get(WS_MUOUT, (size_t)a->n * ld * sizeof(double), &b); if (rc) return rc; mu_ws = (double *)b; kp.mu_out = mu_ws; }
-    }
-    if (o->hat) {
-        if (a->layout == DSQ_LAYOUT_GENE_MAJOR) kp.hat = o->hat;
-        else { void *b; rc = capi_ws_get(WS_HAT, (size_t)a->n * ld * sizeof(double), &b); if (rc) return rc; hat_ws = (double *)b; kp.hat = hat_ws; }
-    }
+    GmOut<double> mu, hat;
+    if ((rc = mu.bind(in, o->mu, WS_MUOUT, &kp.mu_out))) return rc;
+    if ((rc = hat.bind(in, o->hat, WS_HAT, &kp.hat))) return rc;
     prof_begin(st);
     DSQ_HIP(launch_intercept_fit(kp, st));
     prof_end(st);
-    if (mu_ws) DSQ_HIP(launch_transpose_gm_to_r_f64(mu_ws, o->mu, a->n, a->m, ld, st));
-    if (hat_ws) DSQ_HIP(launch_transpose_gm_to_r_f64(hat_ws, o->hat, a->n, a->m, ld, st));
-    return finish_ycheck(ycheck, st);
+    if ((rc = mu.finish(in))) return rc;
+    if ((rc = hat.finish(in))) return rc;
+    return finish_ycheck(in.ycheck, st);
 }
 
 // =============================================================== Cook's distances / replaceOutliers
 static int next_pow2(int n) { int v = 2; while (v < n) v <<= 1; return v; }
 
 int cooks_dev_locked(const DsqCooksArgs *a, const DsqCooksOut *o, hipStream_t st) {
-    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
-    if (a->n < 0 || a->m < 1 || a->p < 1 || a->ncell < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
-    if (!a->y || !a->nf || !a->mu || !a->H || !a->cell_of) return capi_fail(DSQ_ERR_ARG, "NULL input array");
-    if (!o->cooks || !o->maxCooks) return capi_fail(DSQ_ERR_ARG, "NULL output array");
-    if (a->layout == DSQ_LAYOUT_GENE_MAJOR && a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld < m");
+    bool empty;
+    int rc = dev_ready(check_cooks(a, o), a ? a->n : 0, &empty);
+    if (rc || empty) return rc;
     const int m = a->m;
     // design cells -> sample permutation grouped by cell, offsets, ">= 3 in cell" flags
     static thread_local std::vector<int32_t> meta;
     meta.assign((size_t)2 * m + a->ncell + 1, 0);
     int32_t *perm = meta.data(), *in3 = perm + m, *start = in3 + m;
-    for (int j = 0; j < m; j++) {
-        if (a->cell_of[j] < 0 || a->cell_of[j] >= a->ncell) return capi_fail(DSQ_ERR_VALUE, "cell_of[%d] out of range", j);
-        start[a->cell_of[j] + 1]++;
-    }
+    for (int j = 0; j < m; j++) start[a->cell_of[j] + 1]++;
     int maxcell = 0, any3 = 0;
     for (int c = 0; c < a->ncell; c++) {
         int sz = start[c + 1];
@@ -565,23 +605,15 @@ int cooks_dev_locked(const DsqCooksArgs *a, const DsqCooksOut *o, hipStream_t st
         for (int j = 0; j < m; j++) perm[fill[a->cell_of[j]]++] = j;
     }
     for (int j = 0; j < m; j++) in3[j] = (start[a->cell_of[j] + 1] - start[a->cell_of[j]]) >= 3;
-    int rc = capi_check_device();
-    if (rc) return rc;
-    if (a->n == 0) return DSQ_OK;
     CooksKernelParams kp;
     memset(&kp, 0, sizeof kp);
     kp.n = a->n; kp.m = m; kp.p = a->p; kp.ncell = a->ncell; kp.any3 = any3;
     kp.sortcap = next_pow2(any3 ? maxcell : m);
-    bool ycheck = false;
-    long ld = 0;
-    rc = prep_counts(a->y, a->y_type, a->layout, a->ld, a->n, m, st, &kp.y, &ld, &ycheck);
-    if (rc) return rc;
-    kp.ld = ld;
-    kp.nf_is_vector = a->nf_is_vector ? 1 : 0;
-    if (kp.nf_is_vector) kp.nf = a->nf;
-    else { rc = prep_matrix(a->nf, a->layout, a->ld, a->n, m, WS_NF, st, &kp.nf, ld); if (rc) return rc; }
-    rc = prep_matrix(a->mu, a->layout, a->ld, a->n, m, WS_MU, st, &kp.mu, ld); if (rc) return rc;
-    rc = prep_matrix(a->H, a->layout, a->ld, a->n, m, WS_W, st, &kp.H, ld); if (rc) return rc;
+    GmIn in(a, st);
+    if ((rc = in.counts(a->y, a->y_type, &kp.y, &kp.ld))) return rc;
+    if ((rc = in.nf(a->nf, a->nf_is_vector, &kp.nf, &kp.nf_is_vector))) return rc;
+    if ((rc = in.matrix(a->mu, WS_MU, &kp.mu))) return rc;
+    if ((rc = in.matrix(a->H, WS_W, &kp.H))) return rc;
     void *v;
     rc = capi_ws_get(WS_CELLS, meta.size() * sizeof(int32_t) + (size_t)a->n * 8, &v); if (rc) return rc;
     DSQ_HIP(hipMemcpyAsync(v, meta.data(), meta.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -589,40 +621,29 @@ int cooks_dev_locked(const DsqCooksArgs *a, const DsqCooksOut *o, hipStream_t st
     kp.maxCooks = o->maxCooks;
     if (o->robustDisp) kp.robustDisp = o->robustDisp;
     else kp.robustDisp = (double *)((char *)v + ((meta.size() * sizeof(int32_t) + 7) & ~(size_t)7));
-    if (a->layout == DSQ_LAYOUT_GENE_MAJOR) kp.cooks = o->cooks;
-    else { void *b; rc = capi_ws_get(WS_HAT, (size_t)a->n * ld * sizeof(double), &b); if (rc) return rc; kp.cooks = (double *)b; }
+    GmOut<double> cooks;
+    if ((rc = cooks.bind(in, o->cooks, WS_HAT, &kp.cooks))) return rc;
     bool ok = true;
     prof_begin(st);
     DSQ_HIP(launch_cooks(kp, st, &ok));
     prof_end(st);
     if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "m=%d samples: a gene row plus its sort buffer exceeds the 160 KiB LDS", m);
-    if (a->layout != DSQ_LAYOUT_GENE_MAJOR) DSQ_HIP(launch_transpose_gm_to_r_f64(kp.cooks, o->cooks, a->n, m, ld, st));
-    return finish_ycheck(ycheck, st);
+    if ((rc = cooks.finish(in))) return rc;
+    return finish_ycheck(in.ycheck, st);
 }
 
 int replace_dev_locked(const DsqReplaceArgs *a, const DsqReplaceOut *o, hipStream_t st) {
-    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
-    if (a->n < 0 || a->m < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
-    if (!a->y || !a->nf || !a->cooks || !a->replaceable) return capi_fail(DSQ_ERR_ARG, "NULL input array");
-    if (!o->newCounts || !o->replace) return capi_fail(DSQ_ERR_ARG, "NULL output array");
-    if (!(a->trim >= 0.0 && a->trim < 0.5)) return capi_fail(DSQ_ERR_ARG, "trim must be in [0, 0.5)");
-    if (a->layout == DSQ_LAYOUT_GENE_MAJOR && a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld < m");
-    int rc = capi_check_device();
-    if (rc) return rc;
-    if (a->n == 0) return DSQ_OK;
+    bool empty;
+    int rc = dev_ready(check_replace(a, o), a ? a->n : 0, &empty);
+    if (rc || empty) return rc;
     const int m = a->m;
     ReplaceKernelParams kp;
     memset(&kp, 0, sizeof kp);
     kp.n = a->n; kp.m = m; kp.cutoff = a->cooksCutoff; kp.trim = a->trim; kp.sortcap = next_pow2(m);
-    bool ycheck = false;
-    long ld = 0;
-    rc = prep_counts(a->y, a->y_type, a->layout, a->ld, a->n, m, st, &kp.y, &ld, &ycheck);
-    if (rc) return rc;
-    kp.ld = ld;
-    kp.nf_is_vector = a->nf_is_vector ? 1 : 0;
-    if (kp.nf_is_vector) kp.nf = a->nf;
-    else { rc = prep_matrix(a->nf, a->layout, a->ld, a->n, m, WS_NF, st, &kp.nf, ld); if (rc) return rc; }
-    rc = prep_matrix(a->cooks, a->layout, a->ld, a->n, m, WS_COOKS_IN, st, &kp.cooks, ld); if (rc) return rc;
+    GmIn in(a, st);
+    if ((rc = in.counts(a->y, a->y_type, &kp.y, &kp.ld))) return rc;
+    if ((rc = in.nf(a->nf, a->nf_is_vector, &kp.nf, &kp.nf_is_vector))) return rc;
+    if ((rc = in.matrix(a->cooks, WS_COOKS_IN, &kp.cooks))) return rc;
     static thread_local std::vector<int32_t> flags;
     flags.assign(a->replaceable, a->replaceable + m);
     void *v;
@@ -630,15 +651,15 @@ int replace_dev_locked(const DsqReplaceArgs *a, const DsqReplaceOut *o, hipStrea
     DSQ_HIP(hipMemcpyAsync(v, flags.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
     kp.replaceable = (int32_t *)v;
     kp.replace = o->replace;
-    if (a->layout == DSQ_LAYOUT_GENE_MAJOR) kp.newCounts = o->newCounts;
-    else { void *b; rc = capi_ws_get(WS_HAT, (size_t)a->n * ld * sizeof(int32_t), &b); if (rc) return rc; kp.newCounts = (int32_t *)b; }
+    GmOut<int32_t> counts;
+    if ((rc = counts.bind(in, o->newCounts, WS_HAT, &kp.newCounts))) return rc;
     bool ok = true;
     prof_begin(st);
     DSQ_HIP(launch_replace(kp, st, &ok));
     prof_end(st);
     if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "m=%d samples: the sort buffer exceeds the 160 KiB LDS", m);
-    if (a->layout != DSQ_LAYOUT_GENE_MAJOR) DSQ_HIP(launch_transpose_gm_to_r_i32(kp.newCounts, o->newCounts, a->n, m, ld, st));
-    return finish_ycheck(ycheck, st);
+    if ((rc = counts.finish(in))) return rc;
+    return finish_ycheck(in.ycheck, st);
 }
 
 int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o) {
@@ -655,8 +676,7 @@ int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o) {
 
 int size_factors_dev_locked(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o, hipStream_t st) {
     if (int rc = size_factors_check(a, o)) return rc;
-    if (a->layout != DSQ_LAYOUT_R && a->layout != DSQ_LAYOUT_GENE_MAJOR) return capi_fail(DSQ_ERR_ARG, "unknown layout %d", a->layout);
-    if (a->layout == DSQ_LAYOUT_GENE_MAJOR && a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld < m");
+    if (int rc = check_layout(a->layout, a->ld, a->m, true)) return rc;
     const size_t need = size_factors_workspace_bytes(a->n, a->m);
     if (!a->workspace || a->workspace_bytes < (int64_t)need)
         return capi_fail(DSQ_ERR_ARG, "workspace of %lld bytes: dsq_size_factors_workspace_bytes(n, m) = %zu", (long long)a->workspace_bytes, need);
@@ -718,8 +738,7 @@ int vst_check(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stat
 
 int vst_dev_locked(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats, hipStream_t st) {
     if (int rc = vst_check(a, o, transform, stats)) return rc;
-    if (a->layout != DSQ_LAYOUT_R && a->layout != DSQ_LAYOUT_GENE_MAJOR) return capi_fail(DSQ_ERR_ARG, "unknown layout %d", a->layout);
-    if (a->layout == DSQ_LAYOUT_GENE_MAJOR && a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld < m");
+    if (int rc = check_layout(a->layout, a->ld, a->m, true)) return rc;
     if (int rc = capi_check_device()) return rc;
     VstKernelParams kp;
     memset(&kp, 0, sizeof kp);
@@ -757,33 +776,50 @@ int vst_dev_locked(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool
 
 using namespace dsq;
 
+// a `_dev` entry point: the call lock, the stream's context latched for the call, then the body
+template <class F>
+static int dev_entry(void *stream, F &&body) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    WsScope ws((hipStream_t)stream);
+    return body((hipStream_t)stream);
+}
+
 extern "C" {
 
-int dsq_vst_dev(const DsqVstArgs *args, const DsqVstOut *out, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    return vst_dev_locked(args, out, true, false, (hipStream_t)stream);
+#define DSQ_DEV(name, A, O, call) \
+    int name(const A *a, O o, void *s) { return dev_entry(s, [&](hipStream_t st) { return call; }); }
+DSQ_DEV(dsq_fit_beta_dev, DsqFitBetaArgs, const DsqFitBetaOut *, fit_beta_dev_locked(a, o, st))
+DSQ_DEV(dsq_fit_disp_dev, DsqFitDispArgs, const DsqFitDispOut *, fit_disp_dev_locked(a, o, st))
+DSQ_DEV(dsq_fit_disp_grid_dev, DsqFitDispGridArgs, const DsqFitDispGridOut *, fit_disp_grid_dev_locked(a, o, st))
+DSQ_DEV(dsq_prefit_moments_dev, DsqPrefitArgs, const DsqPrefitOut *, prefit_dev_locked(a, o, st))
+DSQ_DEV(dsq_nbinom_loglike_dev, DsqLogLikeArgs, double *, loglike_dev_locked(a, o, st))
+DSQ_DEV(dsq_intercept_fit_dev, DsqInterceptArgs, const DsqInterceptOut *, intercept_dev_locked(a, o, st))
+DSQ_DEV(dsq_cooks_distance_dev, DsqCooksArgs, const DsqCooksOut *, cooks_dev_locked(a, o, st))
+DSQ_DEV(dsq_replace_outliers_dev, DsqReplaceArgs, const DsqReplaceOut *, replace_dev_locked(a, o, st))
+DSQ_DEV(dsq_size_factors_dev, DsqSizeFactorArgs, const DsqSizeFactorOut *, size_factors_dev_locked(a, o, st))
+DSQ_DEV(dsq_vst_dev, DsqVstArgs, const DsqVstOut *, vst_dev_locked(a, o, true, false, st))
+DSQ_DEV(dsq_vst_rowstats_dev, DsqVstArgs, const DsqVstOut *, vst_dev_locked(a, o, false, true, st))
+#undef DSQ_DEV
+int dsq_linear_mu_dev(const DsqPrefitArgs *a, double mu_floor, double *mu, void *s) {
+    return dev_entry(s, [&](hipStream_t st) { return linear_mu_dev_locked(a, mu_floor, mu, st); });
 }
-int dsq_vst_rowstats_dev(const DsqVstArgs *args, const DsqVstOut *out, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    return vst_dev_locked(args, out, false, true, (hipStream_t)stream);
+int dsq_parametric_dispersion_fit_dev(const double *means, const double *disps, int64_t n, double *coefs, int32_t *status,
+                                      void *s) {
+    return dev_entry(s, [&](hipStream_t st) -> int {
+        if (int rc = check_trend_fit(means, disps, n, coefs, status)) return rc;
+        if (int rc = capi_check_device()) return rc;
+        prof_begin(st);
+        void *tws;
+        if (int rc = capi_ws_get(WS_TREND, trend_fit_workspace_bytes(), &tws)) return rc;
+        DSQ_HIP(launch_trend_fit(means, disps, (long)n, coefs, status, tws, st));
+        prof_end(st);
+        return DSQ_OK;
+    });
 }
 
-int dsq_fit_beta_dev(const DsqFitBetaArgs *args, const DsqFitBetaOut *out, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    return fit_beta_dev_locked(args, out, (hipStream_t)stream);
-}
-int dsq_fit_disp_dev(const DsqFitDispArgs *args, const DsqFitDispOut *out, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    return fit_disp_dev_locked(args, out, (hipStream_t)stream);
-}
-int dsq_fit_disp_grid_dev(const DsqFitDispGridArgs *args, const DsqFitDispGridOut *out, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    return fit_disp_grid_dev_locked(args, out, (hipStream_t)stream);
+int64_t dsq_size_factors_workspace_bytes(int32_t n, int32_t m) {
+    if (n < 0 || m < 0) return 0;
+    return (int64_t)size_factors_workspace_bytes(n, m);
 }
 
 int dsq_weights_prep_dev(const double *weights_raw, const double *x, int32_t n, int32_t m, int32_t p, int64_t ld,
@@ -833,64 +869,6 @@ int dsq_from_gene_major_f64(const double *src_gm, double *dst_r, int32_t n, int3
     if (n == 0) return DSQ_OK;
     DSQ_HIP(launch_transpose_gm_to_r_f64(src_gm, dst_r, n, m, ld, (hipStream_t)stream));
     return DSQ_OK;
-}
-
-int dsq_parametric_dispersion_fit_dev(const double *means, const double *disps, int64_t n, double *coefs,
-                                      int32_t *status, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    if (!means || !disps || !coefs || !status || n < 1) return capi_fail(DSQ_ERR_ARG, "bad arguments");
-    if (int rc = capi_check_device()) return rc;
-    prof_begin((hipStream_t)stream);
-    void *tws;
-    if (int rc = capi_ws_get(WS_TREND, trend_fit_workspace_bytes(), &tws)) return rc;
-    DSQ_HIP(launch_trend_fit(means, disps, (long)n, coefs, status, tws, (hipStream_t)stream));
-    prof_end((hipStream_t)stream);
-    return DSQ_OK;
-}
-
-int dsq_prefit_moments_dev(const DsqPrefitArgs *args, const DsqPrefitOut *out, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    return prefit_dev_locked(args, out, (hipStream_t)stream);
-}
-int dsq_linear_mu_dev(const DsqPrefitArgs *args, double mu_floor, double *mu, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    return linear_mu_dev_locked(args, mu_floor, mu, (hipStream_t)stream);
-}
-int dsq_nbinom_loglike_dev(const DsqLogLikeArgs *args, double *loglike, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    return loglike_dev_locked(args, loglike, (hipStream_t)stream);
-}
-
-int dsq_intercept_fit_dev(const DsqInterceptArgs *args, const DsqInterceptOut *out, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    return intercept_dev_locked(args, out, (hipStream_t)stream);
-}
-
-int dsq_cooks_distance_dev(const DsqCooksArgs *args, const DsqCooksOut *out, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    return cooks_dev_locked(args, out, (hipStream_t)stream);
-}
-int dsq_replace_outliers_dev(const DsqReplaceArgs *args, const DsqReplaceOut *out, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    return replace_dev_locked(args, out, (hipStream_t)stream);
-}
-
-int64_t dsq_size_factors_workspace_bytes(int32_t n, int32_t m) {
-    if (n < 0 || m < 0) return 0;
-    return (int64_t)size_factors_workspace_bytes(n, m);
-}
-
-int dsq_size_factors_dev(const DsqSizeFactorArgs *args, const DsqSizeFactorOut *out, void *stream) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    WsScope ws((hipStream_t)stream);
-    return size_factors_dev_locked(args, out, (hipStream_t)stream);
 }
 
 }  // extern "C"

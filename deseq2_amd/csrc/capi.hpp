@@ -31,6 +31,23 @@ int finish_ycheck(bool ycheck, hipStream_t st);
 // a zero-padded copy of a design in a workspace slot of the latched context: column-major rows x p -> rows x pw (memset,
 // then a device-to-device copy of the true columns, on `st`); the calls' wide designs and the chain's three use it
 int capi_pad_design(int slot, const double *src, size_t rows, int p, int pw, hipStream_t st, const double **out);
+// each call's checks, stated once: everything that can be decided from the argument block alone.  Both halves call it
+// first (then: the device, then an empty call returns DSQ_OK); a host entry adds check_host_layout and its row range
+int check_fit_beta(const DsqFitBetaArgs *a, const DsqFitBetaOut *o);
+int check_fit_disp(const DsqFitDispArgs *a, const DsqFitDispOut *o);
+int check_fit_disp_grid(const DsqFitDispGridArgs *a, const DsqFitDispGridOut *o);
+int check_trend_fit(const double *means, const double *disps, int64_t n, const double *coefs, const int32_t *status);
+int check_prefit(const DsqPrefitArgs *a, const DsqPrefitOut *o);
+int check_linear_mu(const DsqPrefitArgs *a, const double *mu);
+int check_loglike(const DsqLogLikeArgs *a, const double *out);
+int check_intercept(const DsqInterceptArgs *a, const DsqInterceptOut *o);
+int check_optim(const DsqOptimArgs *a, const DsqOptimOut *o);
+int check_cooks(const DsqCooksArgs *a, const DsqCooksOut *o);
+int check_replace(const DsqReplaceArgs *a, const DsqReplaceOut *o);
+int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o);
+int vst_check(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats);
+int check_host_layout(int layout);
+// the device-pointer bodies behind the entry points
 int fit_beta_dev_locked(const DsqFitBetaArgs *a, const DsqFitBetaOut *o, hipStream_t st);
 int fit_disp_dev_locked(const DsqFitDispArgs *a, const DsqFitDispOut *o, hipStream_t st);
 int fit_disp_grid_dev_locked(const DsqFitDispGridArgs *a, const DsqFitDispGridOut *o, hipStream_t st);
@@ -40,9 +57,7 @@ int loglike_dev_locked(const DsqLogLikeArgs *a, double *out, hipStream_t st);
 int intercept_dev_locked(const DsqInterceptArgs *a, const DsqInterceptOut *o, hipStream_t st);
 int cooks_dev_locked(const DsqCooksArgs *a, const DsqCooksOut *o, hipStream_t st);
 int replace_dev_locked(const DsqReplaceArgs *a, const DsqReplaceOut *o, hipStream_t st);
-int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o);
 int size_factors_dev_locked(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o, hipStream_t st);
-int vst_check(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats);
 int vst_dev_locked(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats, hipStream_t st);
 
 }  // namespace dsq

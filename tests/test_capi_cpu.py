@@ -222,3 +222,585 @@ def test_exec_lint_flags_the_round_4_pattern_and_not_a_masked_body():
     assert hits[0] == ["v_mov_b32_e32 v116, 0x260"], hits
     assert hits[1] == ["v_mov_b64_e32 v[4:5], 1.0"], hits
     assert hits[2] == [], hits
+
+
+# ---- status codes of the argument checks ---------------------------------------------------------------------------------
+def _tiny_blocks():
+    """valid argument blocks of every block-taking entry at n = 4, m = 6, p = 2 (tests/capi_blocks.py)"""
+    from tests import capi_blocks
+    from tests.helpers import make_case
+    d = make_case(40, 6, "two_group", seed=5)
+    d = {k: (v[:4] if isinstance(v, np.ndarray) and v.shape[:1] == d["counts"].shape[:1] else v) for k, v in d.items()}
+    B = capi_blocks.blocks(d)
+    for k in ("fit_beta", "fit_disp", "fit_disp_grid", "prefit_moments", "nbinom_loglike", "intercept_fit", "optim_rows"):
+        B[k].inputs["weights"] = np.ones((4, 6))           # given but unused: `useWeights without weights` NULLs it
+    return B
+
+
+def _argument_cases():
+    """(case id, thunk returning the status code): from each valid block, one thing broken at a time"""
+    import ctypes as C
+    from deseq2_amd import _lib
+    from tests import capi_blocks as cb
+    L = _lib.lib()
+    cases = []
+    B = _tiny_blocks()
+    for key, b in B.items():
+        entries = [(b.name, "host")] + ([(b.name + "_rows", "rows")] if key.startswith("fit_") else [])
+        if key == "vst":
+            entries += [("dsq_vst_dev", "dev"), ("dsq_vst_rowstats_dev", "dev")]
+        elif b.dev:
+            entries.append((b.dev, "dev"))
+        for ename, how in entries:
+            def run(blk, null_args=False, null_out=False, ename=ename, how=how):
+                keep = {k: (None if v is None else cb.fcol(v)) for k, v in blk.inputs.items()}
+                outs = {k: np.zeros(shape, dtype=dt, order="F") for k, (shape, dt) in blk.outputs.items()}
+                a = blk.args({k: cb.ptr(v) for k, v in keep.items()})
+                tail = {"host": (), "rows": (0, 4), "dev": (None,)}[how]
+                fn = getattr(L, ename)
+                pa = None if null_args else C.byref(a)
+                optr = {k: cb.ptr(v) for k, v in outs.items()}
+                if blk.style == "mu":
+                    return fn(pa, 0.5, None if null_out else optr["mu"], *tail)
+                if blk.style == "vec":
+                    return fn(pa, None if null_out else optr["loglike"], *tail)
+                o = blk.O(**optr, **blk.out_scalars)
+                return fn(pa, None if null_out else C.byref(o), *tail)
+
+            def add(what, blk, run=run, ename=ename, **kw):
+                cases.append(("%s: %s" % (ename, what), lambda blk=blk, kw=kw, run=run: run(blk, **kw)))
+            add("NULL args", b, null_args=True)
+            add("NULL out", b, null_out=True)
+            for f in b.inputs:
+                if b.inputs[f] is not None:
+                    add("args.%s NULL" % f.rstrip("_"), b.but(**{f: None}))
+            if b.style == "ao":
+                for f in b.outputs:
+                    add("out.%s NULL" % f, b.but(drop_out=[f]))
+            add("n = -1", b.but(n=-1))
+            add("m = 0", b.but(m=0))
+            if "p" in b.scalars:
+                add("p = 0", b.but(p=0))
+                add("p = 65", b.but(p=65))
+            if "useWeights" in b.scalars and "weights" in b.inputs and key != "linear_mu":
+                add("useWeights without weights", b.but(useWeights=1, weights=None))
+            if "maxit" in b.scalars:
+                add("maxit = -1", b.but(maxit=-1))
+            if "ngrid" in b.scalars:
+                add("ngrid = 1", b.but(ngrid=1))
+            if "trim" in b.scalars:
+                add("trim = 0.5", b.but(trim=0.5))
+            add("y_type = 7", b.but(y_type=7))
+            if "type" in b.scalars:
+                add("type = 9", b.but(type=9))
+            if "kind" in b.scalars:
+                add("kind = 9", b.but(kind=9))
+            if key == "prefit_moments":
+                add("m <= p", b.but(p=6))
+            if key == "cooks_distance":
+                add("ncell = 0", b.but(ncell=0))
+            if how == "dev":
+                add("gene-major, ld < m", b.but(layout=1, ld=5))
+                add("layout = 7", b.but(layout=7, ld=8))
+            else:
+                add("layout = GENE_MAJOR", b.but(layout=1, ld=8))
+            if how == "rows":
+                cases.append(("%s: row range past n" % ename, lambda b=b, ename=ename: cb._invoke(
+                    b, getattr(L, ename), b.args({k: cb.ptr(None if v is None else cb.fcol(v)) for k, v in b.inputs.items()}),
+                    {k: None for k in b.outputs}, (2, 3))))
+    # the entries that take plain arguments
+    v = np.ones(8)
+    i4 = np.ones(8, np.int32)
+    P = cb.ptr
+    plain = {
+        "dsq_parametric_dispersion_fit": lambda **k: L.dsq_parametric_dispersion_fit(
+            k.get("means", P(v)), P(v), k.get("n", 8), k.get("coefs", P(v)), P(i4)),
+        "dsq_parametric_dispersion_fit_dev": lambda **k: L.dsq_parametric_dispersion_fit_dev(
+            k.get("means", P(v)), P(v), k.get("n", 8), k.get("coefs", P(v)), P(i4), None),
+        "dsq_test_math": lambda **k: L.dsq_test_math(k.get("op", 0), k.get("means", P(v)), None, None, k.get("coefs", P(v)),
+                                                     k.get("n", 8)),
+    }
+    for ename, f in plain.items():
+        cases.append((ename + ": first input NULL", lambda f=f: f(means=None)))
+        cases.append((ename + ": output NULL", lambda f=f: f(coefs=None)))
+        cases.append((ename + ": n = -1", lambda f=f: f(n=-1)))
+    cases.append(("dsq_parametric_dispersion_fit: n = 0", lambda: plain["dsq_parametric_dispersion_fit"](n=0)))
+    cases.append(("dsq_parametric_dispersion_fit_dev: n = 0", lambda: plain["dsq_parametric_dispersion_fit_dev"](n=0)))
+    cases.append(("dsq_test_math: op 7 without b", lambda: plain["dsq_test_math"](op=7)))
+    return cases
+
+
+# the status code of each case as the library of commit e1d44e3 (the parent of the change that states every call's checks
+# once, check_<call> of csrc/capi.hip) returns it.  Only the cases that library decides BEFORE it looks for a device are
+# listed (1 = DSQ_ERR_ARG, 2 = DSQ_ERR_UNSUPPORTED), so the table holds with and without a GPU.
+_ARGUMENT_CODES = {
+    'dsq_fit_beta: NULL args': 1,
+    'dsq_fit_beta: NULL out': 1,
+    'dsq_fit_beta: args.y NULL': 1,
+    'dsq_fit_beta: args.x NULL': 1,
+    'dsq_fit_beta: args.nf NULL': 1,
+    'dsq_fit_beta: args.alpha_hat NULL': 1,
+    'dsq_fit_beta: args.contrast NULL': 1,
+    'dsq_fit_beta: args.beta_mat NULL': 1,
+    'dsq_fit_beta: args.lambda NULL': 1,
+    'dsq_fit_beta: out.beta_mat NULL': 1,
+    'dsq_fit_beta: out.beta_var_mat NULL': 1,
+    'dsq_fit_beta: out.iter NULL': 1,
+    'dsq_fit_beta: out.contrast_num NULL': 1,
+    'dsq_fit_beta: out.contrast_denom NULL': 1,
+    'dsq_fit_beta: out.deviance NULL': 1,
+    'dsq_fit_beta: n = -1': 1,
+    'dsq_fit_beta: m = 0': 1,
+    'dsq_fit_beta: p = 0': 1,
+    'dsq_fit_beta: useWeights without weights': 1,
+    'dsq_fit_beta: layout = GENE_MAJOR': 1,
+    'dsq_fit_beta_rows: NULL args': 1,
+    'dsq_fit_beta_rows: NULL out': 1,
+    'dsq_fit_beta_rows: args.y NULL': 1,
+    'dsq_fit_beta_rows: args.x NULL': 1,
+    'dsq_fit_beta_rows: args.nf NULL': 1,
+    'dsq_fit_beta_rows: args.alpha_hat NULL': 1,
+    'dsq_fit_beta_rows: args.contrast NULL': 1,
+    'dsq_fit_beta_rows: args.beta_mat NULL': 1,
+    'dsq_fit_beta_rows: args.lambda NULL': 1,
+    'dsq_fit_beta_rows: out.beta_mat NULL': 1,
+    'dsq_fit_beta_rows: out.beta_var_mat NULL': 1,
+    'dsq_fit_beta_rows: out.iter NULL': 1,
+    'dsq_fit_beta_rows: out.contrast_num NULL': 1,
+    'dsq_fit_beta_rows: out.contrast_denom NULL': 1,
+    'dsq_fit_beta_rows: out.deviance NULL': 1,
+    'dsq_fit_beta_rows: n = -1': 1,
+    'dsq_fit_beta_rows: m = 0': 1,
+    'dsq_fit_beta_rows: p = 0': 1,
+    'dsq_fit_beta_rows: useWeights without weights': 1,
+    'dsq_fit_beta_rows: layout = GENE_MAJOR': 1,
+    'dsq_fit_beta_rows: row range past n': 1,
+    'dsq_fit_beta_dev: NULL args': 1,
+    'dsq_fit_beta_dev: NULL out': 1,
+    'dsq_fit_beta_dev: args.y NULL': 1,
+    'dsq_fit_beta_dev: args.x NULL': 1,
+    'dsq_fit_beta_dev: args.nf NULL': 1,
+    'dsq_fit_beta_dev: args.alpha_hat NULL': 1,
+    'dsq_fit_beta_dev: args.contrast NULL': 1,
+    'dsq_fit_beta_dev: args.beta_mat NULL': 1,
+    'dsq_fit_beta_dev: args.lambda NULL': 1,
+    'dsq_fit_beta_dev: out.beta_mat NULL': 1,
+    'dsq_fit_beta_dev: out.beta_var_mat NULL': 1,
+    'dsq_fit_beta_dev: out.iter NULL': 1,
+    'dsq_fit_beta_dev: out.contrast_num NULL': 1,
+    'dsq_fit_beta_dev: out.contrast_denom NULL': 1,
+    'dsq_fit_beta_dev: out.deviance NULL': 1,
+    'dsq_fit_beta_dev: n = -1': 1,
+    'dsq_fit_beta_dev: m = 0': 1,
+    'dsq_fit_beta_dev: p = 0': 1,
+    'dsq_fit_beta_dev: p = 65': 2,
+    'dsq_fit_beta_dev: useWeights without weights': 1,
+    'dsq_fit_beta_dev: maxit = -1': 1,
+    'dsq_fit_beta_dev: gene-major, ld < m': 1,
+    'dsq_fit_beta_dev: layout = 7': 1,
+    'dsq_fit_disp: NULL args': 1,
+    'dsq_fit_disp: NULL out': 1,
+    'dsq_fit_disp: args.y NULL': 1,
+    'dsq_fit_disp: args.x NULL': 1,
+    'dsq_fit_disp: args.mu_hat NULL': 1,
+    'dsq_fit_disp: args.log_alpha NULL': 1,
+    'dsq_fit_disp: args.log_alpha_prior_mean NULL': 1,
+    'dsq_fit_disp: out.log_alpha NULL': 1,
+    'dsq_fit_disp: out.last_change NULL': 1,
+    'dsq_fit_disp: out.initial_lp NULL': 1,
+    'dsq_fit_disp: out.initial_dlp NULL': 1,
+    'dsq_fit_disp: out.last_lp NULL': 1,
+    'dsq_fit_disp: out.last_dlp NULL': 1,
+    'dsq_fit_disp: out.last_d2lp NULL': 1,
+    'dsq_fit_disp: out.iter NULL': 1,
+    'dsq_fit_disp: out.iter_accept NULL': 1,
+    'dsq_fit_disp: n = -1': 1,
+    'dsq_fit_disp: m = 0': 1,
+    'dsq_fit_disp: p = 0': 1,
+    'dsq_fit_disp: useWeights without weights': 1,
+    'dsq_fit_disp: layout = GENE_MAJOR': 1,
+    'dsq_fit_disp_rows: NULL args': 1,
+    'dsq_fit_disp_rows: NULL out': 1,
+    'dsq_fit_disp_rows: args.y NULL': 1,
+    'dsq_fit_disp_rows: args.x NULL': 1,
+    'dsq_fit_disp_rows: args.mu_hat NULL': 1,
+    'dsq_fit_disp_rows: args.log_alpha NULL': 1,
+    'dsq_fit_disp_rows: args.log_alpha_prior_mean NULL': 1,
+    'dsq_fit_disp_rows: out.log_alpha NULL': 1,
+    'dsq_fit_disp_rows: out.last_change NULL': 1,
+    'dsq_fit_disp_rows: out.initial_lp NULL': 1,
+    'dsq_fit_disp_rows: out.initial_dlp NULL': 1,
+    'dsq_fit_disp_rows: out.last_lp NULL': 1,
+    'dsq_fit_disp_rows: out.last_dlp NULL': 1,
+    'dsq_fit_disp_rows: out.last_d2lp NULL': 1,
+    'dsq_fit_disp_rows: out.iter NULL': 1,
+    'dsq_fit_disp_rows: out.iter_accept NULL': 1,
+    'dsq_fit_disp_rows: n = -1': 1,
+    'dsq_fit_disp_rows: m = 0': 1,
+    'dsq_fit_disp_rows: p = 0': 1,
+    'dsq_fit_disp_rows: useWeights without weights': 1,
+    'dsq_fit_disp_rows: layout = GENE_MAJOR': 1,
+    'dsq_fit_disp_rows: row range past n': 1,
+    'dsq_fit_disp_dev: NULL args': 1,
+    'dsq_fit_disp_dev: NULL out': 1,
+    'dsq_fit_disp_dev: args.y NULL': 1,
+    'dsq_fit_disp_dev: args.x NULL': 1,
+    'dsq_fit_disp_dev: args.mu_hat NULL': 1,
+    'dsq_fit_disp_dev: args.log_alpha NULL': 1,
+    'dsq_fit_disp_dev: args.log_alpha_prior_mean NULL': 1,
+    'dsq_fit_disp_dev: out.log_alpha NULL': 1,
+    'dsq_fit_disp_dev: out.last_change NULL': 1,
+    'dsq_fit_disp_dev: out.initial_lp NULL': 1,
+    'dsq_fit_disp_dev: out.initial_dlp NULL': 1,
+    'dsq_fit_disp_dev: out.last_lp NULL': 1,
+    'dsq_fit_disp_dev: out.last_dlp NULL': 1,
+    'dsq_fit_disp_dev: out.iter NULL': 1,
+    'dsq_fit_disp_dev: out.iter_accept NULL': 1,
+    'dsq_fit_disp_dev: n = -1': 1,
+    'dsq_fit_disp_dev: m = 0': 1,
+    'dsq_fit_disp_dev: p = 0': 1,
+    'dsq_fit_disp_dev: p = 65': 2,
+    'dsq_fit_disp_dev: useWeights without weights': 1,
+    'dsq_fit_disp_dev: maxit = -1': 1,
+    'dsq_fit_disp_dev: gene-major, ld < m': 1,
+    'dsq_fit_disp_dev: layout = 7': 1,
+    'dsq_fit_disp_grid: NULL args': 1,
+    'dsq_fit_disp_grid: NULL out': 1,
+    'dsq_fit_disp_grid: args.y NULL': 1,
+    'dsq_fit_disp_grid: args.x NULL': 1,
+    'dsq_fit_disp_grid: args.mu_hat NULL': 1,
+    'dsq_fit_disp_grid: args.disp_grid NULL': 1,
+    'dsq_fit_disp_grid: args.log_alpha_prior_mean NULL': 1,
+    'dsq_fit_disp_grid: out.log_alpha NULL': 1,
+    'dsq_fit_disp_grid: n = -1': 1,
+    'dsq_fit_disp_grid: m = 0': 1,
+    'dsq_fit_disp_grid: p = 0': 1,
+    'dsq_fit_disp_grid: useWeights without weights': 1,
+    'dsq_fit_disp_grid: ngrid = 1': 1,
+    'dsq_fit_disp_grid: layout = GENE_MAJOR': 1,
+    'dsq_fit_disp_grid_rows: NULL args': 1,
+    'dsq_fit_disp_grid_rows: NULL out': 1,
+    'dsq_fit_disp_grid_rows: args.y NULL': 1,
+    'dsq_fit_disp_grid_rows: args.x NULL': 1,
+    'dsq_fit_disp_grid_rows: args.mu_hat NULL': 1,
+    'dsq_fit_disp_grid_rows: args.disp_grid NULL': 1,
+    'dsq_fit_disp_grid_rows: args.log_alpha_prior_mean NULL': 1,
+    'dsq_fit_disp_grid_rows: out.log_alpha NULL': 1,
+    'dsq_fit_disp_grid_rows: n = -1': 1,
+    'dsq_fit_disp_grid_rows: m = 0': 1,
+    'dsq_fit_disp_grid_rows: p = 0': 1,
+    'dsq_fit_disp_grid_rows: useWeights without weights': 1,
+    'dsq_fit_disp_grid_rows: ngrid = 1': 1,
+    'dsq_fit_disp_grid_rows: layout = GENE_MAJOR': 1,
+    'dsq_fit_disp_grid_rows: row range past n': 1,
+    'dsq_fit_disp_grid_dev: NULL args': 1,
+    'dsq_fit_disp_grid_dev: NULL out': 1,
+    'dsq_fit_disp_grid_dev: args.y NULL': 1,
+    'dsq_fit_disp_grid_dev: args.x NULL': 1,
+    'dsq_fit_disp_grid_dev: args.mu_hat NULL': 1,
+    'dsq_fit_disp_grid_dev: args.disp_grid NULL': 1,
+    'dsq_fit_disp_grid_dev: args.log_alpha_prior_mean NULL': 1,
+    'dsq_fit_disp_grid_dev: out.log_alpha NULL': 1,
+    'dsq_fit_disp_grid_dev: n = -1': 1,
+    'dsq_fit_disp_grid_dev: m = 0': 1,
+    'dsq_fit_disp_grid_dev: p = 0': 1,
+    'dsq_fit_disp_grid_dev: p = 65': 2,
+    'dsq_fit_disp_grid_dev: useWeights without weights': 1,
+    'dsq_fit_disp_grid_dev: ngrid = 1': 1,
+    'dsq_fit_disp_grid_dev: gene-major, ld < m': 1,
+    'dsq_fit_disp_grid_dev: layout = 7': 1,
+    'dsq_prefit_moments: NULL args': 1,
+    'dsq_prefit_moments: NULL out': 1,
+    'dsq_prefit_moments: args.y NULL': 1,
+    'dsq_prefit_moments: args.nf NULL': 1,
+    'dsq_prefit_moments: args.q NULL': 1,
+    'dsq_prefit_moments: args.a NULL': 1,
+    'dsq_prefit_moments: args.r NULL': 1,
+    'dsq_prefit_moments: out.baseMean NULL': 1,
+    'dsq_prefit_moments: out.baseVar NULL': 1,
+    'dsq_prefit_moments: out.allZero NULL': 1,
+    'dsq_prefit_moments: out.roughDisp NULL': 1,
+    'dsq_prefit_moments: out.beta_init NULL': 1,
+    'dsq_prefit_moments: n = -1': 1,
+    'dsq_prefit_moments: m = 0': 1,
+    'dsq_prefit_moments: p = 0': 1,
+    'dsq_prefit_moments: useWeights without weights': 1,
+    'dsq_prefit_moments: layout = GENE_MAJOR': 1,
+    'dsq_prefit_moments_dev: NULL args': 1,
+    'dsq_prefit_moments_dev: NULL out': 1,
+    'dsq_prefit_moments_dev: args.y NULL': 1,
+    'dsq_prefit_moments_dev: args.nf NULL': 1,
+    'dsq_prefit_moments_dev: args.q NULL': 1,
+    'dsq_prefit_moments_dev: args.a NULL': 1,
+    'dsq_prefit_moments_dev: args.r NULL': 1,
+    'dsq_prefit_moments_dev: out.baseMean NULL': 1,
+    'dsq_prefit_moments_dev: out.baseVar NULL': 1,
+    'dsq_prefit_moments_dev: out.allZero NULL': 1,
+    'dsq_prefit_moments_dev: out.roughDisp NULL': 1,
+    'dsq_prefit_moments_dev: out.beta_init NULL': 1,
+    'dsq_prefit_moments_dev: n = -1': 1,
+    'dsq_prefit_moments_dev: m = 0': 1,
+    'dsq_prefit_moments_dev: p = 0': 1,
+    'dsq_prefit_moments_dev: p = 65': 1,
+    'dsq_prefit_moments_dev: useWeights without weights': 1,
+    'dsq_prefit_moments_dev: m <= p': 1,
+    'dsq_prefit_moments_dev: gene-major, ld < m': 1,
+    'dsq_linear_mu: NULL args': 1,
+    'dsq_linear_mu: NULL out': 1,
+    'dsq_linear_mu: args.y NULL': 1,
+    'dsq_linear_mu: args.nf NULL': 1,
+    'dsq_linear_mu: args.q NULL': 1,
+    'dsq_linear_mu: args.a NULL': 1,
+    'dsq_linear_mu: n = -1': 1,
+    'dsq_linear_mu: m = 0': 1,
+    'dsq_linear_mu: p = 0': 1,
+    'dsq_linear_mu: layout = GENE_MAJOR': 1,
+    'dsq_linear_mu_dev: NULL args': 1,
+    'dsq_linear_mu_dev: NULL out': 1,
+    'dsq_linear_mu_dev: args.y NULL': 1,
+    'dsq_linear_mu_dev: args.nf NULL': 1,
+    'dsq_linear_mu_dev: args.q NULL': 1,
+    'dsq_linear_mu_dev: args.a NULL': 1,
+    'dsq_linear_mu_dev: n = -1': 1,
+    'dsq_linear_mu_dev: m = 0': 1,
+    'dsq_linear_mu_dev: p = 0': 1,
+    'dsq_linear_mu_dev: gene-major, ld < m': 1,
+    'dsq_nbinom_loglike: NULL args': 1,
+    'dsq_nbinom_loglike: NULL out': 1,
+    'dsq_nbinom_loglike: args.y NULL': 1,
+    'dsq_nbinom_loglike: args.mu NULL': 1,
+    'dsq_nbinom_loglike: args.disp NULL': 1,
+    'dsq_nbinom_loglike: n = -1': 1,
+    'dsq_nbinom_loglike: m = 0': 1,
+    'dsq_nbinom_loglike: useWeights without weights': 1,
+    'dsq_nbinom_loglike: layout = GENE_MAJOR': 1,
+    'dsq_nbinom_loglike_dev: NULL args': 1,
+    'dsq_nbinom_loglike_dev: NULL out': 1,
+    'dsq_nbinom_loglike_dev: args.y NULL': 1,
+    'dsq_nbinom_loglike_dev: args.mu NULL': 1,
+    'dsq_nbinom_loglike_dev: args.disp NULL': 1,
+    'dsq_nbinom_loglike_dev: n = -1': 1,
+    'dsq_nbinom_loglike_dev: m = 0': 1,
+    'dsq_nbinom_loglike_dev: useWeights without weights': 1,
+    'dsq_nbinom_loglike_dev: gene-major, ld < m': 1,
+    'dsq_intercept_fit: NULL args': 1,
+    'dsq_intercept_fit: NULL out': 1,
+    'dsq_intercept_fit: args.y NULL': 1,
+    'dsq_intercept_fit: args.nf NULL': 1,
+    'dsq_intercept_fit: args.alpha NULL': 1,
+    'dsq_intercept_fit: out.beta_log2 NULL': 1,
+    'dsq_intercept_fit: out.betaSE NULL': 1,
+    'dsq_intercept_fit: n = -1': 1,
+    'dsq_intercept_fit: m = 0': 1,
+    'dsq_intercept_fit: useWeights without weights': 1,
+    'dsq_intercept_fit: layout = GENE_MAJOR': 1,
+    'dsq_intercept_fit_dev: NULL args': 1,
+    'dsq_intercept_fit_dev: NULL out': 1,
+    'dsq_intercept_fit_dev: args.y NULL': 1,
+    'dsq_intercept_fit_dev: args.nf NULL': 1,
+    'dsq_intercept_fit_dev: args.alpha NULL': 1,
+    'dsq_intercept_fit_dev: out.beta_log2 NULL': 1,
+    'dsq_intercept_fit_dev: out.betaSE NULL': 1,
+    'dsq_intercept_fit_dev: n = -1': 1,
+    'dsq_intercept_fit_dev: m = 0': 1,
+    'dsq_intercept_fit_dev: useWeights without weights': 1,
+    'dsq_intercept_fit_dev: gene-major, ld < m': 1,
+    'dsq_cooks_distance: NULL args': 1,
+    'dsq_cooks_distance: NULL out': 1,
+    'dsq_cooks_distance: args.y NULL': 1,
+    'dsq_cooks_distance: args.nf NULL': 1,
+    'dsq_cooks_distance: args.mu NULL': 1,
+    'dsq_cooks_distance: args.H NULL': 1,
+    'dsq_cooks_distance: args.cell_of NULL': 1,
+    'dsq_cooks_distance: out.cooks NULL': 1,
+    'dsq_cooks_distance: out.maxCooks NULL': 1,
+    'dsq_cooks_distance: n = -1': 1,
+    'dsq_cooks_distance: m = 0': 1,
+    'dsq_cooks_distance: layout = GENE_MAJOR': 1,
+    'dsq_cooks_distance_dev: NULL args': 1,
+    'dsq_cooks_distance_dev: NULL out': 1,
+    'dsq_cooks_distance_dev: args.y NULL': 1,
+    'dsq_cooks_distance_dev: args.nf NULL': 1,
+    'dsq_cooks_distance_dev: args.mu NULL': 1,
+    'dsq_cooks_distance_dev: args.H NULL': 1,
+    'dsq_cooks_distance_dev: args.cell_of NULL': 1,
+    'dsq_cooks_distance_dev: out.cooks NULL': 1,
+    'dsq_cooks_distance_dev: out.maxCooks NULL': 1,
+    'dsq_cooks_distance_dev: n = -1': 1,
+    'dsq_cooks_distance_dev: m = 0': 1,
+    'dsq_cooks_distance_dev: p = 0': 1,
+    'dsq_cooks_distance_dev: ncell = 0': 1,
+    'dsq_cooks_distance_dev: gene-major, ld < m': 1,
+    'dsq_replace_outliers: NULL args': 1,
+    'dsq_replace_outliers: NULL out': 1,
+    'dsq_replace_outliers: args.y NULL': 1,
+    'dsq_replace_outliers: args.nf NULL': 1,
+    'dsq_replace_outliers: args.cooks NULL': 1,
+    'dsq_replace_outliers: args.replaceable NULL': 1,
+    'dsq_replace_outliers: out.newCounts NULL': 1,
+    'dsq_replace_outliers: out.replace NULL': 1,
+    'dsq_replace_outliers: n = -1': 1,
+    'dsq_replace_outliers: m = 0': 1,
+    'dsq_replace_outliers: layout = GENE_MAJOR': 1,
+    'dsq_replace_outliers_dev: NULL args': 1,
+    'dsq_replace_outliers_dev: NULL out': 1,
+    'dsq_replace_outliers_dev: args.y NULL': 1,
+    'dsq_replace_outliers_dev: args.nf NULL': 1,
+    'dsq_replace_outliers_dev: args.cooks NULL': 1,
+    'dsq_replace_outliers_dev: args.replaceable NULL': 1,
+    'dsq_replace_outliers_dev: out.newCounts NULL': 1,
+    'dsq_replace_outliers_dev: out.replace NULL': 1,
+    'dsq_replace_outliers_dev: n = -1': 1,
+    'dsq_replace_outliers_dev: m = 0': 1,
+    'dsq_replace_outliers_dev: trim = 0.5': 1,
+    'dsq_replace_outliers_dev: gene-major, ld < m': 1,
+    'dsq_size_factors: NULL args': 1,
+    'dsq_size_factors: NULL out': 1,
+    'dsq_size_factors: args.y NULL': 1,
+    'dsq_size_factors: args.normMatrix NULL': 1,
+    'dsq_size_factors: out.sizeFactors NULL': 1,
+    'dsq_size_factors: out.normalizationFactors NULL': 1,
+    'dsq_size_factors: out.status NULL': 1,
+    'dsq_size_factors: n = -1': 1,
+    'dsq_size_factors: m = 0': 1,
+    'dsq_size_factors: y_type = 7': 1,
+    'dsq_size_factors: type = 9': 1,
+    'dsq_size_factors: layout = GENE_MAJOR': 1,
+    'dsq_size_factors_dev: NULL args': 1,
+    'dsq_size_factors_dev: NULL out': 1,
+    'dsq_size_factors_dev: args.y NULL': 1,
+    'dsq_size_factors_dev: args.normMatrix NULL': 1,
+    'dsq_size_factors_dev: out.sizeFactors NULL': 1,
+    'dsq_size_factors_dev: out.loggeomeans NULL': 1,
+    'dsq_size_factors_dev: out.normalizationFactors NULL': 1,
+    'dsq_size_factors_dev: out.status NULL': 1,
+    'dsq_size_factors_dev: n = -1': 1,
+    'dsq_size_factors_dev: m = 0': 1,
+    'dsq_size_factors_dev: y_type = 7': 1,
+    'dsq_size_factors_dev: type = 9': 1,
+    'dsq_size_factors_dev: gene-major, ld < m': 1,
+    'dsq_size_factors_dev: layout = 7': 1,
+    'dsq_vst: NULL args': 1,
+    'dsq_vst: NULL out': 1,
+    'dsq_vst: args.y NULL': 1,
+    'dsq_vst: args.nf NULL': 1,
+    'dsq_vst: out.rowMean NULL': 1,
+    'dsq_vst: out.rowMax NULL': 1,
+    'dsq_vst: n = -1': 1,
+    'dsq_vst: m = 0': 1,
+    'dsq_vst: y_type = 7': 1,
+    'dsq_vst: kind = 9': 1,
+    'dsq_vst: layout = GENE_MAJOR': 1,
+    'dsq_vst_dev: NULL args': 1,
+    'dsq_vst_dev: NULL out': 1,
+    'dsq_vst_dev: args.y NULL': 1,
+    'dsq_vst_dev: args.nf NULL': 1,
+    'dsq_vst_dev: out.out NULL': 1,
+    'dsq_vst_dev: n = -1': 1,
+    'dsq_vst_dev: m = 0': 1,
+    'dsq_vst_dev: y_type = 7': 1,
+    'dsq_vst_dev: kind = 9': 1,
+    'dsq_vst_dev: gene-major, ld < m': 1,
+    'dsq_vst_dev: layout = 7': 1,
+    'dsq_vst_rowstats_dev: NULL args': 1,
+    'dsq_vst_rowstats_dev: NULL out': 1,
+    'dsq_vst_rowstats_dev: args.y NULL': 1,
+    'dsq_vst_rowstats_dev: args.nf NULL': 1,
+    'dsq_vst_rowstats_dev: out.rowMean NULL': 1,
+    'dsq_vst_rowstats_dev: out.rowMax NULL': 1,
+    'dsq_vst_rowstats_dev: n = -1': 1,
+    'dsq_vst_rowstats_dev: m = 0': 1,
+    'dsq_vst_rowstats_dev: y_type = 7': 1,
+    'dsq_vst_rowstats_dev: gene-major, ld < m': 1,
+    'dsq_vst_rowstats_dev: layout = 7': 1,
+    'dsq_optim_rows: NULL args': 1,
+    'dsq_optim_rows: NULL out': 1,
+    'dsq_optim_rows: args.y NULL': 1,
+    'dsq_optim_rows: args.x NULL': 1,
+    'dsq_optim_rows: args.nf NULL': 1,
+    'dsq_optim_rows: args.alpha_hat NULL': 1,
+    'dsq_optim_rows: args.lambda NULL': 1,
+    'dsq_optim_rows: args.beta_start NULL': 1,
+    'dsq_optim_rows: out.beta NULL': 1,
+    'dsq_optim_rows: out.betaSE NULL': 1,
+    'dsq_optim_rows: out.conv NULL': 1,
+    'dsq_optim_rows: out.mu NULL': 1,
+    'dsq_optim_rows: out.logLike NULL': 1,
+    'dsq_optim_rows: n = -1': 1,
+    'dsq_optim_rows: m = 0': 1,
+    'dsq_optim_rows: p = 0': 1,
+    'dsq_optim_rows: p = 65': 2,
+    'dsq_optim_rows: useWeights without weights': 1,
+    'dsq_optim_rows: layout = GENE_MAJOR': 1,
+    'dsq_parametric_dispersion_fit: first input NULL': 1,
+    'dsq_parametric_dispersion_fit: output NULL': 1,
+    'dsq_parametric_dispersion_fit: n = -1': 1,
+    'dsq_parametric_dispersion_fit_dev: first input NULL': 1,
+    'dsq_parametric_dispersion_fit_dev: output NULL': 1,
+    'dsq_parametric_dispersion_fit_dev: n = -1': 1,
+    'dsq_test_math: first input NULL': 1,
+    'dsq_test_math: output NULL': 1,
+    'dsq_test_math: n = -1': 1,
+    'dsq_parametric_dispersion_fit: n = 0': 1,
+    'dsq_parametric_dispersion_fit_dev: n = 0': 1,
+    'dsq_test_math: op 7 without b': 1,
+}
+
+
+# What the change itself moved, pinned as it now stands (each decided before the device is looked for).  The host entries run
+# the whole check_<call> first, so an EMPTY call (n == 0), which the parent's host half answered with DSQ_OK once a device was
+# there, now reports what only its device half refused; and a design that is too wide is reported only when nothing else is wrong.
+_CHANGED_CODES = {
+    "dsq_fit_beta: n = 0 and p = 65": 2,
+    "dsq_fit_beta: n = 0 and maxit = -1": 1,
+    "dsq_prefit_moments: n = 0 and m <= p": 1,
+    "dsq_optim_rows: p = 65 and layout = GENE_MAJOR": 2,
+    "dsq_fit_beta_dev: p = 65 and args.y NULL": 1,
+    "dsq_fit_disp_dev: p = 65 and args.log_alpha NULL": 1,
+}
+
+
+def _changed_cases():
+    from deseq2_amd import _lib
+    from tests import capi_blocks as cb
+    B = _tiny_blocks()
+    how = {"dsq_fit_beta": (B["fit_beta"], False), "dsq_prefit_moments": (B["prefit_moments"], False),
+           "dsq_optim_rows": (B["optim_rows"], False), "dsq_fit_beta_dev": (B["fit_beta"], True),
+           "dsq_fit_disp_dev": (B["fit_disp"], True)}
+    edits = {"n = 0 and p = 65": dict(n=0, p=65), "n = 0 and maxit = -1": dict(n=0, maxit=-1), "n = 0 and m <= p": dict(n=0, p=6),
+             "p = 65 and layout = GENE_MAJOR": dict(p=65, layout=1, ld=8), "p = 65 and args.y NULL": dict(p=65, y=None),
+             "p = 65 and args.log_alpha NULL": dict(p=65, log_alpha=None)}
+    out = {}
+    for cid in _CHANGED_CODES:
+        ename, what = cid.split(": ")
+        b, dev = how[ename]
+        b = b.but(**edits[what])
+
+        def run(b=b, dev=dev, ename=ename):
+            a = b.args({k: cb.ptr(None if v is None else cb.fcol(v)) for k, v in b.inputs.items()})
+            outs = {k: np.zeros(shape, dtype=dt, order="F") for k, (shape, dt) in b.outputs.items()}
+            return cb._invoke(b, getattr(_lib.lib(), ename), a, {k: cb.ptr(v) for k, v in outs.items()}, (None,) if dev else ())
+        out[cid] = run
+    return out
+
+
+def test_argument_errors_are_pinned():
+    from deseq2_amd import _lib
+    L = _lib.lib()
+    cases = dict(_argument_cases())
+    assert set(_ARGUMENT_CODES) <= set(cases), sorted(set(_ARGUMENT_CODES) - set(cases))
+    assert len(_ARGUMENT_CODES) > 200
+    cases.update(_changed_cases())
+    wrong = []
+    for cid, want in {**_ARGUMENT_CODES, **_CHANGED_CODES}.items():
+        # dsq_last_error() keeps the last text: leave a known one behind first, so that an entry which fails without
+        # writing its own message is seen
+        assert L.dsq_test_math(0, None, None, None, None, 0) == 1
+        sentinel = L.dsq_last_error()
+        assert sentinel == b"bad arguments"
+        got = cases[cid]()
+        msg = L.dsq_last_error()
+        own_text = bool(msg) and (msg != sentinel or cid.startswith(("dsq_parametric_dispersion_fit", "dsq_test_math")))
+        if got != want or not own_text:
+            wrong.append((cid, want, got, msg))
+    assert not wrong, wrong
