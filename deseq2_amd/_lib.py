@@ -248,6 +248,20 @@ class DsqVstOut(C.Structure):
     _fields_ = [("out", C.c_void_p), ("rowMean", C.c_void_p), ("rowMax", C.c_void_p), ("bad", C.c_void_p)]
 
 
+class DsqRlogArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("m", C.c_int32), ("layout", C.c_int32), ("ld", C.c_int64), ("y", C.c_void_p),
+        ("y_type", C.c_int32), ("nf", C.c_void_p), ("nf_is_vector", C.c_int32), ("dispFit", C.c_void_p),
+        ("betaPriorVar", C.c_double), ("intercept", C.c_void_p), ("tol", C.c_double), ("minmu", C.c_double),
+        ("maxit", C.c_int32),
+    ]
+
+
+class DsqRlogOut(C.Structure):
+    _fields_ = [("rlog", C.c_void_p), ("intercept", C.c_void_p), ("iter", C.c_void_p), ("flag", C.c_void_p),
+                ("bad", C.c_void_p)]
+
+
 DSQ_VST = {"parametric": 0, "mean": 1, "spline": 2, "log2": 3, "normalized": 4}
 DSQ_VST_MAX_KNOTS = 1600
 DSQ_SF = {"ratio": 0, "poscounts": 1}
@@ -277,6 +291,7 @@ EXPORTED_SYMBOLS = [
     "dsq_linear_mu", "dsq_linear_mu_dev", "dsq_cooks_distance", "dsq_cooks_distance_dev", "dsq_replace_outliers", "dsq_replace_outliers_dev",
     "dsq_size_factors", "dsq_size_factors_dev", "dsq_size_factors_workspace_bytes",
     "dsq_vst", "dsq_vst_dev", "dsq_vst_rowstats_dev",
+    "dsq_rlog", "dsq_rlog_dev",
 ]
 
 _lib = None
@@ -346,6 +361,8 @@ def lib():
     L.dsq_vst.argtypes = [C.POINTER(DsqVstArgs), C.POINTER(DsqVstOut)]
     L.dsq_vst_dev.argtypes = [C.POINTER(DsqVstArgs), C.POINTER(DsqVstOut), C.c_void_p]
     L.dsq_vst_rowstats_dev.argtypes = [C.POINTER(DsqVstArgs), C.POINTER(DsqVstOut), C.c_void_p]
+    L.dsq_rlog.argtypes = [C.POINTER(DsqRlogArgs), C.POINTER(DsqRlogOut)]
+    L.dsq_rlog_dev.argtypes = [C.POINTER(DsqRlogArgs), C.POINTER(DsqRlogOut), C.c_void_p]
     L.dsq_deseq_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.dsq_deseq_workspace_bytes.restype = C.c_int64
     L.dsq_profile_get.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double)]

@@ -12,10 +12,13 @@ Size factors: estimateSizeFactors / estimateSizeFactorsForMatrix ("ratio", "posc
 normMatrix) run in the engine too (csrc/size_factors.hip); type = "iterate" is not mirrored.
 
 Transformations: vst / varianceStabilizingTransformation / getVarianceStabilizedData (R/vst.R), normTransform and
-counts(normalized = TRUE) run in the engine as well (csrc/vst.hip); rlog is not mirrored.
+counts(normalized = TRUE) run in the engine as well (csrc/vst.hip); rlog / rlogTransformation
+run there too, for any number of samples (csrc/rlog.hip).
 
 Not mirrored (out of the hot-path scope): local/glmGamPoi dispersion fits, results(), lfcShrink().
 """
+import warnings
+
 import numpy as np
 from scipy import special as sps
 
@@ -1191,6 +1194,7 @@ class DESeqTransform:
 
     def __init__(self, dds, handle, kind):
         self.dds, self.handle, self.kind, self.engine = dds, handle, kind, dds.engine
+        self.attrs, self.mcols = {}, {}          # attr(dt, .) and mcols(dt) of the transform itself (rlog: betaPriorVar, rlogIntercept)
 
     def assay(self):
         return np.asarray(self.engine.to_numpy(self.handle))
@@ -1404,3 +1408,105 @@ def vst(obj, blind=True, nsub=1000, fitType="parametric", engine=None, sfType="r
     dds.dispersionFunction = _fit_trend(work.subset(idx), fitType)                  # :253-257
     dds.attrs["vst_rows"] = idx
     return DESeqTransform(dds, getVarianceStabilizedData(dds), "vst")               # :261
+
+
+# ------------------------------------------------------------------ R/rlog.R
+SPARSE_WARNING = ("the rlog assumes that data is close to a negative binomial distribution, an assumption\n"
+                  "which is sometimes not compatible with datasets where many genes have many zero counts\n"
+                  "despite a few very large counts.\n"
+                  "In this data, for %s%% of genes with a sum of normalized counts above %s, it was the case\n"
+                  "that a single sample's normalized count made up more than %s%% of the sum over all samples.\n"
+                  "the threshold for this warning is %s%% of genes.\n"
+                  "We recommend instead using the varianceStabilizingTransformation or shifted log.")
+
+
+def sparseTest(dds, p=.9, t1=100, t2=.1):
+    """R/rlog.R:274-287 on the engine's row statistics: rowSums = rowMeans * m, the row maxima"""
+    nf, sf = _norm_source(dds)
+    rmean, rmx = dds.engine.row_stats(dds.y, nf, sizeFactors=sf)
+    rs = np.asarray(rmean, np.float64) * dds.m                                      # :275
+    rmx = np.asarray(rmx, np.float64)                                               # :276
+    if (rs <= t1).all():                                                            # :277
+        return
+    big = rs > t1
+    total = float(np.mean((rmx[big] / rs[big]) > p))                                # :278-279
+    if total > t2:                                                                  # :280
+        warnings.warn(SPARSE_WARNING % (round(total, 3) * 100, t1, p * 100, t2 * 100))
+
+
+def rlogData(dds, intercept=None, betaPriorVar=None):
+    """R/rlog.R:172-272.  The fit itself -- fitNbinomGLMs on a design with one coefficient per sample, :249-254 -- is the
+    engine's rlog_fit (csrc/rlog.hip on the device, any number of samples); the weighted upper quantile behind the prior
+    variance stays the host function.  Returns (n x m engine handle, betaPriorVar, fitted intercept or None)."""
+    E = dds.engine
+    if dds.mcols.get("dispFit") is None:
+        raise ValueError("first estimate dispersion")                               # :173-175
+    if dds.has_weights:
+        raise NotImplementedError("rlog: observation weights (a weights assay) are not served")
+    if intercept is not None:
+        intercept = np.asarray(intercept, np.float64).reshape(-1)
+        if intercept.size != dds.n:                                                 # :177-181
+            raise ValueError("intercept should be as long as the number of rows of object")
+    if dds.mcols.get("allZero") is None or dds.mcols.get("baseMean") is None:       # :182-184
+        getBaseMeansAndVariances(dds)
+    allZero = np.asarray(dds.mcols["allZero"], bool) if intercept is None else ~np.isfinite(intercept)   # :223
+    dispFit = np.asarray(dds.mcols["dispFit"], np.float64)
+    if np.isnan(dispFit[~allZero]).any():                                           # stopifnot(all(!is.na(dispFit))), :228
+        raise ValueError("all(!is.na(mcols(objectNZ)$dispFit)) is not TRUE")
+    nf, sf = _norm_source(dds)
+    if betaPriorVar is None:                                                        # :233-240
+        nz = np.where(~allZero)[0]
+        baseMean = np.asarray(dds.mcols["baseMean"], np.float64)[nz]
+        logCounts = np.asarray(E.to_numpy(E.vst_transform(dds.y, nf, "log2", sizeFactors=sf, pc=0.5)))[nz]   # :234
+        logFoldChangeMatrix = logCounts - np.log2(baseMean + 0.5)[:, None]          # :235
+        logFoldChangeVector = np.asarray(logFoldChangeMatrix).flatten(order="F")    # as.numeric(): column-major, :236
+        varlogk = 1.0 / baseMean + dispFit[nz]                                      # :237
+        betaPriorVar = matchWeightedUpperQuantileForVariance(logFoldChangeVector, np.tile(1.0 / varlogk, dds.m))   # :238-239
+    betaPriorVar = float(np.asarray(betaPriorVar, np.float64).reshape(-1)[0]) if np.size(betaPriorVar) == 1 else None
+    if betaPriorVar is None:
+        raise ValueError("length(betaPriorVar) == 1 is not TRUE")                   # :241
+    fit = E.rlog_fit(dds.y, nf, dispFit, betaPriorVar, intercept=intercept, sizeFactors=sf, tol=1e-4, maxit=100, minmu=0.5)
+    nbad = int((np.asarray(fit["flag"]) == 2).sum())
+    if nbad:
+        warnings.warn("%d rows ended the rlog fit with a non-finite coefficient (the rows the reference refits with "
+                      "optim, R/fitNbinomGLMs.R:203-207); that refit is not served: the rows are NaN" % nbad)
+    dds.mcols["rlogIter"], dds.mcols["rlogConv"] = fit["iter"], np.asarray(fit["iter"]) < 100
+    return fit["rlog"], betaPriorVar, (fit["intercept"] if intercept is None else None)
+
+
+def rlog(obj, blind=True, intercept=None, betaPriorVar=None, fitType="parametric", engine=None, sfType="ratio"):
+    """R/rlog.R:108-164.  obj: a DESeqDataSet or a count matrix (then `engine` says where it lives).  Returns a
+    DESeqTransform(kind = "rlog") with attrs["betaPriorVar"] and, when no intercept was given, mcols["rlogIntercept"]; the
+    argument is left as it was."""
+    dds, _ = _vst_object(obj, engine)                                               # :120-125
+    if dds.has_weights:
+        raise NotImplementedError("rlog: observation weights (a weights assay) are not served")
+    if not dds._sf_given:
+        estimateSizeFactors(dds, type=sfType)                                       # :126-128
+    if intercept is None:
+        sparseTest(dds, .9, 100, .1)                                                # :133-135
+    if blind or dds.mcols.get("dispFit") is None:                                   # :136
+        work = _shallow(dds, np.ones((dds.m, 1)) if blind else None)                # :129-131
+        getBaseMeansAndVariances(work)                                              # :138-140
+        allZero = np.asarray(work.mcols["allZero"], bool)
+        if allZero.all():
+            raise ValueError("all genes have zero counts in every sample")
+        nz = np.where(~allZero)[0]
+        sub = work if nz.size == dds.n else work.subset(nz)                         # the dispersion steps skip all-zero rows
+        _fit_trend(sub, fitType)                                                    # :141-142
+        dispFit = np.full(dds.n, np.nan)
+        dispFit[nz] = np.asarray(sub.mcols["dispFit"], np.float64)
+        dds.mcols["dispFit"] = dispFit
+        dds.mcols["baseMean"], dds.mcols["allZero"] = work.mcols["baseMean"], allZero
+        dds.dispersionFunction = sub.dispersionFunction
+    if intercept is not None and np.size(intercept) != dds.n:                       # :144-148
+        raise ValueError("intercept should be as long as the number of rows of object")
+    handle, bpv, icpt = rlogData(dds, intercept, betaPriorVar)                      # :149
+    dt = DESeqTransform(dds, handle, "rlog")
+    dt.attrs["betaPriorVar"] = bpv                                                  # :159
+    if icpt is not None:
+        dt.mcols["rlogIntercept"] = icpt                                            # :160-162
+    return dt
+
+
+rlogTransformation = rlog                                                           # :168

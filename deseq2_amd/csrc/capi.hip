@@ -772,6 +772,44 @@ int vst_dev_locked(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool
     return DSQ_OK;
 }
 
+// the rlog fit (rlog.hip): what both entries check before anything is launched
+int rlog_check(const DsqRlogArgs *a, const DsqRlogOut *o) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->n < 1 || a->m < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
+    if (!a->y || !a->nf || !a->dispFit) return capi_fail(DSQ_ERR_ARG, "NULL counts, size / normalization factors or dispFit");
+    if (a->y_type != DSQ_Y_INT32 && a->y_type != DSQ_Y_FLOAT64) return capi_fail(DSQ_ERR_ARG, "unknown y_type %d", a->y_type);
+    if (!o->rlog || !o->iter || !o->flag) return capi_fail(DSQ_ERR_ARG, "NULL output array");
+    if (a->intercept && o->intercept) return capi_fail(DSQ_ERR_ARG, "an intercept is given: none is fitted");
+    if (!(a->betaPriorVar > 0.0) || a->betaPriorVar - a->betaPriorVar != 0.0)
+        return capi_fail(DSQ_ERR_ARG, "betaPriorVar = %g must be positive and finite", a->betaPriorVar);
+    if (a->maxit < 0 || a->tol != a->tol || a->minmu != a->minmu) return capi_fail(DSQ_ERR_ARG, "bad tol / maxit / minmu");
+    return DSQ_OK;
+}
+
+int rlog_dev_locked(const DsqRlogArgs *a, const DsqRlogOut *o, hipStream_t st) {
+    if (int rc = rlog_check(a, o)) return rc;
+    if (int rc = check_layout(a->layout, a->ld, a->m, true)) return rc;
+    if (int rc = capi_check_device()) return rc;
+    RlogKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.m = a->m;
+    kp.y = a->y;
+    const bool gm = a->layout == DSQ_LAYOUT_GENE_MAJOR;
+    kp.si = gm ? (long)a->ld : 1L;  kp.sj = gm ? 1L : (long)a->n;
+    kp.nf = a->nf; kp.nf_is_vector = a->nf_is_vector ? 1 : 0;
+    kp.dispFit = a->dispFit; kp.intercept = a->intercept;
+    // lambdaNatLogScale <- lambda / log(2)^2 (R/fitNbinomGLMs.R:162), lambda = 1 / betaPriorVar, 1e-6 on the intercept (R/rlog.R:243-247)
+    const double ln2 = 6.93147180559945286227e-01, ln2sq = ln2 * ln2;
+    kp.lambda = (1.0 / a->betaPriorVar) / ln2sq; kp.lambda0 = 1e-6 / ln2sq;
+    kp.tol = a->tol; kp.minmu = a->minmu; kp.maxit = a->maxit;
+    kp.out = o->rlog; kp.intercept_out = o->intercept; kp.iter = o->iter; kp.flag = o->flag;
+    kp.bad = a->y_type == DSQ_Y_FLOAT64 ? o->bad : nullptr;
+    capi_prof_begin("rlog", a->n, st);
+    DSQ_HIP(launch_rlog(kp, a->y_type == DSQ_Y_FLOAT64, st));
+    capi_prof_end(st);
+    return DSQ_OK;
+}
+
 }  // namespace dsq
 
 using namespace dsq;
@@ -799,6 +837,7 @@ DSQ_DEV(dsq_replace_outliers_dev, DsqReplaceArgs, const DsqReplaceOut *, replace
 DSQ_DEV(dsq_size_factors_dev, DsqSizeFactorArgs, const DsqSizeFactorOut *, size_factors_dev_locked(a, o, st))
 DSQ_DEV(dsq_vst_dev, DsqVstArgs, const DsqVstOut *, vst_dev_locked(a, o, true, false, st))
 DSQ_DEV(dsq_vst_rowstats_dev, DsqVstArgs, const DsqVstOut *, vst_dev_locked(a, o, false, true, st))
+DSQ_DEV(dsq_rlog_dev, DsqRlogArgs, const DsqRlogOut *, rlog_dev_locked(a, o, st))
 #undef DSQ_DEV
 int dsq_linear_mu_dev(const DsqPrefitArgs *a, double mu_floor, double *mu, void *s) {
     return dev_entry(s, [&](hipStream_t st) { return linear_mu_dev_locked(a, mu_floor, mu, st); });

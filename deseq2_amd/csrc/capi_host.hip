@@ -749,4 +749,55 @@ int dsq_vst(const DsqVstArgs *a, const DsqVstOut *o) {
     return DSQ_OK;
 }
 
+int dsq_rlog(const DsqRlogArgs *a, const DsqRlogOut *o) {
+    HostCall hc;
+    DSQ_TRY(host_ready(rlog_check(a, o), a ? a->layout : 0));
+    hipStream_t st = hc.st;
+    const size_t n = a->n, m = a->m;
+    // stopifnot(all(!is.na(dispFit))) on the rows that are fitted (R/rlog.R:227-228); a non-positive value has no fit either
+    for (size_t i = 0; i < n; i++) {
+        if (a->dispFit[i] > 0.0 && a->dispFit[i] - a->dispFit[i] == 0.0) continue;
+        bool fitted = false;
+        if (a->intercept) fitted = a->intercept[i] - a->intercept[i] == 0.0;
+        else for (size_t j = 0; j < m && !fitted; j++)
+            fitted = a->y_type == DSQ_Y_INT32 ? ((const int32_t *)a->y)[i + n * j] != 0 : ((const double *)a->y)[i + n * j] != 0.0;
+        if (fitted) return capi_fail(DSQ_ERR_ARG, "dispFit[%zu] = %g on a row that is fitted", i, a->dispFit[i]);
+    }
+    const long ld = round_ld(a->m);
+    DsqRlogArgs d = *a;
+    DsqRlogOut od = *o;
+    Stage s(st, n);
+    stage_prefault(o->rlog, n * m * 8);
+    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->y, a->y_type == DSQ_Y_INT32 ? 4 : 8, a->n, a->m, ld, &d.y));
+    d.layout = DSQ_LAYOUT_GENE_MAJOR; d.ld = ld;
+    if (a->nf_is_vector) DSQ_TRY(s.nf_up(&d.nf, a->nf, 1, m));
+    else {
+        const void *g;
+        DSQ_TRY(up_gene_major(s, WS_H_NF, WS_NF, a->nf, 8, a->n, a->m, ld, &g));
+        d.nf = (const double *)g;
+    }
+    s.gene_vec(&d.dispFit, a->dispFit);
+    if (a->intercept) s.gene_vec(&d.intercept, a->intercept);
+    DSQ_TRY(s.pack_in());
+    int32_t bad = 0;
+    s.out_vec(&od.bad, &bad, 4, 8);
+    if (o->intercept) s.out_gene_vec(&od.intercept, o->intercept);
+    s.out_gene_vec(&od.iter, o->iter);
+    s.out_gene_vec(&od.flag, o->flag);
+    DSQ_TRY(s.pack_out());
+    DSQ_HIP(hipMemsetAsync(od.bad, 0, 8, st));
+    void *g;
+    DSQ_TRY(capi_ws_get(WS_MUOUT, n * ld * 8, &g));
+    double *out_gm = (double *)g;
+    od.rlog = out_gm;
+    DSQ_TRY(rlog_dev_locked(&d, &od, st));
+    DSQ_TRY(s.flush());
+    double *out_r;
+    DSQ_TRY(s.out_mat(WS_H_OUTMAT, &out_r, o->rlog, m));
+    DSQ_HIP(launch_transpose_gm_to_r_f64(out_gm, out_r, a->n, a->m, ld, st));
+    DSQ_TRY(s.finish());
+    if (bad) return capi_fail(DSQ_ERR_VALUE, "count matrix holds negative, non-finite or non-integer values");
+    return DSQ_OK;
+}
+
 }  // extern "C"

@@ -239,6 +239,26 @@ struct VstKernelParams {
 hipError_t launch_vst_transform(const VstKernelParams &kp, int y_f64, hipStream_t st);
 hipError_t launch_vst_rowstats(const VstKernelParams &kp, int y_f64, hipStream_t st);
 
+// the rlog fit (rlog.hip).  Element (i, j) of counts / nf matrix / output sits at [i * si + j * sj].
+struct RlogKernelParams {
+    int n, m;
+    const void *y;
+    long si, sj;
+    const double *nf;            // m-vector (nf_is_vector) or matrix
+    int nf_is_vector;
+    const double *dispFit;       // n
+    const double *intercept;     // n (form B) or nullptr (form A)
+    double lambda, lambda0;      // the ridges on the natural-log scale: samples, intercept
+    double tol, minmu;
+    int maxit;
+    double *out;                 // n x m; beyond the LDS regime the row is the fit's scratch until the result is written
+    double *intercept_out;       // n or nullptr
+    double *iter;                // n
+    int32_t *flag;               // n
+    int32_t *bad;                // float64 counts: as VstKernelParams.bad
+};
+hipError_t launch_rlog(const RlogKernelParams &kp, int y_f64, hipStream_t st);
+
 // gene index of work item i, and the number of work items, of a (possibly row-listed) launch
 #define DSQ_NWORK(kp) ((kp).n_dev ? *(kp).n_dev : (kp).n)
 #define DSQ_GENE(kp, i) ((kp).rows ? (kp).rows[i] : (i))

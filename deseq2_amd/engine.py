@@ -299,6 +299,60 @@ class HostEngine:
             q = K / (np.asarray(sizeFactors, np.float64)[None, :] if sizeFactors is not None else np.asarray(nf, np.float64))
             return q.mean(axis=1), q.max(axis=1)
 
+    def rlog_fit(self, y, nf, dispFit, betaPriorVar, intercept=None, sizeFactors=None, tol=1e-4, maxit=100, minmu=0.5):
+        """The fit of rlogData the way the reference runs it (R/rlog.R:186-254): the dense model matrix [1 | I_m] (no
+        intercept given) or I_m (the caller's intercept folded into the factors, :208-219), the start values of
+        R/fitNbinomGLMs.R:139-155, lambda / log(2)^2 (:162), then the fit module's fitBeta with useQR = TRUE on the rows
+        that are fitted.  The independent host statement of what csrc/rlog.hip computes with two sums per step; it stops
+        where the dense fit stops (DSQ_MAX_P = 64 columns).  Returns dict(rlog: n x m handle, intercept (form A), iter,
+        flag: 0 fitted, 1 row not fitted, 2 a non-finite coefficient)."""
+        K = np.asarray(y, np.float64)
+        n, m = K.shape
+        NF = np.broadcast_to(np.asarray(sizeFactors, np.float64)[None, :], (n, m)) if sizeFactors is not None else np.asarray(nf, np.float64)
+        disp = np.broadcast_to(np.asarray(dispFit, np.float64), (n,))
+        formA = intercept is None
+        p = m + 1 if formA else m
+        if p > 64:
+            raise NotImplementedError("the dense rlog fit of the host engine stops at 64 design columns (m = %d)" % m)
+        if formA:
+            x = np.hstack([np.ones((m, 1)), np.eye(m)])                              # model.matrix(~samples)[-1, ], :192-194
+            fitted = (K != 0).any(axis=1)                                            # !allZero, :227
+            lam = np.r_[1e-6, np.full(m, 1.0 / float(betaPriorVar))]                 # :243-247
+        else:
+            x = np.eye(m)                                                            # model.matrix(~ 0 + samples), :202
+            icpt = np.asarray(intercept, np.float64)
+            fitted = np.isfinite(icpt)                                               # allZero <- infiniteIntercept, :223
+            NF = NF * np.exp2(np.where(fitted, icpt, -10.0))[:, None]                # :216-219
+            lam = np.full(m, 1.0 / float(betaPriorVar))
+        out = np.zeros((n, m), order="F")
+        oi = np.full(n, -np.inf) if formA else None
+        it = np.zeros(n)
+        flag = np.where(fitted, 0, 1).astype(np.int32)
+        idx = np.where(fitted)[0]
+        if idx.size:
+            Ks, NFs = K[idx], np.asfortranarray(NF[idx])
+            q = Ks / NFs
+            if formA:                                                                # not of full rank: R/fitNbinomGLMs.R:147-151
+                b0 = np.zeros((idx.size, p))
+                b0[:, 0] = np.log(q.mean(axis=1))
+            else:                                                                    # Q and R of an identity: :142-145
+                b0 = np.log(q + 0.1)
+            r = self.fit_beta(self.counts(Ks), x, NFs, np.ascontiguousarray(disp[idx]), np.r_[1.0, np.zeros(p - 1)],
+                              np.asfortranarray(b0), lam / np.log(2) ** 2, None, False, tol, maxit, True, minmu,
+                              want_mu=False, want_hat=False)
+            beta = np.log2(np.e) * np.asarray(r["beta_mat"])                         # :194
+            vals = beta @ x.T                                                        # t(modelMatrix %*% t(betaMatrix)), R/rlog.R:254
+            if not formA:
+                vals = vals + icpt[idx][:, None]                                     # :260
+            bad = ~np.isfinite(beta).all(axis=1)
+            vals[bad] = np.nan
+            out[idx] = vals
+            it[idx] = np.asarray(r["iter"]).reshape(-1)
+            flag[idx[bad]] = 2
+            if formA:
+                oi[idx] = np.where(bad, np.nan, beta[:, 0])
+        return {"rlog": out, "intercept": oi, "iter": it, "flag": flag}
+
     def nf_col_geomeans(self, nf):
         """exp(colMeans(log(normalizationFactors))): the approximate size factors of R/vst.R:162"""
         return np.exp(np.log(np.asarray(nf, np.float64)).mean(axis=0))
@@ -621,6 +675,23 @@ class DeviceEngine:
         pack = self._timed("vst_rowstats", y.n, lambda: self.native.vstRowStats_dev(y, f))
         h = self._host(pack).numpy()
         return h[0], h[1]
+
+    def rlog_fit(self, y, nf, dispFit, betaPriorVar, intercept=None, sizeFactors=None, tol=1e-4, maxit=100, minmu=0.5):
+        """the fit of rlogData on the resident counts (csrc/rlog.hip, dsq_rlog_dev) on the current stream, any number of
+        samples; the n x m result is a handle and stays in HBM.  What goes up: dispFit (and the intercept); what comes down:
+        the fitted intercept, the iteration counts and the row flags (n-vectors) and the bad-count word."""
+        t = self.torch
+        f = self._sf_dev(sizeFactors) if sizeFactors is not None else nf
+        bad = t.zeros(2, dtype=t.int32, device=self.device) if y.t.dtype == t.float64 else None
+        r = self._timed("rlog", y.n, lambda: self.native.rlog_dev(
+            y, f, self._vec(dispFit), betaPriorVar, intercept=None if intercept is None else self._vec(intercept),
+            tol=tol, maxit=maxit, minmu=minmu, bad=bad))
+        if bad is not None and int(self._host(bad)[0]) != 0:
+            raise ValueError("count matrix holds negative, non-finite or non-integer values")
+        pack = self._host(t.stack([r["iter"] if r["intercept"] is None else r["intercept"], r["iter"],
+                                   r["flag"].to(t.float64)])).numpy()
+        return {"rlog": r["rlog"], "intercept": None if intercept is not None else pack[0].copy(), "iter": pack[1].copy(),
+                "flag": pack[2].astype(np.int32)}
 
     def nf_col_geomeans(self, nf):
         t = self.torch

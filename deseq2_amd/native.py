@@ -532,6 +532,37 @@ def vst(counts, nf, kind="parametric", asymptDisp=None, extraPois=None, alpha=No
     return out if want_out else (rmean, rmax)
 
 
+def rlog(counts, nf, dispFit, betaPriorVar, intercept=None, tol=1e-4, maxit=100, minmu=0.5):
+    """the fit of rlogData (R/rlog.R:172-272) through dsq_rlog: host arrays in R layout in; dict(rlog n x m, intercept n
+    (form A; None with an intercept given), iter, flag: 0 fitted, 1 row not fitted, 2 a non-finite coefficient).  nf: the
+    m size factors or an n x m matrix; betaPriorVar on the log2 scale."""
+    y, ytype = _counts(counts)
+    if y.ndim != 2:
+        raise ValueError("counts must be a matrix")
+    n, m = y.shape
+    nf = np.asarray(nf, np.float64)
+    vec = nf.ndim == 1
+    nf = np.ascontiguousarray(nf) if vec else _fcol(nf)
+    if nf.shape != ((m,) if vec else (n, m)):
+        raise ValueError("nf must be the m size factors or an n x m matrix")
+    disp = np.ascontiguousarray(np.broadcast_to(np.asarray(dispFit, np.float64), (n,)))
+    icpt = None
+    if intercept is not None:
+        icpt = np.ascontiguousarray(intercept, dtype=np.float64)
+        if icpt.shape != (n,):
+            raise ValueError("intercept should be as long as the number of rows of object")
+    out = np.zeros((n, m), order="F")
+    oi = np.zeros(n) if icpt is None else None
+    it = np.zeros(n)
+    flag = np.zeros(n, dtype=np.int32)
+    a = L.DsqRlogArgs(n=n, m=m, layout=L.DSQ_LAYOUT_R, ld=0, y=_ptr(y), y_type=ytype, nf=_ptr(nf), nf_is_vector=int(vec),
+                      dispFit=_ptr(disp), betaPriorVar=float(betaPriorVar), intercept=_ptr(icpt), tol=float(tol),
+                      minmu=float(minmu), maxit=int(maxit))
+    o = L.DsqRlogOut(rlog=_ptr(out), intercept=_ptr(oi), iter=_ptr(it), flag=_ptr(flag), bad=None)
+    L.check(L.lib().dsq_rlog(C.byref(a), C.byref(o)))
+    return {"rlog": out, "intercept": oi, "iter": it, "flag": flag}
+
+
 _FIT_ERRORS = {1: "parametric dispersion fit failed", 2: "dispersion fit did not converge"}
 
 
@@ -790,6 +821,31 @@ def vstRowStats_dev(y, nf):
     o = L.DsqVstOut(out=None, rowMean=_t_ptr(pack[0]), rowMax=_t_ptr(pack[1]), bad=None)
     L.check(L.lib().dsq_vst_rowstats_dev(C.byref(a), C.byref(o), _stream()))
     return pack
+
+
+def rlog_dev(y, nf, dispFit, betaPriorVar, intercept=None, tol=1e-4, maxit=100, minmu=0.5, bad=None, out=None):
+    """dsq_rlog_dev on resident counts: y GeneMajor (int32 or float64), nf the m size factors (a device tensor) or a
+    GeneMajor matrix with y's ld, dispFit / intercept float64 device vectors of n.  Returns dict(rlog: GeneMajor (padding
+    columns zero; `out`: a GeneMajor of y's shape to write into), intercept (form A) / iter: float64 tensors, flag: int32
+    tensor); nothing is read back."""
+    import torch
+    dev = y.t.device
+    if out is None:
+        out = GeneMajor(torch.empty((y.n, y.ld), dtype=torch.float64, device=dev), y.m)
+        if y.ld > y.m:
+            out.t[:, y.m:] = 0.0
+    assert out.n == y.n and out.ld == y.ld and out.m == y.m
+    assert dispFit.dtype == torch.float64 and dispFit.numel() == y.n and dispFit.is_contiguous()
+    if intercept is not None:
+        assert intercept.dtype == torch.float64 and intercept.numel() == y.n and intercept.is_contiguous()
+    pack = torch.empty((2, y.n), dtype=torch.float64, device=dev)
+    flag = torch.empty(y.n, dtype=torch.int32, device=dev)
+    a = L.DsqRlogArgs(**_vst_dev_args(y, nf), dispFit=_t_ptr(dispFit), betaPriorVar=float(betaPriorVar),
+                      intercept=_t_ptr(intercept), tol=float(tol), minmu=float(minmu), maxit=int(maxit))
+    o = L.DsqRlogOut(rlog=_t_ptr(out.t), intercept=_t_ptr(pack[0]) if intercept is None else None, iter=_t_ptr(pack[1]),
+                     flag=_t_ptr(flag), bad=_t_ptr(bad))
+    L.check(L.lib().dsq_rlog_dev(C.byref(a), C.byref(o), _stream()))
+    return {"rlog": out, "intercept": pack[0] if intercept is None else None, "iter": pack[1], "flag": flag}
 
 
 def prefitMoments_dev(y, nf, q, a, r, weights=None, useWeights=False, nf_is_vector=False):

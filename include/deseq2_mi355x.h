@@ -643,6 +643,48 @@ int dsq_vst_rowstats_dev(const DsqVstArgs *args, const DsqVstOut *out, void *str
 /* host pointers in R layout, one device, synchronous: the transform into out (if non-NULL) and the row statistics (if non-NULL) */
 int dsq_vst(const DsqVstArgs *args, const DsqVstOut *out);
 
+/* ---- dsq_rlog: the regularized-logarithm fit of rlogData (R/rlog.R:172-272) ----------------------
+ * One ridge-penalised coefficient per sample, for ANY number of samples: the design is [1 | I_m] (form A, intercept
+ * NULL) or I_m with the caller's per-gene intercept folded into the factors, nf_ij 2^intercept_i (form B, the rlog of
+ * new samples on a frozen intercept), so an IRLS step of src/DESeq2.cpp:334-383 is two wave-order sums over the
+ * samples plus elementwise work.  lambda = 1 / betaPriorVar / log(2)^2 on every sample, 1e-6 / log(2)^2 on the
+ * intercept; start values as R/fitNbinomGLMs.R:144-151; |beta| > 30 or a NaN convergence measure end the loop with
+ * iter = maxit; maxit = 0 returns the start values.  Output rlog_ij = beta0 log2(e) + beta_j log2(e) (form A),
+ * beta_j log2(e) + intercept_i (form B).  Rows that are not fitted -- all counts zero (A), a non-finite intercept (B) --
+ * get 0, intercept -Inf, iter 0, flag 1; a finite intercept with all-zero counts IS fitted.  A row that ends with a
+ * non-finite coefficient (the rows R/fitNbinomGLMs.R:203-207 hands to optim) comes back NaN with flag 2: the optim
+ * refit is not served.  Observation weights are not served.
+ * _dev: device pointers, asynchronous on `stream`, no allocation, no host synchronisation, no workspace (rows beyond
+ * what registers and LDS hold use their own output row as scratch); padding columns m .. ld-1 of a gene-major output are
+ * not written; a negative, non-finite or non-integer float64 count sets *bad.
+ * dsq_rlog: host pointers in R layout, ONE device, synchronous; DSQ_ERR_VALUE for such a count matrix, DSQ_ERR_ARG for
+ * a NaN or non-positive dispFit on a row that is fitted (R/rlog.R:228).                                                */
+typedef struct {
+    int32_t n, m;
+    int32_t layout;            /* DSQ_LAYOUT_* of y / nf (matrix) / rlog                                            */
+    int64_t ld;                /* leading dimension for DSQ_LAYOUT_GENE_MAJOR (>= m)                                */
+    const void *y;             /* n x m counts                                                                      */
+    int32_t y_type;            /* DSQ_Y_INT32 or DSQ_Y_FLOAT64                                                      */
+    const double *nf;          /* m size factors (nf_is_vector) or n x m normalization factors in `layout`          */
+    int32_t nf_is_vector;
+    const double *dispFit;     /* n: the dispersion trend at the row's mean                                         */
+    double betaPriorVar;       /* log2 scale, finite, > 0                                                           */
+    const double *intercept;   /* n (log2 scale; non-finite = row not fitted), or NULL for form A                   */
+    double tol, minmu;         /* rlogData: 1e-4, 0.5                                                               */
+    int32_t maxit;             /* 100                                                                               */
+} DsqRlogArgs;
+
+typedef struct {
+    double *rlog;              /* n x m in `layout`                                                                 */
+    double *intercept;         /* n, form A only (log2 scale; -Inf on an all-zero row); may be NULL                 */
+    double *iter;              /* n; betaConv = iter < maxit                                                        */
+    int32_t *flag;             /* n: 0 fitted, 1 row not fitted, 2 a non-finite coefficient (row is NaN)            */
+    int32_t *bad;              /* _dev: one device int32 the CALLER has zeroed, or NULL; dsq_rlog: ignored          */
+} DsqRlogOut;
+
+int dsq_rlog_dev(const DsqRlogArgs *args, const DsqRlogOut *out, void *stream);
+int dsq_rlog(const DsqRlogArgs *args, const DsqRlogOut *out);
+
 /* ---- dsq_deseq: DESeq() behind ONE host-pointer call ------------------------------------------------------------
  * What an R session binds as .Call("_DESeq2_mi355x_DESeq", ...) in place of the body of DESeq() between
  * estimateSizeFactors (dsq_size_factors above) and the final bookkeeping (R/core.R:388-426: estimateDispersions -> nbinomWaldTest / nbinomLRT
