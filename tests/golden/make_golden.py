@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""Generates tests/golden/nmath_golden.json: high-precision (mpmath, 50 digits) reference
+"""Generates tests/golden/nmath_golden.json and nmath_golden_pnorm.json: high-precision (mpmath, 50 digits) reference
 values for every scalar primitive the oracle restates (exp, log, log1p, lgamma, digamma,
-trigamma, stirlerr, bd0, NB log-density), on fixed inputs.  The reference implementation
+trigamma, stirlerr, bd0, NB log-density, the two-sided normal tail), on fixed inputs.  The reference implementation
 (R's nmath) cannot run in this image, so these vectors pin the *mathematical* value; the
 tests bound the oracle's error against them in ulps / absolute eps.
 Run:  python tests/golden/make_golden.py      (deterministic; commit the json)"""
@@ -51,6 +51,19 @@ def main():
                 + x * mp.log(mu / (r + mu)))
     out["dnbinom_mu_log"] = {"x": x.tolist(), "size": size.tolist(), "mu": mu.tolist(),
                              "y": [f(nb(*t)) for t in zip(x, size, mu)]}
+    # 2 pnorm(|z|, lower.tail = FALSE) = erfc(|z| / sqrt 2), the Wald p-value (R/core.R:1507): zero, both sides of the two
+    # range limits of Cody's algorithm (0.67448975, sqrt 32), the end of the normal range (37.5) and of the subnormal one
+    # (38.4, 38.5), a log-uniform sweep down to 2^-60 and a uniform sweep over [0, 38.5] (its own generator: the draws
+    # above keep their values)
+    rp = np.random.default_rng(20261017)
+    edges = [0.0, 38.4, 38.5]
+    for e in (0.67448975, float(np.sqrt(32.0)), 37.5):
+        edges += [float(np.nextafter(e, 0.0)), e, float(np.nextafter(e, 100.0))]
+    xs = np.concatenate([edges, np.exp2(rp.uniform(-60, 5.26, 150)), rp.uniform(0, 38.5, 300)])
+    pnorm = {"pnorm_upper2": {"x": xs.tolist(), "y": [f(mp.erfc(mp.mpf(float(v)) / mp.sqrt(2))) for v in xs]}}
+    # (a file of its own beside nmath_golden.json, which is one line: the tests read the two as one table)
+    with open(os.path.join(HERE, "nmath_golden_pnorm.json"), "w") as fh:
+        json.dump(pnorm, fh)
     # literal known answers held by the reference's own tests
     out["kat"] = {
         "test_results_R_9_43_50": {"counts": [100] * 4 + [200] * 4 + [800] * 4,

@@ -636,6 +636,15 @@ def linear_mu(y, nf, q, a, mu_floor=0.0, yn=None):
     return vals, Ms
 
 
+def _mean_var(v):
+    """row mean and row variance of the mp values v -> ((mean, M), (var, M)), the magnitudes of prefit_moments' docstring"""
+    m = len(v)
+    mean = mp.fsum(v) / m
+    sq = mp.fsum((t - mean) ** 2 for t in v)
+    Mvar = (sq + 2 * mp.fsum(abs(t - mean) * (abs(t) + abs(mean)) for t in v)) / (m - 1)
+    return (mean, mp.fsum(abs(t) for t in v) / m), (sq / (m - 1), Mvar)
+
+
 def prefit_moments(y, nf, q, a, r, wts, useWeights):
     """baseMean, baseVar, allZero (R/core.R:2138-2146: row mean and row variance of the [weighted] normalized counts),
     roughDispEstimate (:2422-2437, on the normalized counts, mu = pmax(1, linearModelMu)) and the start values
@@ -646,9 +655,7 @@ def prefit_moments(y, nf, q, a, r, wts, useWeights):
     m, p = q.shape
     yn = [_f(y[j]) / _f(nf[j]) for j in range(m)]
     v = [_f(wts[j]) * yn[j] for j in range(m)] if useWeights else yn
-    mean = mp.fsum(v) / m
-    var = mp.fsum((t - mean) ** 2 for t in v) / (m - 1)
-    Mvar = (mp.fsum((t - mean) ** 2 for t in v) + 2 * mp.fsum(abs(t - mean) * (abs(t) + abs(mean)) for t in v)) / (m - 1)
+    (mean, Mmean), (var, Mvar) = _mean_var(v)
     mu, Mmu = linear_mu(None, np.ones(m), q, a, yn=yn)
     est = Mest = mp.mpf(0)
     for j in range(m):
@@ -669,7 +676,7 @@ def prefit_moments(y, nf, q, a, r, wts, useWeights):
     kap = float(np.linalg.cond(np.asarray(r, float)))
     bmax = max(abs(b) for b in beta)
     Mb = [kap * bmax + mp.fsum(abs(Ri[k, l]) * ua[l] for l in range(p)) for k in range(p)]
-    return {"baseMean": ([mean], [mp.fsum(abs(t) for t in v) / m]), "baseVar": ([var], [Mvar]),
+    return {"baseMean": ([mean], [Mmean]), "baseVar": ([var], [Mvar]),
             "roughDisp": ([max(est, mp.mpf(0))], [Mest]), "beta_init": (beta, Mb),
             "allZero": all(float(t) == 0.0 for t in y)}
 
@@ -814,3 +821,470 @@ def ratio(value, ref, M):
     if M == 0:                                   # (a hat diagonal under a zero weight: exactly zero on both sides)
         return 0.0 if err == 0 else float("inf")
     return float(err / (U * mp.mpf(M)))
+
+
+# ---- the columns between and after the fits: chain_audit -------------------------------------------------------------------
+# One DESeq() call returns every column below together with the columns it is a closed-form function of.  chain_audit
+# recomputes each derived column at 50 digits from the upstream columns THE SAME CALL returned (no search is re-run, no
+# control flow is followed), written from R/core.R, R/fitNbinomGLMs.R and R/expanded.R:
+#   baseMean, baseVar      R/core.R:2138-2146  row mean / variance of counts / nf [* weights]; refitted rows from replaceCounts (:2491)
+#   dispFit                :2166-2190, 894-899, 2512   asymptDisp + extraPois / baseMean, or the coefficient itself ("mean")
+#   trend coefficients     :871   the fit on exactly the rows with dispGeneEst > 100 minDisp
+#   varLogDispEsts         :1137-1150, R/methods.R:180   (1.4826 median |r - median r|)^2, r = log dispGeneEst - log dispFit
+#   dispPriorVar           :1197-1200   max(varLogDispEsts - trigamma((m - p) / 2), 0.25)
+#   dispMAP                :1099-1101   within [minDisp, max(10, m)]
+#   dispOutlier            :1111-1114   log dispGeneEst > log dispFit + 2 sqrt(varLogDispEsts)
+#   dispersion             :1115        dispGeneEst on flagged rows, dispMAP elsewhere
+#   mu                     R/fitNbinomGLMs.R:180   nf exp(x beta), beta = the returned log2 beta / log2(e) (the assay is NOT floored
+#                          at minmu: the floor of src/DESeq2.cpp:359-361 acts inside the fit, on betaSE and H)
+#   betaSE, H              src/DESeq2.cpp:376-465, R/fitNbinomGLMs.R:198   sqrt(diag Sigma) log2(e); the hat diagonals
+#   stat                   R/core.R:1471   beta / betaSE
+#   pvalue                 :1507   2 pnorm(|stat|, lower.tail = FALSE) = erfc(|stat| / sqrt 2)
+#   logLike                :2208-2217, R/fitNbinomGLMs.R:182
+#   logLikeReduced, LRT    :1877-1878, R/fitNbinomGLMs.R:99-137   the closed-form fit of ~ 1; pchisq(2 (logLike - logLikeReduced), df)
+#   cooks, maxCooks        :2333-2359; after a refit :2538-2546 (the replaceable samples do not count)
+#   replace, replaceCounts :2079-2110   any cooks > qf(.99, p, m - p); as.integer(trimmed mean (trim .2) * nf) where above it
+#   betaPriorVar           :1601-1689, 2416-2419, 2762-2800; R/expanded.R:20-98
+# Budgets (BUDGETS below, the file's convention |double - mp| <= K u M): measured on the CPU against the oracle chain
+# (tests/test_chain_audit_cpu.py prints them), K the next power of two at or above twice the worst ratio seen.
+#
+# mu, betaSE, H and a logLike that is taken at mu(beta) carry a CONDITIONING term, derived here from the count of roundings
+# (as tests/vst_spec.py: spec_bound does), not measured.  The returned log2 coefficient is fl(beta_fit * fl(log2 e)): two
+# roundings, so the beta the audit recovers (returned / log2 e, exact at 50 digits) is beta_fit (1 + d), |d| <= 2u.  The
+# fit's own eta_j = sum_k x_jk beta_k is a sum of nnz_j products: |error| <= nnz_j u S_j with S_j = sum_k |x_jk beta_k|
+# (the classical bound of a dot product; an fma only lowers it).  Together |eta_fit - eta_mp| <= (2 + nnz_j) u S_j.  exp()
+# of the engine is within 2 ulp = 4u (tests/test_oracle_math.py holds it to 1.5), the product with nf adds u:
+#     |mu_fit - mu_mp| <= u mu (5 + (2 + nnz_j) S_j) =: u M_mu_j.
+# w_j = mu_j / (1 + alpha mu_j) has d log w / d eta = 1 / (1 + alpha mu) <= 1, so every entry of X'WX moves by at most that
+# relative amount and what passes through A^-1 moves by kappa(A) times it: the M of fit_beta_post's outputs is multiplied
+# by C = max_j (5 + (2 + nnz_j) S_j) / 5 >= 1 -- in units of the five roundings a mu costs anyway.
+BUDGETS.update({
+    #                       K        largest ratio of the oracle chain (CPU, every case of tests/chain_cases.py)
+    "stat":                 1.0,     # derived, not measured: one correctly rounded division is within u |value| (0.995 seen)
+    "dispFit":              4.0,     # 1.71   (paired12)
+    "varLogDispEsts":       0.5,     # 0.154  (bc_weights)
+    "dispPriorVar":         1.0,     # 0.300  (factor4_mean; on the 0.25 floor elsewhere)
+    "pvalue":               16.0,    # 6.63   (bc_4200)
+    "mu":                   1.0,     # 0.363  (paired12; M carries the derived term)
+    "betaSE":               2.0,     # 0.883  (factor4_prior_expanded; M carries the derived term)
+    "H":                    1.0,     # 0.349  (bc_weights; M carries the derived term)
+    "logLike_at_beta":      8.0,     # 2.17   (bc_4200: at mu(beta), refitted rows and the beta-prior fit; M carries the derived term)
+    "logLikeReduced":       4.0,     # 1.89   (bc_weights under LRT; M carries the derived term of the closed-form mu)
+    "LRTStatistic":         4.0,     # 1.05   (bc_weights under LRT)
+    "betaPriorVar":         0.0625,  # 0.021  (factor4_prior_standard_no_refit)
+})
+MIN_DISP = 1e-8
+OUTLIER_TIE_UNITS = 8.0            # see _disp_outlier
+LOG2E = mp.log(2) ** -1
+
+
+def _col(result, k, n):
+    v = result.get(k)
+    return None if v is None else np.asarray(v, np.float64).reshape(n, -1)
+
+
+def cooks_cutoff_mp(p, m):
+    """qf(.99, p, m - p) (R/core.R:2081) by inverting the regularised incomplete beta function: the F distribution
+    function at x is I_{p x / (p x + d2)}(p / 2, d2 / 2)"""
+    from scipy.stats import f as fdist
+    d1, d2 = mp.mpf(p), mp.mpf(m - p)
+    cdf = lambda t: mp.betainc(d1 / 2, d2 / 2, 0, d1 * t / (d1 * t + d2), regularized=True) - mp.mpf("0.99")
+    return mp.findroot(cdf, float(fdist.ppf(.99, p, m - p)), tol=mp.mpf(10) ** -40)
+
+
+def _cells_of(x):
+    _, cell = np.unique(np.asarray(x, float), axis=0, return_inverse=True)
+    cell = cell.reshape(-1)
+    return cell, np.bincount(cell)[cell]
+
+
+def _mp_median(vals):
+    s = sorted(vals)
+    k = len(s)
+    return s[k // 2] if k % 2 else (s[k // 2 - 1] + s[k // 2]) / 2
+
+
+def var_log_disp_ests(dge, dfit):
+    """(mad(r))^2 over r = log dispGeneEst - log dispFit on the rows with dispGeneEst >= 100 minDisp (R/core.R:1137-1150,
+    R/methods.R:180; stats::mad = 1.4826 median |r - median r|, both medians exact selections) -> (value, M).
+    M: the double side takes its logs in double, each within an ulp or two of a value up to L = max (|log dispGeneEst| +
+    |log dispFit| + |r|) in magnitude; the MAD moves by as much, its square by 2 mad times that: M = v + 2 * 1.4826 sqrt(v) L"""
+    rows = [i for i in range(len(dge)) if dge[i] >= 100 * MIN_DISP]
+    la, lf = [mp.log(_f(dge[i])) for i in rows], [mp.log(_f(dfit[i])) for i in rows]
+    r = [a - b for a, b in zip(la, lf)]
+    med = _mp_median(r)
+    mad = mp.mpf("1.4826") * _mp_median([abs(t - med) for t in r])
+    L = max(abs(a) + abs(b) + abs(t) for a, b, t in zip(la, lf, r))
+    return mad * mad, mad * mad + 2 * mp.mpf("1.4826") * mad * L
+
+
+def _disp_outlier(dge, dfit, vlde, outlierSD=2):
+    """R/core.R:1111-1113 at 50 digits -> (flag, tie).  The double evaluation takes two logs (each within 1.5 ulp = 3u of its
+    value), a square root (u), a product by 2 (exact) and a sum (u): with L = |log dispGeneEst| and R = |log dispFit| + 2 sd
+    its two sides are off by at most 3u L + (3 + 1 + 1) u R <= 8u max(L, R).  A row whose margin is within OUTLIER_TIE_UNITS =
+    8 units of u = 2^-53 of the larger side is a tie."""
+    a, b = mp.log(_f(dge)), mp.log(_f(dfit))
+    sd = outlierSD * mp.sqrt(_f(vlde))
+    margin = a - (b + sd)
+    return bool(margin > 0), abs(margin) <= OUTLIER_TIE_UNITS * U * max(abs(a), abs(b) + sd)
+
+
+def _wtd_quantile(x, w, prob):
+    """Hmisc.wtd.quantile(x, weights, prob, normwt = TRUE), type = "quantile" (R/core.R:2762-2800) -> (value, M).  With
+    normwt the weights sum to N exactly; the double side's sum is off by up to N u N, its order statistic `order` with it:
+    M = |value| + N^2 |x_high - x_low| / 2 (a continuous function of `order`); a cumulated weight that close to `low` or
+    `high` is a tie (value None)."""
+    keep = [i for i in range(len(x)) if w[i] != 0]
+    x, w = [x[i] for i in keep], [w[i] for i in keep]
+    N = len(x)
+    tot = mp.fsum(w)
+    pairs = sorted(zip(x, [t * N / tot for t in w]), key=lambda t: t[0])
+    ux, cs = [], []
+    for xv, wv in pairs:
+        if ux and ux[-1] == xv:
+            cs[-1] += wv
+        else:
+            ux.append(xv); cs.append((cs[-1] if cs else mp.mpf(0)) + wv)
+    order = 1 + (N - 1) * _f(prob)
+    low = max(mp.floor(order), 1)
+    high = min(low + 1, N)
+    frac = order - mp.floor(order)
+
+    def stepq(q):                                   # approx(cumsum(wts), x, method = "constant", f = 1, rule = 2)
+        for xv, c in zip(ux, cs):
+            if c != q and abs(c - q) <= N * N * U and q < N:
+                return None
+            if c >= q:
+                return xv
+        return ux[-1]
+    ql, qh = stepq(low), stepq(high)
+    if ql is None or qh is None:
+        return None, None
+    val = (1 - frac) * ql + frac * qh
+    return val, abs(val) + N * N * abs(qh - ql) / 2
+
+
+def beta_prior_var(mle_beta, baseMean, dispFit, x_names, factors=None, expanded=False, weighted=True, upperQuantile=0.05):
+    """estimateBetaPriorVar (R/core.R:1601-1689) with matchWeightedUpperQuantileForVariance (:2416-2419); expanded model
+    matrices: addAllContrasts (R/expanded.R:76-98) and averagePriorsOverLevels (:20-73).  mle_beta: the rows that are not all
+    zero.  x_names: one name per column of the standard matrix, "<factor><level>" for the level indicators.
+    -> [(value, M) or (None, None) on a tie] per column of the (expanded) matrix"""
+    n, p = mle_beta.shape
+    cols = [[_f(v) for v in mle_beta[:, c]] for c in range(p)]
+    names = list(x_names)
+    if expanded:
+        for f in factors:
+            idx = [i for i, nm in enumerate(x_names) if nm.startswith(f) and nm != "Intercept"]
+            for j in range(len(idx) - 1):
+                for i in range(j + 1, len(idx)):
+                    cols.append([a - b for a, b in zip(cols[idx[i]], cols[idx[j]])]); names.append(f + "Cntrst")
+    wts = [1 / (1 / _f(baseMean[i]) + _f(dispFit[i])) for i in range(n)]                       # :1641-1642
+    qn = mp.sqrt(2) * mp.erfinv(1 - mp.mpf(upperQuantile))                                    # qnorm(1 - upperQuantile / 2)
+    pv = []
+    for c, col in enumerate(cols):
+        if names[c] == "Intercept":
+            pv.append((mp.mpf(10) ** 6, mp.mpf(10) ** 6)); continue                          # :1669-1671
+        use = [i for i in range(n) if abs(col[i]) < 10]
+        if not use:
+            pv.append((mp.mpf(10) ** 6, mp.mpf(10) ** 6)); continue
+        q, Mq = _wtd_quantile([abs(col[i]) for i in use], [wts[i] if weighted else mp.mpf(1) for i in use], 1 - upperQuantile)
+        pv.append((None, None) if q is None else ((q / qn) ** 2, 2 * q * Mq / qn ** 2))
+    if not expanded:
+        return pv
+    enames = ["Intercept"] + ["%s%d" % (f, lv) for f, codes in factors.items() for lv in range(int(np.max(codes)) + 1)]
+    out = [(mp.mpf(0), mp.mpf(0))] * len(enames)
+    for c, nm in enumerate(names):
+        if nm in enames:
+            out[enames.index(nm)] = pv[c]
+    for f, codes in factors.items():
+        mm = {"%s%d" % (f, lv) for lv in range(int(np.max(codes)) + 1)} | {f + "Cntrst"}
+        vals = [pv[c] for c, nm in enumerate(names) if nm in mm]
+        mean = (None, None) if any(v[0] is None for v in vals) else (mp.fsum(v[0] for v in vals) / len(vals),
+                                                                      mp.fsum(v[1] for v in vals) / len(vals))
+        for i, nm in enumerate(enames):
+            if nm in mm:
+                out[i] = mean
+    return out
+
+
+def heavy_rows(result, n_max=64):
+    """the rows the mp-heavy relations run on, chosen from the result alone: every replaced row, every dispOutlier row, the rows
+    whose searches ended at their iteration limit (what N_OPTIM_* / N_GRID_* count), the neighbours of the all-zero rows, then
+    the others evenly by baseMean rank"""
+    n = len(result["baseMean"])
+    live = np.nan_to_num(np.asarray(result["allZero"], float), nan=1.0) == 0
+    picked, special = [], True
+
+    def add(rows):
+        for i in rows:
+            if 0 <= i < n and live[i] and i not in picked and (special or len(picked) < n_max):
+                picked.append(int(i))
+    add(np.flatnonzero(np.nan_to_num(np.asarray(result["replace"], float)) == 1))
+    add(np.flatnonzero(np.nan_to_num(np.asarray(result["dispOutlier"], float)) == 1))
+    for k in ("betaIter", "dispIter", "dispGeneIter"):
+        add(np.flatnonzero(np.nan_to_num(np.asarray(result[k], float)) >= 100))
+    n_max = max(n_max, len(picked) + 16)         # (the rows singled out above all count; at least 16 ordinary ones beside them)
+    special = False
+    for i in np.flatnonzero(~live)[:8]:
+        add([i - 1, i + 1])
+    rank = [i for i in np.argsort(np.nan_to_num(np.asarray(result["baseMean"], float)), kind="stable") if live[i]]
+    if rank and len(picked) < n_max:
+        add([rank[int(round(t))] for t in np.linspace(0, len(rank) - 1, n_max - len(picked))])
+    return picked
+
+
+_BUDGET_OF = {"logLike": "nbinomLogLike"}        # (a family held to a budget of another name)
+
+
+class AuditReport:
+    def __init__(self):
+        self.ratios, self.where, self.ties, self.failures, self.counts = {}, {}, {}, [], {}
+
+    def item(self, fam, row, value, ref, M):
+        r = ratio(value, ref, M) if np.isfinite(value) else float("inf")
+        self.counts[fam] = self.counts.get(fam, 0) + 1
+        if r > self.ratios.get(fam, -1.0):
+            self.ratios[fam], self.where[fam] = r, row
+
+    def exact(self, ok, what):
+        self.counts[what.split(":")[0]] = self.counts.get(what.split(":")[0], 0) + 1
+        if not ok:
+            self.failures.append(what)
+
+    def tie(self, fam):
+        self.ties[fam] = self.ties.get(fam, 0) + 1
+
+    def excess(self):
+        """the worst ratio in units of its budget; infinite when an exact relation is broken"""
+        if self.failures:
+            return float("inf")
+        return max([v / BUDGETS[_BUDGET_OF.get(k, k)] for k, v in self.ratios.items()] + [0.0])
+
+    def summary(self):
+        return {k: float("%.3g" % v) for k, v in sorted(self.ratios.items())}
+
+
+def chain_audit(inputs, result, n_heavy=64, scalars=True, trend_fits=None, rows=None):
+    """inputs: counts (n x m), x, sizeFactors or normalizationFactors, weights, minReplicatesForReplace, minmu, fitType, betaPrior,
+    factors, modelMatrixType, x_names -- what the call was given.  result: what it returned (native.DESeq's names: the
+    per-gene columns, the assays mu / H / cooks [/ replaceCounts], dispersionFunction, status [, betaPriorVar, mle_beta]).
+    scalars = False: the all-gene scalars (trend, varLogDispEsts, betaPriorVar) are not rebuilt -- after a refit the rows
+    they came from are overwritten (R/core.R:2533-2534); the caller compares them with the run without a refit instead.
+    trend_fits: {"exact": f, "restated": (f, rtol)}, f(means, disps) -> the two coefficients.  -> AuditReport"""
+    R = AuditReport()
+    y = np.asarray(inputs["counts"])
+    n, m = y.shape
+    x = np.asarray(inputs["x"], np.float64)
+    p = x.shape[1]
+    nf = (np.broadcast_to(np.asarray(inputs["sizeFactors"], np.float64)[None, :], y.shape)
+          if inputs.get("normalizationFactors") is None else np.asarray(inputs["normalizationFactors"], np.float64))
+    wraw = None if inputs.get("weights") is None else np.asarray(inputs["weights"], np.float64)
+    useW = wraw is not None
+    wnorm = wraw / wraw.max(axis=1, keepdims=True) if useW else np.ones(y.shape)          # R/core.R:2702
+    minmu = float(inputs.get("minmu", 0.5))
+    minrep = float(inputs.get("minReplicatesForReplace", 7))
+    col = lambda k: None if result.get(k) is None else np.asarray(result[k], np.float64)          # (_col: the same as n x k)
+    allZero = np.nan_to_num(col("allZero"), nan=1.0) == 1
+    replace = np.nan_to_num(col("replace")) == 1
+    yrep = None if result.get("replaceCounts") is None else np.asarray(result["replaceCounts"])
+    yfit = np.where(replace[:, None], yrep, y) if (replace.any() and yrep is not None) else y
+    live = ~allZero
+    bm, bv, dge, dfit = col("baseMean"), col("baseVar"), col("dispGeneEst"), col("dispFit")
+    dmap, disp, dout = col("dispMAP"), col("dispersion"), col("dispOutlier")
+    fn = result["dispersionFunction"]
+    vlde = fn["varLogDispEsts"]
+    cell, cellsize = _cells_of(x)
+    replaceable = cellsize >= minrep
+    refit_ran = bool(replace.any() and (replace & live).any() and replaceable.any())
+
+    beta, se, stat, pval = (_col(result, k, n) for k in ("beta", "betaSE", "stat", "pvalue"))
+
+    # ---- every row: the cheap relations
+    for i in (range(n) if rows is None else rows):
+        src = yfit[i] if (replace[i] and yrep is not None) else y[i]
+        v = [_f(src[j]) / _f(nf[i, j]) * (_f(wraw[i, j]) if useW else 1) for j in range(m)]
+        (mean, Mm), (var, Mv) = _mean_var(v)
+        R.item("baseMean", i, bm[i], mean, Mm)
+        R.item("baseVar", i, bv[i], var, Mv)
+        if not live[i]:
+            continue
+        if fn["fitType"] == "parametric":
+            a, e = (_f(t) for t in fn["coefficients"])
+            R.item("dispFit", i, dfit[i], a + e / _f(bm[i]), abs(a) + abs(e / _f(bm[i])))
+        elif fn["fitType"] == "mean":
+            R.exact(dfit[i] == float(fn["coefficients"]), "dispFit: row %d is not the trimmed mean" % i)
+        R.exact(MIN_DISP <= dmap[i] <= max(10, m), "dispMAP: row %d outside [minDisp, max(10, m)]" % i)
+        flag, tie = _disp_outlier(dge[i], dfit[i], vlde)
+        if tie:
+            R.tie("dispOutlier")
+        else:
+            R.exact(bool(dout[i]) == flag, "dispOutlier: row %d" % i)
+        R.exact(disp[i] == (dge[i] if dout[i] else dmap[i]), "dispersion: row %d is not %s" % (i, "dispGeneEst" if dout[i] else "dispMAP"))
+        if stat is not None:
+            for c in range(beta.shape[1]):
+                if not (np.isfinite(beta[i, c]) and se[i, c] > 0):
+                    continue
+                q = _f(beta[i, c]) / _f(se[i, c])
+                R.item("stat", i, stat[i, c], q, abs(q))
+                pv = mp.erfc(abs(_f(stat[i, c])) / mp.sqrt(2))
+                if pv < mp.mpf(2) ** -1022:                   # a subnormal result: one denormal step from the nearest double
+                    R.exact(abs(pval[i, c] - float(pv)) <= 2.0 ** -1074, "pvalue: row %d (subnormal)" % i)
+                else:
+                    R.item("pvalue", i, pval[i, c], pv, pv)
+
+    # ---- the all-gene scalars
+    if scalars:
+        use = live & (np.nan_to_num(dge) > 100 * MIN_DISP)                                   # R/core.R:871
+        if fn["fitType"] == "parametric" and trend_fits:
+            got = np.asarray(fn["coefficients"], np.float64)
+            if "exact" in trend_fits:
+                R.exact(np.array_equal(np.asarray(trend_fits["exact"](bm[use], dge[use])), got),
+                        "trend: not the fit on the rows with dispGeneEst > 100 minDisp")
+            if "restated" in trend_fits:
+                f, rtol = trend_fits["restated"]
+                R.exact(np.allclose(np.asarray(f(bm[use], dge[use])), got, rtol=rtol, atol=0), "trend: restatement")
+        if fn["fitType"] == "mean":
+            from fractions import Fraction
+            s = np.sort(dge[live & (np.nan_to_num(dge) > 10 * MIN_DISP)])                   # :894-899
+            k = int(np.floor(s.size * 0.001))
+            kept = s[k: s.size - k]
+            R.exact(float(sum(Fraction(t) for t in kept.tolist()) / kept.size) == float(fn["coefficients"]), "trend: trimmed mean")
+        v, Mv = var_log_disp_ests(dge[live], dfit[live])
+        R.item("varLogDispEsts", -1, vlde, v, Mv)
+    if m > p:
+        tg = mp.psi(1, mp.mpf(m - p) / 2)
+        R.item("dispPriorVar", -1, fn["dispPriorVar"], max(_f(vlde) - tg, mp.mpf("0.25")), _f(vlde) + tg)
+
+    # ---- Cook's cutoff, maxCooks, replace: exact selections on the returned distances, every row
+    ck = col("cooks")
+    cutoff = float(result["cooksCutoff"])
+    cm = cooks_cutoff_mp(p, m)
+    R.exact(abs(_f(cutoff) - cm) <= mp.mpf(10) ** -12 * cm, "cooksCutoff: not qf(.99, p, m - p)")
+    if ck is not None:
+        for3 = cellsize >= 3
+        ckm = np.where(replaceable[None, :], 0.0, ck) if refit_ran else ck                  # :2538-2546: replaceCooks[, replaceable] <- 0
+        if refit_ran and replaceable.all():
+            for3 = np.zeros(m, bool)                                                         # :2539: NA
+        mx = col("maxCooks")
+        for i in np.flatnonzero(live):
+            want = ckm[i, for3].max() if (m > p and for3.any()) else np.nan
+            R.exact((np.isnan(want) and np.isnan(mx[i])) or mx[i] == want, "maxCooks: row %d" % i)
+            if np.isfinite(minrep) and replaceable.any():
+                R.exact(bool(replace[i]) == bool((ck[i] > cutoff).any()), "replace: row %d" % i)   # :2086
+
+    # ---- at most n_heavy rows: the relations that need the model
+    heavy = heavy_rows(result, n_heavy) if rows is None else [i for i in rows if live[i]]
+    prior = bool(inputs.get("betaPrior"))
+    mle = _col(result, "mle_beta", n) if prior else beta
+    xp = x
+    lam_mle = np.full(p, 1e-6) / np.log(2) ** 2                                              # R/fitNbinomGLMs.R:73,162
+    lam_fit = lam_mle
+    if prior:
+        if inputs.get("modelMatrixType", "expanded" if inputs.get("factors") else "standard") == "expanded":
+            f = inputs["factors"]
+            xp = np.column_stack([np.ones(m)] + [(np.asarray(c) == lv).astype(float) for c in f.values()
+                                                 for lv in range(int(np.max(c)) + 1)])     # R/expanded.R:1-18
+        lam_fit = 1.0 / np.asarray(result["betaPriorVar"], np.float64) / np.log(2) ** 2     # :311, :162
+    mu_r, H_r = col("mu"), col("H")
+    iters = np.nan_to_num(col("betaIter"))
+
+    def mu_at(xm, b, i):                             # R/fitNbinomGLMs.R:180: nf * exp(x beta), NOT floored at minmu
+        return [_f(nf[i, j]) * mp.exp(mp.fsum(_f(xm[j, k]) * b[k] for k in range(xm.shape[1]) if xm[j, k] != 0)) for j in range(m)]
+
+    def eta_terms(xm, b):
+        S = [sum(abs(xm[j, k] * b[k]) for k in range(xm.shape[1])) for j in range(m)]
+        return [5 + (2 + int(np.count_nonzero(xm[j]))) * S[j] for j in range(m)]
+    for i in heavy:
+        alpha = disp[i]
+        zero = np.zeros(xp.shape[1])
+        opt = iters[i] >= 100                      # (rows of the optim fallback: mu, betaSE as R/fitNbinomGLMs.R:382-397, H the IRLS's)
+        b_mp = [_f(v) / LOG2E for v in beta[i]]
+        b_fit = [float(v) for v in b_mp]
+        post = fit_beta_post(yfit[i], xp, nf[i], alpha, zero, b_mp, lam_fit, wnorm[i], useW, minmu)
+        T = eta_terms(xp, b_fit)
+        C = max(T) / 5
+        if not opt:
+            for k in range(xp.shape[1]):
+                s = mp.sqrt(post["beta_var_mat"][0][k]) * LOG2E
+                Mk = LOG2E * post["beta_var_mat"][1][k] / (2 * mp.sqrt(post["beta_var_mat"][0][k])) * C
+                R.item("betaSE", i, se[i, k], s, Mk)
+        # mu and H belong to the fit without the prior (R/fitNbinomGLMs.R:256-260, 293), and to the FIRST fit on refitted rows
+        m_mp = [_f(v) / LOG2E for v in mle[i]]
+        own = post if not prior else fit_beta_post(yfit[i], x, nf[i], alpha, np.zeros(p), m_mp, lam_mle, wnorm[i], useW, minmu)
+        Tm = T if not prior else eta_terms(x, [float(_f(v) / LOG2E) for v in mle[i]])
+        if mu_r is not None and not replace[i] and not opt:
+            mus = mu_at(x, m_mp, i)
+            for j in range(m):
+                R.item("mu", i, mu_r[i, j], mus[j], mus[j] * Tm[j])
+                if H_r is not None and not prior:   # (the beta-prior run returns no iteration count of its first fit: the rows
+                    #                                  that left its IRLS -- their H is the last iterate's -- cannot be told apart)
+                    R.item("H", i, H_r[i, j], own["hat_diagonals"][0][j], own["hat_diagonals"][1][j] * max(Tm) / 5)
+        ll = col("logLike")
+        if ll is not None and mu_r is not None:
+            if replace[i] or prior:
+                if not opt:
+                    size = 1 / _f(alpha)
+                    val = M = mp.mpf(0)
+                    mus = mu_at(xp, b_mp, i)
+                    for j in range(m):
+                        w = _f(wnorm[i, j]) if useW else mp.mpf(1)
+                        mj = mus[j]
+                        parts = nb_logpmf_parts(yfit[i][j], mj, size)
+                        val += w * mp.fsum(parts)
+                        g = abs(_f(yfit[i][j]) - mj) / (1 + _f(alpha) * mj)           # |d log f / d eta|
+                        M += abs(w) * (mp.fsum(parts, absolute=True) + g * T[j])
+                    R.item("logLike_at_beta", i, ll[i], val, M)
+            else:                                      # (a row of the optim fallback: at the floored mu, R/fitNbinomGLMs.R:386-399)
+                R.item("logLike", i, ll[i], *nbinomLogLike(y[i], np.maximum(mu_r[i], minmu) if opt else mu_r[i], alpha, wnorm[i], useW))
+        llr, lrt = col("logLikeReduced"), col("LRTStatistic")
+        if (llr is not None or lrt is not None) and ll is not None:
+            # nbinomLRT against ~ 1 (R/core.R:1877): the reduced fit is closed-form (R/fitNbinomGLMs.R:99-137), mu = nf 2^beta with
+            # beta = log2 of the [weighted] mean normalized count.  Derived term of its mu: the mean is m [2m] roundings, log2 within
+            # 2 ulp of beta is 4u |ln mean| in 2^beta, 2^beta 4u, the product u: T = [2] m + 5 + 4 |ln mean|
+            yn = [_f(yfit[i][j]) / _f(nf[i, j]) for j in range(m)]
+            ws = [_f(wnorm[i, j]) if useW else mp.mpf(1) for j in range(m)]
+            mean = mp.fsum(w * t for w, t in zip(ws, yn)) / mp.fsum(ws)
+            Tr = (2 if useW else 1) * m + 5 + 4 * abs(mp.log(mean))
+            size = 1 / _f(alpha)
+            vr = Mr = mp.mpf(0)
+            for j in range(m):
+                mj = _f(nf[i, j]) * mean
+                parts = nb_logpmf_parts(yfit[i][j], mj, size)
+                vr += ws[j] * mp.fsum(parts)
+                Mr += ws[j] * (mp.fsum(parts, absolute=True) + abs(_f(yfit[i][j]) - mj) / (1 + _f(alpha) * mj) * Tr)
+            if llr is not None:
+                R.item("logLikeReduced", i, llr[i], vr, Mr)
+            if lrt is not None and not opt:
+                # the statistic at the returned logLike (audited above): 2 (logLike - logLikeReduced), the reduced side at 50 digits
+                R.item("LRTStatistic", i, lrt[i], 2 * (_f(ll[i]) - vr), 2 * (abs(_f(ll[i])) + Mr))
+                pv = mp.gammainc(mp.mpf(int(result["df"])) / 2, max(_f(lrt[i]), 0) / 2, mp.inf, regularized=True)   # :1878
+                R.exact(abs(_f(col("LRTPvalue")[i]) - pv) <= mp.mpf(10) ** -12 * pv + mp.mpf(2) ** -1074, "LRTPvalue: row %d" % i)
+        if ck is not None and mu_r is not None and H_r is not None:
+            cd = cooks_distance(y[i], nf[i], mu_r[i], H_r[i], x)
+            for j in range(m):
+                if float(H_r[i, j]) < 1.0:
+                    R.item("cooks", i, ck[i, j], cd["cooks"][0][j], cd["cooks"][1][j])
+        if replace[i] and yrep is not None:                                                   # :2088-2098
+            cn = [_f(y[i, j]) / _f(nf[i, j]) for j in range(m)]
+            tm, Mt, _ = _trimmed_mean(cn, mp.mpf("0.2"))
+            for j in range(m):
+                if ck[i, j] > cutoff and replaceable[j]:
+                    t = tm * _f(nf[i, j])
+                    if abs(t - mp.nint(t)) <= 8 * U * Mt * _f(nf[i, j]):
+                        R.tie("replaceCounts")
+                    else:
+                        R.exact(int(yrep[i, j]) == int(mp.floor(t)), "replaceCounts: row %d sample %d is not as.integer(trimmed mean * nf)" % (i, j))
+                else:
+                    R.exact(int(yrep[i, j]) == int(y[i, j]), "replaceCounts: row %d sample %d was not to be replaced" % (i, j))
+
+    # ---- the beta prior variance
+    if prior and scalars and inputs.get("betaPriorVar") is None:
+        names = inputs.get("x_names") or ["Intercept"] + ["V%d" % k for k in range(1, p)]
+        expd = xp.shape[1] != p
+        ref = beta_prior_var(mle[live], bm[live], dfit[live], names, inputs.get("factors"), expd)
+        for k, (v, M) in enumerate(ref):
+            if v is None:
+                R.tie("betaPriorVar")
+            else:
+                R.item("betaPriorVar", k, result["betaPriorVar"][k], v, M)
+    return R

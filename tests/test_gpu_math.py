@@ -18,7 +18,7 @@ def _inputs(rng):
 
 
 @pytest.mark.parametrize("name,op", [("exp", 0), ("log", 1), ("log1p", 2), ("lgamma", 3), ("digamma", 4),
-                                     ("trigamma", 5), ("stirlerr", 6)])
+                                     ("trigamma", 5), ("stirlerr", 6), ("pnorm_upper2", 9)])
 def test_unary_bit_exact(oracle, name, op):
     from deseq2_amd import native
     rng = np.random.default_rng(op + 11)
@@ -30,6 +30,11 @@ def test_unary_bit_exact(oracle, name, op):
     elif name == "log1p":
         x = np.concatenate([rng.uniform(-1, 3, 50000), np.exp(rng.uniform(-60, 60, 20000)),
                             -np.exp(rng.uniform(-60, 0, 20000)), [-1.0, -2.0, np.inf, np.nan, 0.0]])
+    elif name == "pnorm_upper2":            # the Wald p-value: +-40 covers its three ranges and the underflow; the range edges
+        edges = [0.67448975, float(np.sqrt(32.0)), 37.5, 38.4, 38.5]
+        edges = np.array([t for e in edges for t in (np.nextafter(e, 0.0), e, np.nextafter(e, 100.0))])
+        x = np.concatenate([anyx[:40000] * (40.0 / 750.0), anyx[40000:80000] * 20.0, edges, -edges,
+                            [0.0, -0.0, np.inf, -np.inf, np.nan]])
     elif name == "stirlerr":
         x = pos[(pos > 0) & np.isfinite(pos)]
     else:

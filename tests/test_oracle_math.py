@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "nmath_golden.json")))
+GOLD.update(json.load(open(os.path.join(os.path.dirname(__file__), "golden", "nmath_golden_pnorm.json"))))
 EPS = 2.220446049250313e-16
 
 
@@ -16,12 +17,19 @@ def _ulps(got, want):
     return np.max(np.abs(got[ok] - want[ok]) / np.spacing(np.abs(want[ok])))
 
 
-@pytest.mark.parametrize("name,max_ulp", [("exp", 1.5), ("log", 1.5), ("log1p", 1.5), ("trigamma", 8.0)])
+# pnorm_upper2: the largest error seen on the golden arguments is 4.0 spacings of the exact value; where that value is
+# subnormal a spacing is one denormal step, and the error there is 1.0
+@pytest.mark.parametrize("name,max_ulp", [("exp", 1.5), ("log", 1.5), ("log1p", 1.5), ("trigamma", 8.0), ("pnorm_upper2", 5.0)])
 def test_relative_accuracy(oracle, name, max_ulp):
     g = GOLD[name]
     got = oracle.unary(name, np.array(g["x"]))
+    want = np.array(g["y"])
+    sub = np.abs(want) < 2.0 ** -1022
+    if sub.any():            # where the exact value is subnormal (pnorm_upper2 beyond |z| = 37.5): one denormal step
+        assert np.max(np.abs(got[sub] - want[sub])) <= 2.0 ** -1074
+        got, want = got[~sub], want[~sub]
     # golden values are mpmath results rounded to double: allow 0.5 ulp for that rounding
-    assert _ulps(got, g["y"]) <= max_ulp + 0.5
+    assert _ulps(got, want) <= max_ulp + 0.5
 
 
 @pytest.mark.parametrize("name,max_eps", [("lgamma", 50.0), ("digamma", 16.0), ("stirlerr", 80.0)])
@@ -67,6 +75,11 @@ def test_special_values(oracle):
     assert r[0] == -inf and r[1] == 0.0 and r[2] == 1e-20 and np.isnan(r[3])
     assert oracle.unary("lgamma", [1.0, 2.0])[0] == pytest.approx(0.0, abs=1e-14)
     assert np.isnan(oracle.unary("exp", [nan])[0])
+    # 2 pnorm(|z|, lower.tail = FALSE): NaN -> NaN, +-Inf -> 0, |z| >= 38.5 -> 0, 1 at zero, even in z
+    r = oracle.unary("pnorm_upper2", [nan, inf, -inf, 38.5, -38.5, 1e300, 0.0, -0.0])
+    assert np.isnan(r[0]) and r[1:6].tolist() == [0.0] * 5 and r[6:].tolist() == [1.0, 1.0]
+    z = np.array(GOLD["pnorm_upper2"]["x"])
+    assert np.array_equal(oracle.unary("pnorm_upper2", -z), oracle.unary("pnorm_upper2", z))
     # size = Inf is the Poisson limit (nmath/dnbinom.c)
     from scipy.stats import poisson
     got = oracle.dnbinom_mu_log([0.0, 3.0, 40.0], [inf, inf, inf], [2.5, 2.5, 30.0])
