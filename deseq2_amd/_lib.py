@@ -262,6 +262,25 @@ class DsqRlogOut(C.Structure):
                 ("bad", C.c_void_p)]
 
 
+class DsqResultsArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("p", C.c_int32), ("c", C.c_int32), ("test", C.c_int32), ("beta", C.c_void_p),
+        ("betaSE", C.c_void_p), ("stat", C.c_void_p), ("pvalue", C.c_void_p), ("baseMean", C.c_void_p),
+        ("replace", C.c_void_p), ("na_mask", C.c_void_p), ("lfcThreshold", C.c_double), ("altHypothesis", C.c_int32),
+        ("independentFiltering", C.c_int32), ("filter", C.c_void_p), ("theta", C.c_void_p), ("K", C.c_int32),
+        ("alpha", C.c_double), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
+class DsqResultsOut(C.Structure):
+    _fields_ = [("baseMean", C.c_void_p), ("log2FoldChange", C.c_void_p), ("lfcSE", C.c_void_p), ("stat", C.c_void_p),
+                ("pvalue", C.c_void_p), ("filtPadj", C.c_void_p), ("numRej", C.c_void_p), ("cutoffs", C.c_void_p),
+                ("status", C.c_void_p)]
+
+
+DSQ_TEST = {"Wald": 0, "LRT": 1}
+DSQ_ALT = {"greaterAbs": 0, "lessAbs": 1, "greater": 2, "less": 3, "greaterAbs2014": 4}
+DSQ_RESULTS_MAX_K = 4096
 DSQ_VST = {"parametric": 0, "mean": 1, "spline": 2, "log2": 3, "normalized": 4}
 DSQ_VST_MAX_KNOTS = 1600
 DSQ_SF = {"ratio": 0, "poscounts": 1}
@@ -292,6 +311,7 @@ EXPORTED_SYMBOLS = [
     "dsq_size_factors", "dsq_size_factors_dev", "dsq_size_factors_workspace_bytes",
     "dsq_vst", "dsq_vst_dev", "dsq_vst_rowstats_dev",
     "dsq_rlog", "dsq_rlog_dev",
+    "dsq_results", "dsq_results_dev", "dsq_results_workspace_bytes",
 ]
 
 _lib = None
@@ -363,6 +383,10 @@ def lib():
     L.dsq_vst_rowstats_dev.argtypes = [C.POINTER(DsqVstArgs), C.POINTER(DsqVstOut), C.c_void_p]
     L.dsq_rlog.argtypes = [C.POINTER(DsqRlogArgs), C.POINTER(DsqRlogOut)]
     L.dsq_rlog_dev.argtypes = [C.POINTER(DsqRlogArgs), C.POINTER(DsqRlogOut), C.c_void_p]
+    L.dsq_results.argtypes = [C.POINTER(DsqResultsArgs), C.POINTER(DsqResultsOut)]
+    L.dsq_results_dev.argtypes = [C.POINTER(DsqResultsArgs), C.POINTER(DsqResultsOut), C.c_void_p]
+    L.dsq_results_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.dsq_results_workspace_bytes.restype = C.c_int64
     L.dsq_deseq_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.dsq_deseq_workspace_bytes.restype = C.c_int64
     L.dsq_profile_get.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double)]

@@ -916,7 +916,7 @@ def nbinomWaldTest(dds, betaTol=1e-8, maxit=100, useOptim=True, useT=False, df=N
     dds.assays["mu"] = fit["mu"]
     dds.assays["H"] = fit["hat_diagonals"]
     dds.attrs.update(betaPrior=bool(betaPrior), betaPriorVar=bpv, test="Wald",
-                     modelMatrixType=modelMatrixType, factors=factors)
+                     modelMatrixType=modelMatrixType, factors=factors, useT=bool(useT))
     calculateCooksDistance(dds, H, dds.x if modelMatrix is None else np.asarray(modelMatrix, float))   # :1451-1463
     betaMatrix, betaSE = fit["betaMatrix"], fit["betaSE"]
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -1510,3 +1510,370 @@ def rlog(obj, blind=True, intercept=None, betaPriorVar=None, fitType="parametric
 
 
 rlogTransformation = rlog                                                           # :168
+
+
+# ------------------------------------------------------------------ R/results.R
+class DESeqResults:
+    """What results() returns: the six columns baseMean, log2FoldChange, lfcSE, stat, pvalue, padj and metadata(res).  The
+    columns stay where the engine made them (HBM on the device engine) until one is asked for: res["padj"]."""
+    COLUMNS = ("baseMean", "log2FoldChange", "lfcSE", "stat", "pvalue", "padj")
+
+    def __init__(self, tab, priorInfo=None, engine=None):
+        self.tab, self.engine = tab, engine
+        self.metadata = {}
+        self.priorInfo = priorInfo
+        self._set = {}                 # columns assigned from the host (padj; `row` of tidy = TRUE)
+
+    @property
+    def columns(self):
+        return [c for c in ("row",) + self.COLUMNS if c in self._set or (c in self.COLUMNS[:5])]
+
+    @property
+    def n(self):
+        return int(np.shape(self.tab.resident["baseMean"])[0])
+
+    def __getitem__(self, name):
+        if name in self._set:
+            v = self._set[name]
+            return v() if callable(v) else v
+        if name in self.COLUMNS[:5]:
+            return self.tab.column(name)
+        raise KeyError(name)
+
+    def __setitem__(self, name, value):
+        self._set[name] = value if callable(value) else np.asarray(value)
+
+    def __contains__(self, name):
+        return name in self.columns
+
+    def to_dict(self):
+        return {c: self[c] for c in self.columns}
+
+
+def _coef_names(dds, ncoef):
+    names = dds.attrs.get("coefNames")
+    if names is not None and len(names) == ncoef:
+        return list(names)
+    first_ones = dds.x.shape[1] == ncoef and bool((dds.x[:, 0] == 1).all())
+    return ["Intercept" if (k == 0 and first_ones) else "coef%d" % k for k in range(ncoef)]
+
+
+def resultsNames(dds):
+    """resultsNames (R/results.R:619-621): the names of the fitted coefficients -- attrs["coefNames"] when the caller has
+    set them (the column names of the model matrix), else Intercept / coef1 / coef2 ..."""
+    from .fused import finish
+    finish(dds)                      # (an analysis enqueued with wait = False)
+    if "beta" not in dds.mcols:
+        raise RuntimeError("couldn't find results. you should first run DESeq()")
+    return _coef_names(dds, np.shape(dds.mcols["beta"])[1])
+
+
+def p_adjust(p, method="BH"):
+    """stats::p.adjust for the two methods results() is served with: "BH" (NAs left out of n, pmin(1, cummin(n / i * p[o]))[ro])
+    and "none"."""
+    p0 = np.array(p, np.float64)
+    if method == "none":
+        return p0
+    if method != "BH":
+        raise NotImplementedError('p_adjust: method "%s" (served: "BH", "none")' % method)
+    nna = ~np.isnan(p0)
+    pp = p0[nna]
+    n = pp.size
+    if n == 0:
+        return p0
+    o = np.argsort(-pp, kind="stable")
+    ro = np.argsort(o, kind="stable")
+    i = np.arange(n, 0, -1).astype(np.float64)
+    with np.errstate(all="ignore"):
+        p0[nna] = np.minimum(1.0, np.minimum.accumulate((n / i) * pp[o]))[ro]
+    return p0
+
+
+def lowess(x, y, f=2.0 / 3.0, iter=3, delta=None):
+    """stats::lowess as documented (W. S. Cleveland's algorithm): for every x the ns = clamp(int(f n + 1e-7), 2, n) nearest
+    points, tricube weights (1 within 0.001 h, 0 beyond 0.999 h), a weighted local line; `iter` passes of bisquare
+    robustness weights from the residuals (6 times their median absolute value); points closer than delta = 0.01
+    range(x) to the last fitted one are interpolated linearly.  Returns dict(x, y) sorted by x.  Restated from the
+    published algorithm: R's own source is not part of the reference tree, so agreement with R to the last bit is not pinned."""
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    o = np.argsort(x, kind="stable")
+    x, y = x[o], y[o]
+    n = x.size
+    if n < 2:
+        return {"x": x, "y": y.copy()}
+    if delta is None:
+        delta = 0.01 * (x[-1] - x[0])
+    ns = max(2, min(n, int(f * n + 1e-7)))
+    ys, rw, res = np.zeros(n), np.ones(n), np.zeros(n)
+    rng = x[-1] - x[0]
+
+    def lowest(xs, nleft, nright, userw):
+        h = max(xs - x[nleft], x[nright] - xs)
+        h9, h1 = 0.999 * h, 0.001 * h
+        w = np.zeros(n)
+        a = 0.0
+        j = nleft
+        while j < n:
+            r = abs(x[j] - xs)
+            if r <= h9:
+                w[j] = 1.0 if r <= h1 else (1.0 - (r / h) ** 3) ** 3
+                if userw:
+                    w[j] *= rw[j]
+                a += w[j]
+            elif x[j] > xs:
+                break
+            j += 1
+        nrt = j - 1
+        if a <= 0.0:
+            return False, 0.0
+        sl = slice(nleft, nrt + 1)
+        w[sl] /= a
+        if h > 0.0:
+            a = float(np.sum(w[sl] * x[sl]))
+            b = xs - a
+            c = float(np.sum(w[sl] * (x[sl] - a) ** 2))
+            if np.sqrt(c) > 0.001 * rng:
+                b /= c
+                w[sl] = w[sl] * (b * (x[sl] - a) + 1.0)
+        return True, float(np.sum(w[sl] * y[sl]))
+
+    for it in range(iter + 1):
+        nleft, nright, last, i = 0, ns - 1, -1, 0
+        while True:
+            if nright < n - 1:
+                d1, d2 = x[i] - x[nleft], x[nright + 1] - x[i]
+                if d1 > d2:
+                    nleft += 1
+                    nright += 1
+                    continue
+            ok, v = lowest(x[i], nleft, nright, it > 0)
+            ys[i] = v if ok else y[i]
+            if last < i - 1:
+                denom = x[i] - x[last]
+                for j in range(last + 1, i):
+                    al = (x[j] - x[last]) / denom
+                    ys[j] = al * ys[i] + (1.0 - al) * ys[last]
+            last = i
+            cut = x[last] + delta
+            i = last + 1
+            while i < n:
+                if x[i] > cut:
+                    break
+                if x[i] == x[last]:
+                    ys[i] = ys[last]
+                    last = i
+                i += 1
+            i = max(last + 1, i - 1)
+            if last >= n - 1:
+                break
+        res = y - ys
+        if it == iter:
+            break
+        sc = float(np.sum(np.abs(res))) / n
+        ar = np.sort(np.abs(res))
+        m1 = n // 2
+        cmad = 3.0 * (ar[m1] + ar[n - m1 - 1]) if n % 2 == 0 else 6.0 * ar[m1]
+        if cmad < 1e-7 * sc:
+            break
+        c9, c1 = 0.999 * cmad, 0.001 * cmad
+        r = np.abs(res)
+        with np.errstate(all="ignore"):         # (cmad = 0: every branch taken is free of the quotient)
+            rw = np.where(r <= c1, 1.0, np.where(r <= c9, (1.0 - (r / cmad) ** 2) ** 2, 0.0))
+    return {"x": x, "y": ys}
+
+
+def _seq_length(lo, hi, length):
+    """seq(lo, hi, length = length): c(from, from + seq_len(length - 2) * by, to), by = (to - from) / (length - 1)"""
+    by = (hi - lo) / (length - 1)
+    return np.concatenate([[lo], lo + np.arange(1, length - 1) * by, [hi]])
+
+
+def pvalueAdjustment(res, independentFiltering=True, filter=None, theta=None, alpha=0.1, pAdjustMethod="BH"):
+    """pvalueAdjustment (R/results.R:638-718): independent filtering over a grid of quantiles of the filter statistic, the
+    number of rejections per quantile, the choice of the threshold by the lowess rule of :661-692; or the plain adjustment.
+    The adjustments run in the engine (csrc/results.hip on the device); the rule over the K counts runs here."""
+    E = res.engine
+    if pAdjustMethod not in ("BH", "none"):
+        raise NotImplementedError('pAdjustMethod "%s": served are "BH" and "none"' % pAdjustMethod)
+    if not independentFiltering:
+        if pAdjustMethod == "none":
+            _realize(res)
+            res["padj"] = lambda: np.array(res["pvalue"], copy=True)
+        else:
+            tab = _run_filtered_p(res, None, None, alpha)                         # :709
+            res["padj"] = lambda: tab.padj_column(0)
+        return res
+    if pAdjustMethod != "BH":
+        raise NotImplementedError("independent filtering is served with pAdjustMethod = 'BH' only")
+    n = res.n
+    if filter is None:
+        fvals = res["baseMean"] if theta is None else None                       # (the default theta needs mean(filter == 0))
+    else:
+        fvals = np.asarray(filter, np.float64)
+        if fvals.shape != (n,):
+            raise ValueError("length(filter) == nrow(res) is not TRUE")          # :653
+    if theta is None:
+        lowerQuantile = float(np.mean(fvals == 0))                                # :646-648
+        upperQuantile = 0.95 if lowerQuantile < 0.95 else 1.0
+        theta = _seq_length(lowerQuantile, upperQuantile, 50)
+    theta = np.asarray(theta, np.float64)
+    if theta.size <= 1:
+        raise ValueError("length(theta) > 1 is not TRUE")                        # :652
+    tab = _run_filtered_p(res, None if filter is None else fvals, theta, alpha)   # :654-656, 695
+    numRej = np.asarray(tab.numRej, np.float64)
+    lo_fit = lowess(theta, numRej, f=1.0 / 5.0)                                   # :661
+    if numRej.max() <= 10:
+        j = 0
+    else:
+        pos = numRej > 0
+        residual = numRej[pos] - lo_fit["y"][pos]          # (theta ascending: lowess keeps its order)
+        maxFit = float(np.max(lo_fit["y"]))
+        rmse = float(np.sqrt(np.mean(residual ** 2)))
+        thresh = maxFit - rmse
+        j = 0
+        for bound in (thresh, 0.9 * maxFit, 0.8 * maxFit):                       # :680-691
+            hit = np.where(numRej > bound)[0]
+            if hit.size:
+                j = int(hit[0])
+                break
+    res["padj"] = lambda: tab.padj_column(j)
+    res.metadata.update(filterThreshold=float(tab.cutoffs[j]), filterTheta=float(theta[j]),
+                        filterNumRej={"theta": theta, "numRej": np.asarray(tab.numRej).copy()}, alpha=alpha)
+    res.metadata["lo.fit"] = lo_fit
+    return res
+
+
+def _cooks_flags(dds, cooksCutoff):
+    """cooksOutlier over all n rows, also when the n x m assays cover the non-zero rows only (attrs["nz_rows"])"""
+    nz = dds.attrs.get("nz_rows")
+    if nz is None or dds.engine.nrow(dds.assays["cooks"]) == dds.n:
+        return cooksOutlier(dds, cooksCutoff)
+    view = dds.subset(nz)
+    view.mcols, view.assays, view.attrs = {"maxCooks": np.asarray(dds.mcols["maxCooks"])[nz]}, dds.assays, dds.attrs
+    flags = np.zeros(dds.n, bool)
+    flags[nz] = cooksOutlier(view, cooksCutoff)
+    return flags
+
+
+def results(dds, name=None, lfcThreshold=0, altHypothesis="greaterAbs", cooksCutoff=None, independentFiltering=True,
+            alpha=0.1, filter=None, theta=None, pAdjustMethod="BH", filterFun=None, test=None, tidy=False, **not_served):
+    """results (R/results.R:298-615) for one coefficient: `name` is a name of resultsNames(dds) or a column index and
+    defaults to the last coefficient.  cooksCutoff: None = qf(.99, p, m - p), False = no filter, a number = that cutoff.
+    The table, the threshold tests and the adjusted p-values of every filter threshold are engine work (one launch chain
+    on the device, csrc/results.hip); argument checks, the Cook's flags (core.cooksOutlier) and the choice of the threshold
+    stay here.  Not served (NotImplementedError): contrast, addMLE, format, parallel, a threshold test on a useT analysis,
+    pAdjustMethod other than "BH" / "none"."""
+    reasons = {"contrast": "cleanContrast's bookkeeping over level names is not mirrored: fit with the contrast, or pick a coefficient by name",
+               "addMLE": "the MLE column of a beta-prior analysis is not served", "format": "only the table is served",
+               "parallel": "the adjustment is global over the genes and runs on one device", "BPPARAM": "see parallel",
+               "saveCols": "only the six result columns are served", "listValues": "see contrast", "minmu": "see contrast"}
+    for k, v in not_served.items():
+        if k not in reasons:
+            raise TypeError("results() got an unexpected keyword argument '%s'" % k)
+        if not (v is None or v is False or (k == "format" and v == "DataFrame")):
+            raise NotImplementedError("results(%s = ): %s" % (k, reasons[k]))
+    from .fused import finish
+    finish(dds)                      # (an analysis enqueued with wait = False)
+    if altHypothesis not in ("greaterAbs", "lessAbs", "greater", "less", "greaterAbs2014"):
+        raise ValueError("'arg' should be one of greaterAbs, lessAbs, greater, less, greaterAbs2014")
+    if np.ndim(lfcThreshold) != 0 or np.ndim(alpha) != 0:
+        raise ValueError("lfcThreshold and alpha must have length 1")            # :327-328
+    if not lfcThreshold >= 0:
+        raise ValueError("lfcThreshold >= 0 is not TRUE")                        # :326
+    if not (alpha > 0 and alpha < 1):
+        raise ValueError("alpha > 0 & alpha < 1 is not TRUE")                    # :329
+    if "beta" not in dds.mcols:
+        raise RuntimeError("couldn't find results. you should first run DESeq()")   # :333-335
+    if pAdjustMethod not in ("BH", "none"):
+        raise NotImplementedError('pAdjustMethod "%s": served are "BH" and "none"' % pAdjustMethod)
+    objtest = dds.attrs.get("test")
+    if test is None:
+        test = objtest                                                           # :336-337
+    elif test not in ("Wald", "LRT"):
+        raise ValueError("'arg' should be one of Wald, LRT")
+    elif test == "LRT" and objtest == "Wald":
+        raise ValueError("the LRT requires the user run nbinomLRT or DESeq(dds,test='LRT')")   # :341-343
+    if lfcThreshold == 0 and altHypothesis == "lessAbs":
+        raise ValueError("when testing altHypothesis='lessAbs', set the argument lfcThreshold to a positive value")   # :344-346
+    E = dds.engine
+    beta, betaSE = np.asarray(dds.mcols["beta"]), np.asarray(dds.mcols["betaSE"])
+    names = _coef_names(dds, beta.shape[1])
+    if name is None:
+        c = beta.shape[1] - 1                                                    # lastCoefName
+    elif isinstance(name, str):
+        if name not in names:
+            raise ValueError("'%s' is not one of resultsNames(dds): %s" % (name, ", ".join(names)))
+        c = names.index(name)
+    elif isinstance(name, (int, np.integer)) and 0 <= int(name) < beta.shape[1]:
+        c = int(name)
+    else:
+        raise ValueError("the argument 'name' should be a coefficient name or a column index")   # :403-405
+    threshold = not (lfcThreshold == 0 and altHypothesis == "greaterAbs")
+    if threshold:
+        if test == "LRT":
+            raise ValueError("tests of log fold change above or below a theshold must be Wald tests.")   # :465-467
+        if altHypothesis == "lessAbs" and dds.attrs.get("betaPrior"):
+            raise ValueError("testing altHypothesis='lessAbs' requires setting the DESeq() argument betaPrior=FALSE")   # :469-471
+        if dds.attrs.get("useT"):
+            raise NotImplementedError("a threshold test on a useT analysis: there is no Student-t distribution in the engine")
+    lfc, se = beta[:, c], betaSE[:, c]
+    if test == "LRT":
+        stat, pvalue = dds.mcols["LRTStatistic"], dds.mcols["LRTPvalue"]
+    elif "WaldStatistic" in dds.mcols:
+        stat, pvalue = np.asarray(dds.mcols["WaldStatistic"])[:, c], np.asarray(dds.mcols["WaldPvalue"])[:, c]
+    else:
+        with np.errstate(divide="ignore", invalid="ignore"):                     # makeWaldTest (:1101-1118) on an LRT object
+            stat = lfc / se
+        pvalue = E.two_sided_normal_p(stat)
+    na_mask = None
+    if not (cooksCutoff is False) and "maxCooks" in dds.mcols and "dispModelMatrix" in dds.attrs:
+        cut = None if (cooksCutoff is None or cooksCutoff is True) else float(cooksCutoff)     # :524-531
+        na_mask = _cooks_flags(dds, cut)                                         # :534-564
+    replace = dds.mcols.get("replace")
+    if replace is not None:
+        with np.errstate(invalid="ignore"):
+            replace = np.asarray(replace) == 1                                   # (NA is not TRUE, :568-569)
+        if not replace.any():
+            replace = None
+    if dds.attrs.get("betaPrior"):
+        priorInfo = {"type": "normal", "package": "deseq2_amd", "betaPriorVar": dds.attrs.get("betaPriorVar")}   # :579-585
+    else:
+        priorInfo = {"type": "none", "package": "deseq2_amd"}
+    # the table is not launched yet: the adjustment's engine call makes table and adjusted p-values together
+    bm = np.asarray(dds.mcols["baseMean"], np.float64)
+    res = DESeqResults(_ResultsPending((lfc, se, stat, pvalue, bm, replace, na_mask, lfcThreshold, altHypothesis)), priorInfo, E)
+    if filterFun is None:
+        pvalueAdjustment(res, independentFiltering, filter, theta, alpha, pAdjustMethod)   # :591-593
+    else:
+        _realize(res)
+        res = filterFun(res, filter, alpha, pAdjustMethod)                       # :594-596
+    res.metadata["lfcThreshold"] = lfcThreshold                                   # :599
+    if tidy:
+        res["row"] = np.arange(res.n)                                            # :602-610 (the objects carry no row names)
+    return res
+
+
+class _ResultsPending:
+    """the arguments of a table that has not been launched"""
+
+    def __init__(self, args):
+        self.args = args
+        self.resident = {"baseMean": args[4]}
+
+    def column(self, name):
+        assert name == "baseMean"
+        return self.args[4]
+
+
+def _realize(res):
+    if isinstance(res.tab, _ResultsPending):
+        res.tab = res.engine.results_table(*res.tab.args)
+    return res.tab
+
+
+def _run_filtered_p(res, filter, theta, alpha):
+    """the adjustment over `theta`; for a table not launched yet, table and adjustment in ONE engine call"""
+    if isinstance(res.tab, _ResultsPending):
+        res.tab = res.engine.results(*res.tab.args, filter=filter, theta=theta, alpha=alpha)
+        return res.tab
+    return res.engine.filtered_p(res.tab, filter, theta, alpha)

@@ -810,6 +810,59 @@ int rlog_dev_locked(const DsqRlogArgs *a, const DsqRlogOut *o, hipStream_t st) {
     return DSQ_OK;
 }
 
+// results() (results.hip): what both entries check before anything is launched
+int results_check(const DsqResultsArgs *a, const DsqResultsOut *o) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->n < 1) return capi_fail(DSQ_ERR_ARG, "n = %d: at least one gene is needed", a->n);
+    if (a->p < 1 || a->c < 0 || a->c >= a->p) return capi_fail(DSQ_ERR_ARG, "coefficient c = %d outside 0 .. p - 1 (p = %d)", a->c, a->p);
+    if (!a->beta || !a->betaSE || !a->stat || !a->pvalue || !a->baseMean)
+        return capi_fail(DSQ_ERR_ARG, "NULL beta, betaSE, stat, pvalue or baseMean");
+    if (!o->baseMean || !o->log2FoldChange || !o->lfcSE || !o->stat || !o->pvalue || !o->numRej || !o->cutoffs || !o->status)
+        return capi_fail(DSQ_ERR_ARG, "NULL output array");
+    if (a->test != DSQ_TEST_WALD && a->test != DSQ_TEST_LRT) return capi_fail(DSQ_ERR_ARG, "unknown test %d", a->test);
+    if (a->altHypothesis < DSQ_ALT_GREATER_ABS || a->altHypothesis > DSQ_ALT_GREATER_ABS_2014)
+        return capi_fail(DSQ_ERR_ARG, "unknown altHypothesis %d", a->altHypothesis);
+    if (!(a->alpha > 0.0 && a->alpha < 1.0)) return capi_fail(DSQ_ERR_ARG, "alpha = %g must lie in (0, 1)", a->alpha);
+    if (!(a->lfcThreshold >= 0.0)) return capi_fail(DSQ_ERR_ARG, "lfcThreshold = %g must be >= 0", a->lfcThreshold);
+    if (a->lfcThreshold == 0.0 && a->altHypothesis == DSQ_ALT_LESS_ABS)
+        return capi_fail(DSQ_ERR_ARG, "altHypothesis lessAbs needs a positive lfcThreshold");
+    if (a->test == DSQ_TEST_LRT && !(a->lfcThreshold == 0.0 && a->altHypothesis == DSQ_ALT_GREATER_ABS))
+        return capi_fail(DSQ_ERR_ARG, "tests of log fold change above or below a threshold must be Wald tests");
+    if (a->independentFiltering) {
+        if (a->K < 2 || a->K > DSQ_RESULTS_MAX_K) return capi_fail(DSQ_ERR_ARG, "K = %d thresholds: 2 .. %d", a->K, DSQ_RESULTS_MAX_K);
+        if (!a->theta) return capi_fail(DSQ_ERR_ARG, "NULL theta");
+    } else if (a->K != 1) return capi_fail(DSQ_ERR_ARG, "K = %d: independentFiltering = 0 takes K = 1", a->K);
+    return DSQ_OK;
+}
+
+int results_dev_locked(const DsqResultsArgs *a, const DsqResultsOut *o, hipStream_t st) {
+    if (int rc = results_check(a, o)) return rc;
+    const size_t sortb = results_sort_workspace_bytes(a->n);
+    const size_t need = sortb + (o->filtPadj ? 0 : (size_t)a->n * a->K * 8);
+    if (!a->workspace || a->workspace_bytes < (int64_t)need)
+        return capi_fail(DSQ_ERR_ARG, "workspace of %lld bytes: %zu are needed (dsq_results_workspace_bytes)", (long long)a->workspace_bytes, need);
+    if (int rc = capi_check_device()) return rc;
+    ResultsKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.p = a->p; kp.c = a->c;
+    kp.lrt = a->test == DSQ_TEST_LRT;
+    kp.alt = a->altHypothesis;
+    kp.threshold = !(a->lfcThreshold == 0.0 && a->altHypothesis == DSQ_ALT_GREATER_ABS);      // R/results.R:464
+    kp.T = a->lfcThreshold; kp.alpha = a->alpha;
+    kp.beta = a->beta; kp.betaSE = a->betaSE; kp.stat = a->stat; kp.pvalue = a->pvalue; kp.baseMean = a->baseMean;
+    kp.replace = a->replace; kp.na_mask = a->na_mask;
+    kp.filter = a->filter ? a->filter : a->baseMean;
+    kp.theta = a->independentFiltering ? a->theta : nullptr;
+    kp.K = a->K;
+    kp.o_baseMean = o->baseMean; kp.o_lfc = o->log2FoldChange; kp.o_se = o->lfcSE; kp.o_stat = o->stat; kp.o_pvalue = o->pvalue;
+    kp.filtPadj = o->filtPadj ? o->filtPadj : (double *)((char *)a->workspace + sortb);
+    kp.numRej = o->numRej; kp.cutoffs = o->cutoffs; kp.status = o->status;
+    capi_prof_begin("results", a->n, st);
+    DSQ_HIP(launch_results(kp, a->workspace, st));
+    capi_prof_end(st);
+    return DSQ_OK;
+}
+
 }  // namespace dsq
 
 using namespace dsq;
@@ -838,6 +891,7 @@ DSQ_DEV(dsq_size_factors_dev, DsqSizeFactorArgs, const DsqSizeFactorOut *, size_
 DSQ_DEV(dsq_vst_dev, DsqVstArgs, const DsqVstOut *, vst_dev_locked(a, o, true, false, st))
 DSQ_DEV(dsq_vst_rowstats_dev, DsqVstArgs, const DsqVstOut *, vst_dev_locked(a, o, false, true, st))
 DSQ_DEV(dsq_rlog_dev, DsqRlogArgs, const DsqRlogOut *, rlog_dev_locked(a, o, st))
+DSQ_DEV(dsq_results_dev, DsqResultsArgs, const DsqResultsOut *, results_dev_locked(a, o, st))
 #undef DSQ_DEV
 int dsq_linear_mu_dev(const DsqPrefitArgs *a, double mu_floor, double *mu, void *s) {
     return dev_entry(s, [&](hipStream_t st) { return linear_mu_dev_locked(a, mu_floor, mu, st); });
@@ -859,6 +913,12 @@ int dsq_parametric_dispersion_fit_dev(const double *means, const double *disps, 
 int64_t dsq_size_factors_workspace_bytes(int32_t n, int32_t m) {
     if (n < 0 || m < 0) return 0;
     return (int64_t)size_factors_workspace_bytes(n, m);
+}
+
+int64_t dsq_results_workspace_bytes(int32_t n, int32_t K) {
+    if (n < 0 || K < 0) return 0;
+    const size_t sortb = results_sort_workspace_bytes(n);
+    return (int64_t)(((sortb + 7) & ~(size_t)7) + (size_t)n * K * 8);
 }
 
 int dsq_weights_prep_dev(const double *weights_raw, const double *x, int32_t n, int32_t m, int32_t p, int64_t ld,

@@ -47,6 +47,7 @@ int check_replace(const DsqReplaceArgs *a, const DsqReplaceOut *o);
 int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o);
 int vst_check(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats);
 int rlog_check(const DsqRlogArgs *a, const DsqRlogOut *o);
+int results_check(const DsqResultsArgs *a, const DsqResultsOut *o);
 int check_host_layout(int layout);
 // the device-pointer bodies behind the entry points
 int fit_beta_dev_locked(const DsqFitBetaArgs *a, const DsqFitBetaOut *o, hipStream_t st);
@@ -61,5 +62,6 @@ int replace_dev_locked(const DsqReplaceArgs *a, const DsqReplaceOut *o, hipStrea
 int size_factors_dev_locked(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o, hipStream_t st);
 int vst_dev_locked(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats, hipStream_t st);
 int rlog_dev_locked(const DsqRlogArgs *a, const DsqRlogOut *o, hipStream_t st);
+int results_dev_locked(const DsqResultsArgs *a, const DsqResultsOut *o, hipStream_t st);
 
 }  // namespace dsq

@@ -800,4 +800,52 @@ int dsq_rlog(const DsqRlogArgs *a, const DsqRlogOut *o) {
     return DSQ_OK;
 }
 
+
+int dsq_results(const DsqResultsArgs *a, const DsqResultsOut *o) {
+    const auto check = [&]() -> int {
+        if (int rc = results_check(a, o)) return rc;
+        if (!o->filtPadj) return capi_fail(DSQ_ERR_ARG, "NULL filtPadj");
+        if (!a->independentFiltering) return DSQ_OK;
+        const double *f = a->filter ? a->filter : a->baseMean;
+        for (int32_t i = 0; i < a->n; i++)
+            if (f[i] != f[i]) return capi_fail(DSQ_ERR_ARG, "filter[%d] is NaN", i);
+        for (int32_t k = 0; k < a->K; k++)
+            if (!(a->theta[k] >= 0.0 && a->theta[k] <= 1.0)) return capi_fail(DSQ_ERR_ARG, "theta[%d] = %g outside [0, 1]", k, a->theta[k]);
+        return DSQ_OK;
+    };
+    HostCall hc;
+    DSQ_TRY(host_ready(check(), DSQ_LAYOUT_R));
+    hipStream_t st = hc.st;
+    const size_t n = a->n, p = a->p, K = a->K;
+    const size_t tcols = a->test == DSQ_TEST_LRT ? 1 : p;
+    DsqResultsArgs d = *a;
+    DsqResultsOut od = *o;
+    Stage s(st, n);
+    DSQ_TRY(s.table_up(WS_H_MU, &d.beta, a->beta, 8, n, p));
+    DSQ_TRY(s.table_up(WS_H_W, &d.betaSE, a->betaSE, 8, n, p));
+    DSQ_TRY(s.table_up(WS_H_NF, &d.stat, a->stat, 8, n, tcols));
+    DSQ_TRY(s.table_up(WS_H_Y, &d.pvalue, a->pvalue, 8, n, tcols));
+    s.vec(&d.baseMean, a->baseMean, n * 8);
+    s.vec(&d.replace, a->replace, n * 4);
+    s.vec(&d.na_mask, a->na_mask, n * 4);
+    s.vec(&d.filter, a->filter, n * 8);
+    if (a->independentFiltering) s.vec(&d.theta, a->theta, K * 8);
+    DSQ_TRY(s.pack_in());
+    const size_t wsb = results_sort_workspace_bytes(a->n);
+    DSQ_TRY(capi_ws_get(WS_SCRATCH, wsb, &d.workspace));
+    d.workspace_bytes = (int64_t)wsb;
+    s.out_gene_vec(&od.baseMean, o->baseMean);
+    s.out_gene_vec(&od.log2FoldChange, o->log2FoldChange);
+    s.out_gene_vec(&od.lfcSE, o->lfcSE);
+    s.out_gene_vec(&od.stat, o->stat);
+    s.out_gene_vec(&od.pvalue, o->pvalue);
+    s.out_vec(&od.numRej, o->numRej, K * 4);
+    s.out_vec(&od.cutoffs, o->cutoffs, K * 8);
+    s.out_vec(&od.status, o->status, 4, 8);
+    DSQ_TRY(s.pack_out());
+    DSQ_TRY(s.out_mat(WS_H_OUTMAT, &od.filtPadj, o->filtPadj, K));
+    DSQ_TRY(results_dev_locked(&d, &od, st));
+    return s.finish();
+}
+
 }  // extern "C"

@@ -259,6 +259,31 @@ struct RlogKernelParams {
 };
 hipError_t launch_rlog(const RlogKernelParams &kp, int y_f64, hipStream_t st);
 
+// results() (results.hip): the table of one coefficient, the threshold tests, and the Benjamini-
+// Hochberg adjustment over K nested filter subsets from ONE sort of the p-values.  n-vectors and n x p column-major
+// matrices; the second block is carved from the caller's workspace by launch_results.
+struct ResultsKernelParams {
+    int n, p, c;                 // genes, design columns, the coefficient
+    int lrt;                     // stat / pvalue are the n-vectors LRTStatistic / LRTPvalue (else n x p, column c)
+    int alt;                     // DSQ_ALT_* of the public header; threshold: stat / pvalue are recomputed from LFC, SE, T
+    int threshold;
+    double T, alpha;
+    const double *beta, *betaSE, *stat, *pvalue, *baseMean;
+    const int32_t *replace, *na_mask;   // n flags or nullptr
+    const double *filter;        // n (baseMean when the caller gave none)
+    const double *theta;         // K quantile levels, or nullptr: no filtering (K = 1, every non-NA p-value adjusted)
+    int K;
+    double *o_baseMean, *o_lfc, *o_se, *o_stat, *o_pvalue;   // n each
+    double *filtPadj;            // n x K column-major
+    int32_t *numRej;             // K
+    double *cutoffs;             // K
+    int32_t *status;             // bit 0: NaN in filter, bit 1: a theta outside [0, 1]
+    unsigned long long *keyA, *keyB;
+    unsigned int *rowA, *rowB, *hist, *counters;
+};
+hipError_t launch_results(ResultsKernelParams kp, void *workspace, hipStream_t st);
+size_t results_sort_workspace_bytes(long n);     // the sort's part; filtPadj (n K doubles) may follow it
+
 // gene index of work item i, and the number of work items, of a (possibly row-listed) launch
 #define DSQ_NWORK(kp) ((kp).n_dev ? *(kp).n_dev : (kp).n)
 #define DSQ_GENE(kp, i) ((kp).rows ? (kp).rows[i] : (i))

@@ -37,14 +37,6 @@ DSQ_DEV double sf_exp(double v) {
     if (v == -kInf) return 0.0;
     return dexp(v);
 }
-// f64 -> u64 whose unsigned order is the numeric order (no NaN reaches it), and back
-DSQ_DEV unsigned long long sf_key(double d) {
-    const unsigned long long b = d2bits(d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-DSQ_DEV double sf_unkey(unsigned long long k) {
-    return bits2d((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k);
-}
 
 template <typename T>
 DSQ_DEV double sf_count(const SizeFactorKernelParams &kp, long i, long j) {
@@ -123,7 +115,7 @@ __global__ void __launch_bounds__(256) sf_hist_kernel(SizeFactorKernelParams kp,
         if (!live) continue;
         const double v = sf_value<T>(kp, i, j);
         if (!(v > 0.0)) continue;
-        const unsigned long long key = sf_key(sf_log(v) - lgm);
+        const unsigned long long key = order_key(sf_log(v) - lgm);
         if (pass == 0 || ((key ^ prefix) >> (shift + 8)) == 0ull)
             atomicAdd(&hist[(unsigned)((key >> shift) & 255ull) * 64u + lane], 1u);
         if (hi_pending && ((key ^ hiprefix) >> hishift) == 0ull && key < himin) himin = key;
@@ -190,10 +182,10 @@ __global__ void __launch_bounds__(1024) sf_finish_kernel(SizeFactorKernelParams 
         double sf;
         if (c == 0u) sf = dnan();                                          // median(numeric(0)) is NA
         else {
-            const double a = sf_unkey(kp.prefix[j]);
+            const double a = order_unkey(kp.prefix[j]);
             double med = a;
             if ((c & 1u) == 0u) {
-                const double b = kp.histate[j] == 2u ? sf_unkey(kp.hikey[j]) : a;
+                const double b = kp.histate[j] == 2u ? order_unkey(kp.hikey[j]) : a;
                 med = (a + b) * 0.5;
             }
             sf = sf_exp(med);

@@ -152,6 +152,25 @@ def spline_eval(table, u):
     return y[i] + dx * (b[i] + dx * (c[i] + dx * d[i]))
 
 
+class ResultColumns:
+    """The columns of a results table where the engine made them (numpy arrays on the host engine, device vectors on the
+    device engine): column(name) brings one to the host when it is asked for.  After filtered_p: numRej, cutoffs (host,
+    K values each) and padj_column(j)."""
+    numRej = cutoffs = _padj = None
+
+    def __init__(self, cols, fetch=None):
+        self.resident, self._fetch, self._hostcols = cols, fetch, {}
+
+    def column(self, name):
+        if name not in self._hostcols:
+            v = self.resident[name]
+            self._hostcols[name] = np.asarray(v) if self._fetch is None else self._fetch(v)
+        return self._hostcols[name]
+
+    def padj_column(self, j):
+        return np.array(self._padj(int(j)), copy=True)
+
+
 class HostEngine:
     name = "host"
 
@@ -387,6 +406,28 @@ class HostEngine:
     def two_sided_normal_p(self, z):
         """2 * pnorm(abs(z), lower.tail = FALSE), R/core.R:1507 (Cody's algorithm as in R's pnorm, engine arithmetic)"""
         return self.fns.unary("pnorm_upper2", np.asarray(z, np.float64))
+
+    # ---- results() (R/results.R:443-575, 638-740; DESIGN.md section 13): the numpy statement of csrc/results.hip
+    def results_table(self, lfc, se, stat, pvalue, baseMean, replace=None, na_mask=None, lfcThreshold=0.0,
+                      altHypothesis="greaterAbs"):
+        """the five columns of one coefficient (n-vectors in): threshold tests, pvalue NA where na_mask, the nowZero fill"""
+        from . import results_host as R
+        return ResultColumns(R.results_table(self.vexp, lfc, se, stat, pvalue, baseMean, replace, na_mask, lfcThreshold,
+                                             altHypothesis))
+
+    def filtered_p(self, tab, filter=None, theta=None, alpha=0.1):
+        """BH-adjusted p-values of `tab` over filter >= quantile(filter, theta), one column per theta (theta None: one
+        column, no filtering); sets filtPadj / numRej / cutoffs on tab and returns it"""
+        from . import results_host as R
+        f = tab.column("baseMean") if filter is None else filter
+        fp, tab.numRej, tab.cutoffs = R.filtered_p(f, tab.column("pvalue"), theta, alpha)
+        tab._padj = lambda j: fp[:, j]
+        return tab
+
+    def results(self, lfc, se, stat, pvalue, baseMean, replace=None, na_mask=None, lfcThreshold=0.0,
+                altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1):
+        return self.filtered_p(self.results_table(lfc, se, stat, pvalue, baseMean, replace, na_mask, lfcThreshold,
+                                                  altHypothesis), filter, theta, alpha)
 
     # ---- count outliers (R/core.R:2333-2359, 2069-2115)
     def cooks_distance(self, y, nf, mu, H, x):
@@ -754,6 +795,40 @@ class DeviceEngine:
 
     def two_sided_normal_p(self, z):
         return self.native.unary("pnorm_upper2", np.asarray(z, np.float64))
+
+    # ---- results(): HIP kernels (csrc/results.hip) on resident columns; nothing but K cutoffs and counts comes back
+    def results(self, lfc, se, stat, pvalue, baseMean, replace=None, na_mask=None, lfcThreshold=0.0,
+                altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1):
+        t = self.torch
+        col = lambda v: v if t.is_tensor(v) else self._vec(v)
+        flag = lambda v: None if v is None else t.as_tensor(np.ascontiguousarray(np.asarray(v) == 1, dtype=np.int32), device=self.device)
+        n = int(np.shape(baseMean)[0])
+        r = self._timed("results", n, lambda: self.native.results_dev(
+            col(lfc), col(se), col(stat), col(pvalue), col(baseMean), 0, replace=flag(replace), na_mask=flag(na_mask),
+            test="Wald", lfcThreshold=lfcThreshold, altHypothesis=altHypothesis, filter=None if filter is None else col(filter),
+            theta=None if theta is None else self._vec(theta), alpha=alpha))
+        cutoffs, numRej, status = self.native.results_small(self._host(r["_small"]).numpy(), r["K"])
+        if status & 1:
+            raise ValueError("filter holds NA")
+        if status & 2:
+            raise ValueError("theta must lie in [0, 1]")
+        tab = ResultColumns({k: r["table"][i] for i, k in enumerate(("baseMean", "log2FoldChange", "lfcSE", "stat", "pvalue"))},
+                            fetch=lambda v: self._host(v).numpy())
+        tab.numRej, tab.cutoffs = numRej, cutoffs
+        tab._padj = lambda j: self._host(r["filtPadj"][j]).numpy()
+        return tab
+
+    def results_table(self, lfc, se, stat, pvalue, baseMean, replace=None, na_mask=None, lfcThreshold=0.0,
+                      altHypothesis="greaterAbs"):
+        """(the same launch with one unfiltered column: the table comes with p.adjust(pvalue, "BH"))"""
+        return self.results(lfc, se, stat, pvalue, baseMean, replace, na_mask, lfcThreshold, altHypothesis)
+
+    def filtered_p(self, tab, filter=None, theta=None, alpha=0.1):
+        c = tab.resident
+        new = self.results(c["log2FoldChange"], c["lfcSE"], c["stat"], c["pvalue"], c["baseMean"], filter=filter, theta=theta,
+                           alpha=alpha)
+        tab.numRej, tab.cutoffs, tab._padj = new.numRej, new.cutoffs, new._padj
+        return tab
 
     # ---- count outliers: HIP kernels (csrc/outlier.hip)
     def cooks_distance(self, y, nf, mu, H, x):

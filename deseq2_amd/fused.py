@@ -672,6 +672,7 @@ def DESeq(dds, test="Wald", fitType="parametric", reduced=None, minReplicatesFor
             mc["MLE_beta"] = hmle.T
             dds.attrs.update(betaPriorVar=bpv, modelMatrixType=run.prior[1], factors=kw.get("factors"))
         dds.attrs.update(betaPrior=run.prior is not None, test=test, dispModelMatrix=np.asarray(dds.x, np.float64), fused=True,
+                         useT=bool(kw.get("useT")),
                          status={**st, **{k: v for k, v in st2.items() if k.startswith(("N_REPLACE", "N_REFIT")) or k.endswith("_REFIT")}})
         if run.do_replace:
             dds.attrs["replaceable"] = run.replaceable.astype(bool)

@@ -955,3 +955,80 @@ def replaceOutliers_dev(y, nf, cooks, cooksCutoff, replaceable, trim=0.2, nf_is_
     out = L.DsqReplaceOut(newCounts=_t_ptr(newc), replace=_t_ptr(flag))
     L.check(L.lib().dsq_replace_outliers_dev(C.byref(args), C.byref(out), _stream()))
     return {"counts": GeneMajor(newc, m), "replace": flag}
+
+
+def _results_scalars(test, lfcThreshold, altHypothesis, theta):
+    if test not in L.DSQ_TEST:
+        raise ValueError("test should be 'Wald' or 'LRT'")
+    if altHypothesis not in L.DSQ_ALT:
+        raise ValueError("altHypothesis should be one of %s" % ", ".join(L.DSQ_ALT))
+    K = 1 if theta is None else int(len(theta))
+    return dict(test=L.DSQ_TEST[test], lfcThreshold=float(lfcThreshold), altHypothesis=L.DSQ_ALT[altHypothesis],
+                independentFiltering=int(theta is not None), K=K)
+
+
+def results(beta, betaSE, stat, pvalue, baseMean, coef, replace=None, na_mask=None, test="Wald", lfcThreshold=0.0,
+            altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1):
+    """dsq_results on host arrays: the table of coefficient `coef`, the threshold tests, and the Benjamini-Hochberg
+    adjustment over the nested subsets filter >= quantile(filter, theta) (theta None: independentFiltering = FALSE, one
+    column).  beta / betaSE: n x p; stat / pvalue: n x p (Wald) or n (LRT).  Returns the five columns, filtPadj (n x K),
+    numRej, cutoffs."""
+    beta, betaSE = _fcol(beta), _fcol(betaSE)
+    if beta.ndim == 1:
+        beta, betaSE = beta.reshape(-1, 1, order="F"), betaSE.reshape(-1, 1, order="F")
+    n, p = beta.shape
+    stat, pvalue = _fcol(stat), _fcol(pvalue)
+    sc = _results_scalars(test, lfcThreshold, altHypothesis, theta)
+    K = sc["K"]
+    bm = np.ascontiguousarray(baseMean, dtype=np.float64)
+    flags = lambda v: None if v is None else np.ascontiguousarray(np.asarray(v) == 1, dtype=np.int32)
+    rep, na = flags(replace), flags(na_mask)
+    f = None if filter is None else np.ascontiguousarray(filter, dtype=np.float64)
+    th = None if theta is None else np.ascontiguousarray(theta, dtype=np.float64)
+    cols = {k: np.zeros(n) for k in ("baseMean", "log2FoldChange", "lfcSE", "stat", "pvalue")}
+    fp = np.zeros((n, K), order="F")
+    nr, cut, st = np.zeros(K, dtype=np.int32), np.zeros(K), np.zeros(1, dtype=np.int32)
+    a = L.DsqResultsArgs(n=n, p=p, c=int(coef), beta=_ptr(beta), betaSE=_ptr(betaSE), stat=_ptr(stat), pvalue=_ptr(pvalue),
+                         baseMean=_ptr(bm), replace=_ptr(rep), na_mask=_ptr(na), filter=_ptr(f), theta=_ptr(th),
+                         alpha=float(alpha), workspace=None, workspace_bytes=0, **sc)
+    o = L.DsqResultsOut(filtPadj=_ptr(fp), numRej=_ptr(nr), cutoffs=_ptr(cut), status=_ptr(st),
+                        **{k: _ptr(v) for k, v in cols.items()})
+    L.check(L.lib().dsq_results(C.byref(a), C.byref(o)))
+    cols.update(filtPadj=fp, numRej=nr, cutoffs=cut)
+    return cols
+
+
+def results_dev(beta, betaSE, stat, pvalue, baseMean, coef, replace=None, na_mask=None, test="Wald", lfcThreshold=0.0,
+                altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1):
+    """dsq_results_dev on resident columns: beta / betaSE (p, n) tensors (= n x p column-major), stat / pvalue the same or
+    n-vectors (LRT), baseMean / filter n-vectors (float64), replace / na_mask int32 n-vectors, theta a K-vector -- all on
+    the device.  Nothing is read back: the five columns (rows of `table`), filtPadj (K, n): row k is the column of cutoff
+    k, and `_small` = cutoffs (K) | numRej (K int32, in ceil(K / 2) doubles) | status, for one copy."""
+    import torch
+    p, n = (1, beta.numel()) if beta.dim() == 1 else beta.shape
+    dev = beta.device
+    sc = _results_scalars(test, lfcThreshold, altHypothesis, theta)
+    K = sc["K"]
+    table = torch.empty((5, n), dtype=torch.float64, device=dev)
+    fp = torch.empty((K, n), dtype=torch.float64, device=dev)
+    kr = (K + 1) // 2
+    small = torch.zeros(K + kr + 1, dtype=torch.float64, device=dev)
+    wsb = int(L.lib().dsq_results_workspace_bytes(n, 0))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    a = L.DsqResultsArgs(n=n, p=p, c=int(coef), beta=_t_ptr(beta), betaSE=_t_ptr(betaSE), stat=_t_ptr(stat),
+                         pvalue=_t_ptr(pvalue), baseMean=_t_ptr(baseMean), replace=_t_ptr(replace), na_mask=_t_ptr(na_mask),
+                         filter=_t_ptr(filter), theta=_t_ptr(theta), alpha=float(alpha), workspace=_t_ptr(ws),
+                         workspace_bytes=wsb, **sc)
+    base = small.data_ptr()
+    o = L.DsqResultsOut(baseMean=_t_ptr(table[0]), log2FoldChange=_t_ptr(table[1]), lfcSE=_t_ptr(table[2]),
+                        stat=_t_ptr(table[3]), pvalue=_t_ptr(table[4]), filtPadj=_t_ptr(fp), cutoffs=C.c_void_p(base),
+                        numRej=C.c_void_p(base + 8 * K), status=C.c_void_p(base + 8 * (K + kr)))
+    L.check(L.lib().dsq_results_dev(C.byref(a), C.byref(o), _stream()))
+    # (the workspace is stream-ordered scratch: torch's caching allocator hands it out again only to work enqueued later)
+    return {"table": table, "filtPadj": fp, "_small": small, "K": K}
+
+
+def results_small(small, K):
+    """(cutoffs, numRej, status) from the host copy of results_dev's `_small`"""
+    kr = (K + 1) // 2
+    return small[:K].copy(), small[K:K + kr].view(np.int32)[:K].copy(), int(small[K + kr:].view(np.int32)[0])

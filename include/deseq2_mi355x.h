@@ -685,6 +685,56 @@ typedef struct {
 int dsq_rlog_dev(const DsqRlogArgs *args, const DsqRlogOut *out, void *stream);
 int dsq_rlog(const DsqRlogArgs *args, const DsqRlogOut *out);
 
+/* ---- dsq_results: results() for one coefficient (R/results.R:443-575, 638-740) -------------------
+ * The table -- baseMean, log2FoldChange, lfcSE, stat, pvalue of design column c --, the threshold tests of :484-515 under
+ * the normal distribution, pvalue NA where na_mask is set (the Cook's filter of :520-564 is the caller's: a host decision
+ * over a handful of rows), the nowZero fill of :567-575, then independent filtering: cutoffs = quantile(filter, theta)
+ * (type 7), filtPadj[, k] = p.adjust(pvalue[filter >= cutoffs[k]], "BH") for all K cutoffs from ONE radix sort of the
+ * p-values, numRej[k] = sum(filtPadj[, k] < alpha, na.rm = TRUE).  Which column becomes padj (the lowess rule of :661-692)
+ * is the caller's decision over K numbers.  independentFiltering = 0: K = 1, theta ignored, filtPadj is p.adjust(pvalue, "BH").
+ * NA is NaN.  BH is global over the genes: nothing here is sharded, dsq_results runs on ONE device.
+ * Wald: beta, betaSE, stat, pvalue are n x p column-major and column c is read; LRT: stat / pvalue are the n-vectors
+ * LRTStatistic / LRTPvalue.  A threshold test (lfcThreshold > 0 or altHypothesis != DSQ_ALT_GREATER_ABS) recomputes stat and
+ * pvalue from log2FoldChange and lfcSE and needs test = DSQ_TEST_WALD.
+ * _dev: device pointers (theta too), asynchronous on `stream`, no allocation, no host synchronisation.  What cannot be seen
+ * without reading device memory comes back in *status: bit 0 = NaN in filter, bit 1 = a theta outside [0, 1]; dsq_results
+ * checks both on the host and returns DSQ_ERR_ARG.  workspace: dsq_results_workspace_bytes(n, K) bytes =
+ * dsq_results_workspace_bytes(n, 0) for the sort + n K doubles, where filtPadj lives when out.filtPadj is NULL.        */
+enum { DSQ_TEST_WALD = 0, DSQ_TEST_LRT = 1 };
+enum { DSQ_ALT_GREATER_ABS = 0, DSQ_ALT_LESS_ABS = 1, DSQ_ALT_GREATER = 2, DSQ_ALT_LESS = 3, DSQ_ALT_GREATER_ABS_2014 = 4 };
+#define DSQ_RESULTS_MAX_K 4096
+typedef struct {
+    int32_t n, p, c;               /* genes, design columns, the coefficient 0 .. p-1                                */
+    int32_t test;                  /* DSQ_TEST_*                                                                     */
+    const double *beta, *betaSE;   /* n x p column-major, log2 scale                                                 */
+    const double *stat, *pvalue;   /* Wald: n x p column-major; LRT: n                                               */
+    const double *baseMean;        /* n                                                                              */
+    const int32_t *replace;        /* n (1 = replaced; anything else, NA = -1 included, is not), or NULL             */
+    const int32_t *na_mask;        /* n flags: pvalue <- NA, or NULL                                                 */
+    double lfcThreshold;           /* >= 0                                                                           */
+    int32_t altHypothesis;         /* DSQ_ALT_*                                                                      */
+    int32_t independentFiltering;  /* 0: K must be 1                                                                 */
+    const double *filter;          /* n, or NULL = baseMean; no NaN                                                  */
+    const double *theta;           /* K quantile levels in [0, 1] (independentFiltering = 0: ignored, may be NULL)   */
+    int32_t K;                     /* 2 .. DSQ_RESULTS_MAX_K, or 1 with independentFiltering = 0                     */
+    double alpha;                  /* in (0, 1)                                                                      */
+    void *workspace;               /* device; dsq_results: ignored                                                   */
+    int64_t workspace_bytes;
+} DsqResultsArgs;
+
+typedef struct {
+    double *baseMean, *log2FoldChange, *lfcSE, *stat, *pvalue;   /* n each                                           */
+    double *filtPadj;              /* n x K column-major (one cutoff = one contiguous column); _dev: NULL = in the workspace */
+    int32_t *numRej;               /* K                                                                              */
+    double *cutoffs;               /* K (independentFiltering = 0: -Inf)                                             */
+    int32_t *status;               /* 1 value, see above                                                             */
+} DsqResultsOut;
+
+int dsq_results_dev(const DsqResultsArgs *args, const DsqResultsOut *out, void *stream);
+/* host pointers, one device, synchronous */
+int dsq_results(const DsqResultsArgs *args, const DsqResultsOut *out);
+int64_t dsq_results_workspace_bytes(int32_t n, int32_t K);
+
 /* ---- dsq_deseq: DESeq() behind ONE host-pointer call ------------------------------------------------------------
  * What an R session binds as .Call("_DESeq2_mi355x_DESeq", ...) in place of the body of DESeq() between
  * estimateSizeFactors (dsq_size_factors above) and the final bookkeeping (R/core.R:388-426: estimateDispersions -> nbinomWaldTest / nbinomLRT
