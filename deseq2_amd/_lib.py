@@ -290,7 +290,7 @@ DSQ_ST = {k: i for i, k in enumerate((
     "N_NONZERO", "N_GRID_GENEEST", "N_TREND", "TREND_STATUS", "N_ABOVE_MIN", "N_GRID_MAP", "N_OPTIM_GENEEST",
     "N_OPTIM_TEST", "N_REPLACE", "N_REFIT", "N_GRID_GENEEST_REFIT", "N_GRID_MAP_REFIT", "N_OPTIM_GENEEST_REFIT",
     "N_OPTIM_TEST_REFIT"))}
-DSQ_SC_FIT_USED = 4
+DSQ_SC_COEF0, DSQ_SC_COEF1, DSQ_SC_VAR_LOG_DISP, DSQ_SC_DISP_PRIOR_VAR, DSQ_SC_FIT_USED = 0, 1, 2, 3, 4
 DSQ_FIT = {"parametric": 0, "mean": 1, "parametric_or_mean": 2, "given": 3}
 DSQ_ST_COUNT, DSQ_SC_COUNT = 16, 8
 

@@ -610,7 +610,7 @@ def trimmed_mean_fit(dge, minDisp=1e-8, trim=0.001):
     """fitType = "mean" (R/core.R:894-899): mean(dispGeneEst[dispGeneEst > 10 minDisp], na.rm = TRUE, trim = 0.001).
     base::mean.default keeps the order statistics floor(N trim) + 1 ... N - floor(N trim) and takes their long-double
     mean with a correction pass -- to double precision the correctly rounded mean.  The specification shared with the
-    chain's kernel (csrc/pipeline.hip: trend_mean_kernel): every kept value as the integer floor(x 2^128), the exact
+    chain's kernel (csrc/trend.hip: trend_mean_kernel): every kept value as the integer floor(x 2^128), the exact
     integer sum, the quotient rounded once to nearest-even -- Python integers here."""
     import math
     with np.errstate(invalid="ignore"):

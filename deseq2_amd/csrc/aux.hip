@@ -378,138 +378,6 @@ __global__ void __launch_bounds__(256) intercept_fit_kernel(InterceptKernelParam
     }
 }
 
-// ---- parametricDispersionFit (R/core.R:2166-2190) -----------------------------------------
-// The all-gene step between the two dispersion passes: a Gamma-GLM (identity link) IRLS for
-// disp ~ a0 + a1/mean inside the reference's outlier-filter loop.  It touches only two n-vectors,
-// but every rank of a multi-GPU run fits it over ALL gathered genes (DESeqParallel, R/parallel.R:27),
-// so it must not grow with the node: kTrendBlocks workgroups of 16 wavefronts keep the whole nested
-// loop on the device (no host round trip per iteration) and meet at a grid barrier per reduction.
-// Sums in BLOCK ORDER (the oracle's bsum): partial q = i mod 16384 -> (block, wave, lane); wave
-// butterfly; the 16 wave sums of a block added in order; the 16 block sums added in order.  Every
-// block reads the same block sums in the same order, so all blocks take identical branches.
-static constexpr int kTrendBlocks = 16;
-
-struct TrendWs {
-    unsigned int count, gen;
-    unsigned int pad[14];
-    unsigned long long sums[2][kTrendBlocks][8];   // bit patterns of doubles, double-buffered by parity
-};
-
-__device__ __forceinline__ void grid_barrier(TrendWs *ws) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned g = __hip_atomic_load(&ws->gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();
-        unsigned arrived = atomicAdd(&ws->count, 1u);
-        if (arrived == (unsigned)kTrendBlocks - 1u) {
-            atomicExch(&ws->count, 0u);
-            __threadfence();
-            atomicAdd(&ws->gen, 1u);
-        } else {
-            while (__hip_atomic_load(&ws->gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g) __builtin_amdgcn_s_sleep(2);
-        }
-        __threadfence();
-    }
-    __syncthreads();
-}
-
-template <int K>
-__device__ __forceinline__ void grid_sum(double (&v)[K], double (*red)[8], TrendWs *ws, int &parity) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    wave_allreduce_many(v, lane);         // (the bits of K butterflies, dsq_wave.hpp)
-    __syncthreads();                      // previous use of `red` is complete
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; k++) red[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double tot = red[0][threadIdx.x];
-        for (int g = 1; g < 16; g++) tot = tot + red[g][threadIdx.x];
-        __hip_atomic_store(&ws->sums[parity][blockIdx.x][threadIdx.x], (unsigned long long)__double_as_longlong(tot),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    grid_barrier(ws);
-    // the block sums of every workgroup, added in workgroup order: thread k takes sum k -- its 16 loads in flight together
-    // (round 4: every thread used to fetch all K x 16 values itself, two at a time: ~ 60 dependent L2 round trips per pass)
-    // -- and hands the total to the block through LDS
-    if (threadIdx.x < K) {
-        double t[kTrendBlocks];
-#pragma unroll
-        for (int b = 0; b < kTrendBlocks; b++)
-            t[b] = __longlong_as_double((long long)__hip_atomic_load(&ws->sums[parity][b][threadIdx.x], __ATOMIC_RELAXED,
-                                                                    __HIP_MEMORY_SCOPE_AGENT));
-        double tot = t[0];
-#pragma unroll
-        for (int b = 1; b < kTrendBlocks; b++) tot = tot + t[b];
-        red[0][threadIdx.x] = tot;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; k++) v[k] = red[0][k];
-    parity ^= 1;
-}
-
-__global__ void __launch_bounds__(1024) trend_fit_kernel(const double *means, const double *disps, long n,
-                                                         const int32_t *n_dev, double *coefs_out, int32_t *status_out,
-                                                         TrendWs *ws) {
-    __shared__ double red[16][8];
-    if (n_dev) n = (long)*n_dev;            // fused pipeline: the number of genes in the fit lives on the device
-    const long first = (long)blockIdx.x * 1024 + threadIdx.x, stride = 1024L * kTrendBlocks;
-    int parity = 0;
-    double c0 = 0.1, c1 = 1.0;
-    int iter = 0, status = 0;
-    for (;;) {
-        double b0 = c0, b1 = c1;
-        bool converged = false, invalid = false;
-        double devold = 0.0;
-        // One sweep over the genes and ONE grid reduction per IRLS pass: the deviance sums at the current (b0, b1) and
-        // the normal-equation sums the NEXT pass solves (they are taken at the same (b0, b1)) are accumulated together.
-        // Per sum the same terms in the same order as two separate sweeps give, so the bits are the separate sweeps';
-        // the normal-equation sums of a pass that turns out converged / invalid are simply not used.
-        double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int pass = -1; pass < 25 && !invalid; pass++) {
-            if (pass >= 0) {
-                double det = a[0] * a[2] - a[1] * a[1];
-                b0 = (a[2] * a[3] - a[1] * a[4]) / det;
-                b1 = (a[0] * a[4] - a[1] * a[3]) / det;
-            }
-            double v[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // a[0..5) for the next pass | sum log r, sum (r - 1), # invalid means
-#pragma unroll 1
-            for (long i = first; i < n; i += stride) {
-                double mean = means[i], y = disps[i];
-                double res = y / (c0 + c1 / mean);
-                if (!((res > 1e-4) && (res < 15.0))) continue;
-                double x = 1.0 / mean;
-                double mu = b0 + b1 * x;
-                double wgt = 1.0 / (mu * mu);
-                double wx = wgt * x;
-                v[0] += wgt; v[1] += wx; v[2] += wx * x; v[3] += wgt * y; v[4] += wx * y;
-                if (!(mu > 0.0)) { v[7] += 1.0; continue; }
-                double r = y / mu;
-                v[5] += dlog(r); v[6] += r - 1.0;
-            }
-            grid_sum<8>(v, red, ws, parity);
-            for (int k = 0; k < 5; k++) a[k] = v[k];
-            if (v[7] > 0.0) { invalid = true; break; }
-            double dev = -2.0 * (v[5] - v[6]);
-            if (pass >= 0 && __builtin_fabs(dev - devold) / (__builtin_fabs(dev) + 0.1) < 1e-8) { converged = true; break; }
-            devold = dev;
-        }
-        if (invalid) { status = 1; break; }
-        double o0 = c0, o1 = c1;
-        c0 = b0; c1 = b1;
-        if (!(c0 > 0.0 && c1 > 0.0)) { status = 1; break; }
-        double l0 = dlog(c0 / o0), l1 = dlog(c1 / o1);
-        if ((l0 * l0 + l1 * l1 < 1e-6) && converged) break;
-        iter++;
-        if (iter > 10) { status = 2; break; }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { coefs_out[0] = c0; coefs_out[1] = c1; *status_out = status; }
-}
-
-size_t trend_fit_workspace_bytes() { return sizeof(TrendWs); }
-
 // ---- getAndCheckWeights (R/core.R:2697-2751) on resident weights -----------------------------------------------------
 // One wavefront per gene: w / max(w) (:2702), the same floored at 1e-6 for the gene-wise dispersion search (:702), the
 // all(weights >= 0) flag, and the two per-gene rank tests of :2711-2722 on the p x p Gram matrices of w_norm * X and of
@@ -776,32 +644,6 @@ hipError_t launch_xim_flagged(const double *nf, int n, int m, long ld, const int
 hipError_t launch_xim(const double *nf, int n, int m, long ld, double *scratch_m, double *out, hipStream_t st) {
     hipLaunchKernelGGL(xim_kernel, dim3((m + 255) / 256), dim3(256), 0, st, nf, n, m, ld, scratch_m);
     hipLaunchKernelGGL(xim_final_kernel, dim3(1), dim3(64), 0, st, (const double *)scratch_m, m, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_trend_fit(const double *means, const double *disps, long n, double *coefs, int32_t *status,
-                            void *workspace, hipStream_t st) {
-    hipError_t e = hipMemsetAsync(workspace, 0, sizeof(TrendWs), st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(trend_fit_kernel, dim3(kTrendBlocks), dim3(1024), 0, st, means, disps, n, (const int32_t *)nullptr,
-                       coefs, status, (TrendWs *)workspace);
-    return hipGetLastError();
-}
-
-hipError_t launch_trend_fit_dev(const double *means, const double *disps, const int32_t *n_dev, double *coefs,
-                                int32_t *status, void *workspace, hipStream_t st) {
-    hipError_t e = hipMemsetAsync(workspace, 0, sizeof(TrendWs), st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(trend_fit_kernel, dim3(kTrendBlocks), dim3(1024), 0, st, means, disps, 0L, n_dev, coefs, status,
-                       (TrendWs *)workspace);
-    return hipGetLastError();
-}
-
-// ... with the workspace already zeroed by the caller (the chain's one init launch, pipeline.hip)
-hipError_t launch_trend_fit_dev_zeroed(const double *means, const double *disps, const int32_t *n_dev, double *coefs,
-                                       int32_t *status, void *workspace, hipStream_t st) {
-    hipLaunchKernelGGL(trend_fit_kernel, dim3(kTrendBlocks), dim3(1024), 0, st, means, disps, 0L, n_dev, coefs, status,
-                       (TrendWs *)workspace);
     return hipGetLastError();
 }
 

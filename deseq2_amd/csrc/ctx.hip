@@ -37,7 +37,7 @@ const Tuning &tuning() {
                        env_int("DSQ_DISP_LDS_KB", 160), env_int("DSQ_ABLATE", 0), env_int("DSQ_FORCE_ITERS", 0),
                        env_int("DSQ_DISP_XLDS", 1), env_int("DSQ_BETA_XLDS", 1), env_int("DSQ_DYNAMIC", 1),
                        env_int("DSQ_BETA_CELLS", 1), env_int("DSQ_DISP_CELL_MINP", DSQ_DISP_CELL_MINP),
-                       env_int("DSQ_OVERLAP", 1), env_int("DSQ_PRIOR_VAR_ONE_BLOCK", 0), env_int("DSQ_LPT", 1),
+                       env_int("DSQ_OVERLAP", 1), env_int("DSQ_LPT", 1),
                        env_int("DSQ_LPT_MAXN", 16384), env_int("DSQ_LPT_KEY2", 0)};
     return t;
 }

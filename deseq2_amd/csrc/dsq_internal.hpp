@@ -294,9 +294,24 @@ hipError_t launch_prefit(const PrefitKernelParams &kp, hipStream_t st, bool *ok)
 hipError_t launch_linear_mu(const PrefitKernelParams &kp, double mu_floor, double *mu, hipStream_t st, bool *ok);
 hipError_t launch_loglike(const LogLikeKernelParams &kp, hipStream_t st);
 hipError_t launch_intercept_fit(const InterceptKernelParams &kp, hipStream_t st);
+// trend.hip: the trend phase of the chain (DSQ_PH_TREND).  The parametric fit needs trend_fit_workspace_bytes() of device
+// workspace: launch_trend_fit (n on the host) and launch_trend_fit_dev (n on the device) zero it themselves, _zeroed expects
+// it zeroed; launch_prior_var needs prior_var_workspace_bytes(n) ZEROED bytes (0 below the size at which it runs on sixteen
+// workgroups: no workspace then)
 hipError_t launch_trend_fit(const double *means, const double *disps, long n, double *coefs, int32_t *status,
                             void *workspace, hipStream_t st);
+hipError_t launch_trend_fit_dev(const double *means, const double *disps, const int32_t *n_dev, double *coefs,
+                                int32_t *status, void *workspace, hipStream_t st);
+hipError_t launch_trend_fit_dev_zeroed(const double *means, const double *disps, const int32_t *n_dev, double *coefs,
+                                       int32_t *status, void *workspace, hipStream_t st);
 size_t trend_fit_workspace_bytes();
+hipError_t launch_trend_given(double *scalars, int32_t *status, hipStream_t st);
+hipError_t launch_trend_mean(const double *disp, int n, double minDisp, int mode, double *scalars, int32_t *status,
+                             hipStream_t st);
+hipError_t launch_prior_var(const double *mean, const double *disp, int n, double minDisp, double expVarLogDisp, int m_gt_p,
+                            double *resbuf, double *scalars, int32_t *status, const double *fit_in, double pv_in,
+                            void *workspace, hipStream_t st);
+size_t prior_var_workspace_bytes(int n);
 // getAndCheckWeights on resident weights: w / rowmax, pmax(., 1e-6), the weightsFail flags, the negative-weight flag
 hipError_t launch_weights_prep(const double *w_raw, const double *x, int n, int m, int p, long ld, double thr, double *w_norm,
                                double *w_floor, int32_t *force_zero, int32_t *neg, hipStream_t st);
@@ -345,7 +360,6 @@ struct Tuning {
     int disp_cell_minp;      // DSQ_DISP_CELL_MINP (profiling; default = the macro): fitDisp cell mode from this width up
     // the chain (pipeline.hip)
     int overlap;             // DSQ_OVERLAP (default 1): the test's full-row nbinomLogLike on a side stream beside the refit
-    int prior_var_one_block; // DSQ_PRIOR_VAR_ONE_BLOCK (default 0): the one-workgroup prior variance at every size
     int lpt, lpt_maxn;       // DSQ_LPT (default 1), DSQ_LPT_MAXN (16384): longest-expected-first order of the fit_beta rows, up to n
     int lpt_key2;            // DSQ_LPT_KEY2 (default 0) = 1: the test's fit is ordered by baseMean like the gene-wise one
 };

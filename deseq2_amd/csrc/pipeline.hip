@@ -6,8 +6,8 @@
 // (parametricDispersionFit R/core.R:2166-2190, mad of the log residuals R/methods.R:180).  Here each rule is a
 // small elementwise kernel, the rows a rule sends on (fitDispGrid stragglers, replaced-outlier rows) are
 // compacted on the device and fitted by ROW-LISTED launches of the same fit kernels (DispKernelParams::rows /
-// n_dev), and the all-gene steps are single-workgroup kernels, so a phase is one uninterrupted stream of
-// launches: no host decision, no device-to-host copy.  Every formula is evaluated with the operations of the
+// n_dev), and the all-gene steps are kernels of one or sixteen workgroups (trend.hip), so a phase is one uninterrupted
+// stream of launches: no host decision, no device-to-host copy.  Every formula is evaluated with the operations of the
 // host mirror (deseq2_amd/core.py: IEEE + - * / sqrt, the engine's dlog / dexp, numpy's NaN-propagating
 // minimum / maximum), so the results equal the call-by-call chain bit for bit (tests/test_gpu_fused.py).
 #include "capi.hpp"
@@ -21,12 +21,6 @@
 #include <vector>
 
 namespace dsq {
-
-hipError_t launch_trend_fit_dev(const double *means, const double *disps, const int32_t *n_dev, double *coefs,
-                                int32_t *status, void *workspace, hipStream_t st);
-hipError_t launch_trend_fit_dev_zeroed(const double *means, const double *disps, const int32_t *n_dev, double *coefs,
-                                       int32_t *status, void *workspace, hipStream_t st);
-size_t trend_fit_workspace_bytes();
 
 // numpy.minimum / numpy.maximum: NaN if either operand is NaN
 DSQ_DEV double np_min(double a, double b) { return (a != a || b != b) ? a + b : (a < b ? a : b); }
@@ -98,482 +92,6 @@ __global__ void __launch_bounds__(1024) compact_kernel(int mode, int n, int32_t 
         __syncthreads();
     }
     if (t == 0) *count_out = base_s;
-}
-
-// ---- stats::mad of the log dispersion residuals + the prior variance (R/methods.R:172-181, R/core.R:1135-1208) ----
-// Order statistics by radix selection on the order-preserving 64-bit image of the doubles: 8 passes of 8 bits per
-// rank, one workgroup.  A selected order statistic is exact, so the medians equal numpy's.
-DSQ_DEV uint64_t key_of(double d) {
-    uint64_t u = d2bits(d);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
-}
-DSQ_DEV double double_of(uint64_t k) {
-    uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffULL) : ~k;
-    return bits2d(u);
-}
-
-// the rank-th smallest (0-based) of the <= kSelDirect keys in `keys` (LDS), by counting: thread t takes key t and counts the
-// keys that sort before it (smaller, or equal with a smaller index); exactly one thread finds `rank` and publishes its key
-static constexpr int kSelDirect = 1024;       // = hist[2048] reinterpreted as 64-bit keys
-DSQ_DEV uint64_t rank_direct(const uint64_t *keys, int cnt, long rank, unsigned long long *bc) {
-    for (int t = threadIdx.x; t < cnt; t += blockDim.x) {
-        const uint64_t mine = keys[t];
-        int before = 0;
-        for (int j = 0; j < cnt; j++) {
-            const uint64_t o = keys[j];
-            before += (o < mine || (o == mine && j < t)) ? 1 : 0;
-        }
-        if (before == (int)rank) bc[0] = mine;
-    }
-    __syncthreads();
-    const uint64_t r = bc[0];
-    __syncthreads();
-    return r;
-}
-
-template <class F>
-DSQ_DEV double block_select(int n, long rank, F &&value, unsigned *hist, unsigned long long *bc) {
-    // the rank-th smallest (0-based) of value(i), i < n; every thread returns it.  Digits of 11, 11, 11, 11, 11, 9 bits.
-    // (r6) Once the candidates left (the keys that share the digits chosen so far) fit the histogram's LDS -- after two
-    // passes, usually: the first 22 bits of a double leave a handful of 50 000 residuals -- they are gathered there and the
-    // order statistic is taken by direct counting: three passes over the values instead of six, the same (exact) result.
-    uint64_t prefix = 0, mask = 0;
-    int shift = 64;
-    while (shift > 0) {
-        const int bits = shift >= 11 + 9 ? 11 : shift;         // 64 = 5 x 11 + 9
-        shift -= bits;
-        const unsigned nb = 1u << bits;
-        for (unsigned b = threadIdx.x; b < nb; b += blockDim.x) hist[b] = 0;
-        __syncthreads();
-        // (round 4 measured two variants of this pass -- the atomics of lanes that hit the same bin merged by ballot, the
-        //  leading digits of log residuals being few; eight loads in flight per thread -- at 0.41 and 0.25 ms for the
-        //  kernel against 0.24: neither the LDS atomics nor the L2 round trips are what one workgroup spends its time on)
-        for (int i = threadIdx.x; i < n; i += blockDim.x) {
-            uint64_t k = key_of(value(i));
-            if ((k & mask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & (nb - 1u)], 1u);
-        }
-        __syncthreads();
-        // the digit whose cumulative count passes `rank`: one wave scans the bins, 64 at a time
-        if (threadIdx.x < 64) {
-            long r = rank;
-            int found = -1;
-            unsigned inbin = 0;
-            for (unsigned b0 = 0; b0 < nb && found < 0; b0 += 64) {
-                const unsigned h = hist[b0 + threadIdx.x];
-                unsigned incl = h;                              // inclusive prefix over the 64 lanes
-                for (int o = 1; o < 64; o <<= 1) {
-                    unsigned v = __shfl_up(incl, o, 64);
-                    if ((int)threadIdx.x >= o) incl += v;
-                }
-                const unsigned tot = __shfl(incl, 63, 64);
-                if (r < (long)tot) {
-                    const unsigned long long m = __ballot((long)incl > r);
-                    const int l = __ffsll((long long)m) - 1;
-                    const unsigned before = __shfl(incl, l, 64) - __shfl(h, l, 64);
-                    found = (int)b0 + l;
-                    inbin = __shfl(h, l, 64);
-                    r -= (long)before;
-                } else {
-                    r -= (long)tot;
-                }
-            }
-            if (threadIdx.x == 0) { bc[0] = (unsigned long long)(found < 0 ? (int)nb - 1 : found); bc[1] = (unsigned long long)r; bc[2] = found < 0 ? 0ull : inbin; }
-        }
-        __syncthreads();
-        prefix |= (uint64_t)bc[0] << shift;
-        mask |= (uint64_t)(nb - 1u) << shift;
-        rank = (long)bc[1];
-        const unsigned left = (unsigned)bc[2];
-        __syncthreads();
-        if (shift > 0 && left > 0 && left <= (unsigned)kSelDirect) {
-            uint64_t *keys = reinterpret_cast<uint64_t *>(hist);
-            if (threadIdx.x == 0) bc[2] = 0ull;
-            __syncthreads();
-            for (int i = threadIdx.x; i < n; i += blockDim.x) {
-                const uint64_t k = key_of(value(i));
-                if ((k & mask) == prefix) keys[atomicAdd(&bc[2], 1ull)] = k;
-            }
-            __syncthreads();
-            return double_of(rank_direct(keys, (int)left, rank, bc));
-        }
-    }
-    return double_of(prefix);
-}
-
-template <class F>
-DSQ_DEV double block_median(int n, long k, F &&value, unsigned *hist, unsigned long long *bc) {
-    // numpy.median of the k finite values (invalid entries are +inf and sort last): the lower middle order statistic
-    // by selection; for an even count the next one is either the same value (a tie) or the smallest value above it
-    const double a = block_select(n, (k - 1) / 2, value, hist, bc);
-    if (k & 1) return a;
-    __syncthreads();
-    if (threadIdx.x == 0) { bc[0] = 0ull; bc[1] = key_of(__builtin_inf()); }
-    __syncthreads();
-    unsigned long long le = 0, mn = key_of(__builtin_inf());
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const double v = value(i);
-        if (v <= a) le++;
-        else { const unsigned long long kv = key_of(v); if (kv < mn) mn = kv; }
-    }
-    atomicAdd(&bc[0], le);
-    atomicMin(&bc[1], mn);
-    __syncthreads();
-    const double b = ((long)bc[0] > k / 2) ? a : double_of(bc[1]);
-    __syncthreads();
-    return (a + b) * 0.5;
-}
-
-__global__ void __launch_bounds__(1024) prior_var_kernel(const double *mean, const double *disp, int n, double minDisp,
-                                                         double expVarLogDisp, int m_gt_p, double *resbuf,
-                                                         double *scalars, int32_t *status, const double *fit_in,
-                                                         double pv_in) {
-    __shared__ __attribute__((aligned(16))) unsigned hist[2048];
-    __shared__ unsigned long long bc[3];
-    __shared__ int kshared;
-    const double inf = __builtin_inf();
-    const double c0 = scalars[DSQ_SC_COEF0], c1 = scalars[DSQ_SC_COEF1];
-    if (threadIdx.x == 0) kshared = 0;
-    __syncthreads();
-    int c = 0;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        double d = disp[i];
-        bool above = d >= minDisp * 100.0;                       // aboveMinDisp, R/core.R:897 / :1137
-        double r = inf;
-        if (above) {
-            double fit = fit_in ? fit_in[i] : c0 + c1 / mean[i];       // (fit_in: the caller's trend, DSQ_FIT_GIVEN)
-            r = dlog(d) - dlog(fit);
-            c++;
-        }
-        resbuf[i] = r;
-    }
-    atomicAdd(&kshared, c);
-    __syncthreads();
-    const long k = kshared;
-    if (threadIdx.x == 0) status[DSQ_ST_N_ABOVE_MIN] = (int32_t)k;
-    if (k == 0) {
-        if (threadIdx.x == 0) { scalars[DSQ_SC_VAR_LOG_DISP] = dnan(); scalars[DSQ_SC_DISP_PRIOR_VAR] = dnan(); }
-        return;
-    }
-    __threadfence_block();
-    const double med = block_median(n, k, [&](int i) { return resbuf[i]; }, hist, bc);
-    const double med2 = block_median(n, k, [&](int i) {
-        double r = resbuf[i];
-        return (r == inf) ? inf : __builtin_fabs(r - med);
-    }, hist, bc);
-    if (threadIdx.x == 0) {
-        const double mad = 1.4826 * med2;
-        const double v = mad * mad;
-        scalars[DSQ_SC_VAR_LOG_DISP] = v;
-        double pv = v;
-        if (m_gt_p) {
-            const double t = v - expVarLogDisp;
-            pv = (0.25 > t) ? 0.25 : t;                           // max(varLogDispEsts - expVarLogDisp, 0.25), :1200
-        }
-        if (pv_in > 0.0) pv = pv_in;                              // estimateDispersionsMAP(dispPriorVar = x), :989-994
-        scalars[DSQ_SC_DISP_PRIOR_VAR] = pv;
-    }
-}
-
-// ---- the same on SIXTEEN workgroups (round 4): the one-workgroup kernel above spends 0.24 ms on 50 000 genes -- its thirteen
-// selection passes and the two logarithms per gene all on one CU -- and every rank of a gene-sharded run pays it on the
-// gathered vectors.  Here each workgroup histograms its slice, the histograms meet in a global table (one per pass, zeroed
-// by the launch), a grid barrier, and every workgroup scans the table itself: the selected order statistics are exact, so
-// nothing changes in the results.  The workgroups must be co-resident: 16 x 1024 threads on a 256-CU device.
-static constexpr int kSelBlocks = 16;
-struct SelWs {
-    unsigned int count, gen;
-    unsigned int pad[14];
-    unsigned long long cnt[8];
-    unsigned long long inv_min[8];       // ~key of the smallest value above a median candidate (atomicMax; zero = none)
-    unsigned int ghist[16][2048];
-    // (r6) the early exit of a selection: the candidates left after a pass, gathered by all workgroups (one list and one fill
-    // counter per selection: a launch makes two)
-    unsigned long long gfill[2];
-    unsigned long long glist[2][1024];
-};
-size_t prior_var_workspace_bytes() { return sizeof(SelWs); }
-
-DSQ_DEV void sel_barrier(SelWs *ws) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned g = __hip_atomic_load(&ws->gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();
-        unsigned arrived = atomicAdd(&ws->count, 1u);
-        if (arrived == (unsigned)kSelBlocks - 1u) {
-            atomicExch(&ws->count, 0u);
-            __threadfence();
-            atomicAdd(&ws->gen, 1u);
-        } else {
-            while (__hip_atomic_load(&ws->gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g) __builtin_amdgcn_s_sleep(2);
-        }
-        __threadfence();
-    }
-    __syncthreads();
-}
-
-template <class F>
-DSQ_DEV double grid_select(int n, long rank, F &&value, unsigned *hist, unsigned long long *bc, SelWs *ws, int &phase, int slot) {
-    uint64_t prefix = 0, mask = 0;
-    int shift = 64;
-    const long first = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)blockDim.x * kSelBlocks;
-    while (shift > 0) {
-        const int bits = shift >= 11 + 9 ? 11 : shift;         // 64 = 5 x 11 + 9
-        shift -= bits;
-        const unsigned nb = 1u << bits;
-        for (unsigned b = threadIdx.x; b < nb; b += blockDim.x) hist[b] = 0;
-        __syncthreads();
-        for (long i = first; i < n; i += stride) {
-            uint64_t k = key_of(value((int)i));
-            if ((k & mask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & (nb - 1u)], 1u);
-        }
-        __syncthreads();
-        unsigned *gh = ws->ghist[phase];
-        for (unsigned b = threadIdx.x; b < nb; b += blockDim.x) { const unsigned h = hist[b]; if (h) atomicAdd(&gh[b], h); }
-        sel_barrier(ws);
-        for (unsigned b = threadIdx.x; b < nb; b += blockDim.x) hist[b] = __hip_atomic_load(&gh[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            long r = rank;
-            int found = -1;
-            unsigned inbin = 0;
-            for (unsigned b0 = 0; b0 < nb && found < 0; b0 += 64) {
-                const unsigned h = hist[b0 + threadIdx.x];
-                unsigned incl = h;
-                for (int o = 1; o < 64; o <<= 1) {
-                    unsigned v = __shfl_up(incl, o, 64);
-                    if ((int)threadIdx.x >= o) incl += v;
-                }
-                const unsigned tot = __shfl(incl, 63, 64);
-                if (r < (long)tot) {
-                    const unsigned long long m = __ballot((long)incl > r);
-                    const int l = __ffsll((long long)m) - 1;
-                    const unsigned before = __shfl(incl, l, 64) - __shfl(h, l, 64);
-                    found = (int)b0 + l;
-                    inbin = __shfl(h, l, 64);
-                    r -= (long)before;
-                } else {
-                    r -= (long)tot;
-                }
-            }
-            if (threadIdx.x == 0) { bc[0] = (unsigned long long)(found < 0 ? (int)nb - 1 : found); bc[1] = (unsigned long long)r; bc[2] = found < 0 ? 0ull : inbin; }
-        }
-        __syncthreads();
-        prefix |= (uint64_t)bc[0] << shift;
-        mask |= (uint64_t)(nb - 1u) << shift;
-        rank = (long)bc[1];
-        const unsigned left = (unsigned)bc[2];
-        __syncthreads();
-        phase++;
-        // (r6) the candidates left fit one LDS list: every workgroup appends its own to the launch's global list, a grid
-        // barrier, then each workgroup ranks the whole list itself (see block_select) -- the same decision in every
-        // workgroup: `left` comes from the shared histogram
-        if (shift > 0 && left > 0 && left <= (unsigned)kSelDirect) {
-            for (long i = first; i < n; i += stride) {
-                const uint64_t k = key_of(value((int)i));
-                if ((k & mask) == prefix) ws->glist[slot][atomicAdd(&ws->gfill[slot], 1ull)] = k;
-            }
-            sel_barrier(ws);
-            uint64_t *keys = reinterpret_cast<uint64_t *>(hist);
-            for (unsigned t = threadIdx.x; t < left; t += blockDim.x)
-                keys[t] = __hip_atomic_load(&ws->glist[slot][t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __syncthreads();
-            return double_of(rank_direct(keys, (int)left, rank, bc));
-        }
-    }
-    return double_of(prefix);
-}
-
-template <class F>
-DSQ_DEV double grid_median(int n, long k, F &&value, unsigned *hist, unsigned long long *bc, SelWs *ws, int &phase, int slot) {
-    const double a = grid_select(n, (k - 1) / 2, value, hist, bc, ws, phase, slot);
-    if (k & 1) return a;
-    const long first = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)blockDim.x * kSelBlocks;
-    unsigned long long le = 0, inv = 0;
-    for (long i = first; i < n; i += stride) {
-        const double v = value((int)i);
-        if (v <= a) le++;
-        else { const unsigned long long kv = ~key_of(v); if (kv > inv) inv = kv; }
-    }
-    if (le) atomicAdd(&ws->cnt[slot], le);
-    if (inv) atomicMax(&ws->inv_min[slot], inv);
-    sel_barrier(ws);
-    const unsigned long long tot = __hip_atomic_load(&ws->cnt[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long iv = __hip_atomic_load(&ws->inv_min[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const double b = ((long)tot > k / 2) ? a : double_of(~iv);
-    return (a + b) * 0.5;
-}
-
-__global__ void __launch_bounds__(1024) prior_var_grid_kernel(const double *mean, const double *disp, int n, double minDisp,
-                                                              double expVarLogDisp, int m_gt_p, double *resbuf, double *scalars,
-                                                              int32_t *status, const double *fit_in, double pv_in, SelWs *ws) {
-    __shared__ __attribute__((aligned(16))) unsigned hist[2048];
-    __shared__ unsigned long long bc[3];
-    const double inf = __builtin_inf();
-    const double c0 = scalars[DSQ_SC_COEF0], c1 = scalars[DSQ_SC_COEF1];
-    const long first = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)blockDim.x * kSelBlocks;
-    unsigned long long c = 0;
-    for (long i = first; i < n; i += stride) {
-        const double d = disp[i];
-        const bool above = d >= minDisp * 100.0;                 // aboveMinDisp, R/core.R:897 / :1137
-        double r = inf;
-        if (above) {
-            const double fit = fit_in ? fit_in[i] : c0 + c1 / mean[i];
-            r = dlog(d) - dlog(fit);
-            c++;
-        }
-        resbuf[i] = r;                                           // (read back by this thread only)
-    }
-    if (c) atomicAdd(&ws->cnt[7], c);
-    sel_barrier(ws);
-    const long k = (long)__hip_atomic_load(&ws->cnt[7], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
-    if (writer) status[DSQ_ST_N_ABOVE_MIN] = (int32_t)k;
-    if (k == 0) {
-        if (writer) { scalars[DSQ_SC_VAR_LOG_DISP] = dnan(); scalars[DSQ_SC_DISP_PRIOR_VAR] = dnan(); }
-        return;
-    }
-    int phase = 0;
-    const double med = grid_median(n, k, [&](int i) { return resbuf[i]; }, hist, bc, ws, phase, 0);
-    const double med2 = grid_median(n, k, [&](int i) {
-        const double r = resbuf[i];
-        return (r == inf) ? inf : __builtin_fabs(r - med);
-    }, hist, bc, ws, phase, 1);
-    if (writer) {
-        const double mad = 1.4826 * med2;
-        const double v = mad * mad;
-        scalars[DSQ_SC_VAR_LOG_DISP] = v;
-        double pv = v;
-        if (m_gt_p) {
-            const double t = v - expVarLogDisp;
-            pv = (0.25 > t) ? 0.25 : t;                           // max(varLogDispEsts - expVarLogDisp, 0.25), :1200
-        }
-        if (pv_in > 0.0) pv = pv_in;                              // estimateDispersionsMAP(dispPriorVar = x), :989-994
-        scalars[DSQ_SC_DISP_PRIOR_VAR] = pv;
-    }
-}
-
-// ---- fitType = "mean" (R/core.R:894-899): mean(dispGeneEst[dispGeneEst > 10 minDisp], trim = 0.001) ----------------
-// R: the values between the floor(N trim)-th order statistics from either end, then a long-double mean with a
-// correction pass -- to double precision the correctly rounded mean.  Here: the two order statistics by radix selection
-// (exact), the sum of the kept values as a 192-bit integer in units of 2^-128 (exact for every value >= 2^-75, and
-// independent of the order of the additions: a deterministic result without a specified order), the quotient by long
-// division, rounded once to nearest-even.  The mirror (core.py, Python integers) and the oracle restate exactly this.
-struct U192 { uint64_t w[3]; };
-DSQ_DEV void u192_add(U192 &a, const U192 &b) {
-    uint64_t c = 0;
-    for (int k = 0; k < 3; k++) {
-        const uint64_t s = a.w[k] + b.w[k];
-        const uint64_t c1 = s < a.w[k];
-        const uint64_t t = s + c;
-        c = c1 | (uint64_t)(t < s);
-        a.w[k] = t;
-    }
-}
-DSQ_DEV U192 u192_fixed(double x) {           // floor(x 2^128), 0 < x < 2^62 finite
-    const uint64_t u = d2bits(x);
-    int E = (int)((u >> 52) & 0x7ff);
-    uint64_t M = u & ((1ull << 52) - 1ull);
-    if (E) M |= 1ull << 52; else E = 1;
-    const int sh = E - 1075 + 128;
-    U192 r = {{0, 0, 0}};
-    if (sh >= 0) {
-        const int w = sh >> 6, b = sh & 63;
-        if (w < 3) { r.w[w] = M << b; if (b && w + 1 < 3) r.w[w + 1] = M >> (64 - b); }
-    } else if (-sh < 64) r.w[0] = M >> (-sh);
-    return r;
-}
-DSQ_DEV U192 u192_times(double x, unsigned long c) {      // c copies of x (ties at the two cut points)
-    U192 r = {{0, 0, 0}}, v = u192_fixed(x);
-    for (; c; c >>= 1) { if (c & 1ul) u192_add(r, v); U192 d = v; u192_add(v, d); }
-    return r;
-}
-DSQ_DEV double u192_mean(const U192 &S, uint64_t cnt) {   // RN-even(S / cnt) 2^-128 (cnt < 2^32)
-    uint32_t q[6];
-    uint64_t rem = 0;
-    for (int k = 5; k >= 0; k--) {
-        const uint64_t limb = (S.w[k >> 1] >> ((k & 1) * 32)) & 0xffffffffull;
-        const uint64_t cur = (rem << 32) | limb;
-        q[k] = (uint32_t)(cur / cnt);
-        rem = cur % cnt;
-    }
-    int h = -1;
-    for (int k = 5; k >= 0 && h < 0; k--) if (q[k]) h = k * 32 + 31 - __builtin_clz(q[k]);
-    if (h < 0) return 0.0;
-    auto bit_range = [&](int lo, int len) {                // bits [lo, lo + len) of the quotient, len <= 53
-        uint64_t v = 0;
-        for (int b = len - 1; b >= 0; b--) { const int i = lo + b; v = (v << 1) | ((q[i >> 5] >> (i & 31)) & 1u); }
-        return v;
-    };
-    if (h <= 52) return (double)bit_range(0, h + 1) * bits2d((uint64_t)(1023 - 128) << 52);       // (means below 2^-75: truncated)
-    const int shift = h - 52;
-    uint64_t mant = bit_range(shift, 53);
-    const bool half = (q[(shift - 1) >> 5] >> ((shift - 1) & 31)) & 1u;
-    bool below = rem != 0;
-    for (int i = 0; i < shift - 1 && !below; i++) below = (q[i >> 5] >> (i & 31)) & 1u;
-    if (half && (below || (mant & 1ull))) mant++;
-    return (double)mant * bits2d((uint64_t)(1023 + shift - 128) << 52);
-}
-
-// mode DSQ_FIT_MEAN: always; DSQ_FIT_PARAMETRIC_OR_MEAN: only when the parametric trend did not fit.  The trend then is
-// the constant: COEF0 = the mean, COEF1 = 0 (dispFit = COEF0 + COEF1 / baseMean is that constant, exactly).
-__global__ void __launch_bounds__(1024) trend_mean_kernel(const double *disp, int n, double minDisp, int mode, double *scalars,
-                                                          int32_t *status) {
-    __shared__ __attribute__((aligned(16))) unsigned hist[2048];
-    __shared__ unsigned long long bc[3];
-    __shared__ unsigned long long cnts[5];
-    __shared__ U192 part[1024];
-    if (mode == DSQ_FIT_PARAMETRIC_OR_MEAN && status[DSQ_ST_TREND_STATUS] == 0) return;
-    const double inf = __builtin_inf(), thr = 10.0 * minDisp;
-    auto val = [&](int i) { const double d = disp[i]; return (d > thr) ? d : inf; };       // (NaN: not kept, as na.rm)
-    if (threadIdx.x < 5) cnts[threadIdx.x] = 0ull;
-    __syncthreads();
-    unsigned long long c = 0;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) c += val(i) != inf;
-    atomicAdd(&cnts[0], c);
-    __syncthreads();
-    const long N = (long)cnts[0];
-    if (N == 0) {                                           // (cannot happen behind N_TREND > 0; kept a failure)
-        if (threadIdx.x == 0) status[DSQ_ST_TREND_STATUS] = 3;
-        return;
-    }
-    const long k = (long)__builtin_floor((double)N * 0.001);
-    const double a = block_select(n, k, val, hist, bc);
-    const double b = block_select(n, N - 1 - k, val, hist, bc);
-    U192 acc = {{0, 0, 0}};
-    unsigned long long la = 0, ca = 0, lb = 0;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const double v = val(i);
-        if (v == inf) continue;
-        la += v < a; ca += v == a; lb += v < b;
-        if (v > a && v < b) { const U192 f = u192_fixed(v); u192_add(acc, f); }
-    }
-    atomicAdd(&cnts[1], la); atomicAdd(&cnts[2], ca); atomicAdd(&cnts[3], lb);
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) u192_add(part[threadIdx.x], part[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        double mean = a;
-        if (a != b) {                                       // sorted positions k .. N-1-k: the copies of a and of b inside
-            U192 S = part[0];
-            const U192 ta = u192_times(a, (unsigned long)(cnts[1] + cnts[2] - (unsigned long long)k));
-            const U192 tb = u192_times(b, (unsigned long)((unsigned long long)(N - k) - cnts[3]));
-            u192_add(S, ta); u192_add(S, tb);
-            mean = u192_mean(S, (uint64_t)(N - 2 * k));
-        }
-        scalars[DSQ_SC_COEF0] = mean;
-        scalars[DSQ_SC_COEF1] = 0.0;
-        status[DSQ_ST_TREND_STATUS] = 0;
-        scalars[DSQ_SC_FIT_USED] = (double)DSQ_FIT_MEAN;
-    }
-}
-
-__global__ void trend_given_kernel(double *scalars, int32_t *status) {
-    scalars[DSQ_SC_COEF0] = dnan(); scalars[DSQ_SC_COEF1] = dnan();
-    scalars[DSQ_SC_FIT_USED] = (double)DSQ_FIT_GIVEN;
-    status[DSQ_ST_TREND_STATUS] = 0;
 }
 
 // ---- per-gene rules ----------------------------------------------------------------------------------------------
@@ -1641,6 +1159,11 @@ struct InitFills {
     }
 };
 
+// the values the trend phase works on: the gathered vectors of a sharding caller, else this call's genes.  launch_init_fills
+// sizes the prior variance's workspace by it and phase_trend launches with it: launch_prior_var chooses its kernel from the
+// same number
+static int trend_count(const Pipe &P) { return P.a->trend_mean ? P.a->n_trend : P.n; }
+
 // ONE launch for every fill this call needs in front of its first kernel (chain_init_kernel): the dynamic-scheduling
 // counters of the fit launches of THIS call, the ridge (R/fitNbinomGLMs.R:73,162) / default contrast (R/wrappers.R:105-108)
 // / prior block, -- gene-wise phase -- the NA patterns of the result columns and the status block, -- trend phase -- the
@@ -1683,10 +1206,10 @@ static int launch_init_fills(Pipe &P) {
             if ((rc = capi_ws_get(DSQ_WS_PIPE_META, trend_fit_workspace_bytes() + 64, &P.trend_ws))) return rc;
             f.add(P.trend_ws, (trend_fit_workspace_bytes() + 3) / 4 * 4, 0u);
         }
-        const int nt = a->trend_mean ? a->n_trend : n;
-        if (!(tuning().prior_var_one_block || nt < 16384)) {     // (6 250 genes: 0.116 ms on one workgroup, 0.146 on sixteen; 50 000: 0.243 / 0.124)
-            if ((rc = capi_ws_get(DSQ_WS_PIPE_SEL, prior_var_workspace_bytes() + 64, &P.sel_ws))) return rc;
-            f.add(P.sel_ws, (prior_var_workspace_bytes() + 3) / 4 * 4, 0u);
+        const size_t sel_bytes = prior_var_workspace_bytes(trend_count(P));     // (0: on one workgroup, without)
+        if (sel_bytes) {
+            if ((rc = capi_ws_get(DSQ_WS_PIPE_SEL, sel_bytes + 64, &P.sel_ws))) return rc;
+            f.add(P.sel_ws, (sel_bytes + 3) / 4 * 4, 0u);
         }
     }
     if (f.full) return capi_fail(DSQ_ERR_DEVICE, "dsq_deseq_dev: more than %d init segments", kInitSegMax);
@@ -1774,33 +1297,30 @@ static int phase_trend(Pipe &P) {
     hipStream_t st = P.st;
     const double *tm = a->trend_mean ? a->trend_mean : o->baseMean;
     const double *td = a->trend_mean ? a->trend_disp : o->dispGeneEst;
-    const int nt = a->trend_mean ? a->n_trend : P.n;
+    const int nt = trend_count(P);
     if (!(a->phases & DSQ_PH_GENE_EST)) DSQ_HIP(hipMemsetAsync(P.counters + CNT_TREND, 0, sizeof(int32_t), st));      // (else: the status fill)
     hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, st, 1, nt, (int32_t *)nullptr, (const int32_t *)nullptr,
                        tm, td, 100.0 * a->minDisp, (int32_t *)nullptr, P.trend_mean_c, P.trend_disp_c,
                        P.counters + CNT_TREND);
     capi_prof_begin("trend_fit", nt, st);
+    hipError_t e = hipSuccess;
     if (a->dispFit_in) {
-        // the caller's trend (fitType "local" evaluated by R, dispersionFunction<-): nothing to fit; the coefficients are NA
-        hipLaunchKernelGGL(trend_given_kernel, dim3(1), dim3(1), 0, st, o->scalars, o->status);
+        e = launch_trend_given(o->scalars, o->status, st);
     } else {
         if (a->fitType != DSQ_FIT_MEAN)
-            DSQ_HIP(launch_trend_fit_dev_zeroed(P.trend_mean_c, P.trend_disp_c, P.counters + CNT_TREND, o->scalars + DSQ_SC_COEF0,
-                                                 o->status + DSQ_ST_TREND_STATUS, P.trend_ws, st));
-        if (a->fitType != DSQ_FIT_PARAMETRIC)            // R/core.R:894-899 over the same vector, uncompacted
-            hipLaunchKernelGGL(trend_mean_kernel, dim3(1), dim3(1024), 0, st, td, nt, a->minDisp, (int)a->fitType, o->scalars, o->status);
+            e = launch_trend_fit_dev_zeroed(P.trend_mean_c, P.trend_disp_c, P.counters + CNT_TREND, o->scalars + DSQ_SC_COEF0,
+                                            o->status + DSQ_ST_TREND_STATUS, P.trend_ws, st);
+        if (e == hipSuccess && a->fitType != DSQ_FIT_PARAMETRIC)            // R/core.R:894-899 over the same vector, uncompacted
+            e = launch_trend_mean(td, nt, a->minDisp, (int)a->fitType, o->scalars, o->status, st);
     }
     capi_prof_end(st);
+    DSQ_HIP(e);
     capi_prof_begin("prior_var", nt, st);
     const double *fin = a->dispFit_in ? (a->trend_mean ? a->trend_fit_in : a->dispFit_in) : (const double *)nullptr;
-    if (!P.sel_ws)
-        hipLaunchKernelGGL(prior_var_kernel, dim3(1), dim3(1024), 0, st, tm, td, nt, a->minDisp, a->expVarLogDisp,
-                           (P.m > P.p) ? 1 : 0, P.resbuf, o->scalars, o->status, fin, a->dispPriorVar_in);
-    else
-        hipLaunchKernelGGL(prior_var_grid_kernel, dim3(kSelBlocks), dim3(1024), 0, st, tm, td, nt, a->minDisp, a->expVarLogDisp,
-                           (P.m > P.p) ? 1 : 0, P.resbuf, o->scalars, o->status, fin, a->dispPriorVar_in, (SelWs *)P.sel_ws);
+    e = launch_prior_var(tm, td, nt, a->minDisp, a->expVarLogDisp, (P.m > P.p) ? 1 : 0, P.resbuf, o->scalars, o->status, fin,
+                         a->dispPriorVar_in, P.sel_ws, st);
     capi_prof_end(st);
-    DSQ_HIP(hipGetLastError());
+    DSQ_HIP(e);
     return DSQ_OK;
 }
 

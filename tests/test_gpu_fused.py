@@ -289,7 +289,7 @@ def test_residual_df_of_at_most_three_with_the_callers_prior_variance(E, m):
 
 
 def test_all_gene_kernels_above_their_size_thresholds(E):
-    """20 000 genes: the prior variance of the trend runs on sixteen workgroups from 16 384 genes (prior_var_grid_kernel:
+    """20 000 genes: the prior variance of the trend runs on sixteen workgroups from 16 384 genes (prior_var_kernel<16>:
     per-pass histograms in a global table, grid barriers), the ordered compactions take several rounds of four tiles --
     against the call-by-call chain, whose MAD and row lists come from other code (engine.mad, host masks): trend
     coefficients, varLogDispEsts, dispPriorVar and every per-gene column bit for bit"""
