@@ -38,7 +38,7 @@ const Tuning &tuning() {
                        env_int("DSQ_DISP_XLDS", 1), env_int("DSQ_BETA_XLDS", 1), env_int("DSQ_DYNAMIC", 1),
                        env_int("DSQ_BETA_CELLS", 1), env_int("DSQ_DISP_CELL_MINP", DSQ_DISP_CELL_MINP),
                        env_int("DSQ_OVERLAP", 1), env_int("DSQ_LPT", 1),
-                       env_int("DSQ_LPT_MAXN", 16384), env_int("DSQ_LPT_KEY2", 0)};
+                       env_int("DSQ_LPT_MAXN", 16384), env_int("DSQ_LPT_KEY2", 0), env_int("DSQ_OUTLIER_FIRST", 1)};
     return t;
 }
 
@@ -186,6 +186,8 @@ int capi_side_stream(hipStream_t *side, hipEvent_t *fork_ev, hipEvent_t *join_ev
     if (!t_ctx) return capi_fail(DSQ_ERR_DEVICE, "no stream context latched (hipGetDevice failed)");
     SideStream &e = t_ctx->side;
     if (!e.s) {
+        // (default priority: the refit beside the bulk Cook's pass was not measurably quicker with this stream at the lowest,
+        //  profiles/outlier_first.md)
         DSQ_HIP(hipStreamCreateWithFlags(&e.s, hipStreamNonBlocking));
         DSQ_HIP(hipEventCreateWithFlags(&e.f, hipEventDisableTiming));
         DSQ_HIP(hipEventCreateWithFlags(&e.j, hipEventDisableTiming));

@@ -80,6 +80,11 @@ struct BetaKernelParams {
     int p_true;             // WIDE designs: the design's own number of columns (the zero padding follows them); 0 = p.  The
                             // rolled kernel runs at this width -- the padded coefficients' ridge rows and zero columns only
                             // ever add exact zeros to the real ones' sums -- and writes the padding's outputs (0) itself
+    // cell kernel only, with hat_diagonals and mu_out: n flags or NULL -- 1 where some sample's Cook's distance can exceed
+    // cand_cutoff whatever robust dispersion cooks_kernel finds for the row (the bound next to the kernel's output loops);
+    // cand_p: the divisor of the distance, the design's own number of columns
+    int32_t *cand_flag;
+    double cand_cutoff, cand_p;
 };
 
 struct PrefitKernelParams {
@@ -175,6 +180,9 @@ struct CooksKernelParams {
     double *cooks, *maxCooks, *robustDisp;
     const int32_t *rows;         // fused pipeline: see DispKernelParams
     const int32_t *n_dev;
+    const int32_t *skip;         // n flags or NULL: as LogLikeKernelParams.skip
+    int rows_few;                // the list is expected to be short: one block per CU is enough
+    int beside;                  // the launch runs BESIDE another stream's small launches: it leaves them part of every CU
 };
 
 struct ReplaceKernelParams {
@@ -190,6 +198,8 @@ struct ReplaceKernelParams {
     int32_t *newCounts, *replace;
     const int32_t *rows;
     const int32_t *n_dev;
+    const int32_t *skip;         // as CooksKernelParams
+    int rows_few, beside;
 };
 
 // estimateSizeFactors (size_factors.hip).  Element (i, j) of the counts sits at y[i * y_si + j * y_sj] (either layout), of
@@ -362,6 +372,8 @@ struct Tuning {
     int overlap;             // DSQ_OVERLAP (default 1): the test's full-row nbinomLogLike on a side stream beside the refit
     int lpt, lpt_maxn;       // DSQ_LPT (default 1), DSQ_LPT_MAXN (16384): longest-expected-first order of the fit_beta rows, up to n
     int lpt_key2;            // DSQ_LPT_KEY2 (default 0) = 1: the test's fit is ordered by baseMean like the gene-wise one
+    int outlier_first;       // DSQ_OUTLIER_FIRST (default 1): the rows that can hold a count outlier first, their refit beside the
+                             // Cook's distances of all the others (pipeline.hip, phase_outlier_first)
 };
 const Tuning &tuning();
 
@@ -413,6 +425,8 @@ int capi_upload_cells(const int32_t *labels, int m, int slot, hipStream_t st, co
 hipError_t launch_fit_beta_rolled(const BetaKernelParams &kp, hipStream_t st);
 void fit_beta_rolled_scratch_doubles(int n, int m, int p, int useW, size_t *slab, size_t *cscr);
 hipError_t dispatch_fit_beta(int p, const BetaKernelParams &kp, hipStream_t st, bool *ok);
+// a fit at the (kernel) width p with ncell design cells runs on the cell kernel -- the one that writes BetaKernelParams.cand_flag
+static inline bool fit_beta_on_cells(int p, int ncell) { return p <= 32 /* DSQ_SPEC_BETA_CELL_MAXP */ && ncell > 0 && ncell <= DSQ_CMAX && ncell + p <= 64; }
 void dispatch_beta_scratch(int p, int n, int m, int useW, size_t *slab, size_t *cscr);
 hipError_t dispatch_fit_disp(int p, const DispKernelParams &kp, hipStream_t st, bool grid, bool *ok);
 bool fit_disp_rolled_applies(const DispKernelParams &kp, int *p_true);       // fit_disp_wide.hip

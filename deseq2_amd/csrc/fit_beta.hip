@@ -813,6 +813,43 @@ __device__ unsigned long long betac_prof[DSQ_PROF_SLOTS];
 #else
 #define DSQ_CPROF(slot)
 #endif
+// Can this sample's Cook's distance exceed `cutoff`, whatever robust dispersion cooks_kernel (outlier.hip) finds for the row?
+// cooks_kernel computes, from the stored mu and h and with alpha = fmax(robust estimate, 0.04) (a NaN estimate gives 0.04),
+//     V = mu + alpha (mu mu);  d = y - mu;  pr = (d d) / V;  ck = pr / p * h / ((1 - h) (1 - h)),
+// and the row is replaced when some ck > cutoff.  Here the same operations in the same order at alpha = 0.04.  Every
+// operation between alpha and ck is monotone in its changing operand while all values are finite and h >= 0 -- alpha (mu mu)
+// and mu + . do not fall as alpha grows (mu mu >= 0), (d d) / V does not rise as V grows (d d >= 0, V >= 0), . / p, . * h (h >= 0)
+// and . / ((1 - h)(1 - h)) keep the order -- and IEEE rounding is monotone (x <= y gives fl(x) <= fl(y); no contraction:
+// -ffp-contract=off), so the bound B computed here is >= every finite ck the other kernel can compute.  A ck that is not
+// finite (0 / 0 at mu = 0, inf / inf at an overflowed mu, a division by 1 - h = 0, a NaN input) has the same defect here or
+// an infinite B: `!(B <= cutoff)` takes NaN and +inf with it; h < 0, where the order argument fails, is taken outright.
+// (A superset, never the decision: replace_kernel still compares the real distances.)
+DSQ_DEV bool cooks_can_exceed(double y, double mu, double h, double p, double cutoff) {
+    const double V = mu + 0.04 * (mu * mu);
+    const double d = y - mu;
+#ifdef DSQ_CAND_DIVFREE
+    // (make alt ALT_FLAGS=-DDSQ_CAND_DIVFREE ALT_UNITS=fit_beta: measured against the form below, profiles/outlier_first.md.)
+    // The same decision without a division: B > cutoff is d d h > cutoff p V (1 - h)^2 up to rounding.  With u = 2^-53:
+    // L = fl(fl(d d) h) >= d d h (1 - u)^2 - 2^-1074, R = fl(fl(fl(cutoff p) V) fl(omh omh)) <= cutoff p V omh^2 (1 + u)^4 when
+    // nothing underflows on the way, which R >= 1e-280 with omh^2 <= 1 (0 <= h < 1) sees to.  So "L (1 + 2^-40) <= R" gives
+    // d d h / (p V omh^2) < cutoff (1 - 2^-41), and B, that quotient within six roundings (1 + u)^6 plus at most 2^-960 of
+    // underflow (omh >= 2^-53), stays below cutoff.  Everything the comparison does not cover is a candidate: h outside
+    // [0, 1), R not finite or below 1e-280 (V = 0), a cutoff so small that 2^-960 counts (0 included), NaN anywhere (every
+    // comparison with it is false).
+    const double omh = 1.0 - h;
+    const double L = (d * d) * h;
+    const double R = ((cutoff * p) * V) * (omh * omh);
+    const bool below = (L * (1.0 + 0x1p-40) <= R) && (R >= 1e-280) && (R < __builtin_inf()) && (h >= 0.0) && (h < 1.0) &&
+                       (cutoff * p >= 1e-100);
+    return !below;
+#else
+    const double pr = (d * d) / V;
+    const double omh = 1.0 - h;
+    const double B = pr / p * h / (omh * omh);
+    return !(B <= cutoff) || !(h >= 0.0);
+#endif
+}
+
 template <int P, bool USE_W>
 __global__ void __launch_bounds__(256, DSQ_BETA_CELL_MINW) fit_beta_cell_kernel(BetaKernelParams kp) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -1197,23 +1234,32 @@ __global__ void __launch_bounds__(256, DSQ_BETA_CELL_MINW) fit_beta_cell_kernel(
                     }
                 }
                 wave_lds_sync();
+                int cand = 0;
                 for (int k = lane; k < m; k += 64) {
                     const int pk = pc[k];
                     const int j = pk & 0x3ffffff, c = pk >> 26;
                     const double nf = nfg[j];
+                    double hj = 0.0, mj = 0.0;
                     if (kp.hat_diagonals) {
                         const double mu = __builtin_fmax(nf * slab[4 * c], minmu);
                         const double rcp = 1.0 / (1.0 + alpha * mu);
                         double wv;
                         if constexpr (USE_W) wv = mu * (wg[j] * rcp);
                         else wv = mu * rcp;
-                        kp.hat_diagonals[(size_t)g * kp.ld + j] = wv * slab[4 * c + 3];
+                        hj = wv * slab[4 * c + 3];
+                        kp.hat_diagonals[(size_t)g * kp.ld + j] = hj;
                     }
                     if (kp.mu_out) {
                         double v = nf * slab[4 * c + 2];
                         if (kp.mu_floor > 0.0) v = __builtin_fmax(v, kp.mu_floor);
                         kp.mu_out[(size_t)g * kp.ld + j] = v;
+                        mj = v;
                     }
+                    if (kp.cand_flag) cand |= cooks_can_exceed((double)yg[j], mj, hj, kp.cand_p, kp.cand_cutoff) ? 1 : 0;
+                }
+                if (kp.cand_flag) {
+                    const int any = __any(cand);
+                    if (lane == 0) kp.cand_flag[g] = any ? 1 : 0;
                 }
             }
             DSQ_CPROF(6);
@@ -1281,23 +1327,32 @@ __global__ void __launch_bounds__(256, DSQ_BETA_CELL_MINW) fit_beta_cell_kernel(
                 slab[4 * lane + 3] = h;
             }
             wave_lds_sync();
+            int cand = 0;
             for (int k = lane; k < m; k += 64) {
                 const int pk = pc[k];
                 const int j = pk & 0x3ffffff, c = pk >> 26;
                 const double nf = nfg[j];
+                double hj = 0.0, mj = 0.0;
                 if (kp.hat_diagonals) {
                     const double mu = __builtin_fmax(nf * slab[4 * c], minmu);
                     const double rcp = 1.0 / (1.0 + alpha * mu);
                     double wv;
                     if constexpr (USE_W) wv = mu * (wg[j] * rcp);
                     else wv = mu * rcp;
-                    kp.hat_diagonals[(size_t)g * kp.ld + j] = wv * slab[4 * c + 3];
+                    hj = wv * slab[4 * c + 3];
+                    kp.hat_diagonals[(size_t)g * kp.ld + j] = hj;
                 }
                 if (kp.mu_out) {
                     double v = nf * slab[4 * c + 2];
                     if (kp.mu_floor > 0.0) v = __builtin_fmax(v, kp.mu_floor);
                     kp.mu_out[(size_t)g * kp.ld + j] = v;
+                    mj = v;
                 }
+                if (kp.cand_flag) cand |= cooks_can_exceed((double)yg[j], mj, hj, kp.cand_p, kp.cand_cutoff) ? 1 : 0;
+            }
+            if (kp.cand_flag) {
+                const int any = __any(cand);
+                if (lane == 0) kp.cand_flag[g] = any ? 1 : 0;
             }
         }
         DSQ_CPROF(6);
@@ -1733,10 +1788,11 @@ void fit_beta_scratch_doubles<DSQ_P>(int n, int m, int useW, size_t *slab, size_
 #endif
 }
 
+static_assert(DSQ_SPEC_BETA_CELL_MAXP == 32, "fit_beta_on_cells (dsq_internal.hpp) states the widest cell kernel");
 template <>
 hipError_t launch_fit_beta_p<DSQ_P>(const BetaKernelParams &kp0, hipStream_t st) {
     if constexpr (DSQ_P <= DSQ_SPEC_BETA_CELL_MAXP)
-        if (kp0.ncell > 0 && kp0.ncell <= DSQ_CMAX && kp0.ncell + DSQ_P <= 64) return launch_beta_cells<DSQ_P>(kp0, st);
+        if (fit_beta_on_cells(DSQ_P, kp0.ncell)) return launch_beta_cells<DSQ_P>(kp0, st);
 #if DSQ_P >= DSQ_BETA_ROLLED_MIN
     return launch_fit_beta_rolled(kp0, st);
 #else

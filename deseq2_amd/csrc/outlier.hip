@@ -90,6 +90,7 @@ __global__ void __launch_bounds__(256) cooks_kernel(CooksKernelParams kp) {
     const int nwork = DSQ_NWORK(kp);
     for (int wi = blockIdx.x * waves + wave; wi < nwork; wi += gridDim.x * waves) {
         const int g = DSQ_GENE(kp, wi);
+        if (kp.skip && kp.skip[g]) continue;       // (rows an earlier launch has done: pipeline.hip, phase_outlier_first)
         const int32_t *yg = kp.y + (size_t)g * kp.ld;
         const double *nfg = kp.nf_is_vector ? kp.nf : kp.nf + (size_t)g * kp.ld;
         double acc = 0.0;
@@ -226,6 +227,7 @@ __global__ void __launch_bounds__(256) replace_kernel(ReplaceKernelParams kp) {
     const int nwork = DSQ_NWORK(kp);
     for (int wi = blockIdx.x * waves + wave; wi < nwork; wi += gridDim.x * waves) {
         const int g = DSQ_GENE(kp, wi);
+        if (kp.skip && kp.skip[g]) continue;       // (rows an earlier launch has done: pipeline.hip, phase_outlier_first)
         const int32_t *yg = kp.y + (size_t)g * kp.ld;
         const double *nfg = kp.nf_is_vector ? kp.nf : kp.nf + (size_t)g * kp.ld;
         const double *ckg = kp.cooks + (size_t)g * kp.ld;
@@ -252,6 +254,9 @@ __global__ void __launch_bounds__(256) replace_kernel(ReplaceKernelParams kp) {
                 og[j] = (ckg[j] > kp.cutoff && kp.replaceable[j]) ? rep : yg[j];
             }
         }
+        // (the pass over the rows that are no candidates, pipeline.hip phase_outlier_first: `any` is 0 there and so is the flag
+        //  already -- the refit's launch_xim_flagged reads the flags of ALL rows on the other stream meanwhile, so this store
+        //  must stay a store of the value that is there: a pass-through row never gets anything else written here)
         if (lane == 0) kp.replace[g] = any ? 1 : 0;
     }
 }
@@ -278,7 +283,24 @@ static hipError_t launch_outlier(F fn, const KP &kp, size_t doubles_per_wave, hi
     int per_cu = (int)((160 * 1024) / (lds ? lds : 1));
     if (per_cu > 8) per_cu = 8;
     if (per_cu < 1) per_cu = 1;
-    int cap = device_cu_count() * per_cu;
+    if (kp.beside) {
+        // BESIDE the refit of the replaced rows (pipeline.hip: side stream): the grid-stride grid fills every slot it is given
+        // for the whole launch, so it is given HALF of what the kernel can hold of a CU -- registers and LDS, as the runtime
+        // counts them -- and the other stream's (small, latency-bound) launches find room at once.  Measured at 50 000 x 500
+        // (profiles/outlier_first.md): half 8.99 ms per step, three quarters 9.06, all of it 9.09, one pass per block 9.08
+        static thread_local int occ_cache[1];          // (one per kernel: this template's instantiation)
+        static thread_local size_t lds_cache[1];
+        DSQ_CACHE_PER_DEVICE(occ_cache, lds_cache);
+        if (lds_cache[0] != lds || occ_cache[0] == 0) {
+            int occ = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)fn, 64 * waves, lds) != hipSuccess || occ < 1) occ = per_cu;
+            occ_cache[0] = occ; lds_cache[0] = lds;
+        }
+        if (occ_cache[0] < per_cu) per_cu = occ_cache[0];
+        per_cu /= 2;
+        if (per_cu < 1) per_cu = 1;
+    }
+    int cap = device_cu_count() * (kp.rows_few ? 1 : per_cu);
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(fn, dim3(blocks), dim3(64 * waves), lds, st, kp);

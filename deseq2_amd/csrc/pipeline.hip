@@ -279,6 +279,19 @@ __global__ void list_kernel(Rows rw, const int32_t *flag, int want, int32_t *row
     if ((flag[g] != 0) == (want != 0)) rows_out[atomicAdd(count, 1)] = g;
 }
 
+// the rows that can hold a count outlier (the fit's bound, BetaKernelParams.cand_flag) and the rows the optim fallback has
+// rewritten (their stored means are no longer the ones the bound saw) -> list, and the flags once more in a vector that
+// nothing writes until the phase is over (the grid flags go back to the refit's searches)
+__global__ void cand_list_kernel(Rows rw, const int32_t *bound_flag, const int32_t *optim_flag, int32_t *flag_out, int32_t *rows_out,
+                                 int32_t *count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows_count(rw)) return;
+    const int g = rows_gene(rw, i);
+    const int f = (bound_flag[g] != 0 || optim_flag[g] != 0) ? 1 : 0;
+    flag_out[g] = f;
+    if (f) rows_out[atomicAdd(count, 1)] = g;
+}
+
 // refitWithoutOutliers: result columns of rows that became all-zero are NA (R/core.R:2535), only when some row
 // is actually refitted (:2496)
 struct NaRowsParams {
@@ -504,6 +517,9 @@ struct Pipe {
     hipEvent_t ev_fork, ev_join;
     bool overlap, forked, ll_pending;
     LogLikeKernelParams ll;        // the deferred full-row launch (test_fit -> run_chain)
+    // the outlier phase in candidates-first order (phase_outlier_first): asked for by this call; the test's fit has left the
+    // candidate flags in grid_flag; the side stream has recorded ev_fork behind the full-row nbinomLogLike
+    bool outlier_first, cand_ready, ll_event;
     // host-side facts of the design cells
     int any3, maxcell, all_replaceable;
 };
@@ -585,9 +601,10 @@ static DesignSel design_of(const Pipe &P, int which) {
 
 static int launch_fit_beta(Pipe &P, const Rows &rw, const int32_t *y, const double *alpha, const double *weights,
                            double *mu_out, double mu_floor, double *hat, double tol, int maxit, int useQR, double minmu,
-                           const char *name, int which = DES_FULL) {
+                           const char *name, int which = DES_FULL, bool cand = false) {
     const DesignSel ds = design_of(P, which);
     BetaKernelParams kp = fit_head<BetaKernelParams>(P, rw, y, weights);
+    if (cand) { kp.cand_flag = P.grid_flag; kp.cand_cutoff = P.a->cooksCutoff; kp.cand_p = (double)P.p; }
     kp.p = ds.p; kp.x = ds.x; kp.alpha_hat = alpha; kp.contrast = P.contrast;
     kp.beta_init = ds.beta_init; kp.lambda = ds.lam;
     kp.tol = tol; kp.minmu = minmu; kp.mu_floor = mu_floor; kp.maxit = maxit; kp.useQR = useQR ? 1 : 0;
@@ -887,15 +904,23 @@ static int join_side(Pipe &P) {
     return DSQ_OK;
 }
 
+// what the side stream is given from here on runs behind everything enqueued on the chain's stream so far
+static int fork_side(Pipe &P) {
+    if (P.forked) return DSQ_OK;
+    DSQ_HIP(hipEventRecord(P.ev_fork, P.st));
+    DSQ_HIP(hipStreamWaitEvent(P.side, P.ev_fork, 0));
+    P.forked = true;
+    return DSQ_OK;
+}
+
 // the deferred full-row nbinomLogLike: on the side stream (forked here) or on the chain's own stream
 static int launch_pending_ll(Pipe &P, bool beside) {
     if (!P.ll_pending) return DSQ_OK;
     P.ll_pending = false;
     if (beside) {
-        DSQ_HIP(hipEventRecord(P.ev_fork, P.st));
-        DSQ_HIP(hipStreamWaitEvent(P.side, P.ev_fork, 0));
+        const int rc = fork_side(P);
+        if (rc) return rc;
         DSQ_HIP(launch_loglike_side(P.ll, P.side));
-        P.forked = true;
     } else {
         DSQ_HIP(launch_loglike(P.ll, P.st));
     }
@@ -909,10 +934,15 @@ static int test_fit(Pipe &P, const Rows &rw, const int32_t *y, double *mu_out, d
     if (a->betaPrior) return mle_fit(P, rw, y, mu_out, hat);         // (the prior fit follows once lambda is known)
     // (P.beta_iter: the iteration counts of the gene-wise estimate's IRLS on the same rows, when that fit ran)
     const bool by_mean = tuning().lpt_key2 == 1;
+    // (the main chain's fit, when the outlier phase wants the candidate rows first and this fit runs on the kernel that knows
+    //  the bound: the flags go to the grid flags, free between the MAP search and the refit's -- not beside nbinomLRT's
+    //  reduced fit, which counts its optim rows there)
+    const bool cand = P.outlier_first && !P.tag[0] && hat && !(a->test == 1 && a->x_red) && fit_beta_on_cells(P.pk, P.ncell);
     int rc = launch_fit_beta(P, by_mean ? lpt_rows(P, rw, nullptr, o->baseMean, 1) : (a->linearMu ? rw : lpt_rows(P, rw, nullptr, P.beta_iter)),
                              y, o->dispersion, a->weights_norm, mu_out, 0.0, hat,
-                             P.t_tol, P.t_maxit, P.t_useQR, P.t_minmu, "fit_beta");
+                             P.t_tol, P.t_maxit, P.t_useQR, P.t_minmu, "fit_beta", DES_FULL, cand);
     if (rc) return rc;
+    if (cand) P.cand_ready = true;
     LogLikeKernelParams lk = loglike_params(P, rw, y, mu_out, o->logLike);
     // OVERLAP (the main chain, when this call also runs the outlier phase): nothing on the way to the refit of the replaced
     // rows reads the log likelihoods -- beta_post / the optim fallback / Cook's distances / replaceOutliers / the refit's
@@ -1115,6 +1145,8 @@ static int bind(Pipe &P, const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_
     // time every launch on one stream; DSQ_OVERLAP=0 switches it off
     P.overlap = tuning().overlap && !capi_prof_on() && !a->betaPrior && (a->phases & DSQ_PH_MAP_TEST) && (a->phases & DSQ_PH_OUTLIERS);
     if (P.overlap && capi_side_stream(&P.side, &P.ev_fork, &P.ev_join) != DSQ_OK) P.overlap = false;
+    // (phase_outlier_first) the whole chain in one call: the gene-wise phase's fills have zeroed the replace flags
+    P.outlier_first = P.overlap && tuning().outlier_first && a->do_replace && (a->phases & DSQ_PH_GENE_EST);
     const int n = P.n = a->n, m = P.m = a->m;
     P.p = a->p; P.ld = a->ld;
     P.maxDisp = m > 10 ? (double)m : 10.0;
@@ -1349,6 +1381,62 @@ static int phase_prior(Pipe &P, const Rows &nz) {
     return prior_fit(P, nz, P.a->y, CNT_OPT2);
 }
 
+// the parameter blocks of the two outlier kernels over the rows `rw`
+static CooksKernelParams cooks_params(const Pipe &P, const OutlierMeta &M, const Rows &rw) {
+    const DsqDeseqArgs *a = P.a;
+    const DsqDeseqOut *o = P.o;
+    CooksKernelParams ck;
+    memset(&ck, 0, sizeof ck);
+    ck.n = P.n; ck.m = P.m; ck.p = P.p; ck.ld = P.ld; ck.y = a->y; ck.nf = a->nf; ck.nf_is_vector = a->nf_is_vector;
+    ck.mu = o->mu; ck.H = o->H; ck.perm = M.dperm; ck.cell_start = M.dstart; ck.in3 = M.din3; ck.ncell = a->ncell; ck.any3 = M.any3;
+    int cap = 2; while (cap < (M.any3 ? M.maxcell : P.m)) cap <<= 1;
+    ck.sortcap = cap;
+    ck.cooks = o->cooks; ck.maxCooks = o->maxCooks; ck.robustDisp = P.robustDisp;
+    ck.rows = rw.rows; ck.n_dev = rw.n_dev;
+    return ck;
+}
+static ReplaceKernelParams replace_params(const Pipe &P, const OutlierMeta &M, const Rows &rw) {
+    const DsqDeseqArgs *a = P.a;
+    const DsqDeseqOut *o = P.o;
+    ReplaceKernelParams rk;
+    memset(&rk, 0, sizeof rk);
+    rk.n = P.n; rk.m = P.m; rk.ld = P.ld; rk.y = a->y; rk.nf = a->nf; rk.nf_is_vector = a->nf_is_vector;
+    rk.cooks = o->cooks; rk.cutoff = a->cooksCutoff; rk.trim = a->trim; rk.replaceable = M.drepl;
+    int cap2 = 2; while (cap2 < P.m) cap2 <<= 1;
+    rk.sortcap = cap2;
+    rk.newCounts = o->replaceCounts; rk.replace = o->replace;
+    rk.rows = rw.rows; rk.n_dev = rw.n_dev;
+    return rk;
+}
+static int launch_cooks_rows(Pipe &P, const CooksKernelParams &ck, hipStream_t st) {
+    bool ok = true;
+    capi_prof_begin("cooks_distance", P.n, st);
+    DSQ_HIP(launch_cooks(ck, st, &ok));
+    capi_prof_end(st);
+    if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "m=%d samples: a gene row plus its sort buffer exceeds the 160 KiB LDS", P.m);
+    return DSQ_OK;
+}
+static int launch_replace_rows(Pipe &P, const ReplaceKernelParams &rk, hipStream_t st) {
+    bool ok = true;
+    capi_prof_begin("replace_outliers", P.n, st);
+    DSQ_HIP(launch_replace(rk, st, &ok));
+    capi_prof_end(st);
+    if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "m=%d samples: the sort buffer exceeds the 160 KiB LDS", P.m);
+    return DSQ_OK;
+}
+
+// rows with a replacement among `from` (R/core.R:2488-2490) -> their moments on the new counts (:2491) -> the ones that are
+// still non-zero are refitted (:2496-2500)
+static int list_replaced(Pipe &P, const Rows &from) {
+    const DsqDeseqOut *o = P.o;
+    hipLaunchKernelGGL(list_kernel, ew_grid(P.n), dim3(256), 0, P.st, from, (const int32_t *)o->replace, 1, P.rows_rep, P.counters + CNT_REP);
+    const Rows rep = {P.rows_rep, P.counters + CNT_REP, P.n};
+    const int rc = launch_prefit_rows(P, rep, o->replaceCounts);
+    if (rc) return rc;
+    hipLaunchKernelGGL(list_kernel, ew_grid(P.n), dim3(256), 0, P.st, rep, (const int32_t *)o->allZero, 0, P.rows_refit, P.counters + CNT_REFIT);
+    return DSQ_OK;
+}
+
 // count outliers, first half: Cook's distances, replaceOutliers, the lists of the replaced rows and of the ones to refit
 static int phase_outlier_detect(Pipe &P, const Rows &nz, const OutlierMeta &M, bool counters_zeroed) {
     const DsqDeseqArgs *a = P.a;
@@ -1356,43 +1444,62 @@ static int phase_outlier_detect(Pipe &P, const Rows &nz, const OutlierMeta &M, b
     const int n = P.n, m = P.m;
     hipStream_t st = P.st;
     if (!counters_zeroed) DSQ_HIP(hipMemsetAsync(P.counters + CNT_REP, 0, (CNT_N - CNT_REP) * sizeof(int32_t), st));      // REP .. OPT3R
-    CooksKernelParams ck;
-    memset(&ck, 0, sizeof ck);
-    ck.n = n; ck.m = m; ck.p = P.p; ck.ld = P.ld; ck.y = a->y; ck.nf = a->nf; ck.nf_is_vector = a->nf_is_vector;
-    ck.mu = o->mu; ck.H = o->H; ck.perm = M.dperm; ck.cell_start = M.dstart; ck.in3 = M.din3; ck.ncell = a->ncell; ck.any3 = M.any3;
-    int cap = 2; while (cap < (M.any3 ? M.maxcell : m)) cap <<= 1;
-    ck.sortcap = cap;
-    ck.cooks = o->cooks; ck.maxCooks = o->maxCooks; ck.robustDisp = P.robustDisp;
-    ck.rows = nz.rows; ck.n_dev = nz.n_dev;
-    bool ok = true;
-    capi_prof_begin("cooks_distance", n, st);
-    DSQ_HIP(launch_cooks(ck, st, &ok));
-    capi_prof_end(st);
-    if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "m=%d samples: a gene row plus its sort buffer exceeds the 160 KiB LDS", m);
+    int rc = launch_cooks_rows(P, cooks_params(P, M, nz), st);
+    if (rc) return rc;
     // (before the replacement: allZero still says which rows had no fit -- a row that only BECOMES all zero keeps its assays)
     hipLaunchKernelGGL(na_assay_rows_kernel, ew_grid(n), dim3(256), 0, st, n, m, P.ld, (const int32_t *)o->allZero, o->cooks,
                        (double *)nullptr);
     if (!a->do_replace) return DSQ_OK;
-    ReplaceKernelParams rk;
-    memset(&rk, 0, sizeof rk);
-    rk.n = n; rk.m = m; rk.ld = P.ld; rk.y = a->y; rk.nf = a->nf; rk.nf_is_vector = a->nf_is_vector;
-    rk.cooks = o->cooks; rk.cutoff = a->cooksCutoff; rk.trim = a->trim; rk.replaceable = M.drepl;
-    int cap2 = 2; while (cap2 < m) cap2 <<= 1;
-    rk.sortcap = cap2;
-    rk.newCounts = o->replaceCounts; rk.replace = o->replace;
-    rk.rows = nz.rows; rk.n_dev = nz.n_dev;
-    capi_prof_begin("replace_outliers", n, st);
-    DSQ_HIP(launch_replace(rk, st, &ok));
-    capi_prof_end(st);
-    if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "m=%d samples: the sort buffer exceeds the 160 KiB LDS", m);
-    // rows with a replacement (R/core.R:2488-2490) -> their moments on the new counts (:2491) -> the ones that are still
-    // non-zero are refitted (:2496-2500)
-    hipLaunchKernelGGL(list_kernel, ew_grid(n), dim3(256), 0, st, nz, (const int32_t *)o->replace, 1, P.rows_rep, P.counters + CNT_REP);
-    const Rows rep = {P.rows_rep, P.counters + CNT_REP, n};
-    const int rc = launch_prefit_rows(P, rep, o->replaceCounts);
-    if (rc) return rc;
-    hipLaunchKernelGGL(list_kernel, ew_grid(n), dim3(256), 0, st, rep, (const int32_t *)o->allZero, 0, P.rows_refit, P.counters + CNT_REFIT);
-    return DSQ_OK;
+    if ((rc = launch_replace_rows(P, replace_params(P, M, nz), st))) return rc;
+    return list_replaced(P, nz);
+}
+
+static int phase_outlier_refit(Pipe &P, const Rows &nz, const OutlierMeta &M);
+
+// count outliers, both halves, CANDIDATES FIRST (the whole phase in one call, the test's fit has left the flags).  A row's
+// refit needs that row's Cook's distances and replacement and nothing of any other row; the order above waits for the
+// distances of every row only because nobody knows which handful will be replaced.  The fit's bound knows a superset
+// (cooks_can_exceed, fit_beta.hip): a tenth of a per cent of the rows.  So, once the candidates are listed, two branches:
+//   the chain's stream   distances and replacement on the candidates, the lists of the replaced rows, their refit -- a
+//                        serial tail of some twenty-five launches of a dozen lone waves;
+//   the side stream      the full-row nbinomLogLike, then the distances and the pass-through replacement of all the rows
+//                        that are no candidates (`skip`), on half of every CU (launch_outlier: `beside`).
+// They meet in front of the closing steps.  Every kernel writes a row's outputs at the row's own position and none couples
+// two rows: no bit changes (tests/test_gpu_outlier_first.py).
+// What the two streams touch meanwhile: the side stream reads y / mu / H and writes cooks / maxCooks / robustDisp /
+// replaceCounts / replace of rows that are NOT candidates; the chain's stream reads and writes columns of candidates, and
+// the replace flags, where the side stream only writes the zeros that are there already (the fills of the gene-wise phase:
+// the new order is taken only when the call runs that phase too).  The candidate flags sit in rows_lpt (read last by the
+// test's fit), the list in rows_grid until the refit's first grid search takes that back.
+static int phase_outlier_first(Pipe &P, const Rows &nz, const OutlierMeta &M, bool counters_zeroed) {
+    const DsqDeseqOut *o = P.o;
+    const int n = P.n, m = P.m;
+    hipStream_t st = P.st;
+    if (!counters_zeroed) DSQ_HIP(hipMemsetAsync(P.counters + CNT_REP, 0, (CNT_N - CNT_REP) * sizeof(int32_t), st));      // REP .. OPT3R
+    int32_t *skip = P.rows_lpt, *n_cand = next_work_counter(P);       // (a counter the init launch has zeroed)
+    if (getenv("DSQ_VERBOSE")) fprintf(stderr, "[dsq] outlier phase: candidates first (n=%d)\n", n);
+    hipLaunchKernelGGL(cand_list_kernel, ew_grid(n), dim3(256), 0, st, nz, (const int32_t *)P.grid_flag, (const int32_t *)o->optim_test,
+                       skip, P.rows_grid, n_cand);
+    // (allZero still says which rows had no fit: in front of the moments of the replaced rows, which update it)
+    hipLaunchKernelGGL(na_assay_rows_kernel, ew_grid(n), dim3(256), 0, st, n, m, P.ld, (const int32_t *)o->allZero, o->cooks,
+                       (double *)nullptr);
+    // fork -- the flags are all the other rows' pass needs: full-row log likelihoods (an event behind them: the refit's test
+    // fit writes its rows' after them), then Cook's distances and the pass-through replacement of the rows that are no candidates
+    int rc;
+    if ((rc = fork_side(P)) || (rc = launch_pending_ll(P, true))) return rc;
+    DSQ_HIP(hipEventRecord(P.ev_fork, P.side));      // (the fork's wait on this event is enqueued: it keeps the earlier record)
+    P.ll_event = true;
+    CooksKernelParams ck = cooks_params(P, M, nz);
+    ReplaceKernelParams rk = replace_params(P, M, nz);
+    ck.skip = rk.skip = skip;
+    ck.beside = rk.beside = 1;
+    if ((rc = launch_cooks_rows(P, ck, P.side)) || (rc = launch_replace_rows(P, rk, P.side))) return rc;
+    // the chain's stream: the candidates, the lists, the refit
+    const Rows cand = {P.rows_grid, n_cand, n};
+    ck = cooks_params(P, M, cand); rk = replace_params(P, M, cand);
+    ck.rows_few = rk.rows_few = 1;
+    if ((rc = launch_cooks_rows(P, ck, st)) || (rc = launch_replace_rows(P, rk, st)) || (rc = list_replaced(P, cand))) return rc;
+    return phase_outlier_refit(P, nz, M);
 }
 
 // the refit of the replaced rows runs every step on its DEFAULTS: refitWithoutOutliers passes none of the caller's betaTol /
@@ -1422,9 +1529,14 @@ static int phase_outlier_refit(Pipe &P, const Rows &nz, const OutlierMeta &M) {
     }
     if ((rc = gene_est(P, rf, o->replaceCounts, o->mu_hat, CNT_GRID1R, CNT_OPT1R, o->optim_geneest))) return rc;
     if ((rc = map_est(P, rf, o->replaceCounts, o->mu_hat, CNT_GRID2R))) return rc;
-    if ((rc = join_side(P))) return rc;          // the full-row log likelihoods are down before the refit writes its rows'
+    // the full-row log likelihoods are down before the refit writes its rows' (candidates first: the side stream goes on)
+    if (P.ll_event) {
+        P.ll_event = false;
+        DSQ_HIP(hipStreamWaitEvent(P.st, P.ev_fork, 0));
+    } else if ((rc = join_side(P))) return rc;
     if ((rc = test_fit(P, rf, o->replaceCounts, o->mu_hat, nullptr, CNT_OPT2R))) return rc;
     if (a->betaPrior && (rc = prior_fit(P, rf, o->replaceCounts, CNT_OPT2R))) return rc;
+    if ((rc = join_side(P))) return rc;          // (candidates first: every row's Cook's distances in front of the closing steps)
     return a->defer_finish ? DSQ_OK : outlier_finish(P, nz, rep, M, P.counters + CNT_REFIT);
 }
 
@@ -1443,8 +1555,12 @@ static int run_chain(const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_t st
     const bool detect = (ph & (DSQ_PH_OUTLIERS | DSQ_PH_OUTLIERS_DETECT)) != 0, refit = (ph & (DSQ_PH_OUTLIERS | DSQ_PH_OUTLIERS_REFIT)) != 0;
     OutlierMeta M;
     if ((detect || refit || ((ph & DSQ_PH_FINISH) && a->do_replace)) && (rc = outlier_meta(a, P.m, st, &M))) return rc;
-    if (detect && (rc = phase_outlier_detect(P, nz, M, counters_zeroed))) return rc;
-    if (refit && a->do_replace && (rc = phase_outlier_refit(P, nz, M))) return rc;
+    if ((ph & DSQ_PH_OUTLIERS) && P.cand_ready) {
+        if ((rc = phase_outlier_first(P, nz, M, counters_zeroed))) return rc;
+    } else {
+        if (detect && (rc = phase_outlier_detect(P, nz, M, counters_zeroed))) return rc;
+        if (refit && a->do_replace && (rc = phase_outlier_refit(P, nz, M))) return rc;
+    }
     // (sharding callers) the closing steps, with the number of refitted rows over all shards
     if ((ph & DSQ_PH_FINISH) && a->do_replace)
         return outlier_finish(P, nz, Rows{P.rows_rep, P.counters + CNT_REP, P.n}, M, a->n_refit_global ? a->n_refit_global : P.counters + CNT_REFIT);
