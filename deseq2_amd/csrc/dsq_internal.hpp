@@ -370,8 +370,16 @@ struct Tuning {
     int disp_cell_minp;      // DSQ_DISP_CELL_MINP (profiling; default = the macro): fitDisp cell mode from this width up
     // the chain (pipeline.hip)
     int overlap;             // DSQ_OVERLAP (default 1): the test's full-row nbinomLogLike on a side stream beside the refit
-    int lpt, lpt_maxn;       // DSQ_LPT (default 1), DSQ_LPT_MAXN (16384): longest-expected-first order of the fit_beta rows, up to n
-    int lpt_key2;            // DSQ_LPT_KEY2 (default 0) = 1: the test's fit is ordered by baseMean like the gene-wise one
+    // launch orders of the chain's full-size fit launches (pipeline.hip: lpt_scatter_kernel; profiles/launch_order.md)
+    int lpt;                 // DSQ_LPT (default 1: from 256 samples; 2: whatever the row length; 0: every launch in list order)
+    int lpt_maxn;            // DSQ_LPT_MAXN (default 16384; 0: no limit): the MAP fit_disp is ordered up to n genes
+    int lpt_key1;            // DSQ_LPT_KEY1 (default 1): the gene-wise fit_beta by ascending baseMean; 0: list order
+    int lpt_keyd;            // DSQ_LPT_KEYD (default 1): the gene-wise fit_disp by descending baseMean (the same list backwards) for
+                             // 256 <= m <= 1024 without weights; 2: always; 0: list order
+    int lpt_keym;            // DSQ_LPT_KEYM (default 2): the MAP fit_disp by 2 descending baseMean, 3 the gene-wise search's iterations,
+                             // 5 iterations x log2 mean, 6 |start value - prior mean|; 0: list order
+    int lpt_key2;            // DSQ_LPT_KEY2 (default 1): the test's fit_beta by ascending baseMean like the gene-wise one; 0: by the
+                             // gene-wise IRLS's iterations; 2: list order
     int outlier_first;       // DSQ_OUTLIER_FIRST (default 1): the rows that can hold a count outlier first, their refit beside the
                              // Cook's distances of all the others (pipeline.hip, phase_outlier_first)
 };

@@ -94,6 +94,52 @@ __global__ void __launch_bounds__(1024) compact_kernel(int mode, int n, int32_t 
     if (t == 0) *count_out = base_s;
 }
 
+// ---- the bucket key of a launch order (see "longest-expected-first order" below) --------------------------------------
+// A launch order is a counting order of the rows over kLptBins buckets, bucket kLptBins - 1 first.  The key is one of:
+//   LPT_MEAN_UP     a mean count, the rows with FEW counts first: sixths of an octave of 1 + mean
+//   LPT_MEAN_DOWN   the same buckets taken from the other end
+//   LPT_ITER        an iteration count (int32), clamped
+//   LPT_ITER_F64    an iteration count kept as a double (the IRLS's)
+//   LPT_ITER_MEAN   the product of an iteration count and log2(2 + mean), in steps of 4
+//   LPT_DIST        the distance |a - b| of two doubles, in steps of 1 / 16
+// NaN counts as long (an aborted fit).
+constexpr int kLptBins = 128;
+enum { LPT_NONE = 0, LPT_MEAN_UP = 1, LPT_MEAN_DOWN = 2, LPT_ITER = 3, LPT_ITER_F64 = 4, LPT_ITER_MEAN = 5, LPT_DIST = 6 };
+struct LptKey {
+    int kind;
+    const int32_t *ki;
+    const double *kd, *kd2;
+};
+DSQ_DEV int lpt_bin(const LptKey &k, int g) {
+    double kd;
+    if (k.kind == LPT_MEAN_UP || k.kind == LPT_MEAN_DOWN) {
+        kd = 127.0 - 8.656170245333781 * dlog(1.0 + k.kd[g]);      // 6 / ln 2: a mean of 2^21 reaches bin 0
+        if (kd < 0.0) kd = 0.0;
+        if (k.kind == LPT_MEAN_DOWN) kd = 127.0 - kd;
+    } else if (k.kind == LPT_ITER) {
+        kd = (double)k.ki[g];
+    } else if (k.kind == LPT_ITER_MEAN) {
+        kd = 0.25 * (double)k.ki[g] * (1.4426950408889634 * dlog(2.0 + k.kd[g]));
+    } else if (k.kind == LPT_DIST) {
+        kd = 16.0 * __builtin_fabs(k.kd[g] - k.kd2[g]);
+    } else {
+        kd = k.kd[g];
+    }
+    if (!(kd >= 0.0)) kd = 127.0;             // (NaN: an aborted fit -- treat as long)
+    return kd > 127.0 ? 127 : (int)kd;
+}
+// the histogram of a block's rows (bin < 0: this thread has none) in LDS, then one atomic add per occupied bin: called by
+// every thread of the block
+DSQ_DEV void lpt_block_hist(int bin, int *bins) {
+    __shared__ int h[kLptBins];
+    for (int k = threadIdx.x; k < kLptBins; k += blockDim.x) h[k] = 0;
+    __syncthreads();
+    if (bin >= 0) atomicAdd(&h[bin], 1);
+    __syncthreads();
+    for (int k = threadIdx.x; k < kLptBins; k += blockDim.x)
+        if (h[k]) atomicAdd(&bins[k], h[k]);
+}
+
 // ---- per-gene rules ----------------------------------------------------------------------------------------------
 struct RuleParams {
     Rows rw;
@@ -125,20 +171,27 @@ struct RuleParams {
     const double *beta_init;       // the IRLS start values (natural-log scale)
     double *opt_start;             // n x p, log2 scale
     const int32_t *opt_conv;
+    // the rule kernel in front of an ordered fit launch also builds the histogram of that launch's key (kind = LPT_NONE:
+    // no order): alpha_init_kernel, map_init_kernel, map_final_kernel
+    LptKey lpt;
+    int *lpt_bins;                 // kLptBins zeroed counts
 };
 
 // alpha_hat <- pmin(roughDisp, momentsDisp), bounded to [minDisp, maxDisp] (R/core.R:713-728, :2439-2448)
 __global__ void alpha_init_kernel(RuleParams q) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows_count(q.rw)) return;
-    const int g = rows_gene(q.rw, i);
-    const double bm = q.baseMean[g], bv = q.baseVar[g];
-    const double xim = q.xim_dev ? *q.xim_dev : q.xim;
-    const double mom = (bv - xim * bm) / (bm * bm);
-    double a = np_min(q.roughDisp[g], mom);
-    a = np_min(np_max(q.minDisp, a), q.maxDisp);
-    q.alpha_init[g] = a;
-    q.la0[g] = dlog(a);
+    const bool on = i < rows_count(q.rw);
+    const int g = on ? rows_gene(q.rw, i) : 0;
+    if (on) {
+        const double bm = q.baseMean[g], bv = q.baseVar[g];
+        const double xim = q.xim_dev ? *q.xim_dev : q.xim;
+        const double mom = (bv - xim * bm) / (bm * bm);
+        double a = np_min(q.roughDisp[g], mom);
+        a = np_min(np_max(q.minDisp, a), q.maxDisp);
+        q.alpha_init[g] = a;
+        q.la0[g] = dlog(a);
+    }
+    if (q.lpt.kind != LPT_NONE) lpt_block_hist(on ? lpt_bin(q.lpt, g) : -1, q.lpt_bins);
 }
 
 // after the gene-wise fitDisp: accept / convergence / refit rules (R/core.R:785, 826-835)
@@ -171,15 +224,19 @@ __global__ void gene_est_final_kernel(RuleParams q) {
 // dispFit from the trend; start value and prior mean of the MAP search (R/core.R:1019-1024)
 __global__ void map_init_kernel(RuleParams q) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows_count(q.rw)) return;
-    const int g = rows_gene(q.rw, i);
-    const double fit = q.dispFit_in ? q.dispFit_in[g] : q.scalars[DSQ_SC_COEF0] + q.scalars[DSQ_SC_COEF1] / q.baseMean[g];
-    const double d = q.dge[g];
-    double init = (d > 0.1 * fit) ? d : fit;
-    if (init != init) init = fit;
-    q.dispFit[g] = fit;
-    q.log_dfit[g] = dlog(fit);
-    q.la_init[g] = dlog(init);
+    const bool on = i < rows_count(q.rw);
+    const int g = on ? rows_gene(q.rw, i) : 0;
+    if (on) {
+        const double fit = q.dispFit_in ? q.dispFit_in[g] : q.scalars[DSQ_SC_COEF0] + q.scalars[DSQ_SC_COEF1] / q.baseMean[g];
+        const double d = q.dge[g];
+        double init = (d > 0.1 * fit) ? d : fit;
+        if (init != init) init = fit;
+        q.dispFit[g] = fit;
+        q.log_dfit[g] = dlog(fit);
+        q.la_init[g] = dlog(init);
+    }
+    // (LPT_DIST reads log_dfit / la_init of the thread's own row back)
+    if (q.lpt.kind != LPT_NONE) lpt_block_hist(on ? lpt_bin(q.lpt, g) : -1, q.lpt_bins);
 }
 
 // after the MAP fitDisp: dispMAP, convergence, stragglers to the grid (R/core.R:1042-1050)
@@ -198,17 +255,20 @@ __global__ void map_post_kernel(RuleParams q) {
 // dispMAP[refit] <- exp(grid); clamp; dispOutlier; final dispersion (R/core.R:1061-1063, 1099-1115)
 __global__ void map_final_kernel(RuleParams q) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows_count(q.rw)) return;
-    const int g = rows_gene(q.rw, i);
-    double dm = q.dispMAP[g];
-    if (q.grid_flag[g]) dm = dexp(q.la_grid[g]);
-    dm = np_min(np_max(dm, q.minDisp), q.maxDisp);
-    q.dispMAP[g] = dm;
-    const double d = q.dge[g];
-    const double sd = __builtin_sqrt(q.scalars[DSQ_SC_VAR_LOG_DISP]);
-    const bool outlier = dlog(d) > q.log_dfit[g] + q.outlierSD * sd;       // NaN compares false, as the mirror's mask
-    q.dispOutlier[g] = outlier ? 1 : 0;
-    q.dispersion[g] = outlier ? d : dm;
+    const bool on = i < rows_count(q.rw);
+    const int g = on ? rows_gene(q.rw, i) : 0;
+    if (on) {
+        double dm = q.dispMAP[g];
+        if (q.grid_flag[g]) dm = dexp(q.la_grid[g]);
+        dm = np_min(np_max(dm, q.minDisp), q.maxDisp);
+        q.dispMAP[g] = dm;
+        const double d = q.dge[g];
+        const double sd = __builtin_sqrt(q.scalars[DSQ_SC_VAR_LOG_DISP]);
+        const bool outlier = dlog(d) > q.log_dfit[g] + q.outlierSD * sd;       // NaN compares false, as the mirror's mask
+        q.dispOutlier[g] = outlier ? 1 : 0;
+        q.dispersion[g] = outlier ? d : dm;
+    }
+    if (q.lpt.kind != LPT_NONE) lpt_block_hist(on ? lpt_bin(q.lpt, g) : -1, q.lpt_bins);
 }
 
 // the host half of fitNbinomGLMs (R/fitNbinomGLMs.R:185-211) + Wald statistic and p-value (R/core.R:1471,1507)
@@ -376,47 +436,52 @@ __global__ void __launch_bounds__(256) masked_max_kernel(Rows rw, int m, long ld
 }
 
 // ---- longest-expected-first order of a full-size fit launch ---------------------------------------------------------
-// The persistent fit kernels hand out genes in list order through a counter.  With many genes per wave slot the order does
-// not matter (measured at 50 000 genes: 2 %); at one rank's share of an 8-GPU run (6 250 genes on 3 072 wave slots, two genes
-// per slot) a launch ends when the last slot has worked off its two genes, and two slow genes that meet in one slot set the
-// time: fit_beta 0.30 ms against 0.16 ms for an eighth of the 50 000-gene launch.  The second fit of a gene costs about what
-// its first one did (the test's IRLS after the gene-wise IRLS: same counts, nearly the same dispersion), so the rows are
-// listed by DESCENDING iteration count of the first fit: the slow genes start first, the quick ones fill the gaps
-// (longest-processing-time-first).  A counting sort by one workgroup; the order inside a bin is whatever the atomics give --
-// every gene's results are written at its own position and no kernel couples two genes, so the order changes no bit.
+// The persistent fit kernels hand out genes in list order through a counter.  Once the counter runs dry the device empties
+// out while the last genes finish, and nothing else can start: the next launch depends on this one through a rule kernel or
+// the trend.  So every full-size fit launch pays a drain of about one slow gene, four times per step, and what the order
+// decides is which genes are the last: with the slow ones drawn first, the quick ones fill the gaps (longest-processing-
+// time-first).  At one rank's share of an 8-GPU run (6 250 genes on 3 072 wave slots, two genes per slot) two slow genes that
+// meet in one slot set the time of the launch (fit_beta 0.30 ms in list order, 0.21 ms ordered); at 50 000 genes the drain is
+// a few per cent of a launch (figures per launch and per key: profiles/launch_order.md).
+// Every gene's results are written at its own position and no kernel couples two genes, so the order changes no bit
+// (tests/test_gpu_launch_order.py).
 // What an order can and cannot do at 6 250 genes on 3 072 slots (a simulation on the iteration counts of that workload,
 // cost = iterations): fit_beta in list order ends at 2.5x the ideal, longest-first at 1.8x = the slowest single gene (19
 // iterations) -- the floor of any order; the dispersion searches end at 1.4x either way: 6 250 = 2.03 x 3 072, the last
 // hundred genes are a third round whatever the order.
-// small_first: the key is a MEAN COUNT and the slow genes are the ones with few counts (the gene-wise IRLS, which has no
-// earlier fit to go by: its iteration count falls with log(baseMean), correlation -0.84 at C3) -- the bins are sixths of
-// an octave of 1 + mean, taken in ascending order.
-__global__ void __launch_bounds__(1024) lpt_order_kernel(Rows rw, const int32_t *key_i, const double *key_d, int small_first,
-                                                         int32_t *out) {
-    __shared__ int hist[128], cursor[128];
+// The keys (lpt_bin): the second fit of a gene costs about what its first one did (the test's IRLS after the gene-wise IRLS:
+// same counts, nearly the same dispersion), so the test's fit goes by DESCENDING iteration count of the first; the gene-wise
+// IRLS has no earlier fit to go by, its iteration count falls with log(baseMean) (correlation -0.84 at C3): ascending mean;
+// an evaluation of the dispersion search costs more the more distinct counts a row has: descending mean.
+// The order is a counting order in two passes over the rows, both of as many blocks as the rule kernels have.  The
+// histogram is built by the rule kernel that runs over the same rows just in front (lpt_block_hist: per-block LDS bins,
+// one atomic add per occupied bin and block), so an order adds ONE small launch: lpt_scatter_kernel, in which every block
+// rescans the bins for the buckets' start positions, reserves its share of each bucket with one atomic add and writes its
+// rows there.  The order inside a bucket is whatever the atomics give.  `rev` (optional): the same list read backwards,
+// for a launch that wants the other end of the same key first.
+__global__ void __launch_bounds__(256) lpt_scatter_kernel(Rows rw, LptKey key, const int *bins, int *cursor, int32_t *out, int32_t *rev) {
+    __shared__ int h[kLptBins], tot[kLptBins], base[kLptBins];
     const int cnt = rows_count(rw);
-    if (threadIdx.x < 128) hist[threadIdx.x] = 0;
+    if ((int)(blockIdx.x * blockDim.x) >= cnt) return;              // (the whole block)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    for (int k = threadIdx.x; k < kLptBins; k += blockDim.x) { h[k] = 0; tot[k] = bins[k]; }
     __syncthreads();
-    auto key_of = [&](int g) {
-        double kd = key_i ? (double)key_i[g] : key_d[g];
-        if (small_first) {
-            kd = 127.0 - 8.656170245333781 * dlog(1.0 + kd);      // 6 / ln 2: a mean of 2^21 reaches bin 0
-            if (kd < 0.0) kd = 0.0;
-        }
-        if (!(kd >= 0.0)) kd = 127.0;             // (NaN: an aborted fit -- treat as long)
-        return kd > 127.0 ? 127 : (int)kd;
-    };
-    for (int i = threadIdx.x; i < cnt; i += 1024) atomicAdd(&hist[key_of(rows_gene(rw, i))], 1);
+    const bool on = i < cnt;
+    const int g = on ? rows_gene(rw, i) : 0;
+    const int b = on ? lpt_bin(key, g) : 0;
+    const int mine = on ? atomicAdd(&h[b], 1) : 0;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int acc = 0;
-        for (int k = 127; k >= 0; k--) { cursor[k] = acc; acc += hist[k]; }
+    for (int k = threadIdx.x; k < kLptBins; k += blockDim.x) {
+        int start = 0;
+        for (int j = kLptBins - 1; j > k; j--) start += tot[j];     // bucket kLptBins - 1 comes first
+        base[k] = start + (h[k] ? atomicAdd(&cursor[k], h[k]) : 0);
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < cnt; i += 1024) {
-        const int g = rows_gene(rw, i);
-        out[atomicAdd(&cursor[key_of(g)], 1)] = g;
-    }
+    if (!on) return;
+    const int pos = base[b] + mine;
+    if (pos >= cnt) return;            // (cannot happen while the bins are the histogram of this key over these rows)
+    out[pos] = g;
+    if (rev) rev[cnt - 1 - pos] = g;
 }
 
 // ---- the fills in front of a call's first kernel, as ONE launch ----------------------------------------------------
@@ -435,7 +500,7 @@ static constexpr OutF64 kNaMatrices[] = {&DsqDeseqOut::beta, &DsqDeseqOut::betaS
 static constexpr OutI32 kNaInts[] = {&DsqDeseqOut::dispGeneIter, &DsqDeseqOut::dispIter, &DsqDeseqOut::dispOutlier, &DsqDeseqOut::betaConv};
 static constexpr OutI32 kZeroInts[] = {&DsqDeseqOut::replace, &DsqDeseqOut::optim_geneest, &DsqDeseqOut::optim_test};
 template <class T, size_t N> constexpr int count_of(T (&)[N]) { return (int)N; }
-static constexpr int kInitSegMax = 1 /* work counters */ + 1 /* status */ + count_of(kNaVectors) + count_of(kNaMatrices) + 1 /* mle_beta */ +
+static constexpr int kInitSegMax = 1 /* work counters */ + 1 /* launch-order bins */ + 1 /* status */ + count_of(kNaVectors) + count_of(kNaMatrices) + 1 /* mle_beta */ +
                                    count_of(kNaInts) + count_of(kZeroInts) + 1 /* grid flags */ + 3 /* FIT_USED, trend fit, selection */;
 struct InitSeg { uint32_t *p; uint32_t words; uint32_t val; };
 struct InitParams {
@@ -474,7 +539,15 @@ struct Pipe {
     double *opt_start, *opt_beta, *opt_se, *opt_ll;
     int32_t *iter, *iter_accept, *grid_flag, *rows_nz, *rows_grid, *rows_rep, *rows_refit, *counters, *work_counters;
     int32_t *rows_opt, *opt_conv;
-    int32_t *rows_lpt;             // the non-zero rows in longest-expected-first order (lpt_order_kernel)
+    int32_t *rows_lpt;             // the non-zero rows in the order of the next fit launch (lpt_scatter_kernel)
+    // launch orders of this call: kLptBuilds x (kLptBins counts | kLptBins cursors), zeroed by the init launch, behind the
+    // fit kernels' scratch; the reversed list of the gene-wise order while it is alive (it borrows rows_grid); the order of
+    // the test's fit, whose histogram map_final_kernel has built
+    int *lpt_bins;
+    int lpt_next;
+    const int32_t *rows_rev;
+    LptKey lpt_test;
+    int *lpt_test_bins;
     double *lam_prior;             // betaPrior: 1 / betaPriorVar on the natural-log scale (device copy of a->lambda_prior)
     // WIDE designs (10 < p <= 48): the fit kernels run at the padded width pk = 16 / 24 / 32 / 48 on the design zero-padded to pk
     // columns (ridge 1, start value 0, contrast 0 on the padding: the real coefficients keep their bits, csrc/capi.hip
@@ -540,8 +613,10 @@ static int *next_work_counter(Pipe &P) {
 
 static inline dim3 ew_grid(int n) { return dim3((unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1)); }
 
-// a row list that is expected to be short (stragglers, refits): neither the non-zero rows nor their longest-first order
-static inline int rows_few(const Pipe &P, const Rows &rw) { return (rw.rows && rw.rows != P.rows_nz && rw.rows != P.rows_lpt) ? 1 : 0; }
+// a row list that is expected to be short (stragglers, refits): neither the non-zero rows nor one of their launch orders
+static inline int rows_few(const Pipe &P, const Rows &rw) {
+    return (rw.rows && rw.rows != P.rows_nz && rw.rows != P.rows_lpt && rw.rows != P.rows_rev) ? 1 : 0;
+}
 
 // the fields the parameter blocks of the fit kernels share (everything else zero): shape, counts, normalization factors,
 // the weights of this launch when the analysis has any, the rows
@@ -742,13 +817,75 @@ static int launch_optim(Pipe &P, int cnt_optim, const int32_t *y, const double *
     return DSQ_OK;
 }
 
-// the rows of a full-size launch in longest-expected-first order (see lpt_order_kernel); DSQ_LPT=0 switches it off
-static Rows lpt_rows(Pipe &P, const Rows &rw, const int32_t *key_i, const double *key_d, int small_first = 0) {
-    // only where it pays: below ~ 5 genes per resident wave slot (measured, C3 shapes: 6 250 genes fit_beta 0.305 -> 0.256 ms;
-    // 50 000 genes: the launch gains 0.03 ms and the one-workgroup sort in front of it costs 0.1)
-    if (!tuning().lpt || rw.rows != P.rows_nz || P.n > tuning().lpt_maxn) return rw;
-    hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, P.st, rw, key_i, key_d, small_first, P.rows_lpt);
-    return Rows{P.rows_lpt, rw.n_dev, rw.n};
+// ---- launch orders, host half (see lpt_scatter_kernel) -----------------------------------------------------------
+// DSQ_LPT=0 switches every order off.  Only the full-size launches of the main chain are ordered (the non-zero rows), and
+// only from 256 samples: the drain an order can recover is about one slow gene's time, which grows with the row length, and
+// an order costs 0.01 ms -- at C2 (20 000 genes, m = 100) the test's fit gains 0.004 ms by its best key and no other launch
+// gains anything (DSQ_LPT=2: whatever the row length; the tests order their small inputs that way).  The key of each launch
+// is a Tuning field (DSQ_LPT_KEY1 / _KEYD / _KEYM / _KEY2), its default the one that measured best at 50 000, 20 000 and
+// 6 250 genes of C3 (m = 500) and at C2 / C4 (profiles/launch_order.md), list order where no key separated from it:
+//   gene-wise fit_beta   ascending baseMean (C3: 1.25 -> 1.19 ms at 50 000 genes, 0.60 -> 0.50 at 20 000, 0.30 -> 0.20 at 6 250)
+//   gene-wise fit_disp   descending baseMean for rows of 256 .. 1024 samples without weights (C3: 2.48 -> 2.45 ms, 1.23 -> 1.10
+//                        at 20 000 genes).  The same order LOSES 0.035 of 0.39 ms at C2 (m = 100) and 0.4 of 11.1 ms at C4
+//                        (m = 2000, rows through L2): list order there; with weights the search does not run over the
+//                        distinct counts, which is what the mean stands for
+//   MAP fit_disp         descending baseMean up to DSQ_LPT_MAXN = 16 384 genes (0.40 -> 0.37 ms at 6 250); from 20 000 genes no
+//                        key of the four tried separates from list order, and at 50 000 all four are slower
+//   test's fit_beta      ascending baseMean (C3: 1.27 -> 1.22 ms; by the first fit's iterations 1.23; C4: 5.88 -> 5.76)
+constexpr int kLptBuilds = 3;          // per call: the gene-wise phase's list (both directions), the MAP search's, the test's fit's
+static bool lpt_applies(const Pipe &P, const Rows &rw) {
+    return tuning().lpt && rw.rows == P.rows_nz && P.lpt_bins && (tuning().lpt >= 2 || P.m >= 256);
+}
+static LptKey lpt_key(const Pipe &P, int kind) {
+    LptKey k = {kind, nullptr, nullptr, nullptr};
+    switch (kind) {
+    case LPT_MEAN_UP: case LPT_MEAN_DOWN: k.kd = P.o->baseMean; break;
+    case LPT_ITER: k.ki = P.iter; break;                               // the gene-wise search's
+    case LPT_ITER_F64: k.kd = P.beta_iter; break;                      // the gene-wise IRLS's
+    case LPT_ITER_MEAN: k.ki = P.iter; k.kd = P.o->baseMean; break;
+    case LPT_DIST: k.kd = P.la_init; k.kd2 = P.log_dfit; break;        // start value against prior mean
+    default: k.kind = LPT_NONE;
+    }
+    return k;
+}
+static const char *lpt_key_name(int kind) {
+    static const char *const nm[] = {"none", "baseMean ascending", "baseMean descending", "dispersion iterations", "IRLS iterations",
+                                     "dispersion iterations x log2 mean", "|start - prior mean|"};
+    return kind >= 0 && kind <= LPT_DIST ? nm[kind] : "?";
+}
+// the rule kernel in front of the launch builds the histogram: its parameter block gets the key and a zeroed bin block
+static void lpt_arm(Pipe &P, RuleParams &q, int kind) {
+    q.lpt = lpt_key(P, kind);
+    if (q.lpt.kind == LPT_NONE || P.lpt_next >= kLptBuilds) { q.lpt.kind = LPT_NONE; return; }
+    q.lpt_bins = P.lpt_bins + (size_t)2 * kLptBins * P.lpt_next++;
+}
+// DSQ_VERBOSE only: one look at a list the chain has built -- a permutation of the launch's rows? -- and one line per launch
+static int lpt_verbose(Pipe &P, const char *launch, const char *key, const Rows &rw, const int32_t *list) {
+    if (!getenv("DSQ_VERBOSE")) return DSQ_OK;
+    DSQ_HIP(hipStreamSynchronize(P.st));
+    int cnt = 0;
+    DSQ_HIP(hipMemcpy(&cnt, rw.n_dev, sizeof cnt, hipMemcpyDeviceToHost));
+    if (cnt < 0 || cnt > P.n) return capi_fail(DSQ_ERR_DEVICE, "launch order of %s: %d rows of %d", launch, cnt, P.n);
+    std::vector<int32_t> a((size_t)cnt), b((size_t)cnt);
+    if (cnt) {
+        DSQ_HIP(hipMemcpy(a.data(), rw.rows, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
+        DSQ_HIP(hipMemcpy(b.data(), list, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    std::sort(a.begin(), a.end());
+    std::sort(b.begin(), b.end());
+    if (a != b) return capi_fail(DSQ_ERR_DEVICE, "launch order of %s (key: %s): the list is no permutation of the %d rows", launch, key, cnt);
+    fprintf(stderr, "[dsq] launch order: %s by %s, %d rows, permutation ok\n", launch, key, cnt);
+    return DSQ_OK;
+}
+// the second pass: the rows of `rw` by the key of `q` (armed, histogram built by the rule kernel) -> rows_lpt, and backwards
+// -> rev
+static int lpt_scatter(Pipe &P, const Rows &rw, const RuleParams &q, int32_t *rev) {
+    capi_prof_begin("lpt_order", P.n, P.st);
+    hipLaunchKernelGGL(lpt_scatter_kernel, ew_grid(P.n), dim3(256), 0, P.st, rw, q.lpt, (const int *)q.lpt_bins, q.lpt_bins + kLptBins,
+                       P.rows_lpt, rev);
+    capi_prof_end(P.st);
+    DSQ_HIP(hipGetLastError());
+    return DSQ_OK;
 }
 
 // estimateDispersionsGeneEst on the rows `rw` of the count matrix y (R/core.R:657-860, niter = 1); mu-hat -> mu_hat
@@ -756,8 +893,17 @@ static int gene_est(Pipe &P, const Rows &rw, const int32_t *y, double *mu_hat, i
                     int32_t *optim_flag) {
     const DsqDeseqArgs *a = P.a;
     RuleParams q = rule_params(P, rw);
+    // one list by ascending baseMean for the IRLS, read backwards for the search
+    const bool ord_beta = lpt_applies(P, rw) && !a->linearMu && tuning().lpt_key1 != 0;
+    const bool ord_disp = lpt_applies(P, rw) && (tuning().lpt_keyd == 2 || (tuning().lpt_keyd == 1 && P.m >= 256 && P.m <= 1024 && !a->useWeights));
+    if (ord_beta || ord_disp) lpt_arm(P, q, LPT_MEAN_UP);
     hipLaunchKernelGGL(alpha_init_kernel, ew_grid(P.n), dim3(256), 0, P.st, q);
     int rc;
+    const bool ordered = q.lpt.kind != LPT_NONE;
+    int32_t *rev = (ordered && ord_disp) ? P.rows_grid : nullptr;        // (free until gene_est_post_kernel lists the stragglers)
+    if (ordered && (rc = lpt_scatter(P, rw, q, rev))) return rc;
+    const Rows up = {P.rows_lpt, rw.n_dev, rw.n}, down = {rev, rw.n_dev, rw.n};
+    q.lpt.kind = LPT_NONE;
     if (a->linearMu) {
         bool ok = false;
         capi_prof_begin("linear_mu", P.n, P.st);
@@ -769,8 +915,9 @@ static int gene_est(Pipe &P, const Rows &rw, const int32_t *y, double *mu_hat, i
         // to the optim fallback are flagged for the caller
         // (the arguments of THIS fitNbinomGLMs call are its defaults -- betaTol 1e-8, maxit 100, QR, the IRLS's own minmu
         // 0.5, R/core.R:755-757; the caller's minmu is the FLOOR of the fitted means it hands to the search, :763)
-        // (small launches: the rows with the fewest counts first -- they take the most iterations; see lpt_order_kernel)
-        rc = launch_fit_beta(P, lpt_rows(P, rw, nullptr, P.o->baseMean, 1), y, P.alpha_init, a->weights_norm, mu_hat, P.ge_floor, nullptr,
+        // (the rows with the fewest counts first -- they take the most iterations; see lpt_scatter_kernel)
+        if (ordered && ord_beta && (rc = lpt_verbose(P, "gene-wise fit_beta", lpt_key_name(LPT_MEAN_UP), rw, up.rows))) return rc;
+        rc = launch_fit_beta(P, (ordered && ord_beta) ? up : rw, y, P.alpha_init, a->weights_norm, mu_hat, P.ge_floor, nullptr,
                              1e-8, 100, 1, 0.5, "fit_beta");
         if (rc) return rc;
         RuleParams b = rule_params(P, rw);
@@ -781,7 +928,10 @@ static int gene_est(Pipe &P, const Rows &rw, const int32_t *y, double *mu_hat, i
         rc = launch_optim(P, cnt_optim, y, P.alpha_init, a->weights_norm, 0.5, P.ge_floor, P.opt_beta, P.opt_se, P.opt_ll, mu_hat);
         if (rc) return rc;
     }
-    rc = launch_fit_disp(P, rw, y, mu_hat, P.la0, P.la0, false, a->weights_floor, a->useCR != 0, false, "fit_disp");
+    if (rev && (rc = lpt_verbose(P, "gene-wise fit_disp", lpt_key_name(LPT_MEAN_DOWN), rw, rev))) return rc;
+    P.rows_rev = rev;
+    rc = launch_fit_disp(P, rev ? down : rw, y, mu_hat, P.la0, P.la0, false, a->weights_floor, a->useCR != 0, false, "fit_disp");
+    P.rows_rev = nullptr;
     if (rc) return rc;
     q.grid_count = P.counters + cnt_grid;
     hipLaunchKernelGGL(gene_est_post_kernel, ew_grid(P.n), dim3(256), 0, P.st, q);
@@ -797,16 +947,29 @@ static int gene_est(Pipe &P, const Rows &rw, const int32_t *y, double *mu_hat, i
 static int map_est(Pipe &P, const Rows &rw, const int32_t *y, const double *mu_hat, int cnt_grid) {
     const DsqDeseqArgs *a = P.a;
     RuleParams q = rule_params(P, rw);
+    const int keym = (lpt_applies(P, rw) && (tuning().lpt_maxn <= 0 || P.n <= tuning().lpt_maxn)) ? tuning().lpt_keym : 0;
+    if (keym) lpt_arm(P, q, keym);
     hipLaunchKernelGGL(map_init_kernel, ew_grid(P.n), dim3(256), 0, P.st, q);
-    // (no longest-first order here: the gene-wise search's iteration count does not predict the MAP search's -- other start
-    //  value, the prior --; measured at 6 250 genes: 0.435 ms either way)
-    int rc = launch_fit_disp(P, rw, y, mu_hat, P.la_init, P.log_dfit, true, a->weights_norm, a->useCR != 0, false, "fit_disp");
+    int rc;
+    const bool ordered = q.lpt.kind != LPT_NONE;
+    if (ordered && ((rc = lpt_scatter(P, rw, q, nullptr)) || (rc = lpt_verbose(P, "MAP fit_disp", lpt_key_name(q.lpt.kind), rw, P.rows_lpt)))) return rc;
+    q.lpt.kind = LPT_NONE;
+    rc = launch_fit_disp(P, ordered ? Rows{P.rows_lpt, rw.n_dev, rw.n} : rw, y, mu_hat, P.la_init, P.log_dfit, true, a->weights_norm,
+                         a->useCR != 0, false, "fit_disp");
     if (rc) return rc;
     q.grid_count = P.counters + cnt_grid;
     hipLaunchKernelGGL(map_post_kernel, ew_grid(P.n), dim3(256), 0, P.st, q);
     Rows gr = {P.rows_grid, P.counters + cnt_grid, P.n};
     rc = launch_fit_disp(P, gr, y, mu_hat, P.la_init, P.log_dfit, true, a->weights_norm, true, true, "fit_disp_grid");   // useCR = TRUE, :1061
     if (rc) return rc;
+    // the test's fit follows on the same rows (test_fit): its order's histogram is this kernel's.  The key: baseMean as for
+    // the gene-wise fit, or (DSQ_LPT_KEY2 = 0) the iteration counts of the gene-wise estimate's IRLS when that fit ran
+    P.lpt_test.kind = LPT_NONE;
+    if (lpt_applies(P, rw) && !a->betaPrior && tuning().lpt_key2 != 2) {
+        const int kind = tuning().lpt_key2 == 1 ? LPT_MEAN_UP : (a->linearMu ? LPT_NONE : LPT_ITER_F64);
+        lpt_arm(P, q, kind);
+        P.lpt_test = q.lpt; P.lpt_test_bins = q.lpt_bins;
+    }
     hipLaunchKernelGGL(map_final_kernel, ew_grid(P.n), dim3(256), 0, P.st, q);
     DSQ_HIP(hipGetLastError());
     return DSQ_OK;
@@ -932,15 +1095,21 @@ static int test_fit(Pipe &P, const Rows &rw, const int32_t *y, double *mu_out, d
     const DsqDeseqArgs *a = P.a;
     const DsqDeseqOut *o = P.o;
     if (a->betaPrior) return mle_fit(P, rw, y, mu_out, hat);         // (the prior fit follows once lambda is known)
-    // (P.beta_iter: the iteration counts of the gene-wise estimate's IRLS on the same rows, when that fit ran)
-    const bool by_mean = tuning().lpt_key2 == 1;
+    // (the order map_est has prepared for this launch)
+    const bool ordered = P.lpt_test.kind != LPT_NONE && rw.rows == P.rows_nz;
+    int rc;
+    if (ordered) {
+        RuleParams q = rule_params(P, rw);
+        q.lpt = P.lpt_test; q.lpt_bins = P.lpt_test_bins;
+        P.lpt_test.kind = LPT_NONE;
+        if ((rc = lpt_scatter(P, rw, q, nullptr)) || (rc = lpt_verbose(P, "test fit_beta", lpt_key_name(q.lpt.kind), rw, P.rows_lpt))) return rc;
+    }
     // (the main chain's fit, when the outlier phase wants the candidate rows first and this fit runs on the kernel that knows
     //  the bound: the flags go to the grid flags, free between the MAP search and the refit's -- not beside nbinomLRT's
     //  reduced fit, which counts its optim rows there)
     const bool cand = P.outlier_first && !P.tag[0] && hat && !(a->test == 1 && a->x_red) && fit_beta_on_cells(P.pk, P.ncell);
-    int rc = launch_fit_beta(P, by_mean ? lpt_rows(P, rw, nullptr, o->baseMean, 1) : (a->linearMu ? rw : lpt_rows(P, rw, nullptr, P.beta_iter)),
-                             y, o->dispersion, a->weights_norm, mu_out, 0.0, hat,
-                             P.t_tol, P.t_maxit, P.t_useQR, P.t_minmu, "fit_beta", DES_FULL, cand);
+    rc = launch_fit_beta(P, ordered ? Rows{P.rows_lpt, rw.n_dev, rw.n} : rw, y, o->dispersion, a->weights_norm, mu_out, 0.0, hat,
+                         P.t_tol, P.t_maxit, P.t_useQR, P.t_minmu, "fit_beta", DES_FULL, cand);
     if (rc) return rc;
     if (cand) P.cand_ready = true;
     LogLikeKernelParams lk = loglike_params(P, rw, y, mu_out, o->logLike);
@@ -1170,9 +1339,11 @@ static int bind(Pipe &P, const DsqDeseqArgs *a, const DsqDeseqOut *o, hipStream_
         if (c2 > cscr_d) cscr_d = c2;
     }
     void *b;
-    int rc = capi_ws_get(DSQ_WS_PIPE_SCRATCH, (slab_d + cscr_d) * sizeof(double) + 64, &b);
+    const size_t lpt_bytes = tuning().lpt ? (size_t)kLptBuilds * 2 * kLptBins * sizeof(int) : 0;
+    int rc = capi_ws_get(DSQ_WS_PIPE_SCRATCH, (slab_d + cscr_d) * sizeof(double) + 64 + lpt_bytes, &b);
     if (rc) return rc;
     P.scratch = (double *)b; P.cscratch = (double *)b + slab_d;
+    P.lpt_bins = lpt_bytes ? (int *)((double *)b + slab_d + cscr_d + 8) : nullptr;
     return DSQ_OK;
 }
 
@@ -1208,6 +1379,7 @@ static int launch_init_fills(Pipe &P) {
     InitParams &ip = f.ip;
     ip.nseg = 0; f.full = false;
     f.add(P.work_counters, 64 * sizeof(int32_t), 0u);
+    if (P.lpt_bins && (a->phases & (DSQ_PH_GENE_EST | DSQ_PH_MAP_TEST))) f.add(P.lpt_bins, (size_t)kLptBuilds * 2 * kLptBins * sizeof(int), 0u);
     for (int c = 0; c < pmax; c++) {
         ip.blk[c] = c < p ? a->lambda[c] : (c < P.pk ? 1.0 : 0.0);          // (ridge 1 on the padding of a wide design)
         ip.blk[pmax + c] = (c == 0) ? 1.0 : 0.0;
