@@ -278,6 +278,21 @@ class DsqResultsOut(C.Structure):
                 ("status", C.c_void_p)]
 
 
+class DsqContrastsArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("m", C.c_int32), ("p", C.c_int32), ("K", C.c_int32), ("ld", C.c_int64), ("x", C.c_void_p),
+        ("nf", C.c_void_p), ("nf_is_vector", C.c_int32), ("alpha_hat", C.c_void_p), ("beta", C.c_void_p),
+        ("lambda_", C.c_void_p), ("weights", C.c_void_p), ("useWeights", C.c_int32), ("minmu", C.c_double),
+        ("contrasts", C.c_void_p), ("allZero", C.c_void_p), ("counts", C.c_void_p), ("sample_mask", C.c_void_p),
+        ("rule_applies", C.c_void_p), ("cell_of", C.c_void_p), ("ncell", C.c_int32),
+    ]
+
+
+class DsqContrastsOut(C.Structure):
+    _fields_ = [("log2FoldChange", C.c_void_p), ("lfcSE", C.c_void_p), ("stat", C.c_void_p), ("pvalue", C.c_void_p),
+                ("contrastAllZero", C.c_void_p)]
+
+
 DSQ_TEST = {"Wald": 0, "LRT": 1}
 DSQ_ALT = {"greaterAbs": 0, "lessAbs": 1, "greater": 2, "less": 3, "greaterAbs2014": 4}
 DSQ_RESULTS_MAX_K = 4096
@@ -312,6 +327,7 @@ EXPORTED_SYMBOLS = [
     "dsq_vst", "dsq_vst_dev", "dsq_vst_rowstats_dev",
     "dsq_rlog", "dsq_rlog_dev",
     "dsq_results", "dsq_results_dev", "dsq_results_workspace_bytes",
+    "dsq_contrasts", "dsq_contrasts_dev", "dsq_contrasts_max_m",
 ]
 
 _lib = None
@@ -387,6 +403,10 @@ def lib():
     L.dsq_results_dev.argtypes = [C.POINTER(DsqResultsArgs), C.POINTER(DsqResultsOut), C.c_void_p]
     L.dsq_results_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
     L.dsq_results_workspace_bytes.restype = C.c_int64
+    L.dsq_contrasts.argtypes = [C.POINTER(DsqContrastsArgs), C.POINTER(DsqContrastsOut)]
+    L.dsq_contrasts_dev.argtypes = [C.POINTER(DsqContrastsArgs), C.POINTER(DsqContrastsOut), C.c_void_p]
+    L.dsq_contrasts_max_m.argtypes = [C.c_int32]
+    L.dsq_contrasts_max_m.restype = C.c_int32
     L.dsq_deseq_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.dsq_deseq_workspace_bytes.restype = C.c_int64
     L.dsq_profile_get.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double)]

@@ -1761,9 +1761,9 @@ def results(dds, name=None, lfcThreshold=0, altHypothesis="greaterAbs", cooksCut
     defaults to the last coefficient.  cooksCutoff: None = qf(.99, p, m - p), False = no filter, a number = that cutoff.
     The table, the threshold tests and the adjusted p-values of every filter threshold are engine work (one launch chain
     on the device, csrc/results.hip); argument checks, the Cook's flags (core.cooksOutlier) and the choice of the threshold
-    stay here.  Not served (NotImplementedError): contrast, addMLE, format, parallel, a threshold test on a useT analysis,
-    pAdjustMethod other than "BH" / "none"."""
-    reasons = {"contrast": "cleanContrast's bookkeeping over level names is not mirrored: fit with the contrast, or pick a coefficient by name",
+    stay here.  Not served (NotImplementedError): contrast (see resultsContrasts), addMLE, format, parallel, a threshold test
+    on a useT analysis, pAdjustMethod other than "BH" / "none"."""
+    reasons = {"contrast": "contrasts are served by resultsContrasts(dds, contrasts, ...), one covariance pass for all of them",
                "addMLE": "the MLE column of a beta-prior analysis is not served", "format": "only the table is served",
                "parallel": "the adjustment is global over the genes and runs on one device", "BPPARAM": "see parallel",
                "saveCols": "only the six result columns are served", "listValues": "see contrast", "minmu": "see contrast"}
@@ -1772,6 +1772,27 @@ def results(dds, name=None, lfcThreshold=0, altHypothesis="greaterAbs", cooksCut
             raise TypeError("results() got an unexpected keyword argument '%s'" % k)
         if not (v is None or v is False or (k == "format" and v == "DataFrame")):
             raise NotImplementedError("results(%s = ): %s" % (k, reasons[k]))
+    test, _ = _results_checks(dds, lfcThreshold, altHypothesis, alpha, pAdjustMethod, test)
+    beta = np.asarray(dds.mcols["beta"])
+    names = _coef_names(dds, beta.shape[1])
+    if name is None:
+        c = beta.shape[1] - 1                                                    # lastCoefName
+    elif isinstance(name, str):
+        if name not in names:
+            raise ValueError("'%s' is not one of resultsNames(dds): %s" % (name, ", ".join(names)))
+        c = names.index(name)
+    elif isinstance(name, (int, np.integer)) and 0 <= int(name) < beta.shape[1]:
+        c = int(name)
+    else:
+        raise ValueError("the argument 'name' should be a coefficient name or a column index")   # :403-405
+    lfc, se, stat, pvalue = _stored_columns(dds, c, test)
+    return _results_tail(dds, lfc, se, stat, pvalue, lfcThreshold, altHypothesis, cooksCutoff, independentFiltering, alpha,
+                         filter, theta, pAdjustMethod, filterFun, tidy)
+
+
+def _results_checks(dds, lfcThreshold, altHypothesis, alpha, pAdjustMethod, test):
+    """the argument checks of results() (R/results.R:326-346, 464-471) that do not depend on the coefficient; returns the
+    test that is served and whether a threshold test was asked for"""
     from .fused import finish
     finish(dds)                      # (an analysis enqueued with wait = False)
     if altHypothesis not in ("greaterAbs", "lessAbs", "greater", "less", "greaterAbs2014"):
@@ -1795,19 +1816,6 @@ def results(dds, name=None, lfcThreshold=0, altHypothesis="greaterAbs", cooksCut
         raise ValueError("the LRT requires the user run nbinomLRT or DESeq(dds,test='LRT')")   # :341-343
     if lfcThreshold == 0 and altHypothesis == "lessAbs":
         raise ValueError("when testing altHypothesis='lessAbs', set the argument lfcThreshold to a positive value")   # :344-346
-    E = dds.engine
-    beta, betaSE = np.asarray(dds.mcols["beta"]), np.asarray(dds.mcols["betaSE"])
-    names = _coef_names(dds, beta.shape[1])
-    if name is None:
-        c = beta.shape[1] - 1                                                    # lastCoefName
-    elif isinstance(name, str):
-        if name not in names:
-            raise ValueError("'%s' is not one of resultsNames(dds): %s" % (name, ", ".join(names)))
-        c = names.index(name)
-    elif isinstance(name, (int, np.integer)) and 0 <= int(name) < beta.shape[1]:
-        c = int(name)
-    else:
-        raise ValueError("the argument 'name' should be a coefficient name or a column index")   # :403-405
     threshold = not (lfcThreshold == 0 and altHypothesis == "greaterAbs")
     if threshold:
         if test == "LRT":
@@ -1816,6 +1824,12 @@ def results(dds, name=None, lfcThreshold=0, altHypothesis="greaterAbs", cooksCut
             raise ValueError("testing altHypothesis='lessAbs' requires setting the DESeq() argument betaPrior=FALSE")   # :469-471
         if dds.attrs.get("useT"):
             raise NotImplementedError("a threshold test on a useT analysis: there is no Student-t distribution in the engine")
+    return test, threshold
+
+
+def _stored_columns(dds, c, test):
+    """getCoef / getCoefSE / getStat / getPvalue (R/results.R:1052-1099) of coefficient c"""
+    beta, betaSE = np.asarray(dds.mcols["beta"]), np.asarray(dds.mcols["betaSE"])
     lfc, se = beta[:, c], betaSE[:, c]
     if test == "LRT":
         stat, pvalue = dds.mcols["LRTStatistic"], dds.mcols["LRTPvalue"]
@@ -1824,7 +1838,16 @@ def results(dds, name=None, lfcThreshold=0, altHypothesis="greaterAbs", cooksCut
     else:
         with np.errstate(divide="ignore", invalid="ignore"):                     # makeWaldTest (:1101-1118) on an LRT object
             stat = lfc / se
-        pvalue = E.two_sided_normal_p(stat)
+        pvalue = dds.engine.two_sided_normal_p(stat)
+    return lfc, se, stat, pvalue
+
+
+def _results_tail(dds, lfc, se, stat, pvalue, lfcThreshold, altHypothesis, cooksCutoff, independentFiltering, alpha, filter,
+                  theta, pAdjustMethod, filterFun, tidy):
+    """what results() does with the four columns of a coefficient or of a contrast (R/results.R:520-610): the Cook's mask,
+    the replaced rows, the table (launched with the adjustment), pvalueAdjustment, the metadata.  The columns may be host
+    arrays or vectors resident in the engine."""
+    E = dds.engine
     na_mask = None
     if not (cooksCutoff is False) and "maxCooks" in dds.mcols and "dispModelMatrix" in dds.attrs:
         cut = None if (cooksCutoff is None or cooksCutoff is True) else float(cooksCutoff)     # :524-531
@@ -1877,3 +1900,236 @@ def _run_filtered_p(res, filter, theta, alpha):
         res.tab = res.engine.results(*res.tab.args, filter=filter, theta=theta, alpha=alpha)
         return res.tab
     return res.engine.filtered_p(res.tab, filter, theta, alpha)
+
+
+# ------------------------------------------------------------------ contrasts (R/results.R:760-1040, 1146-1201, 1237-1270)
+_CONTRAST_FORMS = ("'contrast' vector should be either a character vector of length 3,\n"
+                   "a list of length 2 containing character vectors,\n"
+                   "or a numeric vector, see the argument description in ?results")
+
+
+def _contrast_form(contrast):
+    """which of R's three forms a contrast is: "character" (a sequence that starts with a str: the factor's name),
+    "list" (a sequence of sequences) or "numeric"; anything else is checkContrast's first error (:1147-1151)"""
+    if isinstance(contrast, (str, bytes, dict)) or not isinstance(contrast, (list, tuple, np.ndarray)):
+        raise ValueError(_CONTRAST_FORMS)
+    if len(contrast) > 0 and isinstance(contrast[0], str):
+        return "character"
+    if len(contrast) > 0 and all(isinstance(e, (list, tuple, np.ndarray)) for e in contrast):
+        return "list"
+    try:
+        np.asarray(contrast, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(_CONTRAST_FORMS)
+    return "numeric"
+
+
+def checkContrast(contrast, resNames):
+    """checkContrast (R/results.R:1146-1201), every message; returns (form, the contrast as the later steps take it)"""
+    form = _contrast_form(contrast)
+    if form == "character":
+        if len(contrast) != 3:                                                    # :1155-1159
+            raise ValueError("'contrast', as a character vector of length 3, should have the form:\n"
+                             "contrast = c('factorName','numeratorLevel','denominatorLevel'),\n"
+                             "see the manual page of ?results for more information")
+        if contrast[1] == contrast[2]:                                            # :1160-1162
+            raise ValueError("%s and %s should be different level names" % (contrast[1], contrast[2]))
+        return form, tuple(contrast)
+    if form == "list":
+        contrast = [list(e) for e in contrast]
+        if len(contrast) == 1:                                                    # :1167-1169
+            contrast = [contrast[0], []]
+        if len(contrast) != 2:                                                    # :1170-1174
+            raise ValueError("'contrast', as a list, should have length 2, or, if length 1,\n"
+                             "an empty vector will be added for the second element.\n"
+                             "see the manual page of ?results for more information")
+        if not all(isinstance(v, str) for e in contrast for v in e):              # :1175-1178
+            raise ValueError("'contrast', as a list of length 2, should have character vectors as elements,\n"
+                             "see the manual page of ?results for more information")
+        if not all(v in resNames for e in contrast for v in e):                   # :1179-1181
+            raise ValueError("all elements of the contrast as a list of length 2 should be elements of 'resultsNames(object)'")
+        if set(contrast[0]) & set(contrast[1]):                                   # :1182-1185
+            raise ValueError("elements in the contrast list should only appear in the numerator (first element of contrast list)\n"
+                             "or the denominator (second element of contrast list), but not both")
+        if len(contrast[0]) + len(contrast[1]) == 0:                              # :1186-1188
+            raise ValueError("one of the two elements in the list should be a character vector of non-zero length")
+        return form, contrast
+    c = np.asarray(contrast, np.float64).reshape(-1)
+    if c.size != len(resNames):                                                   # :1193-1194
+        raise ValueError("numeric contrast vector should have one element for every element of 'resultsNames(object)'")
+    if (c == 0).all():                                                            # :1195-1197
+        raise ValueError("numeric contrast vector cannot have all elements equal to 0")
+    return form, c
+
+
+def _rnum(v):
+    """as.character() of a number as R prints the ones that occur here"""
+    v = float(v)
+    return "%d" % v if v == int(v) and abs(v) < 1e15 else "%.15g" % v
+
+
+def _factor_columns(dds, expanded):
+    """the columns of the fitted model matrix by (factor, level code): found by position in the matrix
+    standard_model_matrix / makeExpandedModelMatrix build from attrs["factors"]"""
+    factors = dds.attrs.get("factors")
+    numeric = "pass the contrast as a numeric vector over resultsNames(dds) instead"
+    if not factors:
+        raise ValueError('a character contrast needs dds.attrs["factors"] (the level codes of the design factors): ' + numeric)
+    xs, _ = standard_model_matrix(factors)
+    if xs.shape != dds.x.shape or not np.array_equal(xs, dds.x):
+        raise ValueError('the model matrix of the analysis is not the one attrs["factors"] generates: ' + numeric)
+    ncoef = np.shape(dds.mcols["beta"])[1]
+    if ncoef != (makeExpandedModelMatrix(factors)[0].shape[1] if expanded else xs.shape[1]):
+        raise ValueError('the fitted coefficients are not those of the matrix attrs["factors"] generates: ' + numeric)
+    cols, k = {}, 1
+    for f, codes in factors.items():
+        for lv in range(0 if expanded else 1, int(np.max(codes)) + 1):
+            cols[(f, lv)] = k
+            k += 1
+    return factors, cols
+
+
+def _contrast_model_matrix(dds):
+    """attr(object, "modelMatrix"): the matrix the coefficients were fitted on -- the expanded one on an expanded-matrix
+    analysis (R/core.R:1374-1380, R/fitNbinomGLMs.R:319-325)"""
+    if dds.attrs.get("betaPrior") and dds.attrs.get("modelMatrixType") == "expanded":
+        return makeExpandedModelMatrix(dds.attrs["factors"])[0]
+    return np.asarray(dds.x, np.float64)
+
+
+def resultsContrasts(dds, contrasts, listValues=(1, -1), minmu=0.5, lfcThreshold=0, altHypothesis="greaterAbs", cooksCutoff=None,
+                     independentFiltering=True, alpha=0.1, filter=None, theta=None, pAdjustMethod="BH", filterFun=None,
+                     test=None, tidy=False, **not_served):
+    """results(object, contrast = .) (R/results.R:375-438, 760-1040) for a SEQUENCE of contrasts: a list of DESeqResults,
+    one per contrast, in order.  Each contrast is one of R's three forms:
+      numeric    a 1-D sequence of numbers, one per element of resultsNames(dds);
+      character  (factor, numLevel, denomLevel): factor names a key of dds.attrs["factors"] (the ordered dict of level codes,
+                 0 = the reference level, that standard_model_matrix / makeExpandedModelMatrix take), the levels are codes;
+      list       one or two sequences of coefficient names, weighted by listValues.
+    getContrast re-enters fitBeta once per contrast; here ALL contrasts that need the covariance of the coefficients go
+    into ONE engine call (csrc/contrasts.hip on the device: one covariance pass per gene), and a character contrast against
+    the reference level is answered from the stored columns (:876-932) with only the all-zero flags from the engine.  Every
+    table then takes the tail of results(): Cook's mask, replaced rows, threshold tests, independent filtering, BH.
+    metadata["contrast"] is the name R builds (:968-1001).  Not served (NotImplementedError): a useT analysis, addMLE,
+    parallel."""
+    reasons = {"addMLE": "the MLE column of a beta-prior analysis is not served",
+               "parallel": "all contrasts share one covariance pass per gene on one device", "BPPARAM": "see parallel",
+               "format": "only the table is served", "saveCols": "only the six result columns are served"}
+    for k, v in not_served.items():
+        if k not in reasons:
+            raise TypeError("resultsContrasts() got an unexpected keyword argument '%s'" % k)
+        if not (v is None or v is False or (k == "format" and v == "DataFrame")):
+            raise NotImplementedError("resultsContrasts(%s = ): %s" % (k, reasons[k]))
+    test, _ = _results_checks(dds, lfcThreshold, altHypothesis, alpha, pAdjustMethod, test)
+    if dds.attrs.get("useT"):
+        raise NotImplementedError("a contrast on a useT analysis: there is no Student-t distribution in the engine")
+    lv = np.asarray(listValues, np.float64).reshape(-1)
+    if lv.size != 2:
+        raise ValueError("length(listValues) == 2 & is.numeric(listValues) is not TRUE")       # :330
+    if not (lv[0] > 0 and lv[1] < 0):
+        raise ValueError("listValues[1] > 0 & listValues[2] < 0 is not TRUE")                  # :331
+    if isinstance(contrasts, (str, bytes, dict)) or not isinstance(contrasts, (list, tuple)):
+        raise ValueError("'contrasts' should be a sequence of contrasts")
+    E = dds.engine
+    resNames = resultsNames(dds)
+    expanded = dds.attrs.get("betaPrior") and dds.attrs.get("modelMatrixType") == "expanded"   # isExpanded, :383
+    X = _contrast_model_matrix(dds)
+    if X.shape[1] != len(resNames):
+        raise ValueError("was expecting a model matrix stored as an attribute of the DESeqDataSet")   # :764-766
+    m = X.shape[0]
+    # cleanContrast for every contrast: `plan` entries are ("pull", column, sign, name, sample mask) or
+    # ("fit", numeric contrast, name, sample mask or None)
+    plan = []
+    for contrast in contrasts:
+        form, contrast = checkContrast(contrast, resNames)                        # :420
+        if form == "character":
+            f, num, den = contrast
+            if dds.attrs.get("factors") is not None and f not in dds.attrs["factors"]:
+                raise ValueError("%s should be the name of a factor in the colData of the DESeqDataSet" % f)   # :844-846
+            factors, cols = _factor_columns(dds, expanded)
+            codes = np.asarray(factors[f])
+            both = np.isin(codes, [num, den])                                     # contrastAllZeroCharacter, :1237-1243
+            name = "%s %s vs %s" % (f, num, den)                                  # :877, :901, :1001
+            # (the no-intercept branch, noInterceptPullCoef :861-862, cannot be reached: the matrix `factors` generates always
+            #  has its intercept)
+            if not expanded:                                                      # case 1, :867-941
+                if den == 0:
+                    if (f, num) not in cols:
+                        raise ValueError("as %s is the reference level, was expecting %s_%s_vs_%s to be present in "
+                                         "'resultsNames(object)'" % (den, f, num, den))   # :884-886
+                    plan.append(("pull", cols[(f, num)], 1.0, name, both))
+                    continue
+                if num == 0:
+                    if (f, den) not in cols:
+                        raise ValueError("as %s is the reference level, was expecting %s_%s_vs_%s to be present in "
+                                         "'resultsNames(object)'" % (num, f, den, num))   # :907-909
+                    plan.append(("pull", cols[(f, den)], -1.0, name, both))
+                    continue
+                if (f, num) not in cols or (f, den) not in cols:                  # :937-940
+                    raise ValueError("%s and %s should be levels of %s such that %s_%s_vs_0 and %s_%s_vs_0 are contained in "
+                                     "'resultsNames(object)'" % (num, den, f, f, num, f, den))
+            elif (f, num) not in cols or (f, den) not in cols:                    # case 2, :946-954
+                raise ValueError("%s%s and %s%s are expected to be in resultsNames(object)" % (f, num, f, den))
+            c = np.zeros(len(resNames))                                           # :997-1000
+            c[cols[(f, num)]], c[cols[(f, den)]] = 1.0, -1.0
+        elif form == "list":
+            l1, l2 = contrast
+            n1, n2 = round(float(lv[0]), 3), round(float(lv[1]), 3)               # :978-990
+            if l1 and l2:
+                n2 = abs(n2)
+                name = "%s%s vs %s%s" % ("" if n1 == 1 else _rnum(n1) + " ", "+".join(l1), "" if n2 == 1 else _rnum(n2) + " ",
+                                         "+".join(l2))
+            elif l1:
+                name = "%s%s effect" % ("" if n1 == 1 else _rnum(n1) + " ", "+".join(l1))
+            else:
+                name = "%s %s effect" % (_rnum(n2), "+".join(l2))
+            c = np.zeros(len(resNames))                                           # :991-994
+            c[[r in l1 for r in resNames]] = lv[0]
+            c[[r in l2 for r in resNames]] = lv[1]
+        else:
+            c = contrast
+            name = ",".join(("+" if v > 0 else "") + _rnum(v) for v in c)         # :969-972
+        # contrastAllZeroNumeric (:1245-1270): no rule when all coefficients share a sign; else the samples X binary(c) != 0
+        mask = None if ((c >= 0).all() or (c <= 0).all()) else (X @ (c != 0).astype(np.float64)) != 0
+        plan.append(("fit", c, name, mask))
+    allZero = np.asarray(dds.mcols["allZero"], bool)
+    fits = [e for e in plan if e[0] == "fit"]
+    pulls = [e for e in plan if e[0] == "pull"]
+    fitted = pulled = None
+    if fits:                                                                      # getContrast, :760-827, once for all of them
+        weights, useWeights = getAndCheckWeights(dds)                             # :787-795
+        ln2 = np.log(2.0)
+        bpv = np.asarray(dds.attrs.get("betaPriorVar", np.full(len(resNames), 1e6)), np.float64)
+        masks = np.array([e[3] if e[3] is not None else np.zeros(m, bool) for e in fits])
+        rule = np.array([e[3] is not None for e in fits])
+        use_sf = dds.sizeFactors is not None
+        fitted = E.contrasts(dds.y, X, None if use_sf else dds.nf, np.asarray(dds.mcols["dispersion"], np.float64),
+                             ln2 * np.asarray(dds.mcols["beta"], np.float64), 1.0 / (ln2 ** 2 * bpv),           # :775-777
+                             np.column_stack([e[1] for e in fits]), weights, useWeights, minmu, allZero,
+                             sample_mask=masks if rule.any() else None, rule_applies=rule if rule.any() else None,
+                             sizeFactors=dds.sizeFactors if use_sf else None)
+    if pulls:
+        pulled = E.contrasts(dds.y, None, None, None, None, None, None, None, False, minmu, allZero,
+                             sample_mask=np.array([e[4] for e in pulls]))
+    out, kf, kp = [], 0, 0
+    for e in plan:
+        if e[0] == "fit":
+            lfc, se, stat, pvalue = fitted.columns(kf)
+            kf += 1
+            name = e[2]
+        else:
+            lfc, se, stat, pvalue = _stored_columns(dds, e[1], test)              # :887-890, :910-913
+            if e[2] < 0:
+                lfc = -1.0 * lfc                                                  # :916
+                if test == "Wald":
+                    stat = -1.0 * stat                                            # :917
+            lfc, stat, pvalue = E.zero_rule(lfc, stat, pvalue, pulled.flags(kp))  # :1023-1028
+            kp += 1
+            name = e[3]
+        if test == "LRT":                                                         # :1030-1037
+            stat, pvalue = dds.mcols["LRTStatistic"], dds.mcols["LRTPvalue"]
+        res = _results_tail(dds, lfc, se, stat, pvalue, lfcThreshold, altHypothesis, cooksCutoff, independentFiltering, alpha,
+                            filter, theta, pAdjustMethod, filterFun, tidy)
+        res.metadata["contrast"] = name
+        out.append(res)
+    return out

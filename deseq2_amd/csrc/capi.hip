@@ -863,6 +863,54 @@ int results_dev_locked(const DsqResultsArgs *a, const DsqResultsOut *o, hipStrea
     return DSQ_OK;
 }
 
+// contrasts (contrasts.hip): what both entries check; a pointer is needed only by the mode that reads it (contrasts == NULL:
+// the all-zero flags alone)
+int contrasts_check(const DsqContrastsArgs *a, const DsqContrastsOut *o) {
+    DSQ_NEED(a && o, "NULL args/out");
+    if (a->n < 0 || a->m < 1 || a->p < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions n=%d m=%d p=%d", a->n, a->m, a->p);
+    if (a->K < 1) return capi_fail(DSQ_ERR_ARG, "K = %d: at least one contrast is needed", a->K);
+    DSQ_NEED(a->contrasts || a->sample_mask, "neither contrasts nor sample_mask given");
+    DSQ_NEED(!a->contrasts || (a->x && a->nf && a->alpha_hat && a->beta && a->lambda), "NULL input array");
+    DSQ_NEED(!a->contrasts || !a->useWeights || a->weights, "useWeights set but weights is NULL");
+    DSQ_NEED(!a->sample_mask || a->counts, "sample_mask given without counts");
+    DSQ_NEED(!a->sample_mask || a->rule_applies, "sample_mask given without rule_applies");
+    DSQ_NEED(!a->contrasts || (o->log2FoldChange && o->lfcSE && o->stat && o->pvalue), "NULL output array");
+    DSQ_NEED(!a->sample_mask || o->contrastAllZero, "sample_mask given but contrastAllZero is NULL");
+    return a->p > DSQ_P_WIDE ? too_wide(a->p) : DSQ_OK;
+}
+
+int contrasts_dev_locked(const DsqContrastsArgs *a, const DsqContrastsOut *o, hipStream_t st) {
+    if (int rc = contrasts_check(a, o)) return rc;
+    if (a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld = %ld < m = %d", (long)a->ld, a->m);
+    if (int rc = capi_check_device()) return rc;
+    if (a->n == 0) return DSQ_OK;
+    ContrastsKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.m = a->m; kp.p = a->p; kp.K = a->K; kp.ld = (long)a->ld;
+    kp.x = a->x; kp.nf = a->nf; kp.nf_is_vector = a->nf_is_vector ? 1 : 0;
+    kp.alpha_hat = a->alpha_hat; kp.beta = a->beta; kp.lambda = a->lambda;
+    kp.useWeights = a->useWeights ? 1 : 0;
+    kp.weights = kp.useWeights ? a->weights : nullptr;
+    kp.minmu = a->minmu;
+    kp.contrasts = a->contrasts; kp.allZero = a->allZero;
+    kp.counts = a->sample_mask ? a->counts : nullptr;
+    kp.sample_mask = a->sample_mask; kp.rule_applies = a->sample_mask ? a->rule_applies : nullptr;
+    kp.lfc = o->log2FoldChange; kp.se = o->lfcSE; kp.stat = o->stat; kp.pvalue = o->pvalue; kp.flags = o->contrastAllZero;
+    // the Gram sums' form is the one dsq_fit_beta_dev takes for this design (fit_beta_on_cells at the kernel width)
+    const int pk = is_wide(a->p) ? wide_width(a->p) : a->p;
+    if (a->contrasts && a->cell_of && a->ncell > 0 && fit_beta_on_cells(pk, 1)) {
+        const int C = capi_upload_cells(a->cell_of, a->m, WS_CELLS_BETA, st, &kp.cell_perm, &kp.cell_start);
+        kp.ncell = fit_beta_on_cells(pk, C) ? C : 0;
+    }
+    bool ok = false;
+    capi_prof_begin("contrasts", a->n, st);
+    DSQ_HIP(launch_contrasts(kp, st, &ok));
+    capi_prof_end(st);
+    if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "rows of m=%d samples at p=%d: the per-sample path takes at most %d", a->m, a->p,
+                              contrasts_max_m(a->p));
+    return DSQ_OK;
+}
+
 }  // namespace dsq
 
 using namespace dsq;
@@ -892,6 +940,7 @@ DSQ_DEV(dsq_vst_dev, DsqVstArgs, const DsqVstOut *, vst_dev_locked(a, o, true, f
 DSQ_DEV(dsq_vst_rowstats_dev, DsqVstArgs, const DsqVstOut *, vst_dev_locked(a, o, false, true, st))
 DSQ_DEV(dsq_rlog_dev, DsqRlogArgs, const DsqRlogOut *, rlog_dev_locked(a, o, st))
 DSQ_DEV(dsq_results_dev, DsqResultsArgs, const DsqResultsOut *, results_dev_locked(a, o, st))
+DSQ_DEV(dsq_contrasts_dev, DsqContrastsArgs, const DsqContrastsOut *, contrasts_dev_locked(a, o, st))
 #undef DSQ_DEV
 int dsq_linear_mu_dev(const DsqPrefitArgs *a, double mu_floor, double *mu, void *s) {
     return dev_entry(s, [&](hipStream_t st) { return linear_mu_dev_locked(a, mu_floor, mu, st); });
@@ -914,6 +963,8 @@ int64_t dsq_size_factors_workspace_bytes(int32_t n, int32_t m) {
     if (n < 0 || m < 0) return 0;
     return (int64_t)size_factors_workspace_bytes(n, m);
 }
+
+int32_t dsq_contrasts_max_m(int32_t p) { return contrasts_max_m(p); }
 
 int64_t dsq_results_workspace_bytes(int32_t n, int32_t K) {
     if (n < 0 || K < 0) return 0;

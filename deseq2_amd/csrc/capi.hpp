@@ -48,6 +48,7 @@ int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o);
 int vst_check(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats);
 int rlog_check(const DsqRlogArgs *a, const DsqRlogOut *o);
 int results_check(const DsqResultsArgs *a, const DsqResultsOut *o);
+int contrasts_check(const DsqContrastsArgs *a, const DsqContrastsOut *o);
 int check_host_layout(int layout);
 // the device-pointer bodies behind the entry points
 int fit_beta_dev_locked(const DsqFitBetaArgs *a, const DsqFitBetaOut *o, hipStream_t st);
@@ -63,5 +64,6 @@ int size_factors_dev_locked(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *
 int vst_dev_locked(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats, hipStream_t st);
 int rlog_dev_locked(const DsqRlogArgs *a, const DsqRlogOut *o, hipStream_t st);
 int results_dev_locked(const DsqResultsArgs *a, const DsqResultsOut *o, hipStream_t st);
+int contrasts_dev_locked(const DsqContrastsArgs *a, const DsqContrastsOut *o, hipStream_t st);
 
 }  // namespace dsq

@@ -848,4 +848,52 @@ int dsq_results(const DsqResultsArgs *a, const DsqResultsOut *o) {
     return s.finish();
 }
 
+int dsq_contrasts(const DsqContrastsArgs *a, const DsqContrastsOut *o) {
+    HostCall hc;
+    DSQ_TRY(host_ready(contrasts_check(a, o), DSQ_LAYOUT_R));
+    if (a->n == 0) return DSQ_OK;
+    hipStream_t st = hc.st;
+    const size_t n = a->n, m = a->m, p = a->p, K = a->K;
+    const long ld = round_ld(a->m);
+    DsqContrastsArgs d = *a;
+    DsqContrastsOut od = *o;
+    d.ld = ld;
+    std::vector<int32_t> labels;
+    Stage s(st, n);
+    const void *g;
+    if (a->sample_mask) {
+        DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->counts, 4, a->n, a->m, ld, &g));
+        d.counts = (const int32_t *)g;
+        s.vec(&d.sample_mask, a->sample_mask, K * m * 4);
+        s.vec(&d.rule_applies, a->rule_applies, K * 4);
+    }
+    if (a->allZero) s.vec(&d.allZero, a->allZero, n * 4);
+    if (a->contrasts) {
+        host_cells(a->x, a->m, a->p, a->cell_of, a->ncell, &labels, &d.cell_of, &d.ncell);
+        if (a->nf_is_vector) DSQ_TRY(s.nf_up(&d.nf, a->nf, 1, m));
+        else {
+            DSQ_TRY(up_gene_major(s, WS_H_NF, WS_NF, a->nf, 8, a->n, a->m, ld, &g));
+            d.nf = (const double *)g;
+        }
+        if (a->useWeights) {
+            DSQ_TRY(up_gene_major(s, WS_H_W, WS_W, a->weights, 8, a->n, a->m, ld, &g));
+            d.weights = (const double *)g;
+        }
+        s.vec(&d.x, a->x, m * p * 8);
+        s.vec(&d.alpha_hat, a->alpha_hat, n * 8);
+        s.vec(&d.beta, a->beta, n * p * 8);
+        s.vec(&d.lambda, a->lambda, p * 8);
+        s.vec(&d.contrasts, a->contrasts, p * K * 8);
+        s.out_vec(&od.log2FoldChange, o->log2FoldChange, n * K * 8);
+        s.out_vec(&od.lfcSE, o->lfcSE, n * K * 8);
+        s.out_vec(&od.stat, o->stat, n * K * 8);
+        s.out_vec(&od.pvalue, o->pvalue, n * K * 8);
+    }
+    DSQ_TRY(s.pack_in());
+    if (o->contrastAllZero) s.out_vec(&od.contrastAllZero, o->contrastAllZero, n * K * 4);
+    DSQ_TRY(s.pack_out());
+    DSQ_TRY(contrasts_dev_locked(&d, &od, st));
+    return s.finish();
+}
+
 }  // extern "C"

@@ -294,6 +294,28 @@ struct ResultsKernelParams {
 hipError_t launch_results(ResultsKernelParams kp, void *workspace, hipStream_t st);
 size_t results_sort_workspace_bytes(long n);     // the sort's part; filtPadj (n K doubles) may follow it
 
+// K contrasts from one covariance pass per gene (contrasts.hip).  n x m matrices gene-major with
+// leading dimension ld, n x p / n x K matrices column-major; ncell > 0 selects the cell-collapsed Gram sums (cell_perm,
+// cell_start as in BetaKernelParams); contrasts == nullptr: the all-zero flags only.
+struct ContrastsKernelParams {
+    int n, m, p, K;
+    long ld;
+    const double *x, *nf;
+    int nf_is_vector;
+    const double *alpha_hat, *beta, *lambda, *weights;
+    int useWeights;
+    double minmu;
+    const double *contrasts;
+    const int32_t *allZero, *counts, *sample_mask, *rule_applies;
+    const int32_t *cell_perm, *cell_start;
+    int ncell;
+    double *lfc, *se, *stat, *pvalue;
+    int32_t *flags;
+};
+// rows of more than contrasts_max_m(p) samples do not fit the per-sample path (*ok = false, nothing launched)
+hipError_t launch_contrasts(const ContrastsKernelParams &kp, hipStream_t st, bool *ok);
+int contrasts_max_m(int p);
+
 // gene index of work item i, and the number of work items, of a (possibly row-listed) launch
 #define DSQ_NWORK(kp) ((kp).n_dev ? *(kp).n_dev : (kp).n)
 #define DSQ_GENE(kp, i) ((kp).rows ? (kp).rows[i] : (i))

@@ -171,6 +171,22 @@ class ResultColumns:
         return np.array(self._padj(int(j)), copy=True)
 
 
+class ContrastColumns:
+    """What an engine's contrasts() returns: the four n x K columns log2FoldChange, lfcSE, stat, pvalue (None in flags-only
+    mode) and the n x K contrastAllZero flags, where the engine made them -- numpy arrays (n, K) on the host engine, device
+    tensors (K, n) on the device engine.  columns(k) / flags(k): the n-vectors of contrast k, still resident."""
+    NAMES = ("log2FoldChange", "lfcSE", "stat", "pvalue")
+
+    def __init__(self, table, flag_matrix, pick):
+        self.table, self.flag_matrix, self._pick = table, flag_matrix, pick
+
+    def columns(self, k):
+        return tuple(self._pick(t, k) for t in self.table)
+
+    def flags(self, k):
+        return self._pick(self.flag_matrix, k)
+
+
 class HostEngine:
     name = "host"
 
@@ -428,6 +444,61 @@ class HostEngine:
                 altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1):
         return self.filtered_p(self.results_table(lfc, se, stat, pvalue, baseMean, replace, na_mask, lfcThreshold,
                                                   altHypothesis), filter, theta, alpha)
+
+    # ---- contrasts (R/results.R:760-827, 1021-1028, 1237-1270): the statement csrc/contrasts.hip equals
+    def contrasts(self, y, x, nf, alpha_hat, beta, lam, contrasts, weights, useWeights, minmu, allZero, sample_mask=None,
+                  rule_applies=None, sizeFactors=None):
+        """K contrasts of the fitted coefficients.  y: the ORIGINAL counts handle (read by the masks only), x: the model
+        matrix the coefficients were fitted on (m x p), nf: the normalization-factor handle (or None with sizeFactors),
+        alpha_hat (n), beta (n x p, natural-log scale), lam (p, natural-log scale), contrasts (p x K, or None: flags
+        only), weights: the normalised handle, allZero (n flags), sample_mask (K x m of 0 / 1) with rule_applies (K).
+        getContrast per contrast -- fitBeta(maxit = 0) on the rows that are not all zero --, log2(exp(1)) on both members,
+        the quotient, the two-sided normal p-value, NA rows, then the all-zero rule.  Returns ContrastColumns."""
+        allZero = np.asarray(allZero, bool)
+        n, live = allZero.size, ~np.asarray(allZero, bool)
+        K = np.shape(contrasts)[1] if contrasts is not None else np.shape(sample_mask)[0]
+        flags = np.zeros((n, K), bool)
+        if sample_mask is not None:
+            cnt = np.asarray(y)
+            rule = np.ones(K, bool) if rule_applies is None else np.asarray(rule_applies, bool)
+            for k in range(K):
+                if rule[k]:
+                    sel = np.asarray(sample_mask[k]) != 0
+                    flags[:, k] = live & ~(cnt[:, sel] != 0).any(axis=1)                  # :1242, :1268-1269, :1023
+        pick = lambda a, k: a[:, k]
+        if contrasts is None:
+            return ContrastColumns(None, flags, pick)
+        contrasts = np.asarray(contrasts, np.float64)
+        x = np.asarray(x, np.float64)
+        nz = np.where(live)[0]
+        m = x.shape[0]
+        nfm = np.asarray(nf) if nf is not None else np.broadcast_to(np.asarray(sizeFactors, np.float64)[None, :], (n, m))
+        ynz = np.asfortranarray(np.asarray(y)[nz])
+        nfnz = np.asfortranarray(nfm[nz])
+        wnz = np.asfortranarray(np.asarray(weights)[nz]) if useWeights else None
+        anz, bnz = np.asarray(alpha_hat, np.float64)[nz], np.asfortranarray(np.asarray(beta, np.float64)[nz])
+        LOG2E = np.log2(np.e)                                                            # log2(exp(1)), :809-810
+        table = [np.full((n, K), np.nan) for _ in range(4)]
+        for k in range(K):
+            if nz.size == 0:
+                break
+            r = self.fit_beta(ynz, x, nfnz, anz, contrasts[:, k], bnz, lam, wnz, useWeights, 1e-8, 0, False, minmu,
+                              want_mu=False, want_hat=False)                              # :797-807
+            lfc = LOG2E * np.asarray(r["contrast_num"]).reshape(-1)
+            se = LOG2E * np.asarray(r["contrast_denom"]).reshape(-1)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                stat = lfc / se
+            pv = self.two_sided_normal_p(stat)                                           # :817
+            for t, v in zip(table, (lfc, se, stat, pv)):
+                t[nz, k] = v                                                             # buildDataFrameWithNARows, :823
+            z = flags[:, k]
+            table[0][z, k], table[2][z, k], table[3][z, k] = 0.0, 0.0, 1.0               # :1024-1028
+        return ContrastColumns(table, flags, pick)
+
+    def zero_rule(self, lfc, stat, pvalue, flag):
+        """res$log2FoldChange[contrastAllZero] <- 0, stat <- 0, pvalue <- 1 (R/results.R:1024-1028) on columns of the host"""
+        flag = np.asarray(flag, bool)
+        return (np.where(flag, 0.0, lfc), np.where(flag, 0.0, stat), np.where(flag, 1.0, pvalue))
 
     # ---- count outliers (R/core.R:2333-2359, 2069-2115)
     def cooks_distance(self, y, nf, mu, H, x):
@@ -829,6 +900,46 @@ class DeviceEngine:
                            alpha=alpha)
         tab.numRej, tab.cutoffs, tab._padj = new.numRej, new.cutoffs, new._padj
         return tab
+
+    # ---- contrasts: ONE launch of csrc/contrasts.hip on the resident data; the n x K columns stay in HBM
+    def contrasts(self, y, x, nf, alpha_hat, beta, lam, contrasts, weights, useWeights, minmu, allZero, sample_mask=None,
+                  rule_applies=None, sizeFactors=None):
+        """HostEngine.contrasts through dsq_contrasts_dev.  What goes up: the n-vectors, the n x p coefficients, the
+        contrasts and the masks; nothing comes down -- ContrastColumns holds (K, n) device tensors."""
+        t = self.torch
+        i32 = lambda v: t.as_tensor(np.ascontiguousarray(np.asarray(v) != 0, dtype=np.int32), device=self.device)
+        az = i32(allZero)
+        mask = rule = None
+        if sample_mask is not None:
+            K = int(np.shape(sample_mask)[0])
+            mask = i32(sample_mask)
+            rule = i32(np.ones(K) if rule_applies is None else rule_applies)
+        pick = lambda a, k: a[k]
+        if contrasts is None:
+            r = self._timed("contrasts", y.n, lambda: self.native.contrasts_dev(
+                None, None, None, None, None, None, allZero=az, counts=y, sample_mask=mask, rule_applies=rule))
+            return ContrastColumns(None, r["contrastAllZero"], pick)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        xd = self.design(x)
+        n, p = y.n, x.shape[1]
+        with np.errstate(invalid="ignore"):
+            dv = self._vec(np.concatenate([np.asarray(alpha_hat, np.float64).reshape(-1), np.asarray(lam, np.float64).reshape(-1),
+                                           np.asarray(beta, np.float64).T.reshape(-1),
+                                           np.asarray(contrasts, np.float64).T.reshape(-1)]))        # one upload
+        K = int(np.shape(contrasts)[1])
+        av, lv, bv, cv = dv[:n], dv[n:n + p], dv[n + p:n + p + n * p].view(p, n), dv[n + p + n * p:].view(K, p)
+        nfh, is_vec = (self._sf_dev(sizeFactors), True) if sizeFactors is not None else (nf, False)
+        r = self._timed("contrasts", n, lambda: self.native.contrasts_dev(
+            xd, nfh, av, bv, lv, cv, weights=weights, useWeights=useWeights, minmu=minmu, allZero=az, counts=y,
+            sample_mask=mask, rule_applies=rule, nf_is_vector=is_vec, cells=self._cells.get(xd.data_ptr())))
+        return ContrastColumns(list(r["table"]), r["contrastAllZero"], pick)
+
+    def zero_rule(self, lfc, stat, pvalue, flag):
+        t = self.torch
+        col = lambda v: v if t.is_tensor(v) else self._vec(v)
+        f = flag != 0
+        zero, one = t.zeros((), dtype=t.float64, device=self.device), t.ones((), dtype=t.float64, device=self.device)
+        return (t.where(f, zero, col(lfc)), t.where(f, zero, col(stat)), t.where(f, one, col(pvalue)))
 
     # ---- count outliers: HIP kernels (csrc/outlier.hip)
     def cooks_distance(self, y, nf, mu, H, x):

@@ -1032,3 +1032,110 @@ def results_small(small, K):
     """(cutoffs, numRej, status) from the host copy of results_dev's `_small`"""
     kr = (K + 1) // 2
     return small[:K].copy(), small[K:K + kr].view(np.int32)[:K].copy(), int(small[K + kr:].view(np.int32)[0])
+
+
+def _contrast_masks(sample_mask, rule_applies, K, m):
+    if sample_mask is None:
+        return None, None
+    mask = np.ascontiguousarray(np.asarray(sample_mask) != 0, dtype=np.int32).reshape(K, m)
+    rule = np.ones(K, dtype=np.int32) if rule_applies is None else np.ascontiguousarray(np.asarray(rule_applies) != 0, dtype=np.int32)
+    if rule.shape != (K,):
+        raise ValueError("rule_applies must have one flag per contrast")
+    return mask, rule
+
+
+def contrasts(x, nf, alpha_hat, beta, lambda_, contrasts, weights=None, useWeights=False, minmu=0.5, allZero=None,
+              counts=None, sample_mask=None, rule_applies=None, K=None):
+    """dsq_contrasts on host arrays: K contrasts from one covariance pass per gene.  x: m x p; nf: n x m (or the m size
+    factors); beta: n x p on the natural-log scale; lambda_: p; contrasts: p x K (a column per contrast) or None for the
+    all-zero flags alone (then K = the number of masks); counts: the ORIGINAL n x m counts, sample_mask: K x m of 0 / 1,
+    rule_applies: K flags.  Returns log2FoldChange, lfcSE, stat, pvalue (n x K) and contrastAllZero (n x K int32)."""
+    ct = None if contrasts is None else _fcol(contrasts)
+    if ct is not None and ct.ndim == 1:
+        ct = ct.reshape(-1, 1, order="F")
+    if ct is None:
+        if sample_mask is None:
+            raise ValueError("neither contrasts nor sample_mask given")
+        K = int(np.shape(sample_mask)[0])
+        n, m = np.shape(counts)
+        p = 1 if x is None else np.shape(x)[1]
+    else:
+        x = _fcol(x)
+        m, p = x.shape
+        K = ct.shape[1]
+        b = _fcol(beta)
+        n = b.shape[0]
+        if ct.shape[0] != p or b.shape != (n, p):
+            raise ValueError("non-conformable arguments")
+    mask, rule = _contrast_masks(sample_mask, rule_applies, K, m)
+    y = None if mask is None else np.asfortranarray(np.asarray(counts).astype(np.int32, copy=False))
+    if y is not None and y.shape != (n, m):
+        raise ValueError("counts must be n x m")
+    az = None if allZero is None else np.ascontiguousarray(np.asarray(allZero) == 1, dtype=np.int32)
+    out = {k: (np.zeros((n, K), order="F") if ct is not None else None) for k in ("log2FoldChange", "lfcSE", "stat", "pvalue")}
+    flags = np.zeros((n, K), dtype=np.int32, order="F")
+    a = L.DsqContrastsArgs(n=n, m=m, p=p, K=K, ld=0, minmu=float(minmu), allZero=_ptr(az), counts=_ptr(y),
+                           sample_mask=_ptr(mask), rule_applies=_ptr(rule))
+    keep = []
+    if ct is not None:
+        nfa = np.asarray(nf, np.float64)
+        is_vec = nfa.ndim == 1
+        nfa = np.ascontiguousarray(nfa) if is_vec else _fcol(nfa)
+        if nfa.shape != ((m,) if is_vec else (n, m)):
+            raise ValueError("nf must be n x m or the m size factors")
+        useW = bool(useWeights)
+        w = _fcol(weights) if useW else None
+        if w is not None and w.shape != (n, m):
+            raise ValueError("weights must be n x m")
+        alpha = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha_hat, np.float64).reshape(-1), (n,)))
+        lam = np.ascontiguousarray(np.asarray(lambda_, np.float64).reshape(-1))
+        if lam.size != p:
+            raise ValueError("lambda must have length ncol(x)")
+        keep = [nfa, w, alpha, lam]
+        a.x, a.nf, a.nf_is_vector, a.alpha_hat, a.beta, a.lambda_ = _ptr(x), _ptr(nfa), int(is_vec), _ptr(alpha), _ptr(b), _ptr(lam)
+        a.weights, a.useWeights, a.contrasts = _ptr(w), int(useW), _ptr(ct)
+    o = L.DsqContrastsOut(contrastAllZero=_ptr(flags), **{k: _ptr(v) for k, v in out.items()})
+    L.check(L.lib().dsq_contrasts(C.byref(a), C.byref(o)))
+    del keep
+    out["contrastAllZero"] = flags
+    return out
+
+
+def contrasts_dev(x, nf, alpha_hat, beta, lambda_, contrasts, weights=None, useWeights=False, minmu=0.5, allZero=None,
+                  counts=None, sample_mask=None, rule_applies=None, nf_is_vector=False, cells=None):
+    """dsq_contrasts_dev on resident data: x a (p, m) tensor (= m x p column-major), nf / weights / counts GeneMajor (nf: the
+    m size factors with nf_is_vector), alpha_hat (n), beta (p, n) on the natural-log scale, lambda_ (p), contrasts (K, p)
+    or None for the flags alone, allZero int32 (n), sample_mask int32 (K, m), rule_applies int32 (K); cells: HOST labels
+    (native.cell_index).  Nothing is read back: `table` (4, K, n) = log2FoldChange | lfcSE | stat | pvalue, each n x K
+    column-major, and contrastAllZero (K, n) int32."""
+    import torch
+    if contrasts is None:
+        assert sample_mask is not None and isinstance(counts, GeneMajor)
+        K, m = sample_mask.shape
+        n, ld, p, dev = counts.n, counts.ld, 1, counts.t.device
+    else:
+        K, p = contrasts.shape
+        n, m, dev = beta.shape[1], x.shape[1], beta.device
+        ld = None
+        for h in (counts if sample_mask is not None else None, None if nf_is_vector else nf, weights if useWeights else None):
+            if h is not None:
+                assert isinstance(h, GeneMajor) and h.n == n and h.m == m and (ld is None or h.ld == ld)
+                ld = h.ld
+        ld = m if ld is None else ld
+    table = torch.empty((4, K, n), dtype=torch.float64, device=dev) if contrasts is not None else None
+    flags = torch.empty((K, n), dtype=torch.int32, device=dev)
+    a = L.DsqContrastsArgs(n=n, m=m, p=p, K=K, ld=ld, minmu=float(minmu), allZero=_t_ptr(allZero),
+                           counts=_t_ptr(counts.t) if sample_mask is not None else None, sample_mask=_t_ptr(sample_mask),
+                           rule_applies=_t_ptr(rule_applies))
+    if contrasts is not None:
+        a.x, a.nf, a.nf_is_vector = _t_ptr(x), _t_ptr(nf if nf_is_vector else nf.t), int(bool(nf_is_vector))
+        a.alpha_hat, a.beta, a.lambda_, a.contrasts = _t_ptr(alpha_hat), _t_ptr(beta), _t_ptr(lambda_), _t_ptr(contrasts)
+        a.weights, a.useWeights = (_t_ptr(weights.t) if useWeights else None), int(bool(useWeights))
+        if cells is not None:
+            cells = np.ascontiguousarray(cells, dtype=np.int32)
+            a.cell_of, a.ncell = _ptr(cells), int(cells.max()) + 1
+    o = L.DsqContrastsOut(contrastAllZero=_t_ptr(flags))
+    if table is not None:
+        o.log2FoldChange, o.lfcSE, o.stat, o.pvalue = (_t_ptr(table[i]) for i in range(4))
+    L.check(L.lib().dsq_contrasts_dev(C.byref(a), C.byref(o), _stream()))
+    return {"table": table, "contrastAllZero": flags}

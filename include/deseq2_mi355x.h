@@ -735,6 +735,57 @@ int dsq_results_dev(const DsqResultsArgs *args, const DsqResultsOut *out, void *
 int dsq_results(const DsqResultsArgs *args, const DsqResultsOut *out);
 int64_t dsq_results_workspace_bytes(int32_t n, int32_t K);
 
+/* ---- dsq_contrasts: K contrasts of the fitted coefficients from ONE covariance pass per gene ----
+ * getContrast (R/results.R:760-827) re-enters fitBeta with maxit = 0 once per contrast; everything in front of the pair
+ * (c' beta, sqrt(c' Sigma c)) -- the fitted means mu = max(nf exp(x beta), minmu), w = [weights] mu / (1 + alpha mu),
+ * G = X'WX, Gi = (G + diag(lambda))^-1, Sigma = (Gi G) Gi (src/DESeq2.cpp:430-455) -- is the same for every contrast and
+ * is built here once per gene.  Per contrast k: log2FoldChange = L c_k' beta, lfcSE = L sqrt(c_k' Sigma c_k) with
+ * L = log2(exp(1)), stat = log2FoldChange / lfcSE, pvalue = 2 pnorm(|stat|, lower.tail = FALSE) (:809-817), each the bits
+ * of dsq_fit_beta_dev(contrast = c_k, maxit = 0): the Gram sums take the cell-collapsed form for the designs that entry
+ * fits on design cells (cell_of given, at most 32 cells, p <= 32) and the per-sample wave-order form otherwise.
+ * The all-zero rule of cleanContrast (:1021-1028): where rule_applies[k] is set and every count of the gene under
+ * sample_mask[k] is 0, contrastAllZero = 1 and log2FoldChange = 0, stat = 0, pvalue = 1 (lfcSE keeps its value).  The
+ * masks read `counts` -- the ORIGINAL counts, as contrastAllZeroCharacter / contrastAllZeroNumeric do (:1239, :1268); the
+ * covariance reads no counts at all (at maxit = 0 nothing does).  Rows flagged in allZero: NaN in the four columns, flag 0.
+ * contrasts == NULL with masks given: flags only -- no covariance, the four table outputs are not written (may be NULL).
+ * n x m matrices (nf as a matrix, weights, counts) are gene-major with leading dimension ld; x is m x p column-major,
+ * beta n x p column-major on the NATURAL-log scale, contrasts p x K column-major (contrast k at contrasts + k p),
+ * sample_mask K x m with mask k at sample_mask + k m; outputs n x K column-major.  K has no upper limit.
+ * _dev: device pointers (cell_of excepted), asynchronous on `stream`, no host synchronisation, no float atomics.  The
+ * p x p matrices of a gene live in LDS next to its m weights: m <= dsq_contrasts_max_m(p) on the per-sample path (7712 at
+ * p = 64, 17040 at p = 32), else DSQ_ERR_UNSUPPORTED; the cell path has no such limit.
+ * dsq_contrasts: host pointers, n x m matrices in R layout (column-major), ONE device, synchronous; the design cells are
+ * derived from x when cell_of is NULL, as dsq_fit_beta does.                                                            */
+typedef struct {
+    int32_t n, m, p, K;
+    int64_t ld;                    /* _dev: leading dimension of the gene-major n x m matrices (>= m); dsq_contrasts: ignored */
+    const double *x;               /* m x p model matrix the coefficients were fitted on, column-major                  */
+    const double *nf;              /* n x m normalization factors, or (nf_is_vector) the m size factors                 */
+    int32_t nf_is_vector;
+    const double *alpha_hat;       /* n dispersions                                                                     */
+    const double *beta;            /* n x p column-major, natural-log scale (log(2) * mcols beta)                       */
+    const double *lambda;          /* p ridge values, natural-log scale (1 / (log(2)^2 betaPriorVar))                   */
+    const double *weights;         /* n x m observation weights (normalised, R/results.R:787-795); NULL when useWeights == 0 */
+    int32_t useWeights;
+    double minmu;
+    const double *contrasts;       /* p x K column-major, or NULL: flags only                                           */
+    const int32_t *allZero;        /* n flags, or NULL                                                                  */
+    const int32_t *counts;         /* n x m int32 ORIGINAL counts; needed if and only if sample_mask is given           */
+    const int32_t *sample_mask;    /* K x m of 0 / 1, or NULL: no all-zero rule                                         */
+    const int32_t *rule_applies;   /* K flags (with sample_mask)                                                        */
+    const int32_t *cell_of;        /* extension: design cells as in DsqFitBetaArgs (HOST, m labels, may be NULL)        */
+    int32_t ncell;
+} DsqContrastsArgs;
+
+typedef struct {
+    double *log2FoldChange, *lfcSE, *stat, *pvalue;   /* n x K column-major (flags only: not written, may be NULL)      */
+    int32_t *contrastAllZero;                         /* n x K column-major; may be NULL when no mask is given          */
+} DsqContrastsOut;
+
+int dsq_contrasts_dev(const DsqContrastsArgs *args, const DsqContrastsOut *out, void *stream);
+int dsq_contrasts(const DsqContrastsArgs *args, const DsqContrastsOut *out);
+int32_t dsq_contrasts_max_m(int32_t p);   /* longest row the per-sample path takes at p design columns */
+
 /* ---- dsq_deseq: DESeq() behind ONE host-pointer call ------------------------------------------------------------
  * What an R session binds as .Call("_DESeq2_mi355x_DESeq", ...) in place of the body of DESeq() between
  * estimateSizeFactors (dsq_size_factors above) and the final bookkeeping (R/core.R:388-426: estimateDispersions -> nbinomWaldTest / nbinomLRT
