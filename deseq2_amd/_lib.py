@@ -268,7 +268,7 @@ class DsqResultsArgs(C.Structure):
         ("betaSE", C.c_void_p), ("stat", C.c_void_p), ("pvalue", C.c_void_p), ("baseMean", C.c_void_p),
         ("replace", C.c_void_p), ("na_mask", C.c_void_p), ("lfcThreshold", C.c_double), ("altHypothesis", C.c_int32),
         ("independentFiltering", C.c_int32), ("filter", C.c_void_p), ("theta", C.c_void_p), ("K", C.c_int32),
-        ("alpha", C.c_double), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+        ("alpha", C.c_double), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("df", C.c_void_p),
     ]
 
 
@@ -284,7 +284,7 @@ class DsqContrastsArgs(C.Structure):
         ("nf", C.c_void_p), ("nf_is_vector", C.c_int32), ("alpha_hat", C.c_void_p), ("beta", C.c_void_p),
         ("lambda_", C.c_void_p), ("weights", C.c_void_p), ("useWeights", C.c_int32), ("minmu", C.c_double),
         ("contrasts", C.c_void_p), ("allZero", C.c_void_p), ("counts", C.c_void_p), ("sample_mask", C.c_void_p),
-        ("rule_applies", C.c_void_p), ("cell_of", C.c_void_p), ("ncell", C.c_int32),
+        ("rule_applies", C.c_void_p), ("cell_of", C.c_void_p), ("ncell", C.c_int32), ("df", C.c_void_p),
     ]
 
 
@@ -296,6 +296,7 @@ class DsqContrastsOut(C.Structure):
 DSQ_TEST = {"Wald": 0, "LRT": 1}
 DSQ_ALT = {"greaterAbs": 0, "lessAbs": 1, "greater": 2, "less": 3, "greaterAbs2014": 4}
 DSQ_RESULTS_MAX_K = 4096
+DSQ_PT = {"lower": 0, "upper": 1, "two_sided": 2}
 DSQ_VST = {"parametric": 0, "mean": 1, "spline": 2, "log2": 3, "normalized": 4}
 DSQ_VST_MAX_KNOTS = 1600
 DSQ_SF = {"ratio": 0, "poscounts": 1}
@@ -328,6 +329,7 @@ EXPORTED_SYMBOLS = [
     "dsq_rlog", "dsq_rlog_dev",
     "dsq_results", "dsq_results_dev", "dsq_results_workspace_bytes",
     "dsq_contrasts", "dsq_contrasts_dev", "dsq_contrasts_max_m",
+    "dsq_pt", "dsq_pt_dev",
 ]
 
 _lib = None
@@ -407,6 +409,8 @@ def lib():
     L.dsq_contrasts_dev.argtypes = [C.POINTER(DsqContrastsArgs), C.POINTER(DsqContrastsOut), C.c_void_p]
     L.dsq_contrasts_max_m.argtypes = [C.c_int32]
     L.dsq_contrasts_max_m.restype = C.c_int32
+    L.dsq_pt.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dsq_pt_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dsq_deseq_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.dsq_deseq_workspace_bytes.restype = C.c_int64
     L.dsq_profile_get.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double)]

@@ -928,6 +928,7 @@ def nbinomWaldTest(dds, betaTol=1e-8, maxit=100, useOptim=True, useT=False, df=N
             df = num - dds.p
         df = np.where(np.asarray(df, float) > 0, df, np.nan)
         WaldPvalue = 2 * tdist.sf(np.abs(WaldStatistic), df=np.asarray(df)[:, None])
+        dds.mcols["tDegreesFreedom"] = np.array(np.broadcast_to(np.asarray(df, np.float64), (dds.n,)))   # :1523-1524
     else:
         WaldPvalue = E.two_sided_normal_p(WaldStatistic)                            # :1507
     logLike = fit["logLike"]                                                    # fitNbinomGLMs.R:182,399
@@ -1020,7 +1021,7 @@ def replaceOutliers(dds, trim=.2, cooksCutoff=None, minReplicates=7, whichSample
 
 
 _RESULT_COLS = ("beta", "betaSE", "WaldStatistic", "WaldPvalue", "LRTStatistic", "LRTPvalue", "betaConv",
-                "fullBetaConv", "betaIter", "deviance", "maxCooks")
+                "fullBetaConv", "betaIter", "deviance", "maxCooks", "tDegreesFreedom")
 
 
 def _dispersion_function(dds, baseMean):
@@ -1761,8 +1762,9 @@ def results(dds, name=None, lfcThreshold=0, altHypothesis="greaterAbs", cooksCut
     defaults to the last coefficient.  cooksCutoff: None = qf(.99, p, m - p), False = no filter, a number = that cutoff.
     The table, the threshold tests and the adjusted p-values of every filter threshold are engine work (one launch chain
     on the device, csrc/results.hip); argument checks, the Cook's flags (core.cooksOutlier) and the choice of the threshold
-    stay here.  Not served (NotImplementedError): contrast (see resultsContrasts), addMLE, format, parallel, a threshold test
-    on a useT analysis, pAdjustMethod other than "BH" / "none"."""
+    stay here.  On a useT analysis (mcols holds tDegreesFreedom, :414) the threshold tests run under Student's t with the
+    rows' degrees of freedom.  Not served (NotImplementedError): contrast (see resultsContrasts), addMLE, format, parallel,
+    pAdjustMethod other than "BH" / "none"."""
     reasons = {"contrast": "contrasts are served by resultsContrasts(dds, contrasts, ...), one covariance pass for all of them",
                "addMLE": "the MLE column of a beta-prior analysis is not served", "format": "only the table is served",
                "parallel": "the adjustment is global over the genes and runs on one device", "BPPARAM": "see parallel",
@@ -1822,9 +1824,37 @@ def _results_checks(dds, lfcThreshold, altHypothesis, alpha, pAdjustMethod, test
             raise ValueError("tests of log fold change above or below a theshold must be Wald tests.")   # :465-467
         if altHypothesis == "lessAbs" and dds.attrs.get("betaPrior"):
             raise ValueError("testing altHypothesis='lessAbs' requires setting the DESeq() argument betaPrior=FALSE")   # :469-471
-        if dds.attrs.get("useT"):
-            raise NotImplementedError("a threshold test on a useT analysis: there is no Student-t distribution in the engine")
+        _student_df(dds)
     return test, threshold
+
+
+def pt(q, df, lower_tail=True, engine=None):
+    """stats::pt(q, df, lower.tail) for real df > 0 in the engine's pinned arithmetic (DESIGN.md section 15): q an n-vector or
+    an n x K matrix, df a number or one value per row.  Accurate in relative terms far into the tail (1e-300 and below); as R's
+    pt, NaN for NaN arguments and df <= 0, the normal distribution at df = Inf.  engine: HostEngine() (the default) or a
+    DeviceEngine -- the same bits."""
+    E = HostEngine() if engine is None else engine
+    q = np.asarray(q, np.float64)
+    if q.ndim not in (1, 2):
+        raise ValueError("q should be a vector or a matrix")
+    df = np.ascontiguousarray(np.broadcast_to(np.asarray(df, np.float64), q.shape[:1]))
+    r = E.pt(q, df, "lower" if lower_tail else "upper")
+    if not isinstance(r, np.ndarray):
+        r = E._host(r).numpy()
+        r = r.T if r.ndim == 2 else r
+    return np.array(r, dtype=np.float64).reshape(q.shape)
+
+
+def _student_df(dds):
+    """the degrees of freedom of a useT analysis, or None: as R/results.R:414, the analysis is on the t distribution when
+    mcols holds tDegreesFreedom.  attrs["useT"] without the column is an object from before the column was stored (or a
+    hand-made one): there is nothing to evaluate Student's t with"""
+    if "tDegreesFreedom" in dds.mcols:
+        return np.asarray(dds.mcols["tDegreesFreedom"], np.float64)
+    if dds.attrs.get("useT"):
+        raise NotImplementedError('attrs["useT"] is set but mcols has no "tDegreesFreedom" column: the Student-t tests need the '
+                                  "degrees of freedom nbinomWaldTest(useT = True) stores")
+    return None
 
 
 def _stored_columns(dds, c, test):
@@ -1864,7 +1894,9 @@ def _results_tail(dds, lfc, se, stat, pvalue, lfcThreshold, altHypothesis, cooks
         priorInfo = {"type": "none", "package": "deseq2_amd"}
     # the table is not launched yet: the adjustment's engine call makes table and adjusted p-values together
     bm = np.asarray(dds.mcols["baseMean"], np.float64)
-    res = DESeqResults(_ResultsPending((lfc, se, stat, pvalue, bm, replace, na_mask, lfcThreshold, altHypothesis)), priorInfo, E)
+    threshold = not (lfcThreshold == 0 and altHypothesis == "greaterAbs")
+    df = _student_df(dds) if threshold else None                                 # :477-515: pt(., df) for pnorm
+    res = DESeqResults(_ResultsPending((lfc, se, stat, pvalue, bm, replace, na_mask, lfcThreshold, altHypothesis), df), priorInfo, E)
     if filterFun is None:
         pvalueAdjustment(res, independentFiltering, filter, theta, alpha, pAdjustMethod)   # :591-593
     else:
@@ -1877,10 +1909,11 @@ def _results_tail(dds, lfc, se, stat, pvalue, lfcThreshold, altHypothesis, cooks
 
 
 class _ResultsPending:
-    """the arguments of a table that has not been launched"""
+    """the arguments of a table that has not been launched (df: the degrees of freedom of a threshold test under Student's t,
+    handed to the engine by keyword)"""
 
-    def __init__(self, args):
-        self.args = args
+    def __init__(self, args, df=None):
+        self.args, self.df = args, df
         self.resident = {"baseMean": args[4]}
 
     def column(self, name):
@@ -1890,14 +1923,14 @@ class _ResultsPending:
 
 def _realize(res):
     if isinstance(res.tab, _ResultsPending):
-        res.tab = res.engine.results_table(*res.tab.args)
+        res.tab = res.engine.results_table(*res.tab.args, df=res.tab.df)
     return res.tab
 
 
 def _run_filtered_p(res, filter, theta, alpha):
     """the adjustment over `theta`; for a table not launched yet, table and adjustment in ONE engine call"""
     if isinstance(res.tab, _ResultsPending):
-        res.tab = res.engine.results(*res.tab.args, filter=filter, theta=theta, alpha=alpha)
+        res.tab = res.engine.results(*res.tab.args, filter=filter, theta=theta, alpha=alpha, df=res.tab.df)
         return res.tab
     return res.engine.filtered_p(res.tab, filter, theta, alpha)
 
@@ -2010,8 +2043,9 @@ def resultsContrasts(dds, contrasts, listValues=(1, -1), minmu=0.5, lfcThreshold
     into ONE engine call (csrc/contrasts.hip on the device: one covariance pass per gene), and a character contrast against
     the reference level is answered from the stored columns (:876-932) with only the all-zero flags from the engine.  Every
     table then takes the tail of results(): Cook's mask, replaced rows, threshold tests, independent filtering, BH.
-    metadata["contrast"] is the name R builds (:968-1001).  Not served (NotImplementedError): a useT analysis, addMLE,
-    parallel."""
+    metadata["contrast"] is the name R builds (:968-1001).  On a useT analysis the fitted contrasts take
+    2 pt(|stat|, tDegreesFreedom, lower.tail = FALSE) (:812-815) and the threshold tests Student's t.  Not served
+    (NotImplementedError): addMLE, parallel."""
     reasons = {"addMLE": "the MLE column of a beta-prior analysis is not served",
                "parallel": "all contrasts share one covariance pass per gene on one device", "BPPARAM": "see parallel",
                "format": "only the table is served", "saveCols": "only the six result columns are served"}
@@ -2021,8 +2055,7 @@ def resultsContrasts(dds, contrasts, listValues=(1, -1), minmu=0.5, lfcThreshold
         if not (v is None or v is False or (k == "format" and v == "DataFrame")):
             raise NotImplementedError("resultsContrasts(%s = ): %s" % (k, reasons[k]))
     test, _ = _results_checks(dds, lfcThreshold, altHypothesis, alpha, pAdjustMethod, test)
-    if dds.attrs.get("useT"):
-        raise NotImplementedError("a contrast on a useT analysis: there is no Student-t distribution in the engine")
+    tdf = _student_df(dds)
     lv = np.asarray(listValues, np.float64).reshape(-1)
     if lv.size != 2:
         raise ValueError("length(listValues) == 2 & is.numeric(listValues) is not TRUE")       # :330
@@ -2107,7 +2140,7 @@ def resultsContrasts(dds, contrasts, listValues=(1, -1), minmu=0.5, lfcThreshold
                              ln2 * np.asarray(dds.mcols["beta"], np.float64), 1.0 / (ln2 ** 2 * bpv),           # :775-777
                              np.column_stack([e[1] for e in fits]), weights, useWeights, minmu, allZero,
                              sample_mask=masks if rule.any() else None, rule_applies=rule if rule.any() else None,
-                             sizeFactors=dds.sizeFactors if use_sf else None)
+                             sizeFactors=dds.sizeFactors if use_sf else None, df=tdf)
     if pulls:
         pulled = E.contrasts(dds.y, None, None, None, None, None, None, None, False, minmu, allZero,
                              sample_mask=np.array([e[4] for e in pulls]))

@@ -850,7 +850,7 @@ int results_dev_locked(const DsqResultsArgs *a, const DsqResultsOut *o, hipStrea
     kp.threshold = !(a->lfcThreshold == 0.0 && a->altHypothesis == DSQ_ALT_GREATER_ABS);      // R/results.R:464
     kp.T = a->lfcThreshold; kp.alpha = a->alpha;
     kp.beta = a->beta; kp.betaSE = a->betaSE; kp.stat = a->stat; kp.pvalue = a->pvalue; kp.baseMean = a->baseMean;
-    kp.replace = a->replace; kp.na_mask = a->na_mask;
+    kp.replace = a->replace; kp.na_mask = a->na_mask; kp.df = a->df;
     kp.filter = a->filter ? a->filter : a->baseMean;
     kp.theta = a->independentFiltering ? a->theta : nullptr;
     kp.K = a->K;
@@ -879,6 +879,14 @@ int contrasts_check(const DsqContrastsArgs *a, const DsqContrastsOut *o) {
     return a->p > DSQ_P_WIDE ? too_wide(a->p) : DSQ_OK;
 }
 
+int pt_check(const double *q, const double *df, int32_t n, int32_t K, int32_t tail, const double *out) {
+    if (n < 0 || K < 0) return capi_fail(DSQ_ERR_ARG, "bad dimensions n=%d K=%d", n, K);
+    if (tail < DSQ_PT_LOWER || tail > DSQ_PT_TWO_SIDED) return capi_fail(DSQ_ERR_ARG, "unknown tail %d", tail);
+    if ((int64_t)n * K > 0 && (!q || !df || !out)) return capi_fail(DSQ_ERR_ARG, "NULL q, df or out");
+    if (((int64_t)n * K + 255) / 256 > 0x7fffffffLL) return capi_fail(DSQ_ERR_ARG, "n K = %lld entries: too many for one launch", (long long)n * K);
+    return DSQ_OK;
+}
+
 int contrasts_dev_locked(const DsqContrastsArgs *a, const DsqContrastsOut *o, hipStream_t st) {
     if (int rc = contrasts_check(a, o)) return rc;
     if (a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld = %ld < m = %d", (long)a->ld, a->m);
@@ -905,6 +913,10 @@ int contrasts_dev_locked(const DsqContrastsArgs *a, const DsqContrastsOut *o, hi
     bool ok = false;
     capi_prof_begin("contrasts", a->n, st);
     DSQ_HIP(launch_contrasts(kp, st, &ok));
+    // a useT analysis: 2 pt(|stat|, df, lower.tail = FALSE) over the stat column (R/results.R:812-815); the entries the
+    // all-zero rule has set to 1 stay (cleanContrast runs after getContrast), rows flagged allZero hold NaN in stat
+    if (ok && a->df && a->contrasts)
+        DSQ_HIP(launch_pt(o->stat, a->df, a->n, a->K, DSQ_PT_TWO_SIDED, a->sample_mask ? o->contrastAllZero : nullptr, o->pvalue, st));
     capi_prof_end(st);
     if (!ok) return capi_fail(DSQ_ERR_UNSUPPORTED, "rows of m=%d samples at p=%d: the per-sample path takes at most %d", a->m, a->p,
                               contrasts_max_m(a->p));
@@ -965,6 +977,14 @@ int64_t dsq_size_factors_workspace_bytes(int32_t n, int32_t m) {
 }
 
 int32_t dsq_contrasts_max_m(int32_t p) { return contrasts_max_m(p); }
+
+int dsq_pt_dev(const double *q, const double *df, int32_t n, int32_t K, int32_t tail, const int32_t *keep, double *out,
+               void *stream) {
+    if (int rc = pt_check(q, df, n, K, tail, out)) return rc;
+    if (int rc = capi_check_device()) return rc;
+    DSQ_HIP(launch_pt(q, df, n, K, tail, keep, out, (hipStream_t)stream));
+    return DSQ_OK;
+}
 
 int64_t dsq_results_workspace_bytes(int32_t n, int32_t K) {
     if (n < 0 || K < 0) return 0;

@@ -49,6 +49,7 @@ int vst_check(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stat
 int rlog_check(const DsqRlogArgs *a, const DsqRlogOut *o);
 int results_check(const DsqResultsArgs *a, const DsqResultsOut *o);
 int contrasts_check(const DsqContrastsArgs *a, const DsqContrastsOut *o);
+int pt_check(const double *q, const double *df, int32_t n, int32_t K, int32_t tail, const double *out);
 int check_host_layout(int layout);
 // the device-pointer bodies behind the entry points
 int fit_beta_dev_locked(const DsqFitBetaArgs *a, const DsqFitBetaOut *o, hipStream_t st);

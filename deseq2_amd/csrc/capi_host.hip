@@ -643,7 +643,7 @@ int dsq_replace_outliers(const DsqReplaceArgs *a, const DsqReplaceOut *o) {
 int dsq_test_math(int op, const double *a, const double *b, const double *c, double *out, int64_t n) {
     std::lock_guard<std::mutex> lk(g_mu);
     WsScope ws(nullptr);
-    if (!a || !out || n < 0 || ((op == 7 || op == 8) && !b) || (op == 8 && !c)) return capi_fail(DSQ_ERR_ARG, "bad arguments");
+    if (!a || !out || n < 0 || ((op == 7 || op == 8 || op == 10 || op == 11) && !b) || (op == 8 && !c)) return capi_fail(DSQ_ERR_ARG, "bad arguments");
     DSQ_TRY(capi_check_device());
     if (n == 0) return DSQ_OK;
     hipStream_t st = nullptr;
@@ -655,6 +655,31 @@ int dsq_test_math(int op, const double *a, const double *b, const double *c, dou
     if (c) DSQ_HIP(hipMemcpyAsync(d + 2 * n, c, n * 8, hipMemcpyHostToDevice, st));
     DSQ_HIP(launch_test_math(op, d, d + n, d + 2 * n, d + 3 * n, n, st));
     DSQ_HIP(hipMemcpyAsync(out, d + 3 * n, n * 8, hipMemcpyDeviceToHost, st));
+    DSQ_HIP(hipStreamSynchronize(st));
+    return DSQ_OK;
+}
+
+// (inputs and results in ONE slot, as dsq_test_math: q | out | df | keep)
+int dsq_pt(const double *q, const double *df, int32_t n, int32_t K, int32_t tail, const int32_t *keep, double *out) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    WsScope ws(nullptr);
+    DSQ_TRY(pt_check(q, df, n, K, tail, out));
+    DSQ_TRY(capi_check_device());
+    const size_t e = (size_t)n * K;
+    if (e == 0) return DSQ_OK;
+    hipStream_t st = nullptr;
+    void *v;
+    DSQ_TRY(capi_ws_get(WS_H_VEC, (2 * e + (size_t)n) * 8 + e * 4, &v));
+    double *dq = (double *)v, *dout = dq + e, *ddf = dout + e;
+    int32_t *dkeep = keep ? (int32_t *)(ddf + n) : nullptr;
+    DSQ_HIP(hipMemcpyAsync(dq, q, e * 8, hipMemcpyHostToDevice, st));
+    DSQ_HIP(hipMemcpyAsync(ddf, df, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    if (keep) {      // the kept entries of out are not written: they go up and come back as they are
+        DSQ_HIP(hipMemcpyAsync(dkeep, keep, e * 4, hipMemcpyHostToDevice, st));
+        DSQ_HIP(hipMemcpyAsync(dout, out, e * 8, hipMemcpyHostToDevice, st));
+    }
+    DSQ_HIP(launch_pt(dq, ddf, n, K, tail, dkeep, dout, st));
+    DSQ_HIP(hipMemcpyAsync(out, dout, e * 8, hipMemcpyDeviceToHost, st));
     DSQ_HIP(hipStreamSynchronize(st));
     return DSQ_OK;
 }
@@ -829,6 +854,7 @@ int dsq_results(const DsqResultsArgs *a, const DsqResultsOut *o) {
     s.vec(&d.replace, a->replace, n * 4);
     s.vec(&d.na_mask, a->na_mask, n * 4);
     s.vec(&d.filter, a->filter, n * 8);
+    s.vec(&d.df, a->df, n * 8);
     if (a->independentFiltering) s.vec(&d.theta, a->theta, K * 8);
     DSQ_TRY(s.pack_in());
     const size_t wsb = results_sort_workspace_bytes(a->n);
@@ -884,6 +910,7 @@ int dsq_contrasts(const DsqContrastsArgs *a, const DsqContrastsOut *o) {
         s.vec(&d.beta, a->beta, n * p * 8);
         s.vec(&d.lambda, a->lambda, p * 8);
         s.vec(&d.contrasts, a->contrasts, p * K * 8);
+        s.vec(&d.df, a->df, n * 8);
         s.out_vec(&od.log2FoldChange, o->log2FoldChange, n * K * 8);
         s.out_vec(&od.lfcSE, o->lfcSE, n * K * 8);
         s.out_vec(&od.stat, o->stat, n * K * 8);

@@ -290,6 +290,7 @@ struct ResultsKernelParams {
     int32_t *status;             // bit 0: NaN in filter, bit 1: a theta outside [0, 1]
     unsigned long long *keyA, *keyB;
     unsigned int *rowA, *rowB, *hist, *counters;
+    const double *df;            // n degrees of freedom: the threshold tests run under Student's t (nullptr: the normal distribution)
 };
 hipError_t launch_results(ResultsKernelParams kp, void *workspace, hipStream_t st);
 size_t results_sort_workspace_bytes(long n);     // the sort's part; filtPadj (n K doubles) may follow it
@@ -314,6 +315,9 @@ struct ContrastsKernelParams {
 };
 // rows of more than contrasts_max_m(p) samples do not fit the per-sample path (*ok = false, nothing launched)
 hipError_t launch_contrasts(const ContrastsKernelParams &kp, hipStream_t st, bool *ok);
+// pt over an n x K column-major column, df per row (student.hip); tail: DSQ_PT_* of the public header
+hipError_t launch_pt(const double *q, const double *df, long n, long K, int tail, const int32_t *keep, double *out,
+                     hipStream_t st);
 int contrasts_max_m(int p);
 
 // gene index of work item i, and the number of work items, of a (possibly row-listed) launch

@@ -40,6 +40,45 @@ DSQ_DEV double pnorm_sd(double x, double se) {
     return dpnorm_lower(q);
 }
 
+// the same five tests with pt(., df) in place of pnorm (R/results.R:477-515 under useT): plain quotients -- pnorm_sd's rules
+// about sd belong to pnorm5 --, gene i with df[i] (the diagonal of what the reference's greaterAbs branch returns, DESIGN.md
+// section 15); a NaN df gives a NaN p-value
+DSQ_DEV void threshold_tests_t(int alt, double lfc, double se, double T, double df, double &stat, double &pv) {
+    switch (alt) {
+    case 0: {
+        stat = lfc / se;
+        const double a = -__builtin_fabs(lfc) + T, b = -__builtin_fabs(lfc) - T;
+        pv = dpt_lower(a / se, df) + dpt_lower(b / se, df);
+        break;
+    }
+    case 4: {
+        const double q = (__builtin_fabs(lfc) - T) / se;
+        stat = r_sign(lfc) * r_pmax(q, 0.0);
+        pv = r_pmin(1.0, 2.0 * dpt_upper(q, df));
+        break;
+    }
+    case 1: {
+        const double qa = (T - lfc) / se, qb = (lfc + T) / se;
+        stat = r_pmin(r_pmax(qa, 0.0), r_pmax(qb, 0.0));
+        pv = r_pmax(dpt_upper(qa, df), dpt_upper(qb, df));
+        break;
+    }
+    case 2: {
+        const double q = (lfc - T) / se;
+        stat = r_pmax(q, 0.0);
+        pv = dpt_upper(q, df);
+        break;
+    }
+    default: {
+        stat = r_pmin((lfc + T) / se, 0.0);
+        pv = dpt_upper((-T - lfc) / se, df);
+        break;
+    }
+    }
+}
+
+// kT: the threshold tests under Student's t with kp.df (launched only when df is given and a threshold test is asked for)
+template <bool kT>
 __global__ void __launch_bounds__(256) results_table_kernel(ResultsKernelParams kp) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= kp.n) return;
@@ -50,6 +89,8 @@ __global__ void __launch_bounds__(256) results_table_kernel(ResultsKernelParams 
     const double bm = kp.baseMean[i];
     if (kp.threshold) {
         const double T = kp.T;
+        if constexpr (kT) threshold_tests_t(kp.alt, lfc, se, T, kp.df[i], stat, pv);
+        else
         switch (kp.alt) {
         case 0: {   // greaterAbs (:484-497)
             stat = lfc / se;
@@ -363,7 +404,8 @@ hipError_t launch_results(ResultsKernelParams kp, void *workspace, hipStream_t s
     e = hipMemsetAsync(kp.status, 0, sizeof(int32_t), st);
     if (e != hipSuccess) return e;
     const int gblocks = (kp.n + 255) / 256;
-    hipLaunchKernelGGL(results_table_kernel, dim3(gblocks), dim3(256), 0, st, kp);
+    if (kp.df && kp.threshold) hipLaunchKernelGGL(results_table_kernel<true>, dim3(gblocks), dim3(256), 0, st, kp);
+    else hipLaunchKernelGGL(results_table_kernel<false>, dim3(gblocks), dim3(256), 0, st, kp);
     if (kp.theta) {
         hipLaunchKernelGGL(sort_keys_kernel, dim3(gblocks), dim3(256), 0, st, kp.filter, kp.n, kp.keyA, (unsigned int *)nullptr,
                            kp.counters + CNT_NAN_FILTER);

@@ -112,6 +112,8 @@ __global__ void test_math_kernel(int op, const double *a, const double *b, const
     case 7: r = dbd0(x, b[i]); break;
     case 8: r = dnbinom_mu_log(x, b[i], c[i]); break;
     case 9: r = dpnorm_upper2(x); break;
+    case 10: r = dpt_upper(x, b[i]); break;
+    case 11: r = dpt_lower(x, b[i]); break;
     default: r = dnan();
     }
     out[i] = r;

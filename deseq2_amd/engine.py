@@ -423,13 +423,33 @@ class HostEngine:
         """2 * pnorm(abs(z), lower.tail = FALSE), R/core.R:1507 (Cody's algorithm as in R's pnorm, engine arithmetic)"""
         return self.fns.unary("pnorm_upper2", np.asarray(z, np.float64))
 
+    # ---- Student's t (DESIGN.md section 15): student_t.py on this engine's exp / log / log1p / stirlerr
+    def pt(self, q, df, tail="lower", keep=None, out=None):
+        """pt over an n x K column (or an n-vector) q with row i's df: tail "lower", "upper" or "two_sided" (2 * upper(|q|));
+        where keep is non-zero the entry of `out` (q when not given) stays.  The statement of csrc/student.hip."""
+        from . import student_t as S
+        q = np.asarray(q, np.float64)
+        d = np.asarray(df, np.float64).reshape((-1,) + (1,) * (q.ndim - 1))
+        r = {"lower": S.pt_lower, "upper": S.pt_upper, "two_sided": S.pt_two_sided}[tail](self.fns, q, d)
+        if keep is not None:
+            r = np.where(np.asarray(keep) != 0, q if out is None else out, r)
+        return r
+
+    def _pt_pair(self, df):
+        if df is None:
+            return None
+        from . import student_t as S
+        df = np.asarray(df, np.float64)
+        return (lambda q: S.pt_lower(self.fns, q, df)), (lambda q: S.pt_upper(self.fns, q, df))
+
     # ---- results() (R/results.R:443-575, 638-740; DESIGN.md section 13): the numpy statement of csrc/results.hip
     def results_table(self, lfc, se, stat, pvalue, baseMean, replace=None, na_mask=None, lfcThreshold=0.0,
-                      altHypothesis="greaterAbs"):
-        """the five columns of one coefficient (n-vectors in): threshold tests, pvalue NA where na_mask, the nowZero fill"""
+                      altHypothesis="greaterAbs", df=None):
+        """the five columns of one coefficient (n-vectors in): threshold tests (under Student's t with the n degrees of
+        freedom df when given), pvalue NA where na_mask, the nowZero fill"""
         from . import results_host as R
         return ResultColumns(R.results_table(self.vexp, lfc, se, stat, pvalue, baseMean, replace, na_mask, lfcThreshold,
-                                             altHypothesis))
+                                             altHypothesis, self._pt_pair(df)))
 
     def filtered_p(self, tab, filter=None, theta=None, alpha=0.1):
         """BH-adjusted p-values of `tab` over filter >= quantile(filter, theta), one column per theta (theta None: one
@@ -441,19 +461,20 @@ class HostEngine:
         return tab
 
     def results(self, lfc, se, stat, pvalue, baseMean, replace=None, na_mask=None, lfcThreshold=0.0,
-                altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1):
+                altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1, df=None):
         return self.filtered_p(self.results_table(lfc, se, stat, pvalue, baseMean, replace, na_mask, lfcThreshold,
-                                                  altHypothesis), filter, theta, alpha)
+                                                  altHypothesis, df=df), filter, theta, alpha)
 
     # ---- contrasts (R/results.R:760-827, 1021-1028, 1237-1270): the statement csrc/contrasts.hip equals
     def contrasts(self, y, x, nf, alpha_hat, beta, lam, contrasts, weights, useWeights, minmu, allZero, sample_mask=None,
-                  rule_applies=None, sizeFactors=None):
+                  rule_applies=None, sizeFactors=None, df=None):
         """K contrasts of the fitted coefficients.  y: the ORIGINAL counts handle (read by the masks only), x: the model
         matrix the coefficients were fitted on (m x p), nf: the normalization-factor handle (or None with sizeFactors),
         alpha_hat (n), beta (n x p, natural-log scale), lam (p, natural-log scale), contrasts (p x K, or None: flags
         only), weights: the normalised handle, allZero (n flags), sample_mask (K x m of 0 / 1) with rule_applies (K).
         getContrast per contrast -- fitBeta(maxit = 0) on the rows that are not all zero --, log2(exp(1)) on both members,
-        the quotient, the two-sided normal p-value, NA rows, then the all-zero rule.  Returns ContrastColumns."""
+        the quotient, the two-sided normal p-value (df, n degrees of freedom, given: 2 pt(|stat|, df, lower.tail = FALSE),
+        :812-815), NA rows, then the all-zero rule.  Returns ContrastColumns."""
         allZero = np.asarray(allZero, bool)
         n, live = allZero.size, ~np.asarray(allZero, bool)
         K = np.shape(contrasts)[1] if contrasts is not None else np.shape(sample_mask)[0]
@@ -489,6 +510,8 @@ class HostEngine:
             with np.errstate(divide="ignore", invalid="ignore"):
                 stat = lfc / se
             pv = self.two_sided_normal_p(stat)                                           # :817
+            if df is not None:
+                pv = self.pt(stat, np.asarray(df, np.float64)[nz], "two_sided")          # :812-815
             for t, v in zip(table, (lfc, se, stat, pv)):
                 t[nz, k] = v                                                             # buildDataFrameWithNARows, :823
             z = flags[:, k]
@@ -868,8 +891,22 @@ class DeviceEngine:
         return self.native.unary("pnorm_upper2", np.asarray(z, np.float64))
 
     # ---- results(): HIP kernels (csrc/results.hip) on resident columns; nothing but K cutoffs and counts comes back
+    def pt(self, q, df, tail="lower", keep=None, out=None):
+        """HostEngine.pt through dsq_pt_dev: q (n, or K x n = n x K column-major), df (n) and keep host arrays or resident
+        tensors; returns a resident tensor shaped as q (q itself is not overwritten)"""
+        t = self.torch
+        col = lambda v: v if t.is_tensor(v) else self._vec(v)
+        qd = col(np.asarray(q, np.float64).T if not t.is_tensor(q) and np.ndim(q) == 2 else q)
+        kd = None
+        if keep is not None:
+            kd = keep if t.is_tensor(keep) else t.as_tensor(np.ascontiguousarray((np.asarray(keep) != 0).T, dtype=np.int32), device=self.device)
+        od = None
+        if keep is not None:
+            od = (qd if out is None else col(np.asarray(out, np.float64).T if not t.is_tensor(out) and np.ndim(out) == 2 else out)).clone()
+        return self.native.pt_dev(qd, col(df), tail, keep=kd, out=od)
+
     def results(self, lfc, se, stat, pvalue, baseMean, replace=None, na_mask=None, lfcThreshold=0.0,
-                altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1):
+                altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1, df=None):
         t = self.torch
         col = lambda v: v if t.is_tensor(v) else self._vec(v)
         flag = lambda v: None if v is None else t.as_tensor(np.ascontiguousarray(np.asarray(v) == 1, dtype=np.int32), device=self.device)
@@ -877,7 +914,7 @@ class DeviceEngine:
         r = self._timed("results", n, lambda: self.native.results_dev(
             col(lfc), col(se), col(stat), col(pvalue), col(baseMean), 0, replace=flag(replace), na_mask=flag(na_mask),
             test="Wald", lfcThreshold=lfcThreshold, altHypothesis=altHypothesis, filter=None if filter is None else col(filter),
-            theta=None if theta is None else self._vec(theta), alpha=alpha))
+            theta=None if theta is None else self._vec(theta), alpha=alpha, df=None if df is None else col(df)))
         cutoffs, numRej, status = self.native.results_small(self._host(r["_small"]).numpy(), r["K"])
         if status & 1:
             raise ValueError("filter holds NA")
@@ -890,9 +927,9 @@ class DeviceEngine:
         return tab
 
     def results_table(self, lfc, se, stat, pvalue, baseMean, replace=None, na_mask=None, lfcThreshold=0.0,
-                      altHypothesis="greaterAbs"):
+                      altHypothesis="greaterAbs", df=None):
         """(the same launch with one unfiltered column: the table comes with p.adjust(pvalue, "BH"))"""
-        return self.results(lfc, se, stat, pvalue, baseMean, replace, na_mask, lfcThreshold, altHypothesis)
+        return self.results(lfc, se, stat, pvalue, baseMean, replace, na_mask, lfcThreshold, altHypothesis, df=df)
 
     def filtered_p(self, tab, filter=None, theta=None, alpha=0.1):
         c = tab.resident
@@ -903,7 +940,7 @@ class DeviceEngine:
 
     # ---- contrasts: ONE launch of csrc/contrasts.hip on the resident data; the n x K columns stay in HBM
     def contrasts(self, y, x, nf, alpha_hat, beta, lam, contrasts, weights, useWeights, minmu, allZero, sample_mask=None,
-                  rule_applies=None, sizeFactors=None):
+                  rule_applies=None, sizeFactors=None, df=None):
         """HostEngine.contrasts through dsq_contrasts_dev.  What goes up: the n-vectors, the n x p coefficients, the
         contrasts and the masks; nothing comes down -- ContrastColumns holds (K, n) device tensors."""
         t = self.torch
@@ -931,7 +968,8 @@ class DeviceEngine:
         nfh, is_vec = (self._sf_dev(sizeFactors), True) if sizeFactors is not None else (nf, False)
         r = self._timed("contrasts", n, lambda: self.native.contrasts_dev(
             xd, nfh, av, bv, lv, cv, weights=weights, useWeights=useWeights, minmu=minmu, allZero=az, counts=y,
-            sample_mask=mask, rule_applies=rule, nf_is_vector=is_vec, cells=self._cells.get(xd.data_ptr())))
+            sample_mask=mask, rule_applies=rule, nf_is_vector=is_vec, cells=self._cells.get(xd.data_ptr()),
+            df=None if df is None else self._vec(df)))
         return ContrastColumns(list(r["table"]), r["contrastAllZero"], pick)
 
     def zero_rule(self, lfc, stat, pvalue, flag):

@@ -649,6 +649,9 @@ def DESeq(dds, test="Wald", fitType="parametric", reduced=None, minReplicatesFor
                     refit = (hi[5] != 0) & ~allZero
                     pval_t[refit] = pval[refit]
                 pval = pval_t
+                # mcols tDegreesFreedom (R/core.R:1523-1524), NA on the all-zero rows as every result column; the refit leaves
+                # it as it is (:2534 overwrites only the columns its sub-object has)
+                mc["tDegreesFreedom"] = np.where(allZero, np.nan, df)
             mc.update(WaldStatistic=hm[2].T, WaldPvalue=pval, betaConv=conv if np.isnan(conv).any() else hi[4].astype(bool))
         else:
             stat = 2 * (hv[7] - hv[8])                                                    # R/core.R:1877-1878

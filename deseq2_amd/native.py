@@ -968,11 +968,11 @@ def _results_scalars(test, lfcThreshold, altHypothesis, theta):
 
 
 def results(beta, betaSE, stat, pvalue, baseMean, coef, replace=None, na_mask=None, test="Wald", lfcThreshold=0.0,
-            altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1):
+            altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1, df=None):
     """dsq_results on host arrays: the table of coefficient `coef`, the threshold tests, and the Benjamini-Hochberg
     adjustment over the nested subsets filter >= quantile(filter, theta) (theta None: independentFiltering = FALSE, one
-    column).  beta / betaSE: n x p; stat / pvalue: n x p (Wald) or n (LRT).  Returns the five columns, filtPadj (n x K),
-    numRej, cutoffs."""
+    column).  beta / betaSE: n x p; stat / pvalue: n x p (Wald) or n (LRT); df: n degrees of freedom -- the threshold
+    tests then run under Student's t.  Returns the five columns, filtPadj (n x K), numRej, cutoffs."""
     beta, betaSE = _fcol(beta), _fcol(betaSE)
     if beta.ndim == 1:
         beta, betaSE = beta.reshape(-1, 1, order="F"), betaSE.reshape(-1, 1, order="F")
@@ -985,12 +985,13 @@ def results(beta, betaSE, stat, pvalue, baseMean, coef, replace=None, na_mask=No
     rep, na = flags(replace), flags(na_mask)
     f = None if filter is None else np.ascontiguousarray(filter, dtype=np.float64)
     th = None if theta is None else np.ascontiguousarray(theta, dtype=np.float64)
+    dfa = None if df is None else np.ascontiguousarray(np.broadcast_to(np.asarray(df, np.float64), (n,)))
     cols = {k: np.zeros(n) for k in ("baseMean", "log2FoldChange", "lfcSE", "stat", "pvalue")}
     fp = np.zeros((n, K), order="F")
     nr, cut, st = np.zeros(K, dtype=np.int32), np.zeros(K), np.zeros(1, dtype=np.int32)
     a = L.DsqResultsArgs(n=n, p=p, c=int(coef), beta=_ptr(beta), betaSE=_ptr(betaSE), stat=_ptr(stat), pvalue=_ptr(pvalue),
                          baseMean=_ptr(bm), replace=_ptr(rep), na_mask=_ptr(na), filter=_ptr(f), theta=_ptr(th),
-                         alpha=float(alpha), workspace=None, workspace_bytes=0, **sc)
+                         alpha=float(alpha), workspace=None, workspace_bytes=0, df=_ptr(dfa), **sc)
     o = L.DsqResultsOut(filtPadj=_ptr(fp), numRej=_ptr(nr), cutoffs=_ptr(cut), status=_ptr(st),
                         **{k: _ptr(v) for k, v in cols.items()})
     L.check(L.lib().dsq_results(C.byref(a), C.byref(o)))
@@ -999,10 +1000,10 @@ def results(beta, betaSE, stat, pvalue, baseMean, coef, replace=None, na_mask=No
 
 
 def results_dev(beta, betaSE, stat, pvalue, baseMean, coef, replace=None, na_mask=None, test="Wald", lfcThreshold=0.0,
-                altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1):
+                altHypothesis="greaterAbs", filter=None, theta=None, alpha=0.1, df=None):
     """dsq_results_dev on resident columns: beta / betaSE (p, n) tensors (= n x p column-major), stat / pvalue the same or
-    n-vectors (LRT), baseMean / filter n-vectors (float64), replace / na_mask int32 n-vectors, theta a K-vector -- all on
-    the device.  Nothing is read back: the five columns (rows of `table`), filtPadj (K, n): row k is the column of cutoff
+    n-vectors (LRT), baseMean / filter / df n-vectors (float64), replace / na_mask int32 n-vectors, theta a K-vector -- all
+    on the device.  Nothing is read back: the five columns (rows of `table`), filtPadj (K, n): row k is the column of cutoff
     k, and `_small` = cutoffs (K) | numRej (K int32, in ceil(K / 2) doubles) | status, for one copy."""
     import torch
     p, n = (1, beta.numel()) if beta.dim() == 1 else beta.shape
@@ -1018,7 +1019,7 @@ def results_dev(beta, betaSE, stat, pvalue, baseMean, coef, replace=None, na_mas
     a = L.DsqResultsArgs(n=n, p=p, c=int(coef), beta=_t_ptr(beta), betaSE=_t_ptr(betaSE), stat=_t_ptr(stat),
                          pvalue=_t_ptr(pvalue), baseMean=_t_ptr(baseMean), replace=_t_ptr(replace), na_mask=_t_ptr(na_mask),
                          filter=_t_ptr(filter), theta=_t_ptr(theta), alpha=float(alpha), workspace=_t_ptr(ws),
-                         workspace_bytes=wsb, **sc)
+                         workspace_bytes=wsb, df=_t_ptr(df), **sc)
     base = small.data_ptr()
     o = L.DsqResultsOut(baseMean=_t_ptr(table[0]), log2FoldChange=_t_ptr(table[1]), lfcSE=_t_ptr(table[2]),
                         stat=_t_ptr(table[3]), pvalue=_t_ptr(table[4]), filtPadj=_t_ptr(fp), cutoffs=C.c_void_p(base),
@@ -1026,6 +1027,31 @@ def results_dev(beta, betaSE, stat, pvalue, baseMean, coef, replace=None, na_mas
     L.check(L.lib().dsq_results_dev(C.byref(a), C.byref(o), _stream()))
     # (the workspace is stream-ordered scratch: torch's caching allocator hands it out again only to work enqueued later)
     return {"table": table, "filtPadj": fp, "_small": small, "K": K}
+
+
+def pt(q, df, tail="lower", keep=None, out=None):
+    """dsq_pt on host arrays: pt(q[i, k], df[i]) over an n-vector or an n x K matrix q; tail "lower", "upper" or "two_sided"
+    (2 * upper(|q|)).  keep: flags shaped as q -- where non-zero the entry of `out` (q when not given) is returned as it is."""
+    q = _fcol(q)
+    n = q.shape[0] if q.ndim else 1
+    K = q.shape[1] if q.ndim == 2 else 1
+    dfa = np.ascontiguousarray(np.broadcast_to(np.asarray(df, np.float64), (n,)))
+    kp = None if keep is None else np.asfortranarray(np.asarray(keep) != 0, dtype=np.int32)
+    res = np.array(q if out is None else _fcol(out), dtype=np.float64, order="F", copy=True)
+    L.check(L.lib().dsq_pt(_ptr(q), _ptr(dfa), n, K, L.DSQ_PT[tail], _ptr(kp), _ptr(res)))
+    return res
+
+
+def pt_dev(q, df, tail="lower", keep=None, out=None):
+    """dsq_pt_dev on resident tensors: q (n) or (K, n) = n x K column-major, df (n), keep int32 shaped as q or None; out: the
+    tensor to write (q itself for in place; a new one when None).  Asynchronous on the current stream."""
+    import torch
+    n = q.shape[-1]
+    K = q.numel() // n if n else 0
+    if out is None:
+        out = torch.empty_like(q)
+    L.check(L.lib().dsq_pt_dev(_t_ptr(q), _t_ptr(df), n, K, L.DSQ_PT[tail], _t_ptr(keep), _t_ptr(out), _stream()))
+    return out
 
 
 def results_small(small, K):
@@ -1045,11 +1071,11 @@ def _contrast_masks(sample_mask, rule_applies, K, m):
 
 
 def contrasts(x, nf, alpha_hat, beta, lambda_, contrasts, weights=None, useWeights=False, minmu=0.5, allZero=None,
-              counts=None, sample_mask=None, rule_applies=None, K=None):
+              counts=None, sample_mask=None, rule_applies=None, K=None, df=None):
     """dsq_contrasts on host arrays: K contrasts from one covariance pass per gene.  x: m x p; nf: n x m (or the m size
     factors); beta: n x p on the natural-log scale; lambda_: p; contrasts: p x K (a column per contrast) or None for the
     all-zero flags alone (then K = the number of masks); counts: the ORIGINAL n x m counts, sample_mask: K x m of 0 / 1,
-    rule_applies: K flags.  Returns log2FoldChange, lfcSE, stat, pvalue (n x K) and contrastAllZero (n x K int32)."""
+    rule_applies: K flags; df: n degrees of freedom (pvalue under Student's t).  Returns log2FoldChange, lfcSE, stat, pvalue (n x K) and contrastAllZero (n x K int32)."""
     ct = None if contrasts is None else _fcol(contrasts)
     if ct is not None and ct.ndim == 1:
         ct = ct.reshape(-1, 1, order="F")
@@ -1091,7 +1117,9 @@ def contrasts(x, nf, alpha_hat, beta, lambda_, contrasts, weights=None, useWeigh
         lam = np.ascontiguousarray(np.asarray(lambda_, np.float64).reshape(-1))
         if lam.size != p:
             raise ValueError("lambda must have length ncol(x)")
-        keep = [nfa, w, alpha, lam]
+        dfa = None if df is None else np.ascontiguousarray(np.broadcast_to(np.asarray(df, np.float64), (n,)))
+        keep = [nfa, w, alpha, lam, dfa]
+        a.df = _ptr(dfa)
         a.x, a.nf, a.nf_is_vector, a.alpha_hat, a.beta, a.lambda_ = _ptr(x), _ptr(nfa), int(is_vec), _ptr(alpha), _ptr(b), _ptr(lam)
         a.weights, a.useWeights, a.contrasts = _ptr(w), int(useW), _ptr(ct)
     o = L.DsqContrastsOut(contrastAllZero=_ptr(flags), **{k: _ptr(v) for k, v in out.items()})
@@ -1102,11 +1130,11 @@ def contrasts(x, nf, alpha_hat, beta, lambda_, contrasts, weights=None, useWeigh
 
 
 def contrasts_dev(x, nf, alpha_hat, beta, lambda_, contrasts, weights=None, useWeights=False, minmu=0.5, allZero=None,
-                  counts=None, sample_mask=None, rule_applies=None, nf_is_vector=False, cells=None):
+                  counts=None, sample_mask=None, rule_applies=None, nf_is_vector=False, cells=None, df=None):
     """dsq_contrasts_dev on resident data: x a (p, m) tensor (= m x p column-major), nf / weights / counts GeneMajor (nf: the
     m size factors with nf_is_vector), alpha_hat (n), beta (p, n) on the natural-log scale, lambda_ (p), contrasts (K, p)
     or None for the flags alone, allZero int32 (n), sample_mask int32 (K, m), rule_applies int32 (K); cells: HOST labels
-    (native.cell_index).  Nothing is read back: `table` (4, K, n) = log2FoldChange | lfcSE | stat | pvalue, each n x K
+    (native.cell_index); df float64 (n) or None.  Nothing is read back: `table` (4, K, n) = log2FoldChange | lfcSE | stat | pvalue, each n x K
     column-major, and contrastAllZero (K, n) int32."""
     import torch
     if contrasts is None:
@@ -1131,6 +1159,7 @@ def contrasts_dev(x, nf, alpha_hat, beta, lambda_, contrasts, weights=None, useW
         a.x, a.nf, a.nf_is_vector = _t_ptr(x), _t_ptr(nf if nf_is_vector else nf.t), int(bool(nf_is_vector))
         a.alpha_hat, a.beta, a.lambda_, a.contrasts = _t_ptr(alpha_hat), _t_ptr(beta), _t_ptr(lambda_), _t_ptr(contrasts)
         a.weights, a.useWeights = (_t_ptr(weights.t) if useWeights else None), int(bool(useWeights))
+        a.df = _t_ptr(df)
         if cells is not None:
             cells = np.ascontiguousarray(cells, dtype=np.int32)
             a.cell_of, a.ncell = _ptr(cells), int(cells.max()) + 1

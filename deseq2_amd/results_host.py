@@ -85,10 +85,14 @@ def _pmin(a, b):
     return np.where(np.isnan(a) | np.isnan(b), np.nan, np.where(a < b, a, b))
 
 
-def threshold_tests(vexp, LFC, SE, T, altHypothesis):
-    """newStat, newPvalue of R/results.R:484-515 (normal distribution)"""
-    up = lambda q: pnorm_both(vexp, q)[1]
+def threshold_tests(vexp, LFC, SE, T, altHypothesis, pt=None):
+    """newStat, newPvalue of R/results.R:484-515 (normal distribution).  pt = (lower, upper), two functions of q: the same
+    tests under Student's t with the rows' degrees of freedom bound into them (:477-515 with useT; plain quotients, gene i
+    with its own df -- DESIGN.md section 15)"""
+    up = (lambda q: pnorm_both(vexp, q)[1]) if pt is None else pt[1]
     with np.errstate(all="ignore"):
+        if altHypothesis == "greaterAbs" and pt is not None:
+            return LFC / SE, pt[0]((-np.abs(LFC) + T) / SE) + pt[0]((-np.abs(LFC) - T) / SE)
         if altHypothesis == "greaterAbs":
             return LFC / SE, _pnorm_sd(vexp, -np.abs(LFC) + T, SE) + _pnorm_sd(vexp, -np.abs(LFC) - T, SE)
         if altHypothesis == "greaterAbs2014":
@@ -106,13 +110,13 @@ def threshold_tests(vexp, LFC, SE, T, altHypothesis):
     raise ValueError("altHypothesis should be one of %s" % ", ".join(ALT))
 
 
-def results_table(vexp, lfc, se, stat, pvalue, baseMean, replace, na_mask, lfcThreshold, altHypothesis):
-    """the five columns of R/results.R:443-575 from the coefficient's columns"""
+def results_table(vexp, lfc, se, stat, pvalue, baseMean, replace, na_mask, lfcThreshold, altHypothesis, pt=None):
+    """the five columns of R/results.R:443-575 from the coefficient's columns (pt: see threshold_tests)"""
     lfc, se = np.array(lfc, np.float64), np.array(se, np.float64)
     stat, pvalue = np.array(stat, np.float64), np.array(pvalue, np.float64)
     bm = np.array(baseMean, np.float64)
     if not (lfcThreshold == 0 and altHypothesis == "greaterAbs"):
-        stat, pvalue = (np.array(v) for v in threshold_tests(vexp, lfc, se, float(lfcThreshold), altHypothesis))
+        stat, pvalue = (np.array(v) for v in threshold_tests(vexp, lfc, se, float(lfcThreshold), altHypothesis, pt))
     if na_mask is not None:
         pvalue[np.asarray(na_mask) == 1] = np.nan
     if replace is not None:

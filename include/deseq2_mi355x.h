@@ -402,7 +402,8 @@ double dsq_profile_last_ms(void);
 
 /* Parity hook for tests: evaluate one scalar primitive of the device math library on
  * the GPU (op: 0 exp, 1 log, 2 log1p, 3 lgamma, 4 digamma, 5 trigamma, 6 stirlerr,
- * 7 bd0(a,b), 8 dnbinom_mu_log(a=x, b=size, c=mu)).  HOST pointers, n elements.       */
+ * 7 bd0(a,b), 8 dnbinom_mu_log(a=x, b=size, c=mu), 9 2 pnorm(-|a|), 10 pt(a, df = b, lower.tail = FALSE), 11 pt(a, df = b)).
+ * HOST pointers, n elements.                                                              */
 int dsq_test_math(int op, const double *a, const double *b, const double *c, double *out, int64_t n);
 
 /* ---- dsq_deseq_dev: the whole DESeq() chain, device-driven ---------------------------
@@ -720,6 +721,8 @@ typedef struct {
     double alpha;                  /* in (0, 1)                                                                      */
     void *workspace;               /* device; dsq_results: ignored                                                   */
     int64_t workspace_bytes;
+    const double *df;              /* n degrees of freedom (a useT analysis, mcols tDegreesFreedom): the threshold tests
+                                      take pt(., df[i]) for pnorm (R/results.R:477-515), NaN df = NaN pvalue; NULL: normal */
 } DsqResultsArgs;
 
 typedef struct {
@@ -775,6 +778,9 @@ typedef struct {
     const int32_t *rule_applies;   /* K flags (with sample_mask)                                                        */
     const int32_t *cell_of;        /* extension: design cells as in DsqFitBetaArgs (HOST, m labels, may be NULL)        */
     int32_t ncell;
+    const double *df;              /* n degrees of freedom or NULL.  Given: pvalue = 2 pt(|stat|, df[i], lower.tail = FALSE)
+                                      (R/results.R:812-815) by a dsq_pt_dev pass behind the kernel; entries the all-zero
+                                      rule has set to 1 keep it even where df is NA                                     */
 } DsqContrastsArgs;
 
 typedef struct {
@@ -785,6 +791,19 @@ typedef struct {
 int dsq_contrasts_dev(const DsqContrastsArgs *args, const DsqContrastsOut *out, void *stream);
 int dsq_contrasts(const DsqContrastsArgs *args, const DsqContrastsOut *out);
 int32_t dsq_contrasts_max_m(int32_t p);   /* longest row the per-sample path takes at p design columns */
+
+/* ---- dsq_pt: Student's t distribution function, elementwise ---------------------------------
+ * out[i + n k] = pt(q[i + n k], df[i]) for real df > 0 in the engine's pinned f64 arithmetic (deseq2_amd/student_t.py states
+ * it operation for operation): q and out n x K column-major, row i's df for every column.  As R's pt: NaN in either
+ * argument or df <= 0 gives NaN, q = -Inf / +Inf the lower tail 0 / 1, df = +Inf the normal distribution; the lower tail of q
+ * has the bits of the upper tail of -q.  Relative error: the tests assert 1e-12 wherever the exact value is a normal number
+ * (tails of 1e-300 included; q^2 may overflow); measured on their 2374-point grid against 50-digit values: 1.4e-13 at most.  keep: n x K flags or NULL -- where non-zero, out is not written.  out == q is allowed.
+ * _dev: device pointers, asynchronous on `stream`, no allocation, no host synchronisation, one thread per entry.
+ * dsq_pt: host pointers, one device, synchronous.                                                                       */
+enum { DSQ_PT_LOWER = 0, DSQ_PT_UPPER = 1, DSQ_PT_TWO_SIDED = 2 };   /* TWO_SIDED: 2 * upper(|q|) */
+int dsq_pt_dev(const double *q, const double *df, int32_t n, int32_t K, int32_t tail, const int32_t *keep, double *out,
+               void *stream);
+int dsq_pt(const double *q, const double *df, int32_t n, int32_t K, int32_t tail, const int32_t *keep, double *out);
 
 /* ---- dsq_deseq: DESeq() behind ONE host-pointer call ------------------------------------------------------------
  * What an R session binds as .Call("_DESeq2_mi355x_DESeq", ...) in place of the body of DESeq() between
