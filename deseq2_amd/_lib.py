@@ -323,6 +323,7 @@ EXPORTED_SYMBOLS = [
     "dsq_intercept_fit", "dsq_intercept_fit_dev", "dsq_deseq_dev", "dsq_deseq_workspace_bytes",
     "dsq_profile_count", "dsq_profile_get",
     "dsq_deseq", "dsq_beta_prior_var", "dsq_weights_prep_dev", "dsq_xim_dev",
+    "dsq_beta_prior_var_dev", "dsq_beta_prior_var_columns", "dsq_beta_prior_var_workspace_bytes",
     "dsq_linear_mu", "dsq_linear_mu_dev", "dsq_cooks_distance", "dsq_cooks_distance_dev", "dsq_replace_outliers", "dsq_replace_outliers_dev",
     "dsq_size_factors", "dsq_size_factors_dev", "dsq_size_factors_workspace_bytes",
     "dsq_vst", "dsq_vst_dev", "dsq_vst_rowstats_dev",
@@ -392,6 +393,11 @@ def lib():
     L.dsq_xim_dev.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dsq_deseq.argtypes = [C.POINTER(DsqDeseqHostArgs), C.POINTER(DsqDeseqHostOut)]
     L.dsq_beta_prior_var.argtypes = [C.POINTER(DsqBetaPriorArgs), C.c_void_p]
+    L.dsq_beta_prior_var_dev.argtypes = [C.POINTER(DsqBetaPriorArgs), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.dsq_beta_prior_var_columns.argtypes = [C.POINTER(DsqBetaPriorArgs)]
+    L.dsq_beta_prior_var_columns.restype = C.c_int32
+    L.dsq_beta_prior_var_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.dsq_beta_prior_var_workspace_bytes.restype = C.c_int64
     L.dsq_size_factors.argtypes = [C.POINTER(DsqSizeFactorArgs), C.POINTER(DsqSizeFactorOut)]
     L.dsq_size_factors_dev.argtypes = [C.POINTER(DsqSizeFactorArgs), C.POINTER(DsqSizeFactorOut), C.c_void_p]
     L.dsq_size_factors_workspace_bytes.argtypes = [C.c_int32, C.c_int32]

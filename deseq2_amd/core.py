@@ -15,7 +15,11 @@ Transformations: vst / varianceStabilizingTransformation / getVarianceStabilized
 counts(normalized = TRUE) run in the engine as well (csrc/vst.hip); rlog / rlogTransformation
 run there too, for any number of samples (csrc/rlog.hip).
 
-Not mirrored (out of the hot-path scope): local/glmGamPoi dispersion fits, results(), lfcShrink().
+results() / resultsContrasts() (R/results.R) and lfcShrink(type = "normal") (R/lfcShrink.R: the Normal prior; the prior
+variance of all columns on the device, csrc/beta_prior.hip) are mirrored at the end of this file.
+
+Not mirrored (out of the hot-path scope): local/glmGamPoi dispersion fits; lfcShrink(type = "apeglm" /
+"ashr"), which delegate to packages whose source is not part of the reference tree.
 """
 import warnings
 
@@ -769,6 +773,8 @@ def Hmisc_wtd_quantile(x, weights, prob, normwt=True, sorter=None):
     x = np.asarray(x, float); w = np.asarray(weights, float)
     keep = ~(np.isnan(w) | (w == 0))
     x, w = x[keep], w[keep]
+    if x.size == 0:                    # (no row with a usable weight: NaN, as csrc/beta_prior.hip returns)
+        return np.nan
     if normwt:
         w = w * x.size / np.cumsum(w)[-1]          # (every sum here is sequential: the order csrc/beta_prior.hip follows)
     o = np.argsort(x, kind="stable") if sorter is None else np.asarray(sorter(x))
@@ -813,14 +819,22 @@ def estimateBetaPriorVar(dds, mleBetaMatrix, names, betaPriorMethod="weighted", 
     beta = np.asarray(mleBetaMatrix, float)
     names = list(names)
     if modelMatrixType == "expanded":                                  # addAllContrasts, expanded.R:76-98
+        pairs = []
         for f, codes in factors.items():
             idx = [i for i, nm in enumerate(names) if nm.startswith(f) and nm != "Intercept"]
             k = len(idx)
             if k > 1:
                 for j in range(k - 1):
                     for i in range(j + 1, k):
-                        beta = np.column_stack([beta, beta[:, idx[i]] - beta[:, idx[j]]])
+                        pairs.append((idx[i], idx[j]))
                         names.append(f + "Cntrst")
+        if pairs:                                                      # (one allocation for all contrast columns)
+            p0 = beta.shape[1]
+            wide = np.empty((beta.shape[0], p0 + len(pairs)))
+            wide[:, :p0] = beta
+            ii, jj = np.array(pairs).T
+            np.subtract(beta[:, ii], beta[:, jj], out=wide[:, p0:])
+            beta = wide
     dispFit = dds.mcols.get("dispFit")
     if dispFit is None:
         dispFit = np.mean(dds.mcols["dispersion"])
@@ -2165,4 +2179,205 @@ def resultsContrasts(dds, contrasts, listValues=(1, -1), minmu=0.5, lfcThreshold
                             filter, theta, pAdjustMethod, filterFun, tidy)
         res.metadata["contrast"] = name
         out.append(res)
+    return out
+
+
+# ------------------------------------------------------------------ lfcShrink (R/lfcShrink.R:145-520)
+def _design_from_factors(dds):
+    """is(design(dds), "formula") in this mirror: attrs["factors"] is set and dds.x is the matrix standard_model_matrix builds
+    from it (the test _factor_columns applies); anything else is a user-supplied matrix"""
+    factors = dds.attrs.get("factors")
+    if not factors:
+        return False
+    xs, _ = standard_model_matrix(factors)
+    return xs.shape == dds.x.shape and bool(np.array_equal(xs, dds.x))
+
+
+def _shrink_object(dds, rows):
+    """the object nbinomWaldTest(dds, betaPrior = TRUE) works on inside lfcShrink: the rows that are not all zero NOW (objectNZ,
+    R/core.R:1351 -- allZero as refitWithoutOutliers left it) over the ORIGINAL counts dds.y, with the dispersions of the
+    finished analysis.  The caller's object is not touched."""
+    sub = _shallow(dds) if rows is None else dds.subset(rows)
+    pick = (lambda v: np.asarray(v)) if rows is None else (lambda v: np.asarray(v)[rows])
+    sub.mcols = {k: pick(dds.mcols[k]) for k in ("baseMean", "baseVar", "allZero", "dispersion", "dispFit") if k in dds.mcols}
+    sub.attrs = {k: dds.attrs[k] for k in ("weightsOK",) if k in dds.attrs}
+    sub.dispersionFunction = dds.dispersionFunction
+    return sub
+
+
+def _shrink_full_rows(dds, sub, rows):
+    """buildDataFrameWithNARows: the per-gene columns of the refitted rows back over all n rows (NA elsewhere), next to the
+    columns results() reads from the analysis itself (baseMean, allZero, replace, the dispersions)"""
+    out = {}
+    for k, v in sub.mcols.items():
+        v = np.asarray(v)
+        if k == "rowsForOptim" or v.shape[:1] != (sub.n,):
+            continue
+        if rows is None:
+            out[k] = v
+        else:
+            full = np.full((dds.n,) + v.shape[1:], np.nan)
+            full[rows] = v
+            out[k] = full
+    for k in ("baseMean", "baseVar", "allZero", "dispersion", "dispFit", "replace", "weightsFail"):
+        if k in dds.mcols:
+            out[k] = dds.mcols[k]
+    return out
+
+
+def lfcShrink(dds, coef=None, contrast=None, res=None, type="normal", lfcThreshold=0, quiet=False, **not_served):
+    """lfcShrink (R/lfcShrink.R:145-520) with the Normal prior of Love et al. (2014): type = "normal".  NOTE the default: R's is
+    type = "apeglm"; "apeglm" and "ashr" delegate to packages whose source is not part of the reference tree and raise
+    NotImplementedError here, so "normal" is the default of this mirror.  `coef` is a name of resultsNames(dds) or a column
+    index (0-based, as results(name = ) takes it), `contrast` one of the three forms resultsContrasts takes, over the names of
+    the EXPANDED model matrix (makeExpandedModelMatrix); one of the two.  Returns `res` (results(dds, name = coef) /
+    resultsContrasts(dds, [contrast])[0] when not given) with log2FoldChange and lfcSE -- and, with lfcThreshold > 0, stat,
+    pvalue and padj -- replaced by those of the shrunken fit (:318-325); priorInfo carries the prior variance.
+    The estimator (:263-316): betaPriorVar = estimateBetaPriorVar over the stored MLE coefficients (the engine's
+    beta_prior_var: csrc/beta_prior.hip on the device), standard matrix for `coef`, expanded for `contrast`; then
+    nbinomWaldTest(betaPrior = TRUE, betaPriorVar, modelMatrixType) ON ITS DEFAULTS -- no useT, minmu = 0.5, betaTol = 1e-8,
+    whatever DESeq() was run with -- on the ORIGINAL counts, also for the rows DESeq() refitted on the replaced counts, over
+    the rows that are not all zero as refitWithoutOutliers left that column; then results() on the refitted object.  This is
+    what R does (its dds.shr is nbinomWaldTest(dds, ...): counts(dds) are the original counts, mcols(dds)$allZero the updated
+    flags), not an oversight of the mirror.
+    Two routes, one result: with lfcThreshold == 0 only log2FoldChange and lfcSE of the refit are read, so only the ridge pass
+    of fitGLMsWithPrior runs (R/fitNbinomGLMs.R:311-325; the MLE pass, mu, the hat diagonals, Cook's distances, the log
+    likelihood and the p-values are skipped) and its coefficients take the tail of results() / resultsContrasts() -- NA on
+    the all-zero rows, the nowZero fill, the all-zero rule of a contrast; with lfcThreshold > 0 the whole nbinomWaldTest
+    runs and the Cook's mask of the new p-values comes from the refitted object.  The ridge pass does not depend on what is
+    skipped: the two give the same log2FoldChange and lfcSE bits.
+    A user-supplied matrix (no attrs["factors"], or another matrix than they generate) is served with `coef` only.
+    Not served (NotImplementedError): type "apeglm" / "ashr", svalue, returnList, format, saveCols, parallel."""
+    import sys
+    from .fused import finish
+    reasons = {"svalue": "s-values belong to type = 'apeglm' / 'ashr'", "returnList": "only type = 'apeglm' / 'ashr' return a list",
+               "format": "only the table is served", "saveCols": "only the six result columns are served",
+               "parallel": "the refit runs on one device", "BPPARAM": "see parallel",
+               "apeAdapt": "type = 'apeglm' is not served", "apeMethod": "type = 'apeglm' is not served"}
+    for k, v in not_served.items():
+        if k not in reasons:
+            raise TypeError("lfcShrink() got an unexpected keyword argument '%s'" % k)
+        if not (v is None or v is False or (k == "format" and v == "DataFrame") or (k == "apeAdapt" and v is True)
+                or (k == "apeMethod" and v == "nbinomCR")):
+            raise NotImplementedError("lfcShrink(%s = ): %s" % (k, reasons[k]))
+    if not isinstance(dds, DESeqDataSet):
+        raise TypeError('is(dds, "DESeqDataSet") is not TRUE')                    # :156
+    if res is not None and not isinstance(res, DESeqResults):
+        raise ValueError("res should be a DESeqResults object, for GRanges output use 'format'")   # :157-159
+    if type not in ("apeglm", "ashr", "normal"):
+        raise ValueError("'arg' should be one of apeglm, ashr, normal")          # :160
+    finish(dds)                      # (an analysis enqueued with wait = False)
+    if "beta" not in dds.mcols:
+        raise RuntimeError("first run DESeq() before running lfcShrink()")        # :162-166
+    if type != "normal":
+        raise NotImplementedError("lfcShrink(type = '%s') delegates to the %s package, whose source is not part of the reference "
+                                  "tree: nothing here could pin it.  Served: type = 'normal'" % (type, type))
+    if dds.attrs.get("betaPrior"):
+        raise ValueError("lfcShrink() should be used downstream of DESeq() with betaPrior=FALSE (the default)")   # :170-173
+    if np.ndim(lfcThreshold) != 0 or not lfcThreshold >= 0:
+        raise ValueError("length(lfcThreshold) == 1 && lfcThreshold >= 0 is not TRUE")   # :174
+    names = resultsNames(dds)                                                     # :175
+    c = None
+    if coef is not None:                                                          # :182-192
+        if isinstance(coef, str):
+            if coef not in names:
+                raise ValueError("coef %in% resultsNamesDDS is not TRUE")
+            c = names.index(coef)
+        elif isinstance(coef, (int, np.integer)) and not isinstance(coef, bool) and 0 <= int(coef) < len(names):
+            c = int(coef)
+        else:
+            raise ValueError("coef <= length(resultsNamesDDS) is not TRUE")
+    if res is None:                                                               # :193-204
+        if coef is not None:
+            res = results(dds, name=c)
+        elif contrast is not None:
+            if _contrast_form(contrast) == "numeric":
+                raise ValueError("for type='normal' and numeric contrast, user must provide 'res' object")   # :197-199
+            res = resultsContrasts(dds, [contrast])[0]
+        else:
+            raise ValueError("one of coef or contrast required if 'res' is missing")
+    if np.isnan(np.asarray(res["lfcSE"], np.float64)).all():
+        raise ValueError("lfcShrink requires standard errors, use default fitType")   # :207-208
+    if "dispersion" not in dds.mcols:
+        raise RuntimeError("type='normal' and 'apeglm' require dispersion estimates, first call estimateDispersions()")   # :211-213
+    if res.n != dds.n:
+        raise ValueError("all(rownames(dds) == rownames(res)) is not TRUE")      # :214 (the objects carry no row names)
+    if coef is None and contrast is None:
+        raise ValueError("type='normal' requires either 'coef' or 'contrast' be specified.")   # :223-225
+    if not quiet:                                                                 # :231-235
+        print("using 'normal' for LFC shrinkage, the Normal prior from Love et al (2014).", file=sys.stderr)
+    formula = _design_from_factors(dds)
+    if not formula and contrast is not None:
+        raise ValueError("user-supplied design matrix supports shrinkage only with 'coef'")   # :243-245, :256-258
+    if coef is not None and contrast is not None:
+        raise ValueError("missing(coef) | missing(contrast) is not TRUE")        # :262
+    factors = dds.attrs.get("factors") if formula else None
+    if contrast is None:
+        modelMatrixType = "standard"                                              # :269-270
+    else:
+        modelMatrixType = "expanded"                                              # :273-287
+        xe, enames = makeExpandedModelMatrix(factors)
+        if _contrast_form(contrast) == "character":
+            if len(contrast) != 3:
+                raise ValueError("length(contrast) == 3 is not TRUE")
+            if contrast[0] not in factors:
+                raise ValueError("contrast[1] %in% names(colData(dds)) is not TRUE")
+            if not all(lv in set(np.asarray(factors[contrast[0]]).tolist()) for lv in contrast[1:]):
+                raise ValueError("all(contrast[2:3] %in% levels(colData(dds)[[contrast[1]]])) is not TRUE")
+        checkContrast(contrast, enames)                                           # :286
+    # estimateBetaPriorVar (:289) over the stored MLE coefficients of the standard matrix -- on an LRT analysis as well
+    E = dds.engine
+    from .native import coef_factor_codes
+    allZero = np.asarray(dds.mcols["allZero"], bool)
+    if factors is not None:
+        cf = coef_factor_codes(factors)
+    else:
+        cf = np.array([0 if nm == "Intercept" else 1 for nm in _coef_names(dds, len(names))], np.int32)
+    dispFit = dds.mcols.get("dispFit")
+    if dispFit is None:
+        dispFit = np.full(dds.n, np.mean(np.asarray(dds.mcols["dispersion"])[~allZero]))   # R/core.R:1637-1640
+    betaPriorVar = E.beta_prior_var(np.asarray(dds.mcols["beta"], np.float64), np.asarray(dds.mcols["baseMean"], np.float64),
+                                    np.asarray(dispFit, np.float64), allZero, cf,
+                                    prior_coef_factor=coef_factor_codes(factors, expanded=True) if contrast is not None else None)
+    betaPriorVar = np.asarray(betaPriorVar, np.float64)
+    if betaPriorVar.size == 0:
+        raise ValueError("length(betaPriorVar) > 0 is not TRUE")                  # :290
+    rows = np.where(~allZero)[0] if allZero.any() else None
+    sub = _shrink_object(dds, rows)
+    if lfcThreshold > 0:                                                          # :293-298
+        nbinomWaldTest(sub, betaPrior=True, betaPriorVar=betaPriorVar, modelMatrixType=modelMatrixType, factors=factors)
+        sub.mcols.pop("MLE_beta", None)
+    else:
+        # only the ridge pass of fitGLMsWithPrior (R/fitNbinomGLMs.R:311-325): nothing else of the refit is read below
+        if (betaPriorVar == 0).any():
+            raise ValueError("beta prior variances are equal to zero for some variables")
+        weights, useWeights = getAndCheckWeights(sub)
+        fit = fitNbinomGLMs(sub, lam=1.0 / betaPriorVar, modelMatrix=xe if contrast is not None else None,
+                            weights=weights, useWeights=useWeights, want_hat=False)
+        sub.mcols.update(beta=fit["betaMatrix"], betaSE=fit["betaSE"])
+        sub.attrs.update(betaPrior=True, betaPriorVar=betaPriorVar, test="Wald", modelMatrixType=modelMatrixType,
+                         factors=factors, useT=False)
+    shr = _shallow(dds)
+    shr.mcols = _shrink_full_rows(dds, sub, rows)
+    shr.assays = sub.assays
+    shr.attrs = {k: v for k, v in sub.attrs.items() if k not in ("prefit", "prefit_for")}
+    if rows is not None:
+        shr.attrs["nz_rows"] = rows
+    if contrast is not None:
+        shr.attrs["coefNames"] = list(enames)
+    elif dds.attrs.get("coefNames") is not None:
+        shr.attrs["coefNames"] = dds.attrs["coefNames"]
+    shr.dispersionFunction = dds.dispersionFunction
+    if contrast is None:                                                          # :309-316
+        res_shr = results(shr, name=c, lfcThreshold=lfcThreshold)
+    else:
+        res_shr = resultsContrasts(shr, [contrast], lfcThreshold=lfcThreshold)[0]
+    out = DESeqResults(res.tab, None, res.engine)
+    out.metadata = dict(res.metadata)
+    out._set = dict(res._set)
+    change = ("log2FoldChange", "lfcSE", "stat", "pvalue", "padj") if lfcThreshold > 0 else ("log2FoldChange", "lfcSE")   # :318-322
+    for col in change:                                                            # :323-325
+        out[col] = (lambda r=res_shr, k=col: r[k])
+    out.metadata["lfcThreshold"] = lfcThreshold                                   # :497
+    out.priorInfo = {"type": "normal", "package": "deseq2_amd", "betaPriorVar": betaPriorVar}   # :498-505
     return out

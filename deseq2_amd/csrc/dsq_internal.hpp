@@ -294,6 +294,13 @@ struct ResultsKernelParams {
 };
 hipError_t launch_results(ResultsKernelParams kp, void *workspace, hipStream_t st);
 size_t results_sort_workspace_bytes(long n);     // the sort's part; filtPadj (n K doubles) may follow it
+// the same pass kernels over `ncols` INDEPENDENT columns of n keys each in one launch chain (grid y = the column; the prior
+// variance of beta_prior.hip sorts a batch of columns so): column c's keys at keyA + c n (keyB, rowA, rowB alike; rows may
+// be nullptr), its (digit, tile) table at hist + c sort_hist_entries(n), its copy flag at const_digit + c.  Stable,
+// ascending, 8 passes A -> B -> A ...: the result is back in A, B is free.
+void radix_sort_columns(unsigned long long *keyA, unsigned long long *keyB, unsigned int *rowA, unsigned int *rowB,
+                        unsigned int *hist, unsigned int *const_digit, int n, int ncols, hipStream_t st);
+size_t sort_hist_entries(long n);                // 256 x the tiles of one column
 
 // K contrasts from one covariance pass per gene (contrasts.hip).  n x m matrices gene-major with
 // leading dimension ld, n x p / n x K matrices column-major; ncell > 0 selects the cell-collapsed Gram sums (cell_perm,

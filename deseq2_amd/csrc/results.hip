@@ -140,10 +140,15 @@ __global__ void __launch_bounds__(256) sort_keys_kernel(const double *v, int n, 
     if (isnan) atomicAdd(nan_count, 1u);
 }
 
+// The three pass kernels sort blockIdx.y INDEPENDENT columns of n keys each (radix_sort_columns; results() has one):
+// column c's keys (and rows) start c n entries into their arrays, its table 256 nblk entries into hist, its copy flag is
+// const_digit[c].
 // hist[digit * nblk + tile]: the keys of the tile with that digit
 __global__ void __launch_bounds__(kSortThreads) sort_hist_kernel(const unsigned long long *key, int n, int shift,
                                                                  unsigned int *hist, int nblk) {
     __shared__ unsigned int h[256];
+    key += (long)blockIdx.y * n;
+    hist += (long)blockIdx.y * 256 * nblk;
     h[threadIdx.x] = 0u;
     __syncthreads();
     const long base = (long)blockIdx.x * kSortTile;
@@ -180,6 +185,8 @@ DSQ_DEV unsigned int block_inclusive_sum(unsigned int x, unsigned int *lds16, un
 __global__ void __launch_bounds__(kBhThreads) sort_scan_kernel(unsigned int *hist, int nblk, int n, unsigned int *const_digit) {
     __shared__ unsigned int lds16[16];
     const long total = 256L * nblk;
+    hist += (long)blockIdx.y * total;
+    const_digit += blockIdx.y;
     const long per = (total + kBhThreads - 1) / kBhThreads;
     const long lo = (long)threadIdx.x * per, hi = lo + per < total ? lo + per : total;
     unsigned int s = 0u;
@@ -208,7 +215,13 @@ __global__ void __launch_bounds__(kSortThreads) sort_scatter_kernel(const unsign
     __shared__ unsigned int base[256];
     __shared__ unsigned int wcnt[kSortThreads / 64][256];
     const long tile0 = (long)blockIdx.x * kSortTile;
-    if (*const_digit) {                                     // (uniform over the grid)
+    {
+        const long col0 = (long)blockIdx.y * n;
+        kin += col0; kout += col0;
+        if (rin) { rin += col0; rout += col0; }
+        offs += (long)blockIdx.y * 256 * nblk;
+    }
+    if (const_digit[blockIdx.y]) {                          // (uniform over the column's blocks)
         for (int it = 0; it < kSortItems; it++) {
             const long i = tile0 + it * kSortThreads + threadIdx.x;
             if (i < n) { kout[i] = kin[i]; if (rin) rout[i] = rin[i]; }
@@ -373,20 +386,27 @@ size_t results_sort_workspace_bytes(long n) {
     return 2 * (size_t)n * 8 + 2 * pad8((size_t)n * 4) + (size_t)256 * sort_tiles(n) * 4 + CNT_COUNT * 4;
 }
 
-// sorts keyA (and rowA when with_rows) ascending; 8 passes A -> B -> A ..., so the result is back in A
-static void radix_sort(const ResultsKernelParams &kp, bool with_rows, hipStream_t st) {
-    const int nblk = sort_tiles(kp.n);
-    unsigned long long *ka = kp.keyA, *kb = kp.keyB;
-    unsigned int *ra = with_rows ? kp.rowA : nullptr, *rb = with_rows ? kp.rowB : nullptr;
+size_t sort_hist_entries(long n) { return (size_t)256 * sort_tiles(n); }
+
+// sorts each of the ncols columns of keyA (and rowA, unless nullptr) ascending; 8 passes A -> B -> A ..., so the result is
+// back in A
+void radix_sort_columns(unsigned long long *ka, unsigned long long *kb, unsigned int *ra, unsigned int *rb, unsigned int *hist,
+                        unsigned int *const_digit, int n, int ncols, hipStream_t st) {
+    const int nblk = sort_tiles(n);
     for (int pass = 0; pass < 8; pass++) {
         const int shift = 8 * pass;
-        hipLaunchKernelGGL(sort_hist_kernel, dim3(nblk), dim3(kSortThreads), 0, st, ka, kp.n, shift, kp.hist, nblk);
-        hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(kBhThreads), 0, st, kp.hist, nblk, kp.n, kp.counters + CNT_CONST_DIGIT);
-        hipLaunchKernelGGL(sort_scatter_kernel, dim3(nblk), dim3(kSortThreads), 0, st, ka, ra, kb, rb, kp.n, shift, kp.hist, nblk,
-                           kp.counters + CNT_CONST_DIGIT);
+        hipLaunchKernelGGL(sort_hist_kernel, dim3(nblk, ncols), dim3(kSortThreads), 0, st, ka, n, shift, hist, nblk);
+        hipLaunchKernelGGL(sort_scan_kernel, dim3(1, ncols), dim3(kBhThreads), 0, st, hist, nblk, n, const_digit);
+        hipLaunchKernelGGL(sort_scatter_kernel, dim3(nblk, ncols), dim3(kSortThreads), 0, st, ka, ra, kb, rb, n, shift, hist, nblk,
+                           const_digit);
         unsigned long long *tk = ka; ka = kb; kb = tk;
         unsigned int *tr = ra; ra = rb; rb = tr;
     }
+}
+
+static void radix_sort(const ResultsKernelParams &kp, bool with_rows, hipStream_t st) {
+    radix_sort_columns(kp.keyA, kp.keyB, with_rows ? kp.rowA : nullptr, with_rows ? kp.rowB : nullptr, kp.hist,
+                       kp.counters + CNT_CONST_DIGIT, kp.n, 1, st);
 }
 
 // carves the caller's workspace (results_sort_workspace_bytes) and enqueues the chain

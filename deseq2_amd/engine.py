@@ -442,6 +442,15 @@ class HostEngine:
         df = np.asarray(df, np.float64)
         return (lambda q: S.pt_lower(self.fns, q, df)), (lambda q: S.pt_upper(self.fns, q, df))
 
+    # ---- the beta prior variance of all columns (R/core.R:1601-1689)
+    def beta_prior_var(self, mle_beta, baseMean, dispFit, allZero, coef_factor, prior_coef_factor=None, prior_coef_src=None):
+        """estimateBetaPriorVar over the n x p MLE coefficients (log2 scale), rows flagged allZero left out; the column coding
+        of native.coef_factor_codes; prior_coef_factor given = the expanded model matrix.  The library's host function
+        (dsq_beta_prior_var: the definition core.estimateBetaPriorVar follows, the same bits)."""
+        from . import native
+        return native.estimateBetaPriorVarHost(mle_beta, baseMean, dispFit, allZero, coef_factor,
+                                               prior_coef_factor=prior_coef_factor, prior_coef_src=prior_coef_src)
+
     # ---- results() (R/results.R:443-575, 638-740; DESIGN.md section 13): the numpy statement of csrc/results.hip
     def results_table(self, lfc, se, stat, pvalue, baseMean, replace=None, na_mask=None, lfcThreshold=0.0,
                       altHypothesis="greaterAbs", df=None):
@@ -889,6 +898,19 @@ class DeviceEngine:
 
     def two_sided_normal_p(self, z):
         return self.native.unary("pnorm_upper2", np.asarray(z, np.float64))
+
+    # ---- the beta prior variance: HIP kernels (csrc/beta_prior.hip); one upload, `columns` values back
+    def beta_prior_var(self, mle_beta, baseMean, dispFit, allZero, coef_factor, prior_coef_factor=None, prior_coef_src=None):
+        """HostEngine.beta_prior_var through dsq_beta_prior_var_dev: the n x p coefficients, baseMean and dispFit go up in
+        one copy, the all-zero flags in another; the contrast columns of the expanded matrix are formed on the device"""
+        t = self.torch
+        mle = np.asarray(mle_beta, np.float64)
+        n, p = mle.shape
+        dv = self._vec(np.concatenate([mle.T.reshape(-1), np.asarray(baseMean, np.float64).reshape(-1),
+                                       np.asarray(dispFit, np.float64).reshape(-1)]))
+        az = t.as_tensor(np.ascontiguousarray(np.asarray(allZero) != 0, dtype=np.int32), device=self.device)
+        return self.native.estimateBetaPriorVar_dev(dv[:n * p].view(p, n), dv[n * p:n * p + n], dv[n * p + n:], az, coef_factor,
+                                                    prior_coef_factor=prior_coef_factor, prior_coef_src=prior_coef_src)
 
     # ---- results(): HIP kernels (csrc/results.hip) on resident columns; nothing but K cutoffs and counts comes back
     def pt(self, q, df, tail="lower", keep=None, out=None):

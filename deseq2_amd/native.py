@@ -289,6 +289,29 @@ def estimateBetaPriorVarHost(mle_beta, baseMean, dispFit, allZero, coef_factor, 
     return out
 
 
+def estimateBetaPriorVar_dev(mle_beta, baseMean, dispFit, allZero, coef_factor, prior_coef_factor=None, prior_coef_src=None,
+                             workspace=None):
+    """dsq_beta_prior_var_dev on resident inputs: mle_beta a (p, n) float64 tensor (= n x p column-major), baseMean /
+    dispFit float64 n-vectors, allZero an int32 n-vector, all on the device; the column coding as estimateBetaPriorVarHost
+    takes it (host).  Returns the host vector (p values, or one per column of the expanded matrix); the call waits for the
+    stream once.  workspace: a uint8 device tensor of dsq_beta_prior_var_workspace_bytes(n, columns) bytes to reuse."""
+    import torch
+    p, n = (1, mle_beta.numel()) if mle_beta.dim() == 1 else mle_beta.shape
+    cf = np.ascontiguousarray(coef_factor, dtype=np.int32)
+    pcf = None if prior_coef_factor is None else np.ascontiguousarray(prior_coef_factor, dtype=np.int32)
+    pcs = None if prior_coef_src is None else np.ascontiguousarray(prior_coef_src, dtype=np.int32)
+    pp = p if pcf is None else pcf.size
+    out = np.zeros(pp)
+    args = L.DsqBetaPriorArgs(n=n, p=p, mle_beta=_t_ptr(mle_beta), baseMean=_t_ptr(baseMean), dispFit=_t_ptr(dispFit),
+                              allZero=_t_ptr(allZero), coef_factor=_ptr(cf), expanded=int(pcf is not None), p_prior=int(pp),
+                              prior_coef_factor=_ptr(pcf), prior_coef_src=_ptr(pcs), upperQuantile=0.05)
+    if workspace is None:
+        wsb = int(L.lib().dsq_beta_prior_var_workspace_bytes(n, L.lib().dsq_beta_prior_var_columns(C.byref(args))))
+        workspace = torch.empty(wsb, dtype=torch.uint8, device=mle_beta.device)
+    L.check(L.lib().dsq_beta_prior_var_dev(C.byref(args), _ptr(out), _t_ptr(workspace), int(workspace.numel()), _stream()))
+    return out
+
+
 def DESeq(counts, x, sizeFactors=None, test="Wald", reduced=None, normalizationFactors=None, weights=None,
           minReplicatesForReplace=7, betaTol=1e-8, maxit=100, useQR=True,
           minmu=0.5, disp_maxit=100, useCR=True, assays=("mu", "H", "cooks"),

@@ -921,6 +921,22 @@ typedef struct {
 } DsqBetaPriorArgs;
 int dsq_beta_prior_var(const DsqBetaPriorArgs *args, double *betaPriorVar);
 
+/* The device twin (csrc/beta_prior.hip): the same definition, the same bits.  mle_beta, baseMean,
+ * dispFit and allZero are DEVICE pointers (the n x p matrix column-major = coefficient-major, as the fits leave it); the
+ * column coding (coef_factor, prior_coef_factor, prior_coef_src) and betaPriorVar stay HOST arrays of a few values.  The
+ * matched columns -- the p design columns, then for the expanded matrix the differences beta_i - beta_j of every pair of
+ * a factor's level columns in addAllContrasts' order (R/expanded.R:76-98), formed in the kernel and never stored -- are
+ * sorted a batch at a time by the radix sort of results(), the order-sensitive sums (sum of the weights in row order, the
+ * weight sums of equal values and their running total in sorted order) are carried by one wave per column, add for add
+ * as dsq_beta_prior_var states them.  dsq_beta_prior_var_columns(args) such columns; workspace: device memory of
+ * dsq_beta_prior_var_workspace_bytes(n, columns) bytes (bounded in n x columns: the columns go through in batches).
+ * Enqueues on `stream`, waits for it ONCE to bring the `columns` variances down, and runs the O(columns) closing steps
+ * (the intercept's 1e6, averagePriorsOverLevels) on the host exactly as dsq_beta_prior_var does.                     */
+int dsq_beta_prior_var_dev(const DsqBetaPriorArgs *args, double *betaPriorVar, void *workspace, int64_t workspace_bytes,
+                           void *stream);
+int32_t dsq_beta_prior_var_columns(const DsqBetaPriorArgs *args);    /* reads n, p, coef_factor, expanded; 0: bad args */
+int64_t dsq_beta_prior_var_workspace_bytes(int32_t n, int32_t columns);
+
 /* kernel timings of the calls since dsq_profile_enable(1): one entry per bracketed launch */
 int dsq_profile_count(void);
 int dsq_profile_get(int i, char *name, int cap, int32_t *genes, double *ms);
