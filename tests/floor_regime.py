@@ -22,9 +22,11 @@ SEEDS = (5, 6, 7)
 NOISE = 1e-5
 
 
-def floor_case(seed, n=500, m=60, frac_pois=0.6):
-    """NB / Poisson mixture, ~batch + condition (p = 4): more than a quarter of the genes start at alpha_0 = 1e-8"""
-    x = simulate.design_batch_condition(m)
+def floor_case(seed, n=500, m=60, frac_pois=0.6, design=None):
+    """NB / Poisson mixture: more than a quarter of the genes start at alpha_0 = 1e-8.  design: the m x p model matrix;
+    ~batch + condition (p = 4) when none is given"""
+    x = simulate.design_batch_condition(m) if design is None else np.asarray(design, np.float64)
+    assert x.shape[0] == m
     rng = np.random.Generator(np.random.PCG64(seed))
     d = simulate.make_counts(n, x, seed=seed)
     counts = d["counts"].copy()

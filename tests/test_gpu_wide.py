@@ -7,6 +7,7 @@ import pytest
 from deseq2_amd import core, native, simulate
 from deseq2_amd.engine import DeviceEngine, HostEngine
 from tests.helpers import assert_same, make_case
+from tests.wide_cases import paired as _paired_design      # ~ patient + treatment (2 * patients samples, p = patients + 1)
 
 pytestmark = pytest.mark.gpu
 
@@ -145,17 +146,6 @@ def test_wide_chain_lrt_matches_oracle(oracle):
     for k in ("dispGeneEst", "dispGeneIter", "dispersion", "dispIter", "beta", "betaSE", "LRTStatistic", "LRTPvalue",
               "fullBetaConv", "betaIter", "deviance", "maxCooks"):
         assert_same(a.mcols[k], b.mcols[k], "wide LRT DESeq()$" + k)
-
-
-def _paired_design(patients, seed=0):
-    """~ patient + treatment: every patient measured under both treatments (2 * patients samples, p = patients + 1,
-    2 * patients design cells -- more than the 32 the cell-collapsed paths take: the general per-sample kernels)"""
-    m = 2 * patients
-    pat = np.repeat(np.arange(patients), 2)
-    trt = np.tile([0.0, 1.0], patients)
-    x = np.column_stack([np.ones(m)] + [(pat == k).astype(float) for k in range(1, patients)] + [trt])
-    assert np.linalg.matrix_rank(x) == patients + 1
-    return x
 
 
 def _native_triplet_vs_oracle(oracle, counts, x, sf, tag, useW=False, seed=0):

@@ -112,7 +112,8 @@ def run_all(F, d):
         b0 = np.zeros((y.shape[0], xe.shape[1]))
         b0[:, 0] = np.log((y / nf).mean(axis=1))                         # :148-151
         alpha = np.minimum(np.maximum(np.exp(mp["log_alpha"]), 1e-8), max(10, y.shape[1]))
-        res["fitBetaPrior"] = F.fitBeta(y, xe, nf, alpha, np.r_[0.0, -1.0, 1.0], b0, d["lam_expanded"], w, uw, 1e-8,
+        contrast = d.get("contrast_expanded", np.r_[0.0, -1.0, 1.0])     # C5: condB against condA
+        res["fitBetaPrior"] = F.fitBeta(y, xe, nf, alpha, contrast, b0, d["lam_expanded"], w, uw, 1e-8,
                                         100, d["useQR"], 0.5)
     return res
 
@@ -272,3 +273,91 @@ def test_seeded_sweep(oracle, lapack, seed):
         kw["zero_w"] = True
     d = _case(n, m, dz, seed=int(rng.integers(1e6)), **kw)
     compare(run_all(oracle, d), run_all(lapack, d), d, "sweep%d" % seed)
+
+
+# ---- designs of 11 to 64 columns (tests/wide_cases.py) -----------------------------------------------------------------
+from tests import wide_cases   # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def wide_runs(oracle, lapack):
+    """(case, oracle results, LAPACK results) of a wide case, computed once for the tests of this module that need it"""
+    done = {}
+
+    def get(name):
+        if name not in done:
+            d = wide_cases.expanded_case(name) if name in wide_cases.EXPANDED else wide_cases.wide_case(name)
+            done[name] = (d, run_all(oracle, d), run_all(lapack, d))
+        return done[name]
+    return get
+
+
+@pytest.mark.parametrize("name", sorted(wide_cases.WIDE))
+def test_oracle_vs_lapack_wide(wide_runs, name):
+    """11 <= p <= 64: factors either side of the last cell-collapsed width, paired designs, a factor with a continuous
+    covariate at the summation-order boundaries of include/dsq_arith_spec.h -- the budgets of compare() as they stand (value
+    tolerances at scale 1, fitBeta$iter equal on every gene, ties <= max(1, 1 %), grid agreement >= 0.95); the share of
+    well-conditioned genes, a property of the inputs, is at least wide_cases.MIN_WELL (measured: profiles/wide_parity.md)"""
+    d, got, ref = wide_runs(name)
+    assert 11 <= d["x"].shape[1] <= 64
+    compare(got, ref, d, name, min_well=wide_cases.MIN_WELL)
+
+
+@pytest.mark.parametrize("name", wide_cases.EXPANDED)
+def test_oracle_vs_lapack_expanded_prior_wide(wide_runs, name):
+    """betaPrior pass 2 on the expanded design of a factor of 12 / 20 / 47 / 63 levels (p = 13, 21, 48, 64; rank
+    deficient), QR and normal equations: iterations equal on every gene and values at scale 1 -- not the 10 x compare()
+    grants the three-column expanded design of C5"""
+    d, got, ref = wide_runs(name)
+    assert d["x_expanded"].shape[1] == d["x"].shape[1] + 1 and np.linalg.matrix_rank(d["x_expanded"]) == d["x"].shape[1]
+    compare(got, ref, d, name, min_well=wide_cases.MIN_WELL)
+    _fit_beta_compare(got["fitBetaPrior"], ref["fitBetaPrior"], name, "fitBetaPrior", 1.0)
+
+
+def _copy(res):
+    return {fn: {k: (np.array(v, copy=True) if v is not None else None) for k, v in r.items()} for fn, r in res.items()}
+
+
+def _steady_gene(d, got, ref):
+    """a gene on which every strict check of compare() applies: fitBeta converged, well conditioned in both searches, the
+    last accepted step far from an ulp-level tie, a dispersion away from 1 and from the floor, the grid results equal"""
+    ok = (ref["fitBeta"]["iter"] < 100) & (d["alpha_init"] > 1e-6)
+    for fn in ("fitDispMLE", "fitDispMAP"):
+        for r in (got[fn], ref[fn]):
+            ok &= (np.exp(r["log_alpha"]) > 1e-5) & np.isfinite(r["initial_lp"]) & (np.abs(r["log_alpha"]) > 0.1)
+            ok &= np.abs(r["last_change"]) > 1e4 * np.spacing(np.abs(ref[fn]["last_lp"]))
+        ok &= (got[fn]["iter"] == ref[fn]["iter"]) & (ref[fn]["iter"] < 99)
+    gg, rg = got["fitDispGrid"]["log_alpha"], ref["fitDispGrid"]["log_alpha"]
+    ok &= (gg == rg) & (np.exp(rg) > 1e-5)
+    assert ok.sum() >= 5, "the case has no gene to mutate"
+    return int(np.flatnonzero(ok)[2])
+
+
+@pytest.mark.parametrize("name", ["paired30_qr", "cont_p31_m124"])
+def test_wide_comparison_has_teeth(wide_runs, name):
+    """the oracle's own output on a paired and on a factor-plus-covariate case, one entry changed at a time by a few times
+    the tolerance it is held to (or one count by one): compare() must refuse each, and pass the unchanged output"""
+    d, got, ref = wide_runs(name)
+    compare(got, ref, d, name, min_well=wide_cases.MIN_WELL)
+    g = _steady_gene(d, got, ref)
+    grid = np.linspace(np.log(1e-8), np.log(max(10, d["counts"].shape[1])), 20)      # run_all's grid
+    fine_step = 2 * (grid[1] - grid[0]) / (grid.size - 1)      # the second pass: 20 points over +- one step of the first
+
+    def bump_iter(r): r["fitBeta"]["iter"][g] += 1
+    def beta_row(r): r["fitBeta"]["beta_mat"][g] *= 1 + 3e-7
+    def var_column(r): r["fitBeta"]["beta_var_mat"][:, -1] *= 1 + 3e-7
+    def hat_row(r): r["fitBeta"]["hat_diagonals"][g] *= 1 + 3e-8
+    def deviance(r): r["fitBeta"]["deviance"][g] *= 1 + 3e-8
+    def map_iter(r): r["fitDispMAP"]["iter"][g] += 1
+    def mle_log_alpha(r): r["fitDispMLE"]["log_alpha"][g] += 3e-7 * abs(r["fitDispMLE"]["log_alpha"][g])
+    def last_lp(r): r["fitDispMLE"]["last_lp"][g] *= 1 + 3e-8
+    def grid_neighbour(r): r["fitDispGrid"]["log_alpha"][g] += fine_step
+
+    for mutate in (bump_iter, beta_row, var_column, hat_row, deviance, map_iter, mle_log_alpha, last_lp, grid_neighbour):
+        m = _copy(got)
+        mutate(m)
+        try:
+            compare(m, ref, d, "%s with %s" % (name, mutate.__name__), min_well=wide_cases.MIN_WELL)
+        except AssertionError:
+            continue
+        pytest.fail("compare() accepted the mutation %s of gene %d" % (mutate.__name__, g))

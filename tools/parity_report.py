@@ -1,6 +1,9 @@
 #!/usr/bin/env python
 """Measured agreement rates against the LAPACK restatement (oracle/lapack_oracle.py): `python tools/parity_report.py hip`
-on the GPU box (HIP path through the host-pointer C ABI), `python tools/parity_report.py oracle` anywhere (the C oracle)."""
+on the GPU box (HIP path through the host-pointer C ABI), `python tools/parity_report.py oracle` anywhere (the C oracle).
+A second argument `wide` reports the designs of 11 to 64 columns (tests/wide_cases.py) instead: the cases, the expanded
+prior designs and the wide floor cases (profiles/wide_parity.md); with DSQ_VERBOSE=1 the launch lines of the HIP path
+precede each row on stderr."""
 import os
 import sys
 
@@ -9,25 +12,47 @@ import tests.test_oracle_vs_lapack as T   # noqa: E402
 from oracle import lapack_oracle          # noqa: E402
 
 which = sys.argv[1] if len(sys.argv) > 1 else "oracle"
+wide = len(sys.argv) > 2 and sys.argv[2] == "wide"
 if which == "hip":
     from deseq2_amd import native as F
 else:
     from oracle import oracle as F
-rows = []
-cases = [(n, T.shape_case(n)) for n in T.SHAPE_NAMES] + list(T.live_cases().items())
-for name, d in cases:
-    st = T.compare(T.run_all(F, d), T.run_all(lapack_oracle, d), d, name)
-    n, m = d["counts"].shape
-    fb = st["fitBeta"]
-    rows.append("| %s | %d x %d, p=%d | %d / %d | %s | %.3f / %.3f | %d / %d | %.1e / %.1e | %.3f |" % (
-        name, n, m, d["x"].shape[1], fb["iter_mismatch"], fb["n"],
-        ("%d / %d" % (st["fitBetaPrior"]["iter_mismatch"], st["fitBetaPrior"]["n"])) if "fitBetaPrior" in st else "-",
-        st["fitDispMLE"]["well"], st["fitDispMAP"]["well"], st["fitDispMLE"]["ties"], st["fitDispMAP"]["ties"],
-        st["fitDispMLE"]["max_rel_log_alpha"], st["fitDispMAP"]["max_rel_log_alpha"], st["fitDispGrid"]["same"]))
 print("# Agreement of the %s path with the LAPACK restatement (oracle/lapack_oracle.py)\n" % which.upper())
 print("Budgets asserted by the tests: fitBeta$iter equal on every gene; fitDisp iter / iter_accept equal outside "
-      "ulp-level ties, ties <= 1 %; well-conditioned share >= 0.95 (m > 12); grid agreement >= 0.95; values within "
-      "1e-7 (beta, log_alpha) / 1e-8 (lp, H, deviance).\n")
-print("| case | shape | fitBeta$iter mismatches | betaPrior pass | well (MLE / MAP) | ties (MLE / MAP) | max rel log alpha | grid same |")
-print("|---|---|---|---|---|---|---|---|")
-print("\n".join(rows))
+      "ulp-level ties, ties <= 1 %%; well-conditioned share >= %s; grid agreement >= 0.95; values within "
+      "1e-7 (beta, log_alpha) / 1e-8 (lp, H, deviance).\n" % ("0.9 (wide cases)" if wide else "0.95 (m > 12)"))
+print("| case | shape | fitBeta$iter mismatches | converged | betaPrior pass (iterations) | well (MLE / MAP) | ties (MLE / MAP) | max rel log alpha | grid same |")
+print("|---|---|---|---|---|---|---|---|---|")
+if wide:
+    from tests import wide_cases as W     # noqa: E402
+    cases = [(n, (lambda n=n: W.wide_case(n)), W.MIN_WELL) for n in W.WIDE]
+    cases += [(n, (lambda n=n: W.expanded_case(n)), W.MIN_WELL) for n in W.EXPANDED]
+else:
+    cases = [(n, (lambda n=n: T.shape_case(n)), None) for n in T.SHAPE_NAMES]
+    cases += [(n, (lambda d=d: d), None) for n, d in T.live_cases().items()]
+for name, build, min_well in cases:
+    d = build()
+    got, ref = T.run_all(F, d), T.run_all(lapack_oracle, d)
+    st = T.compare(got, ref, d, name, min_well=min_well)
+    prior = "-"
+    if "fitBetaPrior" in st:
+        if wide:                          # the wide expanded designs are held at scale 1
+            T._fit_beta_compare(got["fitBetaPrior"], ref["fitBetaPrior"], name, "fitBetaPrior", 1.0)
+        it = ref["fitBetaPrior"]["iter"]
+        prior = "%d / %d (%d .. %d)" % (st["fitBetaPrior"]["iter_mismatch"], st["fitBetaPrior"]["n"], it.min(), it.max())
+    n, m = d["counts"].shape
+    fb = st["fitBeta"]
+    print("| %s | %d x %d, p=%d | %d / %d | %.3f | %s | %.3f / %.3f | %d / %d | %.1e / %.1e | %.3f |" % (
+        name, n, m, d["x"].shape[1], fb["iter_mismatch"], fb["n"], fb["converged"], prior,
+        st["fitDispMLE"]["well"], st["fitDispMAP"]["well"], st["fitDispMLE"]["ties"], st["fitDispMAP"]["ties"],
+        st["fitDispMLE"]["max_rel_log_alpha"], st["fitDispMAP"]["max_rel_log_alpha"], st["fitDispGrid"]["same"]), flush=True)
+if wide:
+    from tests import floor_regime as FR  # noqa: E402
+    print("\n| floor case | shape | floor_start | beta_iter_mismatch | iter_equal_rest | conv_differs | refit_differs | map_conv_differs | dge_abs_max |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for name in W.FLOOR:
+        d = W.floor_wide_case(name)
+        s = FR.assert_visible_parity(FR.visible_chain(F, d), FR.visible_chain(lapack_oracle, d), name)
+        print("| %s | %d x %d, p=%d | %d | %d | %.3f | %d | %d | %d | %.1e |" % (
+            name, d["counts"].shape[0], d["counts"].shape[1], d["x"].shape[1], s["floor_start"], s["beta_iter_mismatch"],
+            s["iter_equal_rest"], s["conv_differs"], s["refit_differs"], s["map_conv_differs"], s["dge_abs_max"]), flush=True)
