@@ -17,6 +17,8 @@
 // A lane only ever reads back what it wrote itself, in all three: no barrier, no fence.
 // Two sweeps per iteration: the first gives sum h and sum h z, the second beta_j, the new mu_j and the deviance term.
 #include "dsq_internal.hpp"
+#include <cstdio>
+#include <cstdlib>
 #include "dsq_math.hpp"
 #include "dsq_wave.hpp"
 
@@ -208,6 +210,9 @@ hipError_t launch_rlog(const RlogKernelParams &kp, int y_f64, hipStream_t st) {
     int blocks = (kp.n + 3) / 4;
     const int most = 8 * device_cu_count();
     if (blocks > most) blocks = most;
+    if (getenv("DSQ_VERBOSE"))
+        fprintf(stderr, "[dsq] rlog n=%d m=%d form %c: mode %d, blocks %d, threads 256\n", kp.n, kp.m, kp.intercept ? 'B' : 'A',
+                kp.m <= 64 * kRlogRegs ? RLOG_REG : kp.m <= kRlogLdsDoubles ? RLOG_LDS : RLOG_ROW, blocks);
     if (y_f64) launch_rlog_t<double>(kp, blocks, st);
     else launch_rlog_t<int32_t>(kp, blocks, st);
     return hipGetLastError();

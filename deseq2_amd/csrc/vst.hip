@@ -15,6 +15,8 @@
 //     Gene-major is its layout: in R layout the lanes of a wave read with stride n (a cache line each) -- correct, served
 //     for completeness of the _dev entry, not a path to time; the engine and the host entry always hand it gene-major.
 #include "dsq_internal.hpp"
+#include <cstdio>
+#include <cstdlib>
 #include "dsq_math.hpp"
 #include "dsq_wave.hpp"
 
@@ -169,6 +171,9 @@ static hipError_t launch_vst_kind(const VstKernelParams &kp, hipStream_t st) {
     const unsigned long long most = (unsigned long long)cu * (KIND == VST_SPLINE ? 4 : 8);
     if (blocks > most) blocks = most;
     if (blocks < 1) blocks = 1;
+    if (getenv("DSQ_VERBOSE"))
+        fprintf(stderr, "[dsq] vst kind=%d n=%d m=%d: mode %s, items %llu, blocks %llu, threads %d\n", KIND, kp.n, kp.m,
+                vec ? "paired" : gm ? "gene-major" : "r-layout", total, blocks, threads);
     if (vec) hipLaunchKernelGGL((vst_transform_kernel<KIND, T, 2, 1>), dim3((unsigned)blocks), dim3(threads), lds, st, kp, total, inner);
     else if (gm) hipLaunchKernelGGL((vst_transform_kernel<KIND, T, 1, 1>), dim3((unsigned)blocks), dim3(threads), lds, st, kp, total, inner);
     else hipLaunchKernelGGL((vst_transform_kernel<KIND, T, 1, 0>), dim3((unsigned)blocks), dim3(threads), lds, st, kp, total, inner);
@@ -195,6 +200,7 @@ hipError_t launch_vst_rowstats(const VstKernelParams &kp, int y_f64, hipStream_t
     int blocks = (kp.n + 3) / 4;
     const int most = 8 * device_cu_count();
     if (blocks > most) blocks = most;
+    if (getenv("DSQ_VERBOSE")) fprintf(stderr, "[dsq] vst_rowstats n=%d m=%d: blocks %d, threads 256\n", kp.n, kp.m, blocks);
     if (y_f64) hipLaunchKernelGGL(vst_rowstats_kernel<double>, dim3(blocks), dim3(256), 0, st, kp);
     else hipLaunchKernelGGL(vst_rowstats_kernel<int32_t>, dim3(blocks), dim3(256), 0, st, kp);
     return hipGetLastError();

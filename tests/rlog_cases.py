@@ -3,6 +3,7 @@ import numpy as np
 
 RTOL = 1e-11          # rlog values against the dense fit, relative to max(|v|, 1)
 TIE_CAP = 0.01        # share of a case's rows whose iteration count may differ by a last-bit tie of the convergence test
+LN2 = np.log(2.0)
 
 
 def inputs(n, m, seed, nf_matrix=False, zero_row=True):
@@ -20,6 +21,49 @@ def inputs(n, m, seed, nf_matrix=False, zero_row=True):
     if zero_row and n > 3:
         k[3] = 0
     return {"counts": k, "nf": nf, "dispFit": disp, "betaPriorVar": float(rng.uniform(0.05, 2.0))}
+
+
+def dense_design(k, nf, disp, bpv, intercept=None):
+    """what rlogData (R/rlog.R:172-272) hands fitBeta for the rows that are fitted: the dense design [1 | I_m] (form A) or
+    I_m with the intercept folded into the factors (form B), its ridge, start values and fixed arguments.  Returns
+    (rows, x, args): args is the positional argument list of a fitBeta (the C oracle's or the LAPACK restatement's)."""
+    k = np.asarray(k, np.float64)
+    n, m = k.shape
+    NF = np.broadcast_to(nf[None, :], (n, m)) if np.ndim(nf) == 1 else np.asarray(nf, np.float64)
+    if intercept is None:
+        rows = np.where((k != 0).any(axis=1))[0]
+        x = np.hstack([np.ones((m, 1)), np.eye(m)])
+        lam = np.r_[1e-6, np.full(m, 1.0 / bpv)]
+        NFs = NF[rows]
+        b0 = np.zeros((rows.size, m + 1))
+        b0[:, 0] = np.log((k[rows] / NFs).mean(axis=1))
+    else:
+        rows = np.where(np.isfinite(intercept))[0]
+        x = np.eye(m)
+        lam = np.full(m, 1.0 / bpv)
+        NFs = NF[rows] * (2.0 ** intercept[rows])[:, None]
+        b0 = np.log(k[rows] / NFs + 0.1)
+    p = x.shape[1]
+    args = (k[rows], x, NFs, disp[rows], np.r_[1.0, np.zeros(p - 1)], b0, lam / LN2 ** 2, np.ones((rows.size, m)), False,
+            1e-4, 100, True, 0.5)
+    return rows, x, args
+
+
+def dense_values(x, r, rows, intercept=None):
+    """the rlog values of a dense fit r = fitBeta(*args): log2(e) beta X' (+ the frozen intercept)"""
+    v = (np.log2(np.e) * r["beta_mat"]) @ x.T
+    if intercept is not None:
+        v = v + np.asarray(intercept)[rows][:, None]
+    return v
+
+
+def dense_lapack(k, nf, disp, bpv, intercept=None):
+    """the reference's route on the rows that are fitted, over the LAPACK restatement (oracle/lapack_oracle.py: numpy's QR
+    and solve, no width limit): returns (rows, rlog values, iter)"""
+    from oracle import lapack_oracle
+    rows, x, args = dense_design(k, nf, disp, bpv, intercept)
+    r = lapack_oracle.fitBeta(*args)
+    return rows, dense_values(x, r, rows, intercept), r["iter"]
 
 
 def compare(got, want, what, it_got=None, it_want=None, rtol=RTOL):
@@ -41,3 +85,38 @@ def compare(got, want, what, it_got=None, it_want=None, rtol=RTOL):
     print("%s: rows with another iteration count %d / %d, largest relative difference %.3g" % (what, ties, keep.size, worst))
     assert worst <= rtol, "%s: relative difference %.3g > %.3g" % (what, worst, rtol)
     return ties, worst
+
+
+_LAPACK = {}
+
+
+def lapack_case(O, n, m):
+    """inputs(n, m, seed=2) with both forms of the specification and of the LAPACK route on them, computed once per shape
+    and left unchanged: form A, then form B on the intercepts form A returned with one made non-finite (row 5) and one
+    finite intercept on all-zero counts (row 7)"""
+    from tests import rlog_spec
+    if (n, m) not in _LAPACK:
+        d = inputs(n, m, seed=2)
+        k, nf, disp, bpv = d["counts"], d["nf"], d["dispFit"], d["betaPriorVar"]
+        sa = rlog_spec.rlog_fit(O, k, nf, disp, bpv)
+        c = np.array(sa["intercept"])
+        c[5] = np.nan
+        k2 = k.copy()
+        k2[7] = 0
+        sb = rlog_spec.rlog_fit(O, k2, nf, disp, bpv, intercept=c)
+        _LAPACK[(n, m)] = dict(d=d, k2=k2, c=c, specA=sa, specB=sb, lapackA=dense_lapack(k, nf, disp, bpv),
+                               lapackB=dense_lapack(k2, nf, disp, bpv, intercept=c))
+    return _LAPACK[(n, m)]
+
+
+def mutants(rlog, it, rows):
+    """two copies of a result the comparison must refuse: one value of a fitted row moved by 3e-11 relative (an element of
+    magnitude >= 1, so that the move is 3e-11 of max(|v|, 1) too), one iteration count off by one"""
+    v = np.array(rlog)
+    sub = np.abs(v[rows])
+    a, b = np.unravel_index(np.argmax(np.where(np.isfinite(sub), sub, 0.0)), sub.shape)
+    assert sub[a, b] >= 1.0
+    v[rows[a], b] *= 1.0 + 3e-11
+    i2 = np.array(it)
+    i2[rows[len(rows) // 2]] += 1.0
+    return (v, np.array(it)), (np.array(rlog), i2)

@@ -243,3 +243,69 @@ def test_optim_rows_matches_oracle(oracle, design, useW):
     for k in ("beta", "betaSE", "conv", "mu", "logLike"):
         assert_same(np.asarray(got[k], float), np.asarray(want[k], float), "optimRows$" + k)
     assert want["conv"].mean() > 0.9
+
+
+# ---- persistent gene loops past one grid round (the table of profiles/contrasts.md) ------------------------------------------
+def _wave_slots():
+    """more genes than any wave-per-gene launch keeps resident, whatever blocks/CU the occupancy query answers: a CU of
+    gfx950 holds at most 32 waves (8 per SIMD)"""
+    import torch
+    return 32 * torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def test_fit_beta_per_sample_kernel_past_one_round(oracle):
+    """fit_beta_kernel's gene loop (`wi = next_gene(..., gridDim.x * waves)`, csrc/fit_beta.hip) on the general per-sample
+    path: 33 samples with a continuous covariate (33 design cells, one more than the cell-collapsed kernel takes) and five
+    genes more than 32 waves per CU hold -- launch_fit_beta_p's grid is CUs x blocks/CU workgroups of `waves` genes, so every
+    resident wave fits a second gene.  The factor designs of the 9 000-gene tests all take fit_beta_cell_kernel."""
+    n = _wave_slots() + 5
+    d = make_case(n, 33, ("factor_cont", 2), seed=41, sf_random=True, drop_all_zero=False)
+    assert d["counts"].shape[0] == n and np.unique(d["x"], axis=0).shape[0] == 33
+    lam = np.full(3, 1e-6) / np.log(2) ** 2
+    got, want = _fit_beta_both(oracle, d, d["alpha_init"], lam, False, True)
+    for k in BETA_KEYS:
+        assert_same(got[k], want[k], "fitBeta$%s, %d genes" % (k, n))
+    assert (want["iter"] < 100).mean() > 0.9
+
+
+@pytest.mark.parametrize("useW", [False, True])
+def test_intercept_fit_past_one_round(oracle, useW):
+    """intercept_fit_kernel's gene loop (`wi += gridDim.x * waves`, csrc/aux.hip; aux_grid: eight workgroups of four waves
+    per CU) on five genes more than that round, against the oracle's closed form"""
+    from deseq2_amd import native
+    n = _wave_slots() + 5                                # (aux_grid's round: 8 x 4 waves per CU)
+    d = make_case(n, 5, "two_group", seed=42, weights=useW, sf_random=True, drop_all_zero=False)
+    assert d["counts"].shape[0] == n
+    args = (d["counts"], d["nf"], d["alpha_init"], d["weights"], useW, 0.5, True)
+    got, want = native.interceptFit(*args), oracle.interceptFit(*args)
+    for k in ("beta", "betaSE", "mu", "hat_diagonals"):
+        assert_same(got[k], want[k], "interceptFit$%s, %d genes" % (k, n))
+
+
+def test_optim_rows_past_one_round(oracle):
+    """optim_rows_kernel's loop (`wi += gridDim.x`, one row per workgroup; launch_optim_p: at most 4 096 workgroups) on five
+    rows more, against the oracle's iteration"""
+    from deseq2_amd import native
+    n = 4096 + 5                                         # launch_optim_p, csrc/fit_beta.hip
+    d = make_case(n, 6, "two_group", seed=43, drop_all_zero=False)
+    y = d["counts"].copy()
+    y[3] = 0; y[3, 1:3] = 1000
+    y[4099] = 0; y[4099, -1] = 7
+    lam = np.array([1e-6, 0.5])
+    start = np.random.default_rng(3).normal(0, 1.0, (n, 2))
+    args = (y, d["x"], d["nf"], d["alpha_init"], lam, d["weights"], False, start, 0.5)
+    got, want = native.optimRows(*args), oracle.optimRows(*args)
+    for k in ("beta", "betaSE", "conv", "mu", "logLike"):
+        assert_same(np.asarray(got[k], float), np.asarray(want[k], float), "optimRows$%s, %d rows" % (k, n))
+    assert want["conv"].mean() > 0.9
+
+
+def test_linear_mu_past_one_round(oracle):
+    """linear_mu_kernel's loop (`wbase += gridDim.x * waves`, csrc/aux.hip; aux_grid) on five genes more than its round: the
+    chain takes it only for designs with as many cells as columns, and the 9 000-gene chains are ~ batch + condition"""
+    from deseq2_amd import native
+    n = _wave_slots() + 5
+    d = make_case(n, 6, "two_group", seed=44, sf_random=True, drop_all_zero=False)
+    assert d["counts"].shape[0] == n
+    assert_same(native.linearMu(d["counts"], d["nf"], d["x"], 0.5), oracle.linearMu(d["counts"], d["nf"], d["x"], mu_floor=0.5),
+                "linearMu, %d genes" % n)

@@ -117,6 +117,19 @@ def test_large_shapes(oracle, shape, mode):
     assert ref["status"] == 0 and np.isfinite(ref["sizeFactors"]).all()
 
 
+def test_normalization_factors_past_one_round(oracle):
+    """sf_norm_factors_kernel's gene loop (`i += nwave`, a wave per gene; launch_size_factors: eight workgroups of four waves
+    per CU, the grid sf_loggeomeans_kernel has too) on five rows more than that round: the normalization-factor matrix, the
+    log geometric means and the factors against the specification.  (test_large_shapes takes sf_loggeomeans_kernel to 50 000
+    rows; its normMatrix shape has 4 000.)"""
+    import torch
+    n = 8 * torch.cuda.get_device_properties(0).multi_processor_count * 4 + 5        # launch_size_factors, csrc/size_factors.hip
+    k = _counts(n, 3, seed=n, zeros=0.0002)
+    nm = np.exp(np.random.default_rng(7).normal(0, 0.3, k.shape))
+    ref, _ = _check(oracle, k, "normMatrix %dx3" % n, normMatrix=nm)
+    assert ref["status"] == 0 and np.isfinite(ref["normalizationFactors"]).all()
+
+
 @pytest.mark.parametrize("variant", ["padded_ld", "r_layout", "float64_gm", "float64_r", "r_layout_normMatrix"])
 def test_layouts_and_count_types(oracle, variant):
     k = _counts(997, 70, seed=17)

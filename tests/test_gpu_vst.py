@@ -3,6 +3,7 @@ tests/vst_spec.py, BIT FOR BIT: dlog / dlog1p equal the oracle's log / log1p, sq
 row sums are wave-order sums, the maximum is exact.  Then core.vst / varianceStabilizingTransformation on the DeviceEngine
 against the same calls on HostEngine(oracle)."""
 import ctypes as C
+import re
 
 import numpy as np
 import pytest
@@ -240,6 +241,79 @@ def test_row_statistics(oracle, variant, shape):
     assert_same(mx, rmx, "row maxima")
     if variant == "nan_sf":
         assert np.isnan(mx).all() and np.isnan(mean).all()
+
+
+# ---- past one grid round ----------------------------------------------------------------------------------------------------
+STATS_LINE = re.compile(r"\[dsq\] vst_rowstats n=(\d+) m=(\d+): blocks (\d+), threads 256")
+KIND_LINE = re.compile(r"\[dsq\] vst kind=(\d) n=(\d+) m=(\d+): mode (paired|gene-major|r-layout), items (\d+), blocks (\d+), threads (\d+)")
+
+
+def _dev_line(monkeypatch, capfd, pattern, *a, **kw):
+    """_dev under DSQ_VERBOSE: the result and the fields of the one line the launch printed (csrc/vst.hip)"""
+    monkeypatch.setenv("DSQ_VERBOSE", "1")
+    capfd.readouterr()
+    got = _dev(*a, **kw)
+    err = capfd.readouterr().err
+    monkeypatch.delenv("DSQ_VERBOSE")
+    lines = pattern.findall(err)
+    assert len(lines) == 1, "no launch line in %r" % err
+    print(err.strip())
+    return got, lines[0]
+
+
+def _cus():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+@pytest.mark.parametrize("variant", ["gm", "nan_sf"])
+@pytest.mark.parametrize("m", [3, 65])
+def test_row_statistics_past_one_round(oracle, monkeypatch, capfd, variant, m):
+    """the persistent loop of vst_rowstats_kernel, `i += gridDim.x * 4`: n = round + 5 rows, launch_vst_rowstats' round being
+    8 workgroups of four waves per CU (from the CU count, confirmed by the launch line); every row of both trips compared"""
+    rnd = 8 * _cus() * 4                                                                # launch_vst_rowstats, csrc/vst.hip
+    n = rnd + 5
+    k = _counts(n, m, seed=n + m)
+    nf = _sf(m, 1)
+    if variant == "nan_sf":
+        nf[0] = np.nan
+    ((mean, mx), _, _), line = _dev_line(monkeypatch, capfd, STATS_LINE, k, nf, "normalized", {}, stats=True, pad=8)
+    assert (int(line[0]), int(line[1])) == (n, m) and 4 * int(line[2]) == rnd < n
+    rmean, rmx = vst_spec.row_stats(k, nf)
+    assert_same(mean, rmean, "rowMeans")
+    assert_same(mx, rmx, "row maxima")
+    if variant == "nan_sf":
+        assert np.isnan(mx).all() and np.isnan(mean).all()
+    else:
+        assert (mx[rnd:] > 0).any() and mx[3] == 0
+
+
+@pytest.mark.parametrize("kind", ["parametric", "spline"])
+@pytest.mark.parametrize("form", ["paired", "gene-major", "r-layout"])
+def test_transform_past_one_round(oracle, monkeypatch, capfd, form, kind):
+    """the grid-stride loop of vst_transform_kernel, `t += gridDim.x * blockDim.x`, on each launch form: pairs of samples
+    (gene-major, even ld), single samples gene-major (odd ld) and R layout, a closed form (workgroups of 256, eight per CU)
+    and the spline (workgroups of 512, four per CU).  The shape is the smallest number of rows that makes more items than
+    launch_vst_kind's round holds, by the CU count; the launch line must show items > blocks x threads.  Every element is
+    compared.  The 64-bit index branch (`total > 0xffffffff`) needs more than 34 GB of counts and output and stays untested."""
+    threads, per_cu = (512, 4) if kind == "spline" else (256, 8)                         # launch_vst_kind, csrc/vst.hip
+    rnd = _cus() * per_cu * threads
+    m = 500 if form == "paired" else 67
+    inner = (m + 1) // 2 if form == "paired" else m                                       # items of a row
+    n = rnd // inner + 3
+    k = _counts(n, m, seed=n + 3 * m)
+    sf = _sf(m, m)
+    params = _kind_params(kind, k, sf, 0)
+    kw = dict(layout="r") if form == "r-layout" else dict(pad=3) if form == "gene-major" else dict(pad=8)
+    ref = vst_spec.transform(oracle, k, sf, kind, **params)
+    (got, full, bad), line = _dev_line(monkeypatch, capfd, KIND_LINE, k, sf, kind, params, **kw)
+    _, ln, lm, mode, items, blocks, lthreads = line
+    assert (int(ln), int(lm), mode, int(lthreads)) == (n, m, form, threads)
+    assert int(items) == n * inner and int(blocks) * threads == rnd < int(items) < 2 * rnd
+    assert_same(got, ref, "%s %s %dx%d" % (kind, form, n, m))
+    if form != "r-layout":
+        assert (full[:, m:] == -777.0).all(), "padding columns were written"
+    assert bad == 0 and np.isfinite(ref).all()
 
 
 @pytest.mark.parametrize("kind", vst_spec.KINDS)

@@ -229,15 +229,20 @@ def test_wide_weights_prep_matches_host(p, m):
     Gram matrices entry-per-lane, the rank test one column per lane): normalised weights, their floor and the
     weightsFail flags against the host mirror -- rows that lose a whole level, a column pair that becomes collinear
     and rows with all-zero weights included"""
+    _weights_prep_case(p, m, 300)
+
+
+def _weights_prep_case(p, m, n, zero_row=None):
     from deseq2_amd.engine import _weights_ok_host
     rng = np.random.default_rng(p * 1000 + m)
     x = simulate.design_factor(m, p)
-    n = 300
     w = rng.uniform(0.02, 1.0, (n, m))
     w[rng.uniform(size=w.shape) < 0.05] = 0.0
     w[3, x[:, 2] == 1] = 0.0                               # a level without a sample: rank(w * X) < p
     w[10, x[:, p - 1] == 1] = 0.005                        # ... only below the threshold: the second test's column drop
     w[20] = 0.0                                            # apply(w, 1, max) = 0: NaN weights
+    if zero_row is not None:
+        w[zero_row] = 0.0
     w[30, (x[:, 1] == 0) & (x[:, 4] == 0)] = 0.0           # only levels 1 and 4 (and no reference sample) left
     E = DeviceEngine("cuda:0")
     wn, wf, fz, neg = E.weights_prep(E.matrix(w), x, 1e-2)
@@ -252,6 +257,19 @@ def test_wide_weights_prep_matches_host(p, m):
     keep = ~np.isnan(want).any(axis=1)
     assert (fail[keep] == ~ok[keep]).all(), np.flatnonzero(fail[keep] != ~ok[keep])
     assert int(E._host(neg).numpy()[0]) == 0
+    return fail
+
+
+@pytest.mark.parametrize("p,m", [(5, 10), (12, 24)])
+def test_weights_prep_past_one_round(p, m):
+    """the gene loops of weights_prep_kernel (`g += gridDim.x * waves`; aux_grid_fwd: eight workgroups of four waves per CU)
+    and weights_prep_wide_kernel (`g += gridDim.x`; launch_weights_prep: at most 256 x 8 workgroups of one gene), csrc/aux.hip:
+    five rows more than a round, the last one with all-zero weights -- the same checks as above on every row"""
+    import torch
+    rnd = 256 * 8 if p > 10 else 8 * torch.cuda.get_device_properties(0).multi_processor_count * 4
+    n = rnd + 5
+    fail = _weights_prep_case(p, m, n, zero_row=n - 1)
+    assert fail.shape == (n,) and fail[n - 1] and not fail[rnd:n - 1].all()
 
 
 def _chain_three_ways(oracle, counts, x, sf, tag, weights=None, **kw):

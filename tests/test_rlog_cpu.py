@@ -8,36 +8,14 @@ import numpy as np
 import pytest
 
 from tests import rlog_spec
-from tests.rlog_cases import inputs, compare, RTOL
-
-LN2 = np.log(2.0)
+from tests.rlog_cases import inputs, compare, dense_design, dense_values, lapack_case, mutants, RTOL, TIE_CAP
 
 
 def _dense(O, k, nf, disp, bpv, intercept=None):
     """the reference's route on the rows that are fitted: returns (rows, rlog values, iter)"""
-    k = np.asarray(k, np.float64)
-    n, m = k.shape
-    NF = np.broadcast_to(nf[None, :], (n, m)) if np.ndim(nf) == 1 else np.asarray(nf, np.float64)
-    if intercept is None:
-        rows = np.where((k != 0).any(axis=1))[0]
-        x = np.hstack([np.ones((m, 1)), np.eye(m)])
-        lam = np.r_[1e-6, np.full(m, 1.0 / bpv)]
-        NFs = NF[rows]
-        b0 = np.zeros((rows.size, m + 1))
-        b0[:, 0] = np.log((k[rows] / NFs).mean(axis=1))
-    else:
-        rows = np.where(np.isfinite(intercept))[0]
-        x = np.eye(m)
-        lam = np.full(m, 1.0 / bpv)
-        NFs = NF[rows] * (2.0 ** intercept[rows])[:, None]
-        b0 = np.log(k[rows] / NFs + 0.1)
-    p = x.shape[1]
-    r = O.fitBeta(k[rows], x, NFs, disp[rows], np.r_[1.0, np.zeros(p - 1)], b0, lam / LN2 ** 2, np.ones((rows.size, m)), False,
-                  1e-4, 100, True, 0.5, cell_mode=0)
-    v = (np.log2(np.e) * r["beta_mat"]) @ x.T
-    if intercept is not None:
-        v = v + intercept[rows][:, None]
-    return rows, v, r["iter"]
+    rows, x, args = dense_design(k, nf, disp, bpv, intercept)
+    r = O.fitBeta(*args, cell_mode=0)
+    return rows, dense_values(x, r, rows, intercept), r["iter"]
 
 
 @pytest.mark.parametrize("nf_matrix", [False, True])
@@ -62,6 +40,43 @@ def test_spec_against_dense_oracle(oracle, m, nf_matrix):
     assert (sb["flag"][[3, 5]] == 1).all() and (sb["rlog"][[3, 5]] == 0).all() and sb["flag"][7] == 0
     rows, v, it = _dense(oracle, k2, nf, disp, bpv, intercept=c)
     compare(sb["rlog"][rows], v, "form B m=%d" % m, sb["iter"][rows], it)
+
+
+# m >= 64: the dense C oracle stops at 64 columns ([1 | I_63]); the LAPACK restatement has no width limit
+LAPACK_SHAPES = [(63, 100), (64, 100), (65, 100), (129, 60), (257, 24)]
+
+
+@pytest.mark.parametrize("m,n", LAPACK_SHAPES)
+def test_spec_against_dense_lapack(oracle, m, n):
+    """The specification against oracle/lapack_oracle.py's fitBeta on the dense [1 | I_m] / I_m design, forms A and B, at
+    the project's RTOL and TIE_CAP.  m = 63 is held to the C oracle too, so this line overlaps the one above.  Measured
+    maxima: profiles/rlog.md.  m > 600 stays with the bit identity of the device to the specification alone: a dense QR
+    at m = 2 049 costs about a minute per gene."""
+    c = lapack_case(oracle, n, m)
+    d = c["d"]
+    for form, spec, ref, k, icpt in (("A", c["specA"], c["lapackA"], d["counts"], None), ("B", c["specB"], c["lapackB"], c["k2"], c["c"])):
+        rows, v, it = ref
+        assert rows.size >= n - 2 and (spec["flag"][rows] == 0).all()
+        compare(spec["rlog"][rows], v, "spec / LAPACK form %s m=%d" % (form, m), spec["iter"][rows], it)
+        if m == 63:
+            orows, ov, oit = _dense(oracle, k, d["nf"], d["dispFit"], d["betaPriorVar"], intercept=icpt)
+            assert (orows == rows).all()
+            compare(ov, v, "oracle / LAPACK form %s m=%d" % (form, m), oit, it)
+            compare(spec["rlog"][rows], ov, "spec / oracle form %s m=%d" % (form, m), spec["iter"][rows], oit)
+    assert (c["specB"]["flag"][[3, 5]] == 1).all() and c["specB"]["flag"][7] == 0
+
+
+def test_lapack_comparison_has_teeth(oracle):
+    """the comparison of test_spec_against_dense_lapack refuses one value moved by 3e-11 relative and one iteration count
+    off by one (one row of 99 is above TIE_CAP), and passes the unchanged result"""
+    c = lapack_case(oracle, 100, 65)
+    rows, v, it = c["lapackA"]
+    spec = c["specA"]
+    compare(spec["rlog"][rows], v, "unchanged", spec["iter"][rows], it)
+    assert TIE_CAP * rows.size < 1
+    for name, (mv, mi) in zip(("value", "iteration count"), mutants(spec["rlog"], spec["iter"], rows)):
+        with pytest.raises(AssertionError):
+            compare(mv[rows], v, "mutant: " + name, mi[rows], it)
 
 
 def _spec_of(O, dt, counts, intercept=None):
