@@ -9,8 +9,9 @@ from .core import (vst, varianceStabilizingTransformation, getVarianceStabilized
                    normalized_counts, DESeqTransform)
 from .core import results, resultsContrasts, resultsNames, DESeqResults, p_adjust, pvalueAdjustment, lowess  # noqa: F401
 from .core import pt  # noqa: F401
+from .core import unmix  # noqa: F401
 
 __all__ = ["fitBeta", "fitDisp", "fitDispGrid", "estimateSizeFactors", "estimateSizeFactorsForMatrix", "vst",
            "varianceStabilizingTransformation", "getVarianceStabilizedData", "normTransform", "normalized_counts",
            "DESeqTransform", "results", "resultsContrasts", "resultsNames", "DESeqResults", "p_adjust", "pvalueAdjustment", "lowess",
-           "pt"]
+           "pt", "unmix"]

@@ -262,6 +262,18 @@ class DsqRlogOut(C.Structure):
                 ("bad", C.c_void_p)]
 
 
+class DsqUnmixArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("m", C.c_int32), ("k", C.c_int32), ("ld", C.c_int64), ("x", C.c_void_p), ("pure", C.c_void_p),
+        ("has_alpha", C.c_int32), ("has_shift", C.c_int32), ("alpha", C.c_double), ("shift", C.c_double),
+        ("power", C.c_int32), ("maxit", C.c_int32),
+    ]
+
+
+class DsqUnmixOut(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("loss", C.c_void_p), ("iter", C.c_void_p), ("flag", C.c_void_p)]
+
+
 class DsqResultsArgs(C.Structure):
     _fields_ = [
         ("n", C.c_int32), ("p", C.c_int32), ("c", C.c_int32), ("test", C.c_int32), ("beta", C.c_void_p),
@@ -299,6 +311,7 @@ DSQ_RESULTS_MAX_K = 4096
 DSQ_PT = {"lower": 0, "upper": 1, "two_sided": 2}
 DSQ_VST = {"parametric": 0, "mean": 1, "spline": 2, "log2": 3, "normalized": 4}
 DSQ_VST_MAX_KNOTS = 1600
+DSQ_UNMIX_MAX_K = 16
 DSQ_SF = {"ratio": 0, "poscounts": 1}
 DSQ_PH_GENE_EST, DSQ_PH_TREND, DSQ_PH_MAP_TEST, DSQ_PH_OUTLIERS, DSQ_PH_FINISH, DSQ_PH_PRIOR = 1, 2, 4, 8, 16, 32
 DSQ_PH_OUTLIERS_DETECT, DSQ_PH_OUTLIERS_REFIT = 64, 128
@@ -328,6 +341,7 @@ EXPORTED_SYMBOLS = [
     "dsq_size_factors", "dsq_size_factors_dev", "dsq_size_factors_workspace_bytes",
     "dsq_vst", "dsq_vst_dev", "dsq_vst_rowstats_dev",
     "dsq_rlog", "dsq_rlog_dev",
+    "dsq_unmix", "dsq_unmix_dev", "dsq_unmix_workspace_bytes", "dsq_unmix_block_threads",
     "dsq_results", "dsq_results_dev", "dsq_results_workspace_bytes",
     "dsq_contrasts", "dsq_contrasts_dev", "dsq_contrasts_max_m",
     "dsq_pt", "dsq_pt_dev",
@@ -407,6 +421,12 @@ def lib():
     L.dsq_vst_rowstats_dev.argtypes = [C.POINTER(DsqVstArgs), C.POINTER(DsqVstOut), C.c_void_p]
     L.dsq_rlog.argtypes = [C.POINTER(DsqRlogArgs), C.POINTER(DsqRlogOut)]
     L.dsq_rlog_dev.argtypes = [C.POINTER(DsqRlogArgs), C.POINTER(DsqRlogOut), C.c_void_p]
+    L.dsq_unmix.argtypes = [C.POINTER(DsqUnmixArgs), C.POINTER(DsqUnmixOut)]
+    L.dsq_unmix_dev.argtypes = [C.POINTER(DsqUnmixArgs), C.POINTER(DsqUnmixOut), C.c_void_p, C.c_int64, C.c_void_p]
+    L.dsq_unmix_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.dsq_unmix_workspace_bytes.restype = C.c_int64
+    L.dsq_unmix_block_threads.argtypes = []
+    L.dsq_unmix_block_threads.restype = C.c_int32
     L.dsq_results.argtypes = [C.POINTER(DsqResultsArgs), C.POINTER(DsqResultsOut)]
     L.dsq_results_dev.argtypes = [C.POINTER(DsqResultsArgs), C.POINTER(DsqResultsOut), C.c_void_p]
     L.dsq_results_workspace_bytes.argtypes = [C.c_int32, C.c_int32]

@@ -2381,3 +2381,96 @@ def lfcShrink(dds, coef=None, contrast=None, res=None, type="normal", lfcThresho
     out.metadata["lfcThreshold"] = lfcThreshold                                   # :497
     out.priorInfo = {"type": "normal", "package": "deseq2_amd", "betaPriorVar": betaPriorVar}   # :498-505
     return out
+
+
+# ------------------------------------------------------------------ R/helper.R:70-132
+UNMIX_COR_WARNING = ("some columns of 'pure' are highly correlated (>.99 after VST),\n"
+                     "  may result in instabilty of unmix(). visually inspect correlations of 'pure'")
+
+
+class NamedMatrix(np.ndarray):
+    """a host matrix that carries dimnames: rownames / colnames are lists of names or None"""
+    rownames = colnames = None
+
+    def __array_finalize__(self, obj):
+        self.rownames, self.colnames = getattr(obj, "rownames", None), getattr(obj, "colnames", None)
+
+
+def _named(a, rownames=None, colnames=None):
+    out = np.asarray(a, np.float64).view(NamedMatrix)
+    out.rownames, out.colnames = rownames, colnames
+    return out
+
+
+def _colnames_of(a):
+    names = getattr(a, "colnames", None)
+    if names is None:
+        names = getattr(a, "columns", None)
+    return None if names is None else [str(v) for v in names]
+
+
+def _r_stopifnot(ok, expr):
+    if not ok:
+        raise ValueError("%s is not TRUE" % expr)
+
+
+def unmix(x, pure, alpha=None, shift=None, power=1, format="matrix", quiet=False, engine=None):
+    """R/helper.R:70-132.  x: the n x m samples to unmix -- normalized counts or TPMs as a host matrix, an engine handle, or the
+    DESeqTransform that normalized_counts() returns (it stays resident on a device engine); pure: the n x k pure components, a
+    host matrix.  alpha: the dispersion of a negative binomial fit (the asymptotic or mean value of the trend); shift: for TPMs;
+    exactly one of them.  Returns mix, m x k with rows summing to 1 (format = "matrix"), or dict(mix, cor, fitted)
+    (format = "list").  Column names of pure and x (attributes colnames or columns) carry through.  `quiet` is accepted: there is
+    no progress bar.  The fits are the engine's unmix_fit (csrc/unmix.hip on the device): R's objective, box and start, the
+    library's own deterministic optimiser in place of optim's L-BFGS-B."""
+    if format not in ("matrix", "list"):                                             # :72
+        raise ValueError("'arg' should be one of 'matrix', 'list'")
+    if alpha is None:
+        _r_stopifnot(shift is not None, "!missing(shift)")                           # :73
+    if shift is None:
+        _r_stopifnot(alpha is not None, "!missing(alpha)")                           # :74
+    _r_stopifnot(shift is None or alpha is None, "missing(shift) | missing(alpha)")  # :75
+    _r_stopifnot(power in (1, 2), "power %in% 1:2")                                  # :76
+    xnames = _colnames_of(x)
+    if isinstance(x, DESeqTransform):
+        E = x.engine if engine is None else engine
+        handle = x.handle
+    else:
+        E = HostEngine() if engine is None else engine
+        handle = x if hasattr(x, "ld") else np.asarray(x, np.float64)
+        if isinstance(handle, np.ndarray) and handle.ndim != 2:
+            raise ValueError("x should be a matrix")
+    pnames = _colnames_of(pure)
+    pure = np.asarray(pure, np.float64)
+    if pure.ndim != 2:
+        raise ValueError("pure should be a matrix")
+    nrow_x = handle.shape[0] if isinstance(handle, np.ndarray) else E.nrow(handle)
+    _r_stopifnot(nrow_x == pure.shape[0], "nrow(x) == nrow(pure)")                   # :77
+    _r_stopifnot(pure.shape[1] > 1, "ncol(pure) > 1")                                # :78
+    if shift is None:
+        _r_stopifnot(alpha > 0, "alpha > 0")                                         # :88
+        al = float(alpha)
+        v = lambda q: (2 * np.arcsinh(np.sqrt(al * q)) - np.log(al) - np.log(4)) / np.log(2)    # :90
+    else:
+        _r_stopifnot(shift > 0, "shift > 0")                                         # :101
+        sh = float(shift)
+        v = lambda q: np.log(q + sh)                                                 # :103
+    with np.errstate(all="ignore"):
+        pure_cor = np.corrcoef(v(pure), rowvar=False)                                # :91, :104
+        np.fill_diagonal(pure_cor, 0.0)
+        if (pure_cor > .99).any():                                                   # :92, :105
+            warnings.warn(UNMIX_COR_WARNING)
+    if pure.shape[1] > 16:
+        raise NotImplementedError("unmix: %d pure components (at most 16 are served)" % pure.shape[1])
+    fit = E.unmix_fit(handle, pure, alpha=None if alpha is None else float(alpha), shift=None if shift is None else float(shift),
+                      power=int(power), maxit=200)                                   # :96-99, :109-112
+    from . import unmix_host
+    mix = _named(unmix_host.mix_from_p(fit["p"]), xnames, pnames)                    # :115-118
+    if format == "matrix":
+        return mix
+    fitted = pure @ np.asarray(mix).T                                                # :123
+    xh = np.asarray(E.to_numpy(handle), np.float64) if not isinstance(handle, np.ndarray) else handle
+    cor = np.empty(xh.shape[1])
+    with np.errstate(all="ignore"):
+        for i in range(xh.shape[1]):                                                 # diag(cor(., .)), :124-129
+            cor[i] = np.corrcoef(v(xh[:, i]), v(fitted[:, i]))[0, 1]
+    return {"mix": mix, "cor": cor, "fitted": _named(fitted, None, xnames)}

@@ -810,6 +810,44 @@ int rlog_dev_locked(const DsqRlogArgs *a, const DsqRlogOut *o, hipStream_t st) {
     return DSQ_OK;
 }
 
+// unmix() (unmix.hip): what both entries check before anything is launched
+int unmix_check(const DsqUnmixArgs *a, const DsqUnmixOut *o) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->n < 1 || a->m < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
+    if (a->k < 2) return capi_fail(DSQ_ERR_ARG, "k = %d pure components: at least two are needed", a->k);
+    if (a->k > DSQ_UNMIX_MAX_K) return capi_fail(DSQ_ERR_UNSUPPORTED, "k = %d pure components: at most %d", a->k, DSQ_UNMIX_MAX_K);
+    if (!a->x || !a->pure) return capi_fail(DSQ_ERR_ARG, "NULL x or pure");
+    if (!o->p || !o->loss || !o->iter || !o->flag) return capi_fail(DSQ_ERR_ARG, "NULL output array");
+    if (!a->has_alpha == !a->has_shift) return capi_fail(DSQ_ERR_ARG, "exactly one of alpha and shift is to be given");
+    const double v = a->has_alpha ? a->alpha : a->shift;
+    if (!(v > 0.0) || v - v != 0.0) return capi_fail(DSQ_ERR_ARG, "%s = %g must be positive and finite", a->has_alpha ? "alpha" : "shift", v);
+    if (a->power != 1 && a->power != 2) return capi_fail(DSQ_ERR_ARG, "power = %d: 1 or 2", a->power);
+    if (a->maxit < 0) return capi_fail(DSQ_ERR_ARG, "maxit = %d is negative", a->maxit);
+    return DSQ_OK;
+}
+
+int unmix_dev_locked(const DsqUnmixArgs *a, const DsqUnmixOut *o, void *workspace, int64_t workspace_bytes, hipStream_t st) {
+    if (int rc = unmix_check(a, o)) return rc;
+    if (a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld = %ld < m = %d", (long)a->ld, a->m);
+    const size_t need = unmix_workspace_bytes(a->n, a->m);
+    if (!workspace || workspace_bytes < (int64_t)need)
+        return capi_fail(DSQ_ERR_ARG, "workspace of %lld bytes: %zu are needed (dsq_unmix_workspace_bytes)", (long long)workspace_bytes, need);
+    if (int rc = capi_check_device()) return rc;
+    UnmixKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.m = a->m; kp.k = a->k; kp.ld = (long)a->ld;
+    kp.x = a->x; kp.pure = a->pure;
+    kp.alpha_form = a->has_alpha ? 1 : 0;
+    kp.a = a->has_alpha ? a->alpha : a->shift;
+    kp.power = a->power; kp.maxit = a->maxit;
+    kp.vx = (double *)workspace;
+    kp.p = o->p; kp.loss = o->loss; kp.iter = o->iter; kp.flag = o->flag;
+    capi_prof_begin("unmix", a->m, st);
+    DSQ_HIP(launch_unmix(kp, st));
+    capi_prof_end(st);
+    return DSQ_OK;
+}
+
 // results() (results.hip): what both entries check before anything is launched
 int results_check(const DsqResultsArgs *a, const DsqResultsOut *o) {
     if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
@@ -970,6 +1008,15 @@ int dsq_parametric_dispersion_fit_dev(const double *means, const double *disps, 
         return DSQ_OK;
     });
 }
+
+int dsq_unmix_dev(const DsqUnmixArgs *a, const DsqUnmixOut *o, void *workspace, int64_t workspace_bytes, void *s) {
+    return dev_entry(s, [&](hipStream_t st) { return unmix_dev_locked(a, o, workspace, workspace_bytes, st); });
+}
+int64_t dsq_unmix_workspace_bytes(int32_t n, int32_t m, int32_t k) {
+    if (n < 1 || m < 1 || k < 1) return 0;
+    return (int64_t)unmix_workspace_bytes(n, m);
+}
+int32_t dsq_unmix_block_threads(void) { return kUnmixThreads; }
 
 int64_t dsq_size_factors_workspace_bytes(int32_t n, int32_t m) {
     if (n < 0 || m < 0) return 0;

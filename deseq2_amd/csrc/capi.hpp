@@ -17,6 +17,9 @@ enum {  // workspace slots
 };
 static_assert(WS_COUNT <= DSQ_WS_PIPE_PADXR, "pipeline workspace slots follow the call slots");
 
+// unmix(): the threads of a workgroup, i.e. the T of the summation order of DESIGN.md section 17 (thread t adds genes t, t + T, ...)
+constexpr int kUnmixThreads = 256;
+
 static inline long round_ld(int m) { return ((long)m + 7) & ~7L; }
 static inline bool is_wide(int p) { return p > DSQ_P_REG && p <= DSQ_P_WIDE; }
 static inline int wide_width(int p) { return dsq_wide_width(p); }   // padded width for a wide p
@@ -47,6 +50,7 @@ int check_replace(const DsqReplaceArgs *a, const DsqReplaceOut *o);
 int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o);
 int vst_check(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats);
 int rlog_check(const DsqRlogArgs *a, const DsqRlogOut *o);
+int unmix_check(const DsqUnmixArgs *a, const DsqUnmixOut *o);
 int results_check(const DsqResultsArgs *a, const DsqResultsOut *o);
 int contrasts_check(const DsqContrastsArgs *a, const DsqContrastsOut *o);
 int pt_check(const double *q, const double *df, int32_t n, int32_t K, int32_t tail, const double *out);
@@ -64,6 +68,7 @@ int replace_dev_locked(const DsqReplaceArgs *a, const DsqReplaceOut *o, hipStrea
 int size_factors_dev_locked(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o, hipStream_t st);
 int vst_dev_locked(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats, hipStream_t st);
 int rlog_dev_locked(const DsqRlogArgs *a, const DsqRlogOut *o, hipStream_t st);
+int unmix_dev_locked(const DsqUnmixArgs *a, const DsqUnmixOut *o, void *workspace, int64_t workspace_bytes, hipStream_t st);
 int results_dev_locked(const DsqResultsArgs *a, const DsqResultsOut *o, hipStream_t st);
 int contrasts_dev_locked(const DsqContrastsArgs *a, const DsqContrastsOut *o, hipStream_t st);
 

@@ -826,6 +826,42 @@ int dsq_rlog(const DsqRlogArgs *a, const DsqRlogOut *o) {
 }
 
 
+int dsq_unmix(const DsqUnmixArgs *a, const DsqUnmixOut *o) {
+    const auto check = [&]() -> int {
+        if (int rc = unmix_check(a, o)) return rc;
+        // (R would carry a negative or missing value into optim's objective; here it is refused)
+        const size_t nx = (size_t)a->n * a->m, np = (size_t)a->n * a->k;
+        for (size_t t = 0; t < nx; t++)
+            if (!(a->x[t] >= 0.0) || a->x[t] - a->x[t] != 0.0) return capi_fail(DSQ_ERR_VALUE, "x holds a negative or non-finite value");
+        for (size_t t = 0; t < np; t++)
+            if (!(a->pure[t] >= 0.0) || a->pure[t] - a->pure[t] != 0.0) return capi_fail(DSQ_ERR_VALUE, "pure holds a negative or non-finite value");
+        return DSQ_OK;
+    };
+    HostCall hc;
+    DSQ_TRY(host_ready(check(), DSQ_LAYOUT_R));
+    hipStream_t st = hc.st;
+    const size_t m = a->m, k = a->k;
+    const long ld = round_ld(a->m);
+    DsqUnmixArgs d = *a;
+    DsqUnmixOut od = *o;
+    Stage s(st, a->n);
+    const void *g;
+    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->x, 8, a->n, a->m, ld, &g));
+    d.x = (const double *)g; d.ld = ld;
+    DSQ_TRY(up_gene_major(s, WS_H_X, WS_PAD_X, a->pure, 8, a->n, a->k, (long)k, &g));
+    d.pure = (const double *)g;
+    s.out_vec(&od.p, o->p, m * k * 8);
+    s.out_vec(&od.loss, o->loss, m * 8);
+    s.out_vec(&od.iter, o->iter, m * 4);
+    s.out_vec(&od.flag, o->flag, m * 4);
+    DSQ_TRY(s.pack_out());
+    const size_t wsb = unmix_workspace_bytes(a->n, a->m);
+    void *w;
+    DSQ_TRY(capi_ws_get(WS_SCRATCH, wsb, &w));
+    DSQ_TRY(unmix_dev_locked(&d, &od, w, (int64_t)wsb, st));
+    return s.finish();
+}
+
 int dsq_results(const DsqResultsArgs *a, const DsqResultsOut *o) {
     const auto check = [&]() -> int {
         if (int rc = results_check(a, o)) return rc;

@@ -269,6 +269,23 @@ struct RlogKernelParams {
 };
 hipError_t launch_rlog(const RlogKernelParams &kp, int y_f64, hipStream_t st);
 
+// unmix() (unmix.hip): x gene-major (element (g, i) at [g * ld + i]), pure gene-major with k
+// contiguous doubles per gene; vx: the caller's workspace, m x n, written by the preparation kernel and read by the fit.
+struct UnmixKernelParams {
+    int n, m, k;
+    long ld;
+    const double *x, *pure;
+    int alpha_form;              // 1: v of a negative binomial with dispersion a; 0: log(q + a)
+    double a;                    // alpha or shift
+    int power, maxit;
+    double *vx;
+    double *p;                   // m x k, k contiguous per sample
+    double *loss;                // m
+    int32_t *iter, *flag;        // m
+};
+size_t unmix_workspace_bytes(int n, int m);
+hipError_t launch_unmix(const UnmixKernelParams &kp, hipStream_t st);
+
 // results() (results.hip): the table of one coefficient, the threshold tests, and the Benjamini-
 // Hochberg adjustment over K nested filter subsets from ONE sort of the p-values.  n-vectors and n x p column-major
 // matrices; the second block is carved from the caller's workspace by launch_results.

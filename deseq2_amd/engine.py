@@ -388,6 +388,13 @@ class HostEngine:
                 oi[idx] = np.where(bad, np.nan, beta[:, 0])
         return {"rlog": out, "intercept": oi, "iter": it, "flag": flag}
 
+    def unmix_fit(self, x, pure, alpha=None, shift=None, power=1, maxit=200):
+        """the fits of unmix() (R/helper.R:96-112): x an n x m handle (or array) of normalized counts / TPMs, pure an n x k
+        array.  The iteration of csrc/unmix.hip stated in numpy over this engine's log (unmix_host.py), the same bits.
+        Returns dict(p m x k, loss m, iter m, flag m) on the host."""
+        from . import unmix_host
+        return unmix_host.unmix_fit(self.vlog, np.asarray(x, np.float64), pure, alpha=alpha, shift=shift, power=power, maxit=maxit)
+
     def nf_col_geomeans(self, nf):
         """exp(colMeans(log(normalizationFactors))): the approximate size factors of R/vst.R:162"""
         return np.exp(np.log(np.asarray(nf, np.float64)).mean(axis=0))
@@ -836,6 +843,22 @@ class DeviceEngine:
                                    r["flag"].to(t.float64)])).numpy()
         return {"rlog": r["rlog"], "intercept": None if intercept is not None else pack[0].copy(), "iter": pack[1].copy(),
                 "flag": pack[2].astype(np.int32)}
+
+    def unmix_fit(self, x, pure, alpha=None, shift=None, power=1, maxit=200):
+        """the fits of unmix() on the device (csrc/unmix.hip, dsq_unmix_dev) on the current stream: x a resident n x m float64
+        handle (what normalized_counts returns) or a host matrix, which goes up once; pure (n x k) goes up; p, loss, iter and
+        flag (m x k and three m-vectors) come down in one copy."""
+        t = self.torch
+        if not isinstance(x, self.native.GeneMajor):
+            x = self.matrix(x)
+        pure = np.ascontiguousarray(pure, dtype=np.float64)
+        k = pure.shape[1]
+        r = self._timed("unmix", x.m, lambda: self.native.unmix_dev(
+            x, self._vec(pure), alpha=alpha, shift=shift, power=power, maxit=maxit))
+        pack = self._host(t.cat([r["p"], r["loss"][:, None], r["iter"].to(t.float64)[:, None],
+                                 r["flag"].to(t.float64)[:, None]], dim=1)).numpy()
+        return {"p": pack[:, :k].copy(), "loss": pack[:, k].copy(), "iter": pack[:, k + 1].astype(np.int32),
+                "flag": pack[:, k + 2].astype(np.int32)}
 
     def nf_col_geomeans(self, nf):
         t = self.torch

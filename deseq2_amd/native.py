@@ -871,6 +871,47 @@ def rlog_dev(y, nf, dispFit, betaPriorVar, intercept=None, tol=1e-4, maxit=100, 
     return {"rlog": out, "intercept": pack[0] if intercept is None else None, "iter": pack[1], "flag": flag}
 
 
+def _unmix_form(alpha, shift, power, maxit):
+    return dict(has_alpha=int(alpha is not None), has_shift=int(shift is not None),
+                alpha=float(alpha) if alpha is not None else 0.0, shift=float(shift) if shift is not None else 0.0,
+                power=int(power), maxit=int(maxit))
+
+
+def unmix(x, pure, alpha=None, shift=None, power=1, maxit=200):
+    """the fits of unmix() (R/helper.R:96-112) through dsq_unmix: host arrays in R layout in (x n x m, pure n x k);
+    dict(p m x k, loss m, iter m, flag m) out.  mix = p / rowSums(p) is the caller's."""
+    x, pure = _fcol(x), _fcol(pure)
+    if x.ndim != 2 or pure.ndim != 2 or pure.shape[0] != x.shape[0]:
+        raise ValueError("x and pure must be matrices with the same number of rows")
+    (n, m), k = x.shape, pure.shape[1]
+    p, loss = np.zeros((m, k)), np.zeros(m)
+    it, flag = np.zeros(m, np.int32), np.zeros(m, np.int32)
+    a = L.DsqUnmixArgs(n=n, m=m, k=k, ld=0, x=_ptr(x), pure=_ptr(pure), **_unmix_form(alpha, shift, power, maxit))
+    o = L.DsqUnmixOut(p=_ptr(p), loss=_ptr(loss), iter=_ptr(it), flag=_ptr(flag))
+    L.check(L.lib().dsq_unmix(C.byref(a), C.byref(o)))
+    return {"p": p, "loss": loss, "iter": it, "flag": flag}
+
+
+def unmix_dev(x, pure, alpha=None, shift=None, power=1, maxit=200, workspace=None):
+    """dsq_unmix_dev on resident matrices: x a GeneMajor float64 handle (n x m), pure an (n, k) contiguous float64 device
+    tensor.  Returns dict(p: (m, k) float64 tensor, loss: (m,) float64, iter / flag: (m,) int32 tensors); nothing is read
+    back.  workspace: a uint8 device tensor of dsq_unmix_workspace_bytes(n, m, k) bytes to reuse."""
+    import torch
+    assert isinstance(x, GeneMajor) and x.t.dtype == torch.float64
+    assert pure.dtype == torch.float64 and pure.dim() == 2 and pure.is_contiguous() and pure.shape[0] == x.n
+    dev, m, k = x.t.device, x.m, pure.shape[1]
+    p = torch.empty((m, k), dtype=torch.float64, device=dev)
+    loss = torch.empty(m, dtype=torch.float64, device=dev)
+    ints = torch.empty((2, m), dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(8, int(L.lib().dsq_unmix_workspace_bytes(x.n, m, k))), dtype=torch.uint8, device=dev)
+    a = L.DsqUnmixArgs(n=x.n, m=m, k=k, ld=x.ld, x=_t_ptr(x.t), pure=_t_ptr(pure), **_unmix_form(alpha, shift, power, maxit))
+    o = L.DsqUnmixOut(p=_t_ptr(p), loss=_t_ptr(loss), iter=_t_ptr(ints[0]), flag=_t_ptr(ints[1]))
+    L.check(L.lib().dsq_unmix_dev(C.byref(a), C.byref(o), _t_ptr(workspace), int(workspace.numel()), _stream()))
+    # (the workspace is stream-ordered scratch: torch's caching allocator hands it out again only to work enqueued later)
+    return {"p": p, "loss": loss, "iter": ints[0], "flag": ints[1]}
+
+
 def prefitMoments_dev(y, nf, q, a, r, weights=None, useWeights=False, nf_is_vector=False):
     """device flavour of prefitMoments: y / nf / weights GeneMajor, q / a (p, m) and r (p, p)
     contiguous CUDA tensors (= column-major m x p / p x p)."""

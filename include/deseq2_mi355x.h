@@ -686,6 +686,47 @@ typedef struct {
 int dsq_rlog_dev(const DsqRlogArgs *args, const DsqRlogOut *out, void *stream);
 int dsq_rlog(const DsqRlogArgs *args, const DsqRlogOut *out);
 
+/* ---- dsq_unmix: unmix() (R/helper.R:70-132) ------------------------------------------------------
+ * Sample i, column i of x (n genes x m samples), is unmixed into k pure components (pure: n x k): minimise over the box
+ * [lo, 100]^k     L_i(p) = sum_g | v(x_gi) - v(sum_j pure_gj p_j) |^power,     power 1 or 2,     from p = 1, with
+ *   alpha given:   v(q) = (2 asinh(sqrt(alpha q)) - log alpha - log 4) / log 2,   lo = 1e-6
+ *   shift given:   v(q) = log(q + shift),                                         lo = 0
+ * R reaches the minimum by L-BFGS-B on numerical gradients; the library minimises the same objective on the same box by
+ * its own deterministic iteration (projected Levenberg-Marquardt on the reweighted Gauss-Newton system, DESIGN.md
+ * section 17), every operation rounded once in a stated order.  The caller forms mix = p / sum(p).
+ * flag: 0 stopped by the tolerance or for lack of an improving step, 1 maxit reached, 2 the loss at the start is not
+ * finite (p and loss of that sample are NaN).
+ * _dev: device pointers, asynchronous on `stream`, no allocation, no host synchronisation; x gene-major with leading
+ * dimension ld >= m (padding is not read), pure gene-major with k contiguous doubles per gene; workspace: at least
+ * dsq_unmix_workspace_bytes(n, m, k) bytes (v(x), sample-major), else DSQ_ERR_ARG.
+ * dsq_unmix: host pointers, x and pure in R layout (column-major), ONE device, synchronous; DSQ_ERR_VALUE for a negative
+ * or non-finite entry of x or pure.  p comes back with the k values of a sample contiguous in both.
+ * DSQ_ERR_ARG: k < 2, both or neither of alpha / shift, a non-positive or non-finite one, power outside {1, 2};
+ * DSQ_ERR_UNSUPPORTED: k > DSQ_UNMIX_MAX_K.  All decided before a device is asked for.                                  */
+#define DSQ_UNMIX_MAX_K 16
+typedef struct {
+    int32_t n, m, k;
+    int64_t ld;                /* _dev: leading dimension of x (>= m); dsq_unmix: ignored                            */
+    const double *x;           /* n x m                                                                             */
+    const double *pure;        /* n x k                                                                             */
+    int32_t has_alpha, has_shift;  /* exactly one of them                                                           */
+    double alpha, shift;       /* the one that is given: finite, > 0                                                */
+    int32_t power;             /* 1 or 2                                                                            */
+    int32_t maxit;             /* >= 0; unmix(): 200                                                                */
+} DsqUnmixArgs;
+
+typedef struct {
+    double *p;                 /* m x k, the k coefficients of a sample contiguous                                  */
+    double *loss;              /* m                                                                                 */
+    int32_t *iter;             /* m: iterations started                                                             */
+    int32_t *flag;             /* m                                                                                 */
+} DsqUnmixOut;
+
+int64_t dsq_unmix_workspace_bytes(int32_t n, int32_t m, int32_t k);
+int32_t dsq_unmix_block_threads(void);   /* the T of the summation order: thread t of T adds genes t, t + T, ...       */
+int dsq_unmix_dev(const DsqUnmixArgs *args, const DsqUnmixOut *out, void *workspace, int64_t workspace_bytes, void *stream);
+int dsq_unmix(const DsqUnmixArgs *args, const DsqUnmixOut *out);
+
 /* ---- dsq_results: results() for one coefficient (R/results.R:443-575, 638-740) -------------------
  * The table -- baseMean, log2FoldChange, lfcSE, stat, pvalue of design column c --, the threshold tests of :484-515 under
  * the normal distribution, pvalue NA where na_mask is set (the Cook's filter of :520-564 is the caller's: a host decision
