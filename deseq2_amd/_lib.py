@@ -274,6 +274,18 @@ class DsqUnmixOut(C.Structure):
     _fields_ = [("p", C.c_void_p), ("loss", C.c_void_p), ("iter", C.c_void_p), ("flag", C.c_void_p)]
 
 
+class DsqSfIterateArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("m", C.c_int32), ("ld", C.c_int64), ("y", C.c_void_p), ("mu", C.c_void_p), ("sf", C.c_void_p),
+        ("disp", C.c_void_p), ("rows", C.c_void_p), ("Q", C.c_double), ("maxit", C.c_int32),
+    ]
+
+
+class DsqSfIterateOut(C.Structure):
+    _fields_ = [("s", C.c_void_p), ("sf", C.c_void_p), ("F", C.c_void_p), ("iter", C.c_void_p), ("evals", C.c_void_p),
+                ("flag", C.c_void_p)]
+
+
 class DsqResultsArgs(C.Structure):
     _fields_ = [
         ("n", C.c_int32), ("p", C.c_int32), ("c", C.c_int32), ("test", C.c_int32), ("beta", C.c_void_p),
@@ -342,6 +354,7 @@ EXPORTED_SYMBOLS = [
     "dsq_vst", "dsq_vst_dev", "dsq_vst_rowstats_dev",
     "dsq_rlog", "dsq_rlog_dev",
     "dsq_unmix", "dsq_unmix_dev", "dsq_unmix_workspace_bytes", "dsq_unmix_block_threads",
+    "dsq_sf_iterate", "dsq_sf_iterate_dev", "dsq_sf_iterate_workspace_bytes", "dsq_sf_iterate_slice_genes",
     "dsq_results", "dsq_results_dev", "dsq_results_workspace_bytes",
     "dsq_contrasts", "dsq_contrasts_dev", "dsq_contrasts_max_m",
     "dsq_pt", "dsq_pt_dev",
@@ -427,6 +440,12 @@ def lib():
     L.dsq_unmix_workspace_bytes.restype = C.c_int64
     L.dsq_unmix_block_threads.argtypes = []
     L.dsq_unmix_block_threads.restype = C.c_int32
+    L.dsq_sf_iterate.argtypes = [C.POINTER(DsqSfIterateArgs), C.POINTER(DsqSfIterateOut)]
+    L.dsq_sf_iterate_dev.argtypes = [C.POINTER(DsqSfIterateArgs), C.POINTER(DsqSfIterateOut), C.c_void_p, C.c_int64, C.c_void_p]
+    L.dsq_sf_iterate_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.dsq_sf_iterate_workspace_bytes.restype = C.c_int64
+    L.dsq_sf_iterate_slice_genes.argtypes = []
+    L.dsq_sf_iterate_slice_genes.restype = C.c_int32
     L.dsq_results.argtypes = [C.POINTER(DsqResultsArgs), C.POINTER(DsqResultsOut)]
     L.dsq_results_dev.argtypes = [C.POINTER(DsqResultsArgs), C.POINTER(DsqResultsOut), C.c_void_p]
     L.dsq_results_workspace_bytes.argtypes = [C.c_int32, C.c_int32]

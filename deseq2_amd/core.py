@@ -9,7 +9,8 @@ Cook's distances, outlier replacement and the refit loop are mirro
 O(n m) parts run in the engine.
 
 Size factors: estimateSizeFactors / estimateSizeFactorsForMatrix ("ratio", "poscounts", geoMeans, controlGenes,
-normMatrix) run in the engine too (csrc/size_factors.hip); type = "iterate" is not mirrored.
+normMatrix) run in the engine too (csrc/size_factors.hip); type = "iterate" (estimateSizeFactorsIterate) alternates the
+dispersion steps with the engine's solve of the log size factors (csrc/sf_iterate.hip).
 
 Transformations: vst / varianceStabilizingTransformation / getVarianceStabilizedData (R/vst.R), normTransform and
 counts(normalized = TRUE) run in the engine as well (csrc/vst.hip); rlog / rlogTransformation
@@ -247,8 +248,8 @@ def xim_size_factors(sf):
 # ------------------------------------------------------------------ size factors
 def _sf_args(n, type, geoMeans, controlGenes):
     if type == "iterate":
-        raise NotImplementedError('estimateSizeFactors(type = "iterate") is an optim(L-BFGS-B) loop around '
-                                  "estimateDispersions (R/core.R:2589-2622): VERDICT's open row f4")
+        raise NotImplementedError('type = "iterate" belongs to estimateSizeFactors on an object (R/methods.R:374-375, VERDICT '
+                                  "row f4): R's estimateSizeFactorsForMatrix has no such type")
     if type not in ("ratio", "poscounts"):
         raise ValueError("'arg' should be one of 'ratio', 'poscounts', 'iterate'")
     if type == "poscounts":
@@ -274,6 +275,12 @@ def estimateSizeFactors(dds, type="ratio", geoMeans=None, controlGenes=None, nor
     handle), the matrix of estimateNormFactors (R/core.R:2159-2163) with dds.sizeFactors = None.  Works on the resident
     counts: an object made by from_device() needs no host copy of them."""
     E = dds.engine
+    if type == "iterate":                                  # R/methods.R:374-375: geoMeans, controlGenes, normMatrix are not looked at
+        info = {}
+        sf = estimateSizeFactorsIterate(dds, info=info)
+        _install_size_factors(dds, sf)
+        dds.attrs["sfIterateRounds"] = info["rounds"]
+        return dds
     geoMeans, ctl = _sf_args(dds.n, type, geoMeans, controlGenes)
     nmh = normMatrix
     if normMatrix is not None and isinstance(normMatrix, (np.ndarray, list, tuple)):
@@ -282,24 +289,77 @@ def estimateSizeFactors(dds, type="ratio", geoMeans=None, controlGenes=None, nor
             raise ValueError("normMatrix must have the dimensions of the counts")
         nmh = E.matrix(nm)
     r = E.size_factors(dds.y, type=type, geoMeans=geoMeans, control=ctl, normMatrix=nmh)
-    for k in ("prefit", "prefit_for"):                     # baseMean / baseVar belong to the old factors
-        dds.attrs.pop(k, None)
-    dds._sf_given = True
     if normMatrix is not None:
+        for k in ("prefit", "prefit_for"):                 # baseMean / baseVar belong to the old factors
+            dds.attrs.pop(k, None)
+        dds._sf_given = True
         dds.sizeFactors = None
         dds.nf = r["normalizationFactors"] if E.name == "device" else E.matrix(r["normalizationFactors"])
         return dds
-    sf = dds.sizeFactors = np.asarray(r["sizeFactors"], np.float64)
+    return _install_size_factors(dds, r["sizeFactors"], r.get("sizeFactors_dev"))
+
+
+def _install_size_factors(dds, sf, sfd=None):
+    """sizeFactors(dds) <- sf: the m-vector, the normalization-factor handle R builds from it (getSizeOrNormFactors,
+    R/core.R:2221-2227) and the dropped prefit cache.  sfd: the resident copy of sf on a device engine, if there is one."""
+    E = dds.engine
+    for k in ("prefit", "prefit_for"):                     # baseMean / baseVar belong to the old factors
+        dds.attrs.pop(k, None)
+    dds._sf_given = True
+    sf = dds.sizeFactors = np.asarray(sf, np.float64)
     if E.name == "device":
         # the chain reads the resident m-vector (fused._Run looks it up by its bytes); the n x m matrix is built from it
         # on the device, and only if a step asks for it
-        sfd = r["sizeFactors_dev"]
+        if sfd is None:
+            sfd = E._vec(sf)
         E._cache[("sf", np.ascontiguousarray(sf).tobytes())] = sfd
         n = dds.n
         dds._nf, dds._nf_src = None, (lambda: sfd[:, None].expand(sfd.numel(), n).contiguous())
     else:
         dds.nf = E.matrix(np.broadcast_to(sf[None, :], (dds.n, dds.m)))
     return dds
+
+
+SF_ITERATE_WITHIN = "iterative size factor normalization did not converge within an iteration"     # R/core.R:2609
+SF_ITERATE_OUTER = "iterative size factor normalization did not converge"                          # R/core.R:2617
+
+
+def estimateSizeFactorsIterate(dds, niter=10, Q=0.05, info=None):
+    """R/core.R:2589-2622 on either engine: the m size factors (host).  Each round fits the dispersions of the intercept
+    design at the current factors (estimateDispersions(fitType = "mean")) and maximises, over the log size factors, the sum
+    of the gene log likelihoods above their Q quantile at q = t(t(mu) / sf) and those dispersions.  R hands that objective
+    to optim(L-BFGS-B); here it is the engine's sf_iterate_solve (csrc/sf_iterate.hip on the device): the same objective,
+    the library's own deterministic safeguarded Newton iteration.  R's two stop() messages come as
+    ValueError.  info: a dict that receives the number of rounds."""
+    E = dds.engine
+    m = dds.m
+    if m - 1 <= 3:
+        raise NotImplementedError("estimateSizeFactors(type = \"iterate\") fits the dispersions of the intercept design: with "
+                                  "%d samples its residual df is <= 3, where the reference's seeded Monte-Carlo prior "
+                                  "variance is not mirrored (VERDICT row f4)" % m)
+    work = _shallow(dds, np.ones((m, 1)))                                            # design(object) <- ~ 1, :2590
+    sf = np.ones(m)                                                                  # :2591
+    _install_size_factors(work, sf)
+    allZero = getBaseMeansAndVariances(work).mcols["allZero"]                        # idx <- rowSums(counts(object)) > 0, :2592
+    if allZero.any():
+        work = work.subset(np.where(~allZero)[0])                                    # (the engine fits the non-zero rows)
+    rows = np.ones(work.n, dtype=bool)
+    for i in range(1, int(niter) + 1):                                               # :2594
+        _install_size_factors(work, sf)                                              # :2595
+        work.mcols, work.assays = {}, {}
+        estimateDispersions(work, fitType="mean")                                    # :2596
+        r = E.sf_iterate_solve(work.y, work.assays["mu"], sf, work.mcols["dispersion"], rows, Q=Q, maxit=100)   # :2597-2607
+        if r["flag"] != 0:
+            raise ValueError(SF_ITERATE_WITHIN)                                      # :2608-2610
+        sf_old, sf = sf, np.asarray(r["sf"], np.float64)                             # :2599, :2611
+        dl = E.vlog(sf_old) - E.vlog(sf)
+        if i > 1 and np.cumsum(dl * dl)[-1] < 1e-4:                                  # :2613
+            break
+        if i == niter:
+            raise ValueError(SF_ITERATE_OUTER)                                       # :2616-2618
+    if info is not None:
+        info["rounds"] = i
+    return sf
 
 
 def modelMatrixGroups(x):
@@ -1163,7 +1223,7 @@ def _DESeqNZ(dds, test, fitType, reduced, minReplicatesForReplace, disp_maxit=10
 
 def DESeq(dds, test="Wald", fitType="parametric", reduced=None, minReplicatesForReplace=7, sfType=None, **kw):
     """R/core.R:280-432, serial path.  sfType = None takes the size / normalization factors of the object as given;
-    "ratio" or "poscounts" estimates them first, as DESeq() does (R/core.R:304,378-389).
+    "ratio", "poscounts" or "iterate" estimates them first, as DESeq() does (R/core.R:304,378-389).
     minReplicatesForReplace = np.inf switches the outlier refit off.
     Rows whose counts are all zero are set aside as every step of the reference does (objectNZ,
     e.g. R/core.R:705,1351) and come back as NA (NaN) rows of mcols (buildDataFrameWithNARows);

@@ -848,6 +848,37 @@ int unmix_dev_locked(const DsqUnmixArgs *a, const DsqUnmixOut *o, void *workspac
     return DSQ_OK;
 }
 
+// the solve of estimateSizeFactors(type = "iterate") (sf_iterate.hip): what both entries check before anything is launched
+int sf_iterate_check(const DsqSfIterateArgs *a, const DsqSfIterateOut *o) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->n < 1 || a->m < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
+    if (!a->y || !a->mu || !a->sf || !a->disp || !a->rows) return capi_fail(DSQ_ERR_ARG, "NULL input array");
+    if (!o->s || !o->sf || !o->F || !o->iter || !o->evals || !o->flag) return capi_fail(DSQ_ERR_ARG, "NULL output array");
+    if (!(a->Q >= 0.0 && a->Q < 1.0)) return capi_fail(DSQ_ERR_ARG, "Q = %g: a probability below 1", a->Q);
+    if (a->maxit < 0) return capi_fail(DSQ_ERR_ARG, "maxit = %d is negative", a->maxit);
+    return DSQ_OK;
+}
+
+int sf_iterate_dev_locked(const DsqSfIterateArgs *a, const DsqSfIterateOut *o, void *workspace, int64_t workspace_bytes, hipStream_t st) {
+    if (int rc = sf_iterate_check(a, o)) return rc;
+    if (a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld = %ld < m = %d", (long)a->ld, a->m);
+    const size_t need = sf_iterate_workspace_bytes(a->n, a->m);
+    if (!workspace || workspace_bytes < (int64_t)need)
+        return capi_fail(DSQ_ERR_ARG, "workspace of %lld bytes: %zu are needed (dsq_sf_iterate_workspace_bytes)", (long long)workspace_bytes, need);
+    if (int rc = capi_check_device()) return rc;
+    SfIterateKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.m = a->m; kp.ld = (long)a->ld;
+    kp.y = a->y; kp.mu = a->mu; kp.sf = a->sf; kp.disp = a->disp; kp.rows = a->rows;
+    kp.Q = a->Q; kp.maxit = a->maxit;
+    kp.s_out = o->s; kp.sf_out = o->sf; kp.F_out = o->F;
+    kp.iter_out = o->iter; kp.evals_out = o->evals; kp.flag_out = o->flag;
+    capi_prof_begin("sf_iterate", a->n, st);
+    DSQ_HIP(launch_sf_iterate(kp, workspace, st));
+    capi_prof_end(st);
+    return DSQ_OK;
+}
+
 // results() (results.hip): what both entries check before anything is launched
 int results_check(const DsqResultsArgs *a, const DsqResultsOut *o) {
     if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
@@ -1017,6 +1048,15 @@ int64_t dsq_unmix_workspace_bytes(int32_t n, int32_t m, int32_t k) {
     return (int64_t)unmix_workspace_bytes(n, m);
 }
 int32_t dsq_unmix_block_threads(void) { return kUnmixThreads; }
+
+int dsq_sf_iterate_dev(const DsqSfIterateArgs *a, const DsqSfIterateOut *o, void *workspace, int64_t workspace_bytes, void *s) {
+    return dev_entry(s, [&](hipStream_t st) { return sf_iterate_dev_locked(a, o, workspace, workspace_bytes, st); });
+}
+int64_t dsq_sf_iterate_workspace_bytes(int32_t n, int32_t m) {
+    if (n < 1 || m < 1) return 0;
+    return (int64_t)sf_iterate_workspace_bytes(n, m);
+}
+int32_t dsq_sf_iterate_slice_genes(void) { return kSfIterSliceGenes; }
 
 int64_t dsq_size_factors_workspace_bytes(int32_t n, int32_t m) {
     if (n < 0 || m < 0) return 0;

@@ -19,6 +19,9 @@ static_assert(WS_COUNT <= DSQ_WS_PIPE_PADXR, "pipeline workspace slots follow th
 
 // unmix(): the threads of a workgroup, i.e. the T of the summation order of DESIGN.md section 17 (thread t adds genes t, t + T, ...)
 constexpr int kUnmixThreads = 256;
+// estimateSizeFactors(type = "iterate"): the consecutive genes one partial column sum of the gradient covers, i.e. the G of
+// the summation order of DESIGN.md section 18
+constexpr int kSfIterSliceGenes = 64;
 
 static inline long round_ld(int m) { return ((long)m + 7) & ~7L; }
 static inline bool is_wide(int p) { return p > DSQ_P_REG && p <= DSQ_P_WIDE; }
@@ -51,6 +54,7 @@ int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o);
 int vst_check(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats);
 int rlog_check(const DsqRlogArgs *a, const DsqRlogOut *o);
 int unmix_check(const DsqUnmixArgs *a, const DsqUnmixOut *o);
+int sf_iterate_check(const DsqSfIterateArgs *a, const DsqSfIterateOut *o);
 int results_check(const DsqResultsArgs *a, const DsqResultsOut *o);
 int contrasts_check(const DsqContrastsArgs *a, const DsqContrastsOut *o);
 int pt_check(const double *q, const double *df, int32_t n, int32_t K, int32_t tail, const double *out);
@@ -69,6 +73,7 @@ int size_factors_dev_locked(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *
 int vst_dev_locked(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats, hipStream_t st);
 int rlog_dev_locked(const DsqRlogArgs *a, const DsqRlogOut *o, hipStream_t st);
 int unmix_dev_locked(const DsqUnmixArgs *a, const DsqUnmixOut *o, void *workspace, int64_t workspace_bytes, hipStream_t st);
+int sf_iterate_dev_locked(const DsqSfIterateArgs *a, const DsqSfIterateOut *o, void *workspace, int64_t workspace_bytes, hipStream_t st);
 int results_dev_locked(const DsqResultsArgs *a, const DsqResultsOut *o, hipStream_t st);
 int contrasts_dev_locked(const DsqContrastsArgs *a, const DsqContrastsOut *o, hipStream_t st);
 

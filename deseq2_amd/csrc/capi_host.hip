@@ -862,6 +862,49 @@ int dsq_unmix(const DsqUnmixArgs *a, const DsqUnmixOut *o) {
     return s.finish();
 }
 
+int dsq_sf_iterate(const DsqSfIterateArgs *a, const DsqSfIterateOut *o) {
+    const auto check = [&]() -> int {
+        if (int rc = sf_iterate_check(a, o)) return rc;
+        const size_t nm = (size_t)a->n * a->m;
+        for (size_t t = 0; t < nm; t++) {
+            if (a->y[t] < 0) return capi_fail(DSQ_ERR_VALUE, "the count matrix holds a negative value");
+            if (!(a->mu[t] >= 0.0) || a->mu[t] - a->mu[t] != 0.0) return capi_fail(DSQ_ERR_VALUE, "mu holds a negative or non-finite value");
+        }
+        for (int j = 0; j < a->m; j++)
+            if (!(a->sf[j] > 0.0) || a->sf[j] - a->sf[j] != 0.0) return capi_fail(DSQ_ERR_VALUE, "sf[%d] = %g is not positive and finite", j, a->sf[j]);
+        return DSQ_OK;
+    };
+    HostCall hc;
+    DSQ_TRY(host_ready(check(), DSQ_LAYOUT_R));
+    hipStream_t st = hc.st;
+    const size_t n = a->n, m = a->m;
+    const long ld = round_ld(a->m);
+    DsqSfIterateArgs d = *a;
+    DsqSfIterateOut od = *o;
+    Stage s(st, n);
+    const void *g;
+    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->y, 4, a->n, a->m, ld, &g));
+    d.y = (const int32_t *)g; d.ld = ld;
+    DSQ_TRY(up_gene_major(s, WS_H_NF, WS_NF, a->mu, 8, a->n, a->m, ld, &g));
+    d.mu = (const double *)g;
+    s.vec(&d.sf, a->sf, m * 8);
+    s.vec(&d.disp, a->disp, n * 8);
+    s.vec(&d.rows, a->rows, n * 4);
+    DSQ_TRY(s.pack_in());
+    s.out_vec(&od.s, o->s, m * 8);
+    s.out_vec(&od.sf, o->sf, m * 8);
+    s.out_vec(&od.F, o->F, 8);
+    s.out_vec(&od.iter, o->iter, 4);
+    s.out_vec(&od.evals, o->evals, 4);
+    s.out_vec(&od.flag, o->flag, 4);
+    DSQ_TRY(s.pack_out());
+    const size_t wsb = sf_iterate_workspace_bytes(a->n, a->m);
+    void *w;
+    DSQ_TRY(capi_ws_get(WS_SCRATCH, wsb, &w));
+    DSQ_TRY(sf_iterate_dev_locked(&d, &od, w, (int64_t)wsb, st));
+    return s.finish();
+}
+
 int dsq_results(const DsqResultsArgs *a, const DsqResultsOut *o) {
     const auto check = [&]() -> int {
         if (int rc = results_check(a, o)) return rc;

@@ -286,6 +286,23 @@ struct UnmixKernelParams {
 size_t unmix_workspace_bytes(int n, int m);
 hipError_t launch_unmix(const UnmixKernelParams &kp, hipStream_t st);
 
+// the solve of estimateSizeFactors(type = "iterate") (sf_iterate.hip): y / mu gene-major, read only;
+// launch_sf_iterate carves its state from the caller's workspace, runs the host loop (one small record read back per
+// evaluation of F: it synchronises `st`) and writes the outputs.
+struct SfIterateKernelParams {
+    int n, m;
+    long ld;
+    const int32_t *y;
+    const double *mu, *sf, *disp;
+    const int32_t *rows;
+    double Q;
+    int maxit;
+    double *s_out, *sf_out, *F_out;       // m, m, 1
+    int32_t *iter_out, *evals_out, *flag_out;
+};
+size_t sf_iterate_workspace_bytes(long n, long m);
+hipError_t launch_sf_iterate(const SfIterateKernelParams &kp, void *workspace, hipStream_t st);
+
 // results() (results.hip): the table of one coefficient, the threshold tests, and the Benjamini-
 // Hochberg adjustment over K nested filter subsets from ONE sort of the p-values.  n-vectors and n x p column-major
 // matrices; the second block is carved from the caller's workspace by launch_results.

@@ -755,4 +755,19 @@ DSQ_DEV double nb_split_var(double y, double size, double alpha, double mu, bool
     return dnbinom_mu_log(y, size, mu);
 }
 
+// log / exp with the values at the edges of the domain spelled out (R's log(0) = -Inf, log(Inf) = Inf, log(< 0) = NaN):
+// the size-factor units (size_factors.hip, sf_iterate.hip)
+DSQ_DEV double sf_log(double v) {
+    if (v > 0.0 && v < kInf) return dlog(v);
+    if (v == 0.0) return -kInf;
+    if (v == kInf) return kInf;
+    return dnan();
+}
+DSQ_DEV double sf_exp(double v) {
+    if (v != v) return v;
+    if (v == kInf) return kInf;
+    if (v == -kInf) return 0.0;
+    return dexp(v);
+}
+
 }  // namespace dsq

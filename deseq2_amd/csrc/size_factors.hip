@@ -24,20 +24,6 @@
 
 namespace dsq {
 
-// log / exp with the values at the edges of the domain spelled out (R's log(0) = -Inf, log(Inf) = Inf, log(< 0) = NaN)
-DSQ_DEV double sf_log(double v) {
-    if (v > 0.0 && v < kInf) return dlog(v);
-    if (v == 0.0) return -kInf;
-    if (v == kInf) return kInf;
-    return dnan();
-}
-DSQ_DEV double sf_exp(double v) {
-    if (v != v) return v;
-    if (v == kInf) return kInf;
-    if (v == -kInf) return 0.0;
-    return dexp(v);
-}
-
 template <typename T>
 DSQ_DEV double sf_count(const SizeFactorKernelParams &kp, long i, long j) {
     return (double)((const T *)kp.y)[i * kp.y_si + j * kp.y_sj];

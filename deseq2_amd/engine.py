@@ -395,6 +395,16 @@ class HostEngine:
         from . import unmix_host
         return unmix_host.unmix_fit(self.vlog, np.asarray(x, np.float64), pure, alpha=alpha, shift=shift, power=power, maxit=maxit)
 
+    def sf_iterate_solve(self, y, mu, sf, disp, rows, Q=0.05, maxit=100):
+        """the solve of one round of estimateSizeFactorsIterate (R/core.R:2600-2611): y / mu n x m handles, sf the m size
+        factors mu was fitted with, disp n, rows n flags (rowSums > 0).  The iteration of csrc/sf_iterate.hip stated in numpy
+        over this engine's nbinomLogLike, log and exp (sf_iterate_host.py), the same bits.  Returns dict(s, sf, F, iter,
+        evals, flag) on the host."""
+        from . import sf_iterate_host
+        loglike = lambda K, mu_, a: self.fns.nbinomLogLike(K, mu_, a, None, False)
+        return sf_iterate_host.solve(loglike, self.vexp, self.vlog, y, mu, sf, disp, rows, float(Q), int(maxit),
+                                     sf_iterate_host.SLICE_GENES)
+
     def nf_col_geomeans(self, nf):
         """exp(colMeans(log(normalizationFactors))): the approximate size factors of R/vst.R:162"""
         return np.exp(np.log(np.asarray(nf, np.float64)).mean(axis=0))
@@ -859,6 +869,19 @@ class DeviceEngine:
                                  r["flag"].to(t.float64)[:, None]], dim=1)).numpy()
         return {"p": pack[:, :k].copy(), "loss": pack[:, k].copy(), "iter": pack[:, k + 1].astype(np.int32),
                 "flag": pack[:, k + 2].astype(np.int32)}
+
+    def sf_iterate_solve(self, y, mu, sf, disp, rows, Q=0.05, maxit=100):
+        """the solve of one round of estimateSizeFactorsIterate on the device (csrc/sf_iterate.hip, dsq_sf_iterate_dev) on
+        the current stream: y / mu resident handles; sf, disp and the row flags go up; s, sf, F and the three counters come
+        down in one copy."""
+        t = self.torch
+        rv = t.as_tensor(np.ascontiguousarray(np.asarray(rows) != 0, dtype=np.int32)).to(self.device)
+        r = self._timed("sf_iterate", y.n, lambda: self.native.sf_iterate_dev(
+            y, mu, self._vec(sf), self._vec(np.where(np.asarray(rows) != 0, disp, np.nan)), rv, Q=Q, maxit=maxit))
+        m = y.m
+        pack = self._host(r["_pack"]).numpy()
+        return {"s": pack[:m].copy(), "sf": pack[m:2 * m].copy(), "F": float(pack[2 * m]), "iter": int(pack[2 * m + 1]),
+                "evals": int(pack[2 * m + 2]), "flag": int(pack[2 * m + 3])}
 
     def nf_col_geomeans(self, nf):
         t = self.torch

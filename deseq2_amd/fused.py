@@ -445,7 +445,7 @@ def DESeq(dds, test="Wald", fitType="parametric", reduced=None, minReplicatesFor
     prepares the next one and post-processes the previous one, and the result copy (a side stream) runs beside the
     next chain's kernels -- bench.py's pipelined steps.
 
-    sfType = "ratio" / "poscounts": estimateSizeFactors first (R/core.R:304,378-389), on the resident counts; the chain then
+    sfType = "ratio" / "poscounts" / "iterate": estimateSizeFactors first (R/core.R:304,378-389), on the resident counts; the chain then
     reads the resident m-vector.  The host sees the m size factors (xim is their mean reciprocal): one small copy.  (A
     gene shard would estimate from its own rows only: as in R/parallel.R, estimate on the whole matrix before the split.)"""
     if sfType is not None:

@@ -486,8 +486,8 @@ def estimateSizeFactorsForMatrix(counts, type="ratio", geoMeans=None, controlGen
     or a logical vector.  A matrix whose every gene has a zero raises DsqError (DSQ_ERR_FIT)."""
     from .engine import control_flags
     if type == "iterate":
-        raise NotImplementedError('type = "iterate" is an optim(L-BFGS-B) loop around estimateDispersions '
-                                  "(R/core.R:2589-2622): VERDICT's open row f4")
+        raise NotImplementedError('type = "iterate" belongs to estimateSizeFactors on an object (core.estimateSizeFactors, '
+                                  "VERDICT row f4): R's estimateSizeFactorsForMatrix has no such type")
     if type not in L.DSQ_SF:
         raise ValueError("type should be 'ratio' or 'poscounts'")
     y, ytype = _counts(counts)
@@ -910,6 +910,53 @@ def unmix_dev(x, pure, alpha=None, shift=None, power=1, maxit=200, workspace=Non
     L.check(L.lib().dsq_unmix_dev(C.byref(a), C.byref(o), _t_ptr(workspace), int(workspace.numel()), _stream()))
     # (the workspace is stream-ordered scratch: torch's caching allocator hands it out again only to work enqueued later)
     return {"p": p, "loss": loss, "iter": ints[0], "flag": ints[1]}
+
+
+def sf_iterate_solve(counts, mu, sf, disp, rows, Q=0.05, maxit=100):
+    """the solve of one round of estimateSizeFactorsIterate (R/core.R:2600-2611) through dsq_sf_iterate: host arrays in R
+    layout in (counts / mu n x m, sf m, disp n, rows n flags); dict(s, sf, F, iter, evals, flag) out."""
+    y = np.asfortranarray(counts, dtype=np.int32)
+    mu = _fcol(mu)
+    if y.ndim != 2 or mu.shape != y.shape:
+        raise ValueError("counts and mu must be matrices of the same shape")
+    n, m = y.shape
+    sf = np.ascontiguousarray(sf, dtype=np.float64)
+    disp = np.ascontiguousarray(disp, dtype=np.float64)
+    rows = np.ascontiguousarray(np.asarray(rows) != 0, dtype=np.int32)
+    if sf.shape != (m,) or disp.shape != (n,) or rows.shape != (n,):
+        raise ValueError("sf must have one entry per sample, disp and rows one per gene")
+    s, e, F = np.zeros(m), np.zeros(m), np.zeros(1)
+    ints = np.zeros(3, np.int32)
+    a = L.DsqSfIterateArgs(n=n, m=m, ld=0, y=_ptr(y), mu=_ptr(mu), sf=_ptr(sf), disp=_ptr(disp), rows=_ptr(rows), Q=float(Q),
+                           maxit=int(maxit))
+    o = L.DsqSfIterateOut(s=_ptr(s), sf=_ptr(e), F=_ptr(F), iter=_ptr(ints[0:1]), evals=_ptr(ints[1:2]), flag=_ptr(ints[2:3]))
+    L.check(L.lib().dsq_sf_iterate(C.byref(a), C.byref(o)))
+    return {"s": s, "sf": e, "F": float(F[0]), "iter": int(ints[0]), "evals": int(ints[1]), "flag": int(ints[2])}
+
+
+def sf_iterate_dev(y, mu, sf, disp, rows, Q=0.05, maxit=100, workspace=None):
+    """dsq_sf_iterate_dev on resident matrices: y (int32) and mu (float64) GeneMajor handles of one leading dimension, sf (m)
+    and disp (n) float64 device tensors, rows (n) an int32 device tensor.  The call synchronises the current stream (the
+    host loop reads a record back per evaluation).  Returns dict(s, sf: (m,) float64 tensors, F: (1,), iter / evals / flag:
+    (1,) int32 tensors, _pack: all of them as one float64 tensor).  workspace: a uint8 device tensor of
+    dsq_sf_iterate_workspace_bytes(n, m) bytes to reuse."""
+    import torch
+    assert isinstance(y, GeneMajor) and y.t.dtype == torch.int32
+    assert isinstance(mu, GeneMajor) and mu.t.dtype == torch.float64 and mu.ld == y.ld and mu.n == y.n and mu.m == y.m
+    assert sf.dtype == torch.float64 and sf.numel() == y.m and disp.dtype == torch.float64 and disp.numel() == y.n
+    assert rows.dtype == torch.int32 and rows.numel() == y.n
+    dev, n, m = y.t.device, y.n, y.m
+    pack = torch.empty(2 * m + 1, dtype=torch.float64, device=dev)
+    ints = torch.empty(3, dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(8, int(L.lib().dsq_sf_iterate_workspace_bytes(n, m))), dtype=torch.uint8, device=dev)
+    a = L.DsqSfIterateArgs(n=n, m=m, ld=y.ld, y=_t_ptr(y.t), mu=_t_ptr(mu.t), sf=_t_ptr(sf), disp=_t_ptr(disp), rows=_t_ptr(rows),
+                           Q=float(Q), maxit=int(maxit))
+    o = L.DsqSfIterateOut(s=_t_ptr(pack[:m]), sf=_t_ptr(pack[m:2 * m]), F=_t_ptr(pack[2 * m:]), iter=_t_ptr(ints[0:1]),
+                          evals=_t_ptr(ints[1:2]), flag=_t_ptr(ints[2:3]))
+    L.check(L.lib().dsq_sf_iterate_dev(C.byref(a), C.byref(o), _t_ptr(workspace), int(workspace.numel()), _stream()))
+    return {"s": pack[:m], "sf": pack[m:2 * m], "F": pack[2 * m:], "iter": ints[0:1], "evals": ints[1:2], "flag": ints[2:3],
+            "_pack": torch.cat([pack, ints.to(torch.float64)])}
 
 
 def prefitMoments_dev(y, nf, q, a, r, weights=None, useWeights=False, nf_is_vector=False):

@@ -727,6 +727,48 @@ int32_t dsq_unmix_block_threads(void);   /* the T of the summation order: thread
 int dsq_unmix_dev(const DsqUnmixArgs *args, const DsqUnmixOut *out, void *workspace, int64_t workspace_bytes, void *stream);
 int dsq_unmix(const DsqUnmixArgs *args, const DsqUnmixOut *out);
 
+/* ---- dsq_sf_iterate: the solve of estimateSizeFactors(type = "iterate") (R/core.R:2600-2611) ------
+ * One outer round of estimateSizeFactorsIterate fixes the counts k, q_ij = mu_ij / sf_j and the dispersions a_i over the
+ * rows whose flag is set, and maximises over s (sum s = 0)
+ *     F(s) = sum of L_i over the rows with L_i > quantile(L, Q),    L_i = sum_j log NB(k_ij; mu = q_ij exp(s_j), size = 1/a_i)
+ * R hands F to optim(method = "L-BFGS-B") with numerical gradients; the library maximises the same F by its own
+ * deterministic iteration -- on the kept set the objective separates in the samples, so Newton's step under the gauge is
+ * closed, and an Armijo test on the true F (cut re-evaluated at every trial) safeguards it --, every operation rounded
+ * once in a stated order (tests/sf_iterate_spec.py).
+ * flag: 0 stopped by the tolerance, for lack of an ascent direction or on an empty kept set, 1 maxit reached or no
+ * acceptable step, 2 F at the start is not finite.  iter: iterations started; evals: evaluations of F.
+ * _dev: device pointers; y int32 and mu double, gene-major with leading dimension ld >= m (padding is not read; neither
+ * buffer is written); the dispersion of a row whose flag is 0 is not read.  The host decides every step from a small
+ * record it reads back, so the call SYNCHRONISES `stream` (a few dozen times) and the outputs are complete on return.
+ * workspace: at least dsq_sf_iterate_workspace_bytes(n, m) bytes, else DSQ_ERR_ARG.
+ * dsq_sf_iterate: host pointers, y and mu in R layout (column-major), ONE device, synchronous; DSQ_ERR_VALUE for a
+ * negative count, a negative or non-finite mu, a size factor that is not positive and finite.
+ * The column sums of the gradient add the genes in slices of dsq_sf_iterate_slice_genes() consecutive genes, each slice in
+ * gene order, then the slices in order: the constant is part of the summation order.                                   */
+typedef struct {
+    int32_t n, m;
+    int64_t ld;                /* _dev: leading dimension of y and mu (>= m); dsq_sf_iterate: ignored               */
+    const int32_t *y;          /* n x m counts                                                                      */
+    const double *mu;          /* n x m fitted means of the round                                                   */
+    const double *sf;          /* m: the size factors mu was fitted with; the start is log(sf) - mean(log(sf))      */
+    const double *disp;        /* n                                                                                 */
+    const int32_t *rows;       /* n: non-zero = the row takes part (rowSums(counts) > 0)                            */
+    double Q;                  /* in [0, 1); estimateSizeFactorsIterate(): 0.05                                     */
+    int32_t maxit;             /* >= 0; optim(): 100                                                                */
+} DsqSfIterateArgs;
+
+typedef struct {
+    double *s;                 /* m: the centred log size factors                                                   */
+    double *sf;                /* m: exp(s)                                                                         */
+    double *F;                 /* 1                                                                                 */
+    int32_t *iter, *evals, *flag;   /* 1 each                                                                       */
+} DsqSfIterateOut;
+
+int64_t dsq_sf_iterate_workspace_bytes(int32_t n, int32_t m);
+int32_t dsq_sf_iterate_slice_genes(void);
+int dsq_sf_iterate_dev(const DsqSfIterateArgs *args, const DsqSfIterateOut *out, void *workspace, int64_t workspace_bytes, void *stream);
+int dsq_sf_iterate(const DsqSfIterateArgs *args, const DsqSfIterateOut *out);
+
 /* ---- dsq_results: results() for one coefficient (R/results.R:443-575, 638-740) -------------------
  * The table -- baseMean, log2FoldChange, lfcSE, stat, pvalue of design column c --, the threshold tests of :484-515 under
  * the normal distribution, pvalue NA where na_mask is set (the Cook's filter of :520-564 is the caller's: a host decision
