@@ -397,6 +397,38 @@ static int fit_rows(const A *a, const O *o, int64_t row_lo, int64_t row_cnt, Che
     });
 }
 
+// R-layout counts (or an n x m matrix of doubles) up into `h_slot`, then gene-major into `gm_slot` with leading dimension ld
+template <class T>
+static int up_gene_major(Stage &s, int h_slot, int gm_slot, const void *host, size_t elem, int n, int m, long ld, const T **gm) {
+    const void *r;
+    void *g;
+    DSQ_TRY(s.genes_up(h_slot, &r, host, elem, m));
+    DSQ_TRY(capi_ws_get(gm_slot, (size_t)n * ld * elem, &g));
+    if (elem == 4) DSQ_HIP(launch_transpose_r_to_gm_i32((const int32_t *)r, (int32_t *)g, n, m, ld, s.st));
+    else DSQ_HIP(launch_transpose_r_to_gm_f64((const double *)r, (double *)g, n, m, ld, s.st));
+    *gm = (const T *)g;
+    return DSQ_OK;
+}
+// normalization factors: a vector of m size factors as it is, or an n x m matrix in R layout, which goes up gene-major
+static int nf_up_gene_major(Stage &s, const double **field, const double *nf, int is_vector, int n, int m, long ld) {
+    if (is_vector) return s.nf_up(field, nf, 1, m);
+    return up_gene_major(s, WS_H_NF, WS_NF, nf, 8, n, m, ld, field);
+}
+// an n x m result that the kernels write gene-major: its slot, taken before the launch; and, after flush(), its way back to
+// the caller's matrix in R layout (which comes down in finish())
+static int gm_result_slot(size_t n, long ld, double **field) {
+    void *w;
+    DSQ_TRY(capi_ws_get(WS_MUOUT, n * ld * 8, &w));
+    *field = (double *)w;
+    return DSQ_OK;
+}
+static int gm_result_down(Stage &s, const double *gm, double *host, int n, int m, long ld) {
+    double *r;
+    DSQ_TRY(s.out_mat(WS_H_OUTMAT, &r, host, m));
+    DSQ_HIP(launch_transpose_gm_to_r_f64(gm, r, n, m, ld, s.st));
+    return DSQ_OK;
+}
+
 extern "C" {
 
 int dsq_fit_beta(const DsqFitBetaArgs *a, const DsqFitBetaOut *o) { return dsq_fit_beta_rows(a, o, 0, a ? a->n : 0); }
@@ -531,18 +563,6 @@ int dsq_intercept_fit(const DsqInterceptArgs *a, const DsqInterceptOut *o) {
     DSQ_TRY(s.out_mat(WS_H_OUTMAT2, &od.hat, o->hat, m));
     DSQ_TRY(intercept_dev_locked(&d, &od, st));
     return s.finish();
-}
-
-// R-layout counts (or an n x m matrix of doubles) up into `h_slot`, then gene-major into `gm_slot` with leading dimension ld
-static int up_gene_major(Stage &s, int h_slot, int gm_slot, const void *host, size_t elem, int n, int m, long ld, const void **gm) {
-    const void *r;
-    void *g;
-    DSQ_TRY(s.genes_up(h_slot, &r, host, elem, m));
-    DSQ_TRY(capi_ws_get(gm_slot, (size_t)n * ld * elem, &g));
-    if (elem == 4) DSQ_HIP(launch_transpose_r_to_gm_i32((const int32_t *)r, (int32_t *)g, n, m, ld, s.st));
-    else DSQ_HIP(launch_transpose_r_to_gm_f64((const double *)r, (double *)g, n, m, ld, s.st));
-    *gm = g;
-    return DSQ_OK;
 }
 
 int dsq_optim_rows(const DsqOptimArgs *a, const DsqOptimOut *o) {
@@ -695,14 +715,9 @@ int dsq_size_factors(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o) {
     Stage s(st, n);
     DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->y, a->y_type == DSQ_Y_INT32 ? 4 : 8, a->n, a->m, ld, &d.y));
     d.layout = DSQ_LAYOUT_GENE_MAJOR; d.ld = ld;
-    double *nf_gm = nullptr;
     if (a->normMatrix) {
-        const void *g;
-        void *w;
-        DSQ_TRY(up_gene_major(s, WS_H_NF, WS_NF, a->normMatrix, 8, a->n, a->m, ld, &g));
-        d.normMatrix = (const double *)g;
-        DSQ_TRY(capi_ws_get(WS_MUOUT, n * ld * 8, &w));
-        od.normalizationFactors = nf_gm = (double *)w;
+        DSQ_TRY(up_gene_major(s, WS_H_NF, WS_NF, a->normMatrix, 8, a->n, a->m, ld, &d.normMatrix));
+        DSQ_TRY(gm_result_slot(n, ld, &od.normalizationFactors));
     }
     s.vec(&d.geoMeans, a->geoMeans, n * 8);
     s.vec(&d.control, a->control, n * 4);
@@ -716,11 +731,7 @@ int dsq_size_factors(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o) {
     DSQ_TRY(s.pack_out());
     DSQ_TRY(size_factors_dev_locked(&d, &od, st));
     DSQ_TRY(s.flush());
-    if (nf_gm) {
-        double *nf_r;
-        DSQ_TRY(s.out_mat(WS_H_OUTMAT, &nf_r, o->normalizationFactors, m));
-        DSQ_HIP(launch_transpose_gm_to_r_f64(nf_gm, nf_r, a->n, a->m, ld, st));
-    }
+    if (a->normMatrix) DSQ_TRY(gm_result_down(s, od.normalizationFactors, o->normalizationFactors, a->n, a->m, ld));
     DSQ_TRY(s.finish());
     if (*o->status == 1)
         return capi_fail(DSQ_ERR_FIT, "every gene contains at least one zero, cannot compute log geometric means");
@@ -744,31 +755,17 @@ int dsq_vst(const DsqVstArgs *a, const DsqVstOut *o) {
     if (transform) stage_prefault(o->out, n * m * 8);
     DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->y, a->y_type == DSQ_Y_INT32 ? 4 : 8, a->n, a->m, ld, &d.y));
     d.layout = DSQ_LAYOUT_GENE_MAJOR; d.ld = ld;
-    if (a->nf_is_vector) DSQ_TRY(s.nf_up(&d.nf, a->nf, 1, m));
-    else {
-        const void *g;
-        DSQ_TRY(up_gene_major(s, WS_H_NF, WS_NF, a->nf, 8, a->n, a->m, ld, &g));
-        d.nf = (const double *)g;
-    }
+    DSQ_TRY(nf_up_gene_major(s, &d.nf, a->nf, a->nf_is_vector, a->n, a->m, ld));
     int32_t bad = 0;
     s.out_vec(&od.bad, &bad, 4, 8);
     s.out_gene_vec(&od.rowMean, o->rowMean);
     s.out_gene_vec(&od.rowMax, o->rowMax);
     DSQ_TRY(s.pack_out());
     DSQ_HIP(hipMemsetAsync(od.bad, 0, 8, st));
-    double *out_gm = nullptr;
-    if (transform) {
-        void *g;
-        DSQ_TRY(capi_ws_get(WS_MUOUT, n * ld * 8, &g));
-        od.out = out_gm = (double *)g;
-    }
+    if (transform) DSQ_TRY(gm_result_slot(n, ld, &od.out));
     DSQ_TRY(vst_dev_locked(&d, &od, transform, stats, st));
     DSQ_TRY(s.flush());
-    if (out_gm) {
-        double *out_r;
-        DSQ_TRY(s.out_mat(WS_H_OUTMAT, &out_r, o->out, m));
-        DSQ_HIP(launch_transpose_gm_to_r_f64(out_gm, out_r, a->n, a->m, ld, st));
-    }
+    if (transform) DSQ_TRY(gm_result_down(s, od.out, o->out, a->n, a->m, ld));
     DSQ_TRY(s.finish());
     if (bad) return capi_fail(DSQ_ERR_VALUE, "count matrix holds negative, non-finite or non-integer values");
     return DSQ_OK;
@@ -795,12 +792,7 @@ int dsq_rlog(const DsqRlogArgs *a, const DsqRlogOut *o) {
     stage_prefault(o->rlog, n * m * 8);
     DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->y, a->y_type == DSQ_Y_INT32 ? 4 : 8, a->n, a->m, ld, &d.y));
     d.layout = DSQ_LAYOUT_GENE_MAJOR; d.ld = ld;
-    if (a->nf_is_vector) DSQ_TRY(s.nf_up(&d.nf, a->nf, 1, m));
-    else {
-        const void *g;
-        DSQ_TRY(up_gene_major(s, WS_H_NF, WS_NF, a->nf, 8, a->n, a->m, ld, &g));
-        d.nf = (const double *)g;
-    }
+    DSQ_TRY(nf_up_gene_major(s, &d.nf, a->nf, a->nf_is_vector, a->n, a->m, ld));
     s.gene_vec(&d.dispFit, a->dispFit);
     if (a->intercept) s.gene_vec(&d.intercept, a->intercept);
     DSQ_TRY(s.pack_in());
@@ -811,15 +803,10 @@ int dsq_rlog(const DsqRlogArgs *a, const DsqRlogOut *o) {
     s.out_gene_vec(&od.flag, o->flag);
     DSQ_TRY(s.pack_out());
     DSQ_HIP(hipMemsetAsync(od.bad, 0, 8, st));
-    void *g;
-    DSQ_TRY(capi_ws_get(WS_MUOUT, n * ld * 8, &g));
-    double *out_gm = (double *)g;
-    od.rlog = out_gm;
+    DSQ_TRY(gm_result_slot(n, ld, &od.rlog));
     DSQ_TRY(rlog_dev_locked(&d, &od, st));
     DSQ_TRY(s.flush());
-    double *out_r;
-    DSQ_TRY(s.out_mat(WS_H_OUTMAT, &out_r, o->rlog, m));
-    DSQ_HIP(launch_transpose_gm_to_r_f64(out_gm, out_r, a->n, a->m, ld, st));
+    DSQ_TRY(gm_result_down(s, od.rlog, o->rlog, a->n, a->m, ld));
     DSQ_TRY(s.finish());
     if (bad) return capi_fail(DSQ_ERR_VALUE, "count matrix holds negative, non-finite or non-integer values");
     return DSQ_OK;
@@ -845,11 +832,9 @@ int dsq_unmix(const DsqUnmixArgs *a, const DsqUnmixOut *o) {
     DsqUnmixArgs d = *a;
     DsqUnmixOut od = *o;
     Stage s(st, a->n);
-    const void *g;
-    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->x, 8, a->n, a->m, ld, &g));
-    d.x = (const double *)g; d.ld = ld;
-    DSQ_TRY(up_gene_major(s, WS_H_X, WS_PAD_X, a->pure, 8, a->n, a->k, (long)k, &g));
-    d.pure = (const double *)g;
+    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->x, 8, a->n, a->m, ld, &d.x));
+    d.ld = ld;
+    DSQ_TRY(up_gene_major(s, WS_H_X, WS_PAD_X, a->pure, 8, a->n, a->k, (long)k, &d.pure));
     s.out_vec(&od.p, o->p, m * k * 8);
     s.out_vec(&od.loss, o->loss, m * 8);
     s.out_vec(&od.iter, o->iter, m * 4);
@@ -882,11 +867,9 @@ int dsq_sf_iterate(const DsqSfIterateArgs *a, const DsqSfIterateOut *o) {
     DsqSfIterateArgs d = *a;
     DsqSfIterateOut od = *o;
     Stage s(st, n);
-    const void *g;
-    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->y, 4, a->n, a->m, ld, &g));
-    d.y = (const int32_t *)g; d.ld = ld;
-    DSQ_TRY(up_gene_major(s, WS_H_NF, WS_NF, a->mu, 8, a->n, a->m, ld, &g));
-    d.mu = (const double *)g;
+    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->y, 4, a->n, a->m, ld, &d.y));
+    d.ld = ld;
+    DSQ_TRY(up_gene_major(s, WS_H_NF, WS_NF, a->mu, 8, a->n, a->m, ld, &d.mu));
     s.vec(&d.sf, a->sf, m * 8);
     s.vec(&d.disp, a->disp, n * 8);
     s.vec(&d.rows, a->rows, n * 4);
@@ -965,25 +948,16 @@ int dsq_contrasts(const DsqContrastsArgs *a, const DsqContrastsOut *o) {
     d.ld = ld;
     std::vector<int32_t> labels;
     Stage s(st, n);
-    const void *g;
     if (a->sample_mask) {
-        DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->counts, 4, a->n, a->m, ld, &g));
-        d.counts = (const int32_t *)g;
+        DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->counts, 4, a->n, a->m, ld, &d.counts));
         s.vec(&d.sample_mask, a->sample_mask, K * m * 4);
         s.vec(&d.rule_applies, a->rule_applies, K * 4);
     }
     if (a->allZero) s.vec(&d.allZero, a->allZero, n * 4);
     if (a->contrasts) {
         host_cells(a->x, a->m, a->p, a->cell_of, a->ncell, &labels, &d.cell_of, &d.ncell);
-        if (a->nf_is_vector) DSQ_TRY(s.nf_up(&d.nf, a->nf, 1, m));
-        else {
-            DSQ_TRY(up_gene_major(s, WS_H_NF, WS_NF, a->nf, 8, a->n, a->m, ld, &g));
-            d.nf = (const double *)g;
-        }
-        if (a->useWeights) {
-            DSQ_TRY(up_gene_major(s, WS_H_W, WS_W, a->weights, 8, a->n, a->m, ld, &g));
-            d.weights = (const double *)g;
-        }
+        DSQ_TRY(nf_up_gene_major(s, &d.nf, a->nf, a->nf_is_vector, a->n, a->m, ld));
+        if (a->useWeights) DSQ_TRY(up_gene_major(s, WS_H_W, WS_W, a->weights, 8, a->n, a->m, ld, &d.weights));
         s.vec(&d.x, a->x, m * p * 8);
         s.vec(&d.alpha_hat, a->alpha_hat, n * 8);
         s.vec(&d.beta, a->beta, n * p * 8);

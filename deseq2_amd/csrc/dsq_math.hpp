@@ -31,8 +31,16 @@ constexpr double kInf = __builtin_huge_val();
 
 DSQ_DEV double dnan() { return __builtin_nan(""); }
 DSQ_DEV bool dfinite(double x) { return __builtin_fabs(x) < kInf; }
+// a count as a double; a count that arrives as a double is checked on the way (negative, non-finite or non-integer: *bad |= 1)
+template <typename T>
+DSQ_DEV double count_value(T k, int32_t *bad) { return (double)k; }
+template <>
+DSQ_DEV double count_value<double>(double k, int32_t *bad) {
+    if (bad && !(k >= 0.0 && k < kInf && k == __builtin_floor(k))) atomicOr(bad, 1);
+    return k;
+}
 // f64 -> u64 whose unsigned order is the numeric order (the caller keeps NaN away from it), and back: the keys of the radix
-// selection of size_factors.hip and of the radix sort of results.hip
+// selections of dsq_select.hpp and size_factors.hip and of the radix sort of results.hip
 DSQ_DEV unsigned long long order_key(double d) {
     const unsigned long long b = d2bits(d);
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);

@@ -7,6 +7,7 @@
 #pragma once
 #include <type_traits>
 #include <hip/hip_runtime.h>
+#include "dsq_math.hpp"
 
 // The per-width kernels (one translation unit per design width, -DDSQ_P=p, p <= 10) want every p-loop of the
 // wave-uniform algebra fully unrolled so that the p x p state stays in registers.  The WIDE translation units
@@ -731,6 +732,34 @@ DSQ_DEV void sweep_batched(int m, int lane, LoadF &&load, UseF &&use) {
             if (j < m) use(j, b);
         }
     }
+}
+
+// nbinomLogLike (R/core.R:2208-2217) on the closed split of the density (dsq_math.hpp): K' -- the mu-independent part of the
+// row's sum, samples in their natural order -- plus one sweep with two logarithms per sample.  The fitBeta launch that
+// fitted the row hands K' over (kconst; same counts, dispersions, weights: its constants pass computes it beside its own);
+// without it the constants pass runs here.  Round 4: R's dnbinom_mu sample by sample cost 8.2 k instructions per gene for
+// this one pass.  Against 40-digit arithmetic the split's terms lose four to five digits to cancellation where bd0 loses
+// none (|error| ~ 4e-12 on a log likelihood of -430 against 5e-13); at the dispersion floor (size 1e8) dnbinom_mu's own
+// log1p(-x/n) loses nine and the split none -- there the two differ by R's error, ~ 6e-10 per sample, a term of (y, size)
+// that cancels in an LRT statistic (tests/test_loglike_cpu.py).
+// Users: loglike_kernel (aux.hip) and the first row pass of sf_iterate.hip.
+template <bool USE_W>
+DSQ_DEV double loglike_constants(const int32_t *yg, const double *wg, int m, int lane, double alpha, double size, bool fast) {
+    if (!fast) return 0.0;
+    const double st_size = dstirlerr(size);
+    double pacc = 0.0;
+    for (int j = lane; j < m; j += 64) {
+        const double y = (double)yg[j];
+        double pj = 0.0;
+        if (y != 0.0 && cell_dev_closed(y, size, fast)) {
+            double base, t;
+            nb_split_const(y, alpha, size, st_size, base, t);
+            pj = base + t;
+        }
+        if constexpr (USE_W) pacc += wg[j] * pj;
+        else pacc += pj;
+    }
+    return wave_allreduce(pacc);
 }
 
 }  // namespace dsq

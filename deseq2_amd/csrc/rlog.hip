@@ -31,14 +31,6 @@ constexpr double kRlogLarge = 30.0;
 
 enum { RLOG_REG = 0, RLOG_LDS = 1, RLOG_ROW = 2 };
 
-template <typename T>
-DSQ_DEV double rlog_count(T k, int32_t *bad) { return (double)k; }
-template <>
-DSQ_DEV double rlog_count<double>(double k, int32_t *bad) {
-    if (bad && !(k >= 0.0 && k < kInf && k == __builtin_floor(k))) atomicOr(bad, 1);
-    return k;
-}
-
 // the per-sample coefficients of one gene
 template <int MODE>
 struct RlogState {
@@ -83,7 +75,7 @@ __global__ void __launch_bounds__(256) rlog_kernel(RlogKernelParams kp) {
             fscale = dexp((zero_row ? -10.0 : c) * kRlogLn2);
             RLOG_FOR_SAMPLES(k, j) {
                 const long at = row + (long)j * kp.sj;
-                const double yj = rlog_count<T>(y[at], kp.bad);
+                const double yj = count_value<T>(y[at], kp.bad);
                 const double nfj = kp.nf[kp.nf_is_vector ? (long)j : at] * fscale;
                 st.set(k, j, dlog(yj / nfj + 0.1));
             }
@@ -92,7 +84,7 @@ __global__ void __launch_bounds__(256) rlog_kernel(RlogKernelParams kp) {
             int nz = 0;
             RLOG_FOR_SAMPLES(k, j) {
                 const long at = row + (long)j * kp.sj;
-                const double yj = rlog_count<T>(y[at], kp.bad);
+                const double yj = count_value<T>(y[at], kp.bad);
                 s += yj / kp.nf[kp.nf_is_vector ? (long)j : at];
                 nz |= yj != 0.0;
                 st.set(k, j, 0.0);

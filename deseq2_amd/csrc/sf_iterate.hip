@@ -14,9 +14,9 @@
 // Kernels.  sfi_row_kernel: one wave per gene over its gene-major row, L_i = K'_i + the wave-order sum of nb_split_var,
 // exactly loglike_kernel's sums (aux.hip) at mu = (mu_ij / sf_j) exp(s_j); the division is redone in every sweep (it is
 // rounded once either way; an n x m workspace and its traffic are saved), K'_i is computed in the first sweep and kept.
-// sfi_cut_kernel: one workgroup; the two order statistics around (n' - 1) Q by radix selection over order-preserving
-// keys (8 passes of 8 bits for the lower one, one more pass for the upper one: the smallest key above it, or itself when
-// it is tied), the type-7 cut, and F = the kept L_i added by thread t of T = 1024 over the rows t, t + T, ..., the 64
+// sfi_cut_kernel: one workgroup; one sweep counts the rows n' and the NaN among their L_i, the two order statistics around
+// (n' - 1) Q come from the library's selection (dsq_select.hpp: radix_select for the lower one, next_order_stat for the
+// upper one), then the type-7 cut, and F = the kept L_i added by thread t of T = 1024 over the rows t, t + T, ..., the 64
 // lanes of a wave by the butterfly, the 16 waves in order.  sfi_col_kernel, only at an accepted point: lanes along the
 // samples, one wave per (slice of kSfIterSliceGenes consecutive genes, tile of 64 samples), the genes of a slice in
 // order, a row that is not kept a wave-uniform skip; the partial sums go to the workspace.  sfi_colsum_kernel adds them in
@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "dsq_math.hpp"
+#include "dsq_select.hpp"
 #include "dsq_wave.hpp"
 
 namespace dsq {
@@ -98,25 +99,7 @@ __global__ void __launch_bounds__(kSfiVecThreads) sfi_trial_kernel(int m, const 
     }
 }
 
-// ---- the row pass: L_i at the point whose exponentials are e
-// K' as loglike_constants of aux.hip computes it: the mu-independent part of the row's sum, in wave order
-DSQ_DEV double sfi_constants(const int32_t *yg, int m, int lane, double alpha, double size, bool fast) {
-    if (!fast) return 0.0;
-    const double st_size = dstirlerr(size);
-    double pacc = 0.0;
-    for (int j = lane; j < m; j += 64) {
-        const double y = (double)yg[j];
-        double pj = 0.0;
-        if (y != 0.0 && cell_dev_closed(y, size, fast)) {
-            double base, t;
-            nb_split_const(y, alpha, size, st_size, base, t);
-            pj = base + t;
-        }
-        pacc += pj;
-    }
-    return wave_allreduce(pacc);
-}
-
+// ---- the row pass: L_i at the point whose exponentials are e; K' is loglike_constants (dsq_wave.hpp), without weights
 template <bool CONSTS>
 __global__ void __launch_bounds__(256) sfi_row_kernel(SfIterateKernelParams kp, double *kconst, const double *e, double *L) {
     const int lane = threadIdx.x & 63;
@@ -131,7 +114,7 @@ __global__ void __launch_bounds__(256) sfi_row_kernel(SfIterateKernelParams kp, 
         const bool fast = nb_split_fast(alpha, size);
         double Kp;
         if constexpr (CONSTS) {
-            Kp = sfi_constants(yg, m, lane, alpha, size, fast);
+            Kp = loglike_constants<false>(yg, nullptr, m, lane, alpha, size, fast);
             if (lane == 0) kconst[g] = Kp;
         } else Kp = kconst[g];
         double acc = 0.0;
@@ -166,92 +149,46 @@ DSQ_DEV void sfi_sweep(const SfIterateKernelParams &kp, const double *L, Fn fn) 
 }
 
 __global__ void __launch_bounds__(kSfiCutThreads) sfi_cut_kernel(SfIterateKernelParams kp, const double *L, SfiRecord *rec) {
-    __shared__ unsigned int hist[256];
-    __shared__ unsigned int s_cnt[4];
-    __shared__ unsigned long long s_prefix, s_min;
-    __shared__ unsigned int s_rank, s_rows, s_lo;
-    __shared__ double s_gq;
+    __shared__ __attribute__((aligned(16))) unsigned hist[2048];
+    __shared__ unsigned long long bc[3];
+    __shared__ unsigned int s_cnt[3];                  // the rows n' | the NaN among their L_i | the rows kept
     __shared__ double s_wave[kSfiCutWaves];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (tid < 4) s_cnt[tid] = 0u;
-    if (tid == 0) s_min = ~0ull;
-    // the order statistic lo = floor((n' - 1) Q) by radix selection over order-preserving keys, 8 passes of 8 bits; the
-    // first pass also counts the rows n' (its histogram's total) and the NaN among the L_i
-    unsigned long long prefix = 0ull;
-    unsigned int rank = 0u;
-    for (int pass = 0; pass < 8; pass++) {
-        const int shift = 56 - 8 * pass;
-        if (tid < 256) hist[tid] = 0u;
-        __syncthreads();
-        unsigned int nb = 0u;
-        sfi_sweep(kp, L, [&](double v) {
-            const unsigned long long key = order_key(v);
-            if (pass == 0) {
-                if (v != v) nb++;
-                atomicAdd(&hist[(unsigned)(key >> 56)], 1u);
-            } else if (((key ^ prefix) >> (shift + 8)) == 0ull) atomicAdd(&hist[(unsigned)((key >> shift) & 255ull)], 1u);
-        });
-        if (nb) atomicAdd(&s_cnt[1], nb);
-        __syncthreads();
-        if (wave == 0) {
-            // the bin that holds the rank: lane l scans the bins 4 l .. 4 l + 3 behind a prefix sum over the lanes
-            const unsigned int h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
-            const unsigned int own = h0 + h1 + h2 + h3;
-            unsigned int incl = own;
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned int v = __shfl_up(incl, off, 64);
-                if (lane >= off) incl += v;
-            }
-            if (pass == 0) {
-                // quantile(L, Q), type 7: h = (n' - 1) Q between the order statistics lo = floor(h) and lo + 1
-                const unsigned int nrows = __shfl(incl, 63, 64);
-                const double hq = (double)(nrows ? nrows - 1u : 0u) * kp.Q;
-                rank = (unsigned int)__builtin_floor(hq);
-                if (lane == 0) { s_rows = nrows; s_lo = rank; s_gq = hq - (double)rank; }
-            }
-            const unsigned int excl = incl - own;
-            if (rank >= excl && rank < incl) {
-                unsigned int r = rank - excl;
-                int d = 4 * lane;
-                if (r >= h0) { r -= h0; d++; if (r >= h1) { r -= h1; d++; if (r >= h2) { r -= h2; d++; } } }
-                s_prefix = prefix | ((unsigned long long)(unsigned)d << shift);
-                s_rank = r;
-            }
+    if (tid < 3) s_cnt[tid] = 0u;
+    __syncthreads();
+    // the rows n' and the NaN among their L_i, before any key is formed (order_key must not see a NaN)
+    unsigned int nr = 0u, nb = 0u;
+    sfi_sweep(kp, L, [&](double v) {
+        nr++;
+        if (v != v) nb++;
+    });
+    if (nr) atomicAdd(&s_cnt[0], nr);
+    if (nb) atomicAdd(&s_cnt[1], nb);
+    __syncthreads();
+    const unsigned int nrows = s_cnt[0], nbad = s_cnt[1];
+    if (nrows == 0u || nbad != 0u) {                   // a NaN among the L_i: F is not finite
+        if (tid == 0) {
+            rec->F = nbad ? dnan() : 0.0;
+            rec->cut = dnan();
+            rec->nrows = (int32_t)nrows; rec->nkept = 0; rec->nbad = (int32_t)nbad;
         }
-        __syncthreads();
-        if (pass == 0) {
-            const unsigned int nrows = s_rows, nbad = s_cnt[1];
-            if (nrows == 0u || nbad != 0u) {           // a NaN among the L_i: F is not finite
-                if (tid == 0) {
-                    rec->F = nbad ? dnan() : 0.0;
-                    rec->cut = dnan();
-                    rec->nrows = (int32_t)nrows; rec->nkept = 0; rec->nbad = (int32_t)nbad;
-                }
-                return;
-            }
-        }
-        prefix = s_prefix;
-        rank = s_rank;
+        return;
     }
-    const unsigned int lo = s_lo;
-    const double gq = s_gq;
-    const double slo = order_unkey(prefix);
+    // quantile(L, Q), type 7: h = (n' - 1) Q between the order statistics lo = floor(h) and lo + 1.  Both by the shared
+    // selection over all n entries, a row that does not take part entering as +inf (as in trend_mean_kernel): the n - n'
+    // sentinels sort last, lo <= n' - 1 is never one of them, and gq != 0 means h < n' - 1, so lo + 1 <= n' - 1 is not either.
+    const double hq = (double)(nrows - 1u) * kp.Q;
+    const unsigned int lo = (unsigned int)__builtin_floor(hq);
+    const double gq = hq - (double)lo;
+    const double inf = __builtin_inf();
+    const auto val = [&](int i) { return kp.rows[i] != 0 ? L[i] : inf; };
+    SelState sel = {hist, bc, nullptr, 0};
+    const double slo = radix_select<1>(kp.n, (long)lo, val, sel, 0);
     double cut = slo;
     if (gq != 0.0) {
-        // the next order statistic: the key itself when more rows than lo + 1 are at or below it, else the smallest key above
-        unsigned int le = 0u;
-        unsigned long long mn = ~0ull;
-        sfi_sweep(kp, L, [&](double v) {
-            const unsigned long long key = order_key(v);
-            if (key <= prefix) le++;
-            else if (key < mn) mn = key;
-        });
-        if (le) atomicAdd(&s_cnt[2], le);
-        if (mn != ~0ull) atomicMin(&s_min, mn);
-        __syncthreads();
-        const double shi = s_cnt[2] >= lo + 2u ? slo : order_unkey(s_min);
+        const double shi = next_order_stat<1>(kp.n, slo, (long)lo, val, sel, 0);
         if (!(shi == slo)) cut = (1.0 - gq) * slo + gq * shi;
     }
     // F: the kept rows, thread t over the rows t, t + T, ..., then the butterfly, then the waves in order
@@ -262,14 +199,14 @@ __global__ void __launch_bounds__(kSfiCutThreads) sfi_cut_kernel(SfIterateKernel
     });
     acc = wave_allreduce(acc);
     if (lane == 0) s_wave[wave] = acc;
-    if (nk) atomicAdd(&s_cnt[3], nk);
+    if (nk) atomicAdd(&s_cnt[2], nk);
     __syncthreads();
     if (tid == 0) {
         double F = s_wave[0];
         for (int w = 1; w < kSfiCutWaves; w++) F = F + s_wave[w];
         rec->F = F;
         rec->cut = cut;
-        rec->nrows = (int32_t)s_rows; rec->nkept = (int32_t)s_cnt[3]; rec->nbad = 0;
+        rec->nrows = (int32_t)nrows; rec->nkept = (int32_t)s_cnt[2]; rec->nbad = 0;
     }
 }
 

@@ -68,14 +68,6 @@ DSQ_DEV double vst_apply(const VstKernelParams &kp, double q, double ope, double
     }
 }
 
-template <typename T>
-DSQ_DEV double vst_count(T k, int32_t *bad) { return (double)k; }
-template <>
-DSQ_DEV double vst_count<double>(double k, int32_t *bad) {
-    if (bad && !(k >= 0.0 && k < kInf && k == __builtin_floor(k))) atomicOr(bad, 1);
-    return k;
-}
-
 template <typename T> struct VstPair;
 template <> struct VstPair<int32_t> { typedef int2 type; };
 template <> struct VstPair<double> { typedef double2 type; };
@@ -107,19 +99,19 @@ vst_transform_kernel(VstKernelParams kp, unsigned long long total, unsigned int 
                 const typename VstPair<T>::type kk = *(const typename VstPair<T>::type *)(y + at);
                 const double2 f = *(const double2 *)(kp.nf + (kp.nf_is_vector ? j : at));
                 double2 r;
-                r.x = vst_apply<KIND>(kp, vst_count<T>(kk.x, kp.bad) / f.x, ope, a4, la, l4, vst_tab);
-                r.y = vst_apply<KIND>(kp, vst_count<T>(kk.y, kp.bad) / f.y, ope, a4, la, l4, vst_tab);
+                r.x = vst_apply<KIND>(kp, count_value<T>(kk.x, kp.bad) / f.x, ope, a4, la, l4, vst_tab);
+                r.y = vst_apply<KIND>(kp, count_value<T>(kk.y, kp.bad) / f.y, ope, a4, la, l4, vst_tab);
                 *(double2 *)(kp.out + at) = r;
             } else {
                 const double f = kp.nf[kp.nf_is_vector ? j : at];
-                kp.out[at] = vst_apply<KIND>(kp, vst_count<T>(y[at], kp.bad) / f, ope, a4, la, l4, vst_tab);
+                kp.out[at] = vst_apply<KIND>(kp, count_value<T>(y[at], kp.bad) / f, ope, a4, la, l4, vst_tab);
             }
         } else {
             // gene-major: (gene hi, sample lo); R layout: (sample hi, gene lo) -- the fast index runs along memory
             const long i = GM ? (long)hi : (long)lo, j = GM ? (long)lo : (long)hi;
             const long at = i * kp.si + j * kp.sj;
             const double f = kp.nf[kp.nf_is_vector ? j : at];
-            kp.out[at] = vst_apply<KIND>(kp, vst_count<T>(y[at], kp.bad) / f, ope, a4, la, l4, vst_tab);
+            kp.out[at] = vst_apply<KIND>(kp, count_value<T>(y[at], kp.bad) / f, ope, a4, la, l4, vst_tab);
         }
     }
 }
@@ -136,7 +128,7 @@ __global__ void __launch_bounds__(256) vst_rowstats_kernel(VstKernelParams kp) {
         double s = 0.0, mx = -kInf, anynan = 0.0;
         for (int j = lane; j < kp.m; j += 64) {
             const long at = (long)i * kp.si + (long)j * kp.sj;
-            const double q = vst_count<T>(y[at], kp.bad) / kp.nf[kp.nf_is_vector ? (long)j : at];
+            const double q = count_value<T>(y[at], kp.bad) / kp.nf[kp.nf_is_vector ? (long)j : at];
             s += q;
             if (q != q) anynan = 1.0;
             else if (q > mx) mx = q;

@@ -128,6 +128,60 @@ def test_content(oracle, name, kw):
         assert (c["disp"][c["rows"] != 0] == 1e-12).any() and (c["disp"][c["rows"] != 0] == 65.0).any()
 
 
+SEL_DIRECT = 1024        # kSelDirect of csrc/dsq_select.hpp: that many candidates or fewer are ranked by direct counting
+SEL_SHIFTS = (53, 42, 31, 20, 9, 0)      # what is left below the digits of 11, 11, 11, 11, 11, 9 bits
+
+
+def _selection_regime(oracle, c, Q):
+    """What the cut's selection meets at the start point, from the specification's L: the number of rows that take part and
+    equal the lower order statistic s[lo]; whether rank lo + 1 is one of them; and the candidates left after each radix digit
+    (the entries -- a row that does not take part is +inf -- whose key agrees with s[lo]'s above the digit's shift; the L
+    are negative, so agreeing bits of the doubles are agreeing bits of the keys)."""
+    P = S.Problem(oracle, Q=Q, **c)
+    L = P.evaluate(S._exp(oracle, P.start()))[0]
+    s = np.sort(L[P.rows])
+    h = (s.size - 1) * Q
+    lo = int(np.floor(h))
+    assert h != lo and lo + 1 < s.size and s[-1] < 0.0            # the upper statistic is needed
+    bits = np.where(P.rows, L, np.inf).view(np.uint64)
+    want = s[lo:lo + 1].view(np.uint64)[0]
+    left = [int(((bits >> np.uint64(sh)) == (want >> np.uint64(sh))).sum()) for sh in SEL_SHIFTS]
+    return int((s == s[lo]).sum()), bool(s[lo + 1] == s[lo]), left
+
+
+@pytest.mark.parametrize("name,kw,Q", [
+    ("radix passes, then direct ranking", dict(n_rows=3000, m=5, seed=41), 0.05),
+    ("the same with excluded rows", dict(n_rows=3000, m=5, seed=42, interleave=True), 0.05),
+    ("exactly 1024 candidates", dict(n_rows=4096, m=5, seed=43, dup=1024), 0.05),
+    ("1025 tied candidates", dict(n_rows=4100, m=5, seed=43, dup=1025), 0.05),
+    ("the upper statistic tied", dict(n_rows=2200, m=5, seed=44, dup=1100), 0.05),
+    ("the upper statistic the smallest above", dict(n_rows=6000, m=5, seed=45, dup=1500), 0.25),
+])
+def test_the_shared_selection_past_one_pass_and_at_large_ties(oracle, name, kw, Q):
+    """sfi_cut_kernel's order statistics come from radix_select / next_order_stat (csrc/dsq_select.hpp): the smallest shapes at
+    which those take paths the cases above do not -- a real histogram pass in front of the direct ranking, with and without
+    sentinel entries; a tie block of exactly kSelDirect candidates (ranked directly) and of one more (never: every digit
+    runs, the result is the prefix); the next order statistic inside a block of more than kSelDirect ties and just above one.
+    Each case first proves from the specification that it is in its regime."""
+    c = CS.solve_case(**kw)
+    if name == "the same with excluded rows":
+        assert c["rows"].size == 5000
+    ties, next_tied, left = _selection_regime(oracle, c, Q)
+    direct = [k for k, v in enumerate(left[:-1]) if v <= SEL_DIRECT]           # (the last digit never hands over)
+    if name in ("radix passes, then direct ranking", "the same with excluded rows"):
+        assert left[0] > SEL_DIRECT and direct and ties <= 2
+    elif name == "exactly 1024 candidates":
+        assert ties == 1024 and direct and left[direct[0]] == 1024
+    elif name == "1025 tied candidates":
+        assert ties == 1025 and not direct
+    elif name == "the upper statistic tied":
+        assert ties == 1100 and next_tied
+    else:
+        assert ties == 1500 and not next_tied
+    want = S.solve(oracle, maxit=3, Q=Q, **c)
+    _same(_dev(c, Q=Q, maxit=3), want, name)
+
+
 def test_a_second_stream_padding_maxit_and_q(oracle):
     import torch
     c = CS.solve_case(n_rows=97, m=5, seed=400, interleave=True)
