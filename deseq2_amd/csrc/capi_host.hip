@@ -663,7 +663,9 @@ int dsq_replace_outliers(const DsqReplaceArgs *a, const DsqReplaceOut *o) {
 int dsq_test_math(int op, const double *a, const double *b, const double *c, double *out, int64_t n) {
     std::lock_guard<std::mutex> lk(g_mu);
     WsScope ws(nullptr);
-    if (!a || !out || n < 0 || ((op == 7 || op == 8 || op == 10 || op == 11) && !b) || (op == 8 && !c)) return capi_fail(DSQ_ERR_ARG, "bad arguments");
+    const bool need_b = op == 7 || op == 8 || op == 10 || op == 11 || op == 15 || op == 17 || op == 22;
+    const bool need_c = op == 8 || op == 22;
+    if (!a || !out || n < 0 || (need_b && !b) || (need_c && !c)) return capi_fail(DSQ_ERR_ARG, "bad arguments");
     DSQ_TRY(capi_check_device());
     if (n == 0) return DSQ_OK;
     hipStream_t st = nullptr;

@@ -7,7 +7,13 @@
 // atanh-series log/log1p, Stirling + upward-shift lgamma/digamma/trigamma, and the
 // Loader saddle-point NB density (stirlerr / bd0) that R's dnbinom_mu uses.
 // Every rounding is explicit: compile with -ffp-contract=off; fma only where written.
-// tests/test_gpu_math.py compares these bit-for-bit with the CPU oracle.
+// tests/test_gpu_math.py compares these bit-for-bit with the CPU oracle, each entry point on its own through the hook
+// dsq_test_math (util.hip): dexp, dlog / dlog_full / dlog_pn, dlog1p, dlgamma, ddigamma, dtrigamma, dlgamma_digamma (both
+// outputs), dstirlerr / dstirlerr_n, dbd0 in both division forms, dnbinom_mu_log in every regime, dpnorm_upper2 /
+// dpnorm_lower / dpnorm_upper, the closed split (nb_split_fast + cell_dev_closed + nb_split_const + nb_split_var) and
+// sf_log / sf_exp; drcp_n / ddiv_n against IEEE division; order_key / order_unkey by their properties -- on random
+// arguments, on the nextafter neighbours of every threshold below and, where a branch is taken once per wave, in both
+// kinds of wave (tests/math_cases.py).  dpt_upper / dpt_lower: tests/test_gpu_student_t.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -94,6 +100,14 @@ DSQ_DEV double dexp(double x) {
 // the residual fma(-x, q0, a), the correction fma(res, r, q0) -- WITHOUT the range scaling around it (v_div_scale x 2,
 // v_div_fmas, v_div_fixup: no-ops when nothing needs scaling).  Same operations on the same values, so the same
 // correctly rounded quotient as `a / x` (and as the CPU checker's division), at 7 instead of 11 instructions.
+// Held to IEEE division bit for bit (tests/test_gpu_math.py: test_div_n_and_rcp_n_are_ieee_division) over divisors of
+// both signs with |x| in [1e-200, 1e200], numerators +0 or |a| >= 1e-250 and quotients in [1e-250, 1e250] -- wider than
+// any call site (n p down to 1e-180, x / (n p) up to 1e240) --, quotients a relative 2^-107 from a rounding midpoint
+// among them; no operand in that range was found to differ.  The one limit found: a numerator of -0 comes back as +0
+// whatever the divisor's sign (the residual of a zero is +0 and the closing fma adds it to q0 = -0; it is v_div_fixup
+// that restores the sign), where IEEE division gives -0 over a positive divisor.  No caller forms a -0 numerator: f of
+// log_core is m - 1 (+0 when m = 1) or an |x| >= 2^-53, x - np is +0 when the two are equal, every other numerator is
+// a nonzero constant, count, size or mean.
 DSQ_DEV double drcp_n(double x) {
     double r = __builtin_amdgcn_rcp(x);
     double e = __builtin_fma(-x, r, 1.0);

@@ -97,10 +97,14 @@ hipError_t launch_transpose_gm_to_r_i32(const int32_t *src, int32_t *dst, int n,
 }
 
 // ---- device math test hook -------------------------------------------------------
+// Thread i evaluates element i and nothing else: blocks of 256 = 4 waves of 64, so wave w of the launch holds the elements
+// [64 w, 64 w + 64) and the lanes past n of the last wave are inactive.  The wave-uniform branches of dsq_math.hpp
+// (__any over the active lanes) therefore see exactly the aligned 64-blocks of the input; the wave layouts of
+// tests/math_cases.py are built on that, so keep the mapping linear.
 __global__ void test_math_kernel(int op, const double *a, const double *b, const double *c, double *out, long n) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    double x = a[i], r;
+    double x = a[i], r, r2;
     switch (op) {
     case 0: r = dexp(x); break;
     case 1: r = dlog(x); break;
@@ -114,6 +118,34 @@ __global__ void test_math_kernel(int op, const double *a, const double *b, const
     case 9: r = dpnorm_upper2(x); break;
     case 10: r = dpt_upper(x, b[i]); break;
     case 11: r = dpt_lower(x, b[i]); break;
+    // the variants the kernels call (tests/test_gpu_math.py: each against a reference that is not the code under test)
+    case 12: r = dlog_full(x); break;
+    case 13: r = dlog_pn(x); break;                   // positive normal finite arguments only
+    case 14: r = drcp_n(x); break;
+    case 15: r = ddiv_n(x, b[i]); break;
+    case 16: r = dstirlerr_n(x); break;               // 0 < x < 1e100
+    case 17: r = dbd0(x, b[i], true); break;
+    case 18: dlgamma_digamma(x, r, r2); break;
+    case 19: dlgamma_digamma(x, r2, r); break;
+    case 20: r = dpnorm_lower(x); break;
+    case 21: r = dpnorm_upper(x); break;
+    case 22: {   // one sample of nbinomLogLike: a = y, b = alpha, c = mu; K' as loglike_constants, the sweep as loglike_kernel (aux.hip)
+        const double alpha = b[i], size = 1.0 / alpha;
+        const bool fast = nb_split_fast(alpha, size);
+        double kp = 0.0;
+        if (fast && x != 0.0 && cell_dev_closed(x, size, fast)) {
+            double base, t;
+            nb_split_const(x, alpha, size, dstirlerr(size), base, t);
+            kp = base + t;
+        }
+        const double d = nb_split_var(x, size, alpha, c[i], fast);
+        r = (fast ? 0.0 + kp : 0.0) + (0.0 + d);
+        break;
+    }
+    case 23: r = sf_log(x); break;
+    case 24: r = sf_exp(x); break;
+    case 25: r = bits2d(order_key(x)); break;         // the key's 64 bits, carried in the double buffer
+    case 26: r = order_unkey(order_key(x)); break;
     default: r = dnan();
     }
     out[i] = r;

@@ -613,6 +613,10 @@ def test_math(op, a, b=None, c=None):
 
 
 UNARY_OPS = {"exp": 0, "log": 1, "log1p": 2, "lgamma": 3, "digamma": 4, "trigamma": 5, "stirlerr": 6, "pnorm_upper2": 9}
+# every op of the hook by name (include/deseq2_mi355x.h: dsq_test_math); 12 and up are the variants the kernels call
+MATH_OPS = dict(UNARY_OPS, bd0=7, dnbinom_mu_log=8, pt_upper=10, pt_lower=11, log_full=12, log_pn=13, rcp_n=14, div_n=15,
+                stirlerr_n=16, bd0_fast=17, lgamma_pair_lg=18, lgamma_pair_dg=19, pnorm_lower=20, pnorm_upper=21, nb_split=22,
+                sf_log=23, sf_exp=24, order_key=25, order_roundtrip=26)
 
 
 def unary(name, x):

@@ -402,7 +402,12 @@ double dsq_profile_last_ms(void);
 
 /* Parity hook for tests: evaluate one scalar primitive of the device math library on
  * the GPU (op: 0 exp, 1 log, 2 log1p, 3 lgamma, 4 digamma, 5 trigamma, 6 stirlerr,
- * 7 bd0(a,b), 8 dnbinom_mu_log(a=x, b=size, c=mu), 9 2 pnorm(-|a|), 10 pt(a, df = b, lower.tail = FALSE), 11 pt(a, df = b)).
+ * 7 bd0(a,b), 8 dnbinom_mu_log(a=x, b=size, c=mu), 9 2 pnorm(-|a|), 10 pt(a, df = b, lower.tail = FALSE), 11 pt(a, df = b);
+ * the variants the kernels call: 12 log_full, 13 log_pn (positive normal a), 14 rcp_n, 15 div_n(a, b) = a / b, 16 stirlerr_n
+ * (0 < a < 1e100), 17 bd0_fast(a, b), 18 / 19 the lgamma / digamma output of the paired routine, 20 pnorm(a), 21 pnorm(a,
+ * lower.tail = FALSE), 22 nb_split(a = y, b = alpha, c = mu): one sample of nbinomLogLike on the closed split, 23 sf_log,
+ * 24 sf_exp, 25 order_key (the key's 64 bits in the double), 26 order_unkey(order_key(a))).  Ops 7, 8, 10, 11, 15, 17, 22
+ * need b; 8 and 22 need c.  Element i is evaluated by thread i: wave w of the launch holds elements [64 w, 64 w + 64).
  * HOST pointers, n elements.                                                              */
 int dsq_test_math(int op, const double *a, const double *b, const double *c, double *out, int64_t n);
 

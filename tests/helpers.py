@@ -60,6 +60,19 @@ def make_case(n, m, design, seed=1, weights=False, sf_random=False, **kw):
     return d
 
 
+def assert_bits(a, b, what):
+    """the same 64 bits in every float64 entry -- the sign of a zero included, which assert_same lets pass; where both
+    sides are NaN any payload is accepted"""
+    a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
+    assert a.shape == b.shape, "%s: shape %s vs %s" % (what, a.shape, b.shape)
+    ok = (a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))
+    if not ok.all():
+        bad = np.argwhere(~ok)
+        i = tuple(bad[0])
+        raise AssertionError("%s: %d of %d entries differ in bits; first at %s: %r (%s) vs %r (%s)" %
+                             (what, bad.shape[0], a.size, i, a[i], a[i].hex(), b[i], b[i].hex()))
+
+
 def assert_same(a, b, what, exact=True, rtol=1e-6):
     """bit-for-bit (NaN == NaN, -0 == +0) when exact, else north_star's 1e-6 relative"""
     a = np.asarray(a); b = np.asarray(b)

@@ -317,7 +317,7 @@ def _argument_cases():
             k.get("means", P(v)), P(v), k.get("n", 8), k.get("coefs", P(v)), P(i4)),
         "dsq_parametric_dispersion_fit_dev": lambda **k: L.dsq_parametric_dispersion_fit_dev(
             k.get("means", P(v)), P(v), k.get("n", 8), k.get("coefs", P(v)), P(i4), None),
-        "dsq_test_math": lambda **k: L.dsq_test_math(k.get("op", 0), k.get("means", P(v)), None, None, k.get("coefs", P(v)),
+        "dsq_test_math": lambda **k: L.dsq_test_math(k.get("op", 0), k.get("means", P(v)), k.get("b"), None, k.get("coefs", P(v)),
                                                      k.get("n", 8)),
     }
     for ename, f in plain.items():
@@ -327,6 +327,10 @@ def _argument_cases():
     cases.append(("dsq_parametric_dispersion_fit: n = 0", lambda: plain["dsq_parametric_dispersion_fit"](n=0)))
     cases.append(("dsq_parametric_dispersion_fit_dev: n = 0", lambda: plain["dsq_parametric_dispersion_fit_dev"](n=0)))
     cases.append(("dsq_test_math: op 7 without b", lambda: plain["dsq_test_math"](op=7)))
+    for op in (8, 10, 11, 15, 17, 22):
+        cases.append(("dsq_test_math: op %d without b" % op, lambda op=op: plain["dsq_test_math"](op=op)))
+    for op in (8, 22):
+        cases.append(("dsq_test_math: op %d with b, without c" % op, lambda op=op: plain["dsq_test_math"](op=op, b=P(v))))
     return cases
 
 
@@ -760,6 +764,12 @@ _CHANGED_CODES = {
 }
 
 
+# The math hook's ops that read b or c refuse a call without them (the ops from 12 up came with the hook's extension to the
+# entry points the kernels call; an op that reads a alone is not listed: it gets past the checks and needs a device).
+_MATH_HOOK_CODES = dict([("dsq_test_math: op %d without b" % op, 1) for op in (8, 10, 11, 15, 17, 22)] +
+                        [("dsq_test_math: op %d with b, without c" % op, 1) for op in (8, 22)])
+
+
 def _changed_cases():
     from deseq2_amd import _lib
     from tests import capi_blocks as cb
@@ -792,7 +802,8 @@ def test_argument_errors_are_pinned():
     assert len(_ARGUMENT_CODES) > 200
     cases.update(_changed_cases())
     wrong = []
-    for cid, want in {**_ARGUMENT_CODES, **_CHANGED_CODES}.items():
+    assert set(_MATH_HOOK_CODES) <= set(cases)
+    for cid, want in {**_ARGUMENT_CODES, **_CHANGED_CODES, **_MATH_HOOK_CODES}.items():
         # dsq_last_error() keeps the last text: leave a known one behind first, so that an entry which fails without
         # writing its own message is seen
         assert L.dsq_test_math(0, None, None, None, None, 0) == 1
