@@ -10,8 +10,9 @@ from .core import (vst, varianceStabilizingTransformation, getVarianceStabilized
 from .core import results, resultsContrasts, resultsNames, DESeqResults, p_adjust, pvalueAdjustment, lowess  # noqa: F401
 from .core import pt  # noqa: F401
 from .core import unmix  # noqa: F401
+from .core import rowVars, sampleDists, pca, plotPCA, PCAData  # noqa: F401
 
 __all__ = ["fitBeta", "fitDisp", "fitDispGrid", "estimateSizeFactors", "estimateSizeFactorsForMatrix", "vst",
            "varianceStabilizingTransformation", "getVarianceStabilizedData", "normTransform", "normalized_counts",
            "DESeqTransform", "results", "resultsContrasts", "resultsNames", "DESeqResults", "p_adjust", "pvalueAdjustment", "lowess",
-           "pt", "unmix"]
+           "pt", "unmix", "rowVars", "sampleDists", "pca", "plotPCA", "PCAData"]

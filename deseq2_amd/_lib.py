@@ -286,6 +286,29 @@ class DsqSfIterateOut(C.Structure):
                 ("flag", C.c_void_p)]
 
 
+class DsqTopVarArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("m", C.c_int32), ("ld", C.c_int64), ("x", C.c_void_p),
+                ("ntop", C.c_int32)]
+
+
+class DsqTopVarOut(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("rowMean", C.c_void_p), ("rowVar", C.c_void_p), ("select", C.c_void_p)]
+
+
+class DsqSamplePairsArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("m", C.c_int32), ("ld", C.c_int64), ("x", C.c_void_p),
+                ("kind", C.c_int32), ("nrows", C.c_int32), ("rows", C.c_void_p), ("centre", C.c_void_p)]
+
+
+class DsqSamplePairsOut(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("out", C.c_void_p)]
+
+
+def sized(cls, **kw):
+    """an argument block that carries its own size in struct_size"""
+    return cls(struct_size=C.sizeof(cls), **kw)
+
+
 class DsqResultsArgs(C.Structure):
     _fields_ = [
         ("n", C.c_int32), ("p", C.c_int32), ("c", C.c_int32), ("test", C.c_int32), ("beta", C.c_void_p),
@@ -325,6 +348,7 @@ DSQ_VST = {"parametric": 0, "mean": 1, "spline": 2, "log2": 3, "normalized": 4}
 DSQ_VST_MAX_KNOTS = 1600
 DSQ_UNMIX_MAX_K = 16
 DSQ_SF = {"ratio": 0, "poscounts": 1}
+DSQ_PAIRS = {"dist2": 0, "dist": 1, "gram": 2}
 DSQ_PH_GENE_EST, DSQ_PH_TREND, DSQ_PH_MAP_TEST, DSQ_PH_OUTLIERS, DSQ_PH_FINISH, DSQ_PH_PRIOR = 1, 2, 4, 8, 16, 32
 DSQ_PH_OUTLIERS_DETECT, DSQ_PH_OUTLIERS_REFIT = 64, 128
 DSQ_ST = {k: i for i, k in enumerate((
@@ -355,6 +379,8 @@ EXPORTED_SYMBOLS = [
     "dsq_rlog", "dsq_rlog_dev",
     "dsq_unmix", "dsq_unmix_dev", "dsq_unmix_workspace_bytes", "dsq_unmix_block_threads",
     "dsq_sf_iterate", "dsq_sf_iterate_dev", "dsq_sf_iterate_workspace_bytes", "dsq_sf_iterate_slice_genes",
+    "dsq_top_var", "dsq_top_var_dev", "dsq_sample_pairs", "dsq_sample_pairs_dev", "dsq_sample_pairs_slice_rows",
+    "dsq_row_vars_register_width",
     "dsq_results", "dsq_results_dev", "dsq_results_workspace_bytes",
     "dsq_contrasts", "dsq_contrasts_dev", "dsq_contrasts_max_m",
     "dsq_pt", "dsq_pt_dev",
@@ -446,6 +472,14 @@ def lib():
     L.dsq_sf_iterate_workspace_bytes.restype = C.c_int64
     L.dsq_sf_iterate_slice_genes.argtypes = []
     L.dsq_sf_iterate_slice_genes.restype = C.c_int32
+    L.dsq_top_var.argtypes = [C.POINTER(DsqTopVarArgs), C.POINTER(DsqTopVarOut)]
+    L.dsq_top_var_dev.argtypes = [C.POINTER(DsqTopVarArgs), C.POINTER(DsqTopVarOut), C.c_void_p]
+    L.dsq_sample_pairs.argtypes = [C.POINTER(DsqSamplePairsArgs), C.POINTER(DsqSamplePairsOut)]
+    L.dsq_sample_pairs_dev.argtypes = [C.POINTER(DsqSamplePairsArgs), C.POINTER(DsqSamplePairsOut), C.c_void_p]
+    L.dsq_sample_pairs_slice_rows.argtypes = [C.c_int64, C.c_int32]
+    L.dsq_sample_pairs_slice_rows.restype = C.c_int64
+    L.dsq_row_vars_register_width.argtypes = []
+    L.dsq_row_vars_register_width.restype = C.c_int32
     L.dsq_results.argtypes = [C.POINTER(DsqResultsArgs), C.POINTER(DsqResultsOut)]
     L.dsq_results_dev.argtypes = [C.POINTER(DsqResultsArgs), C.POINTER(DsqResultsOut), C.c_void_p]
     L.dsq_results_workspace_bytes.argtypes = [C.c_int32, C.c_int32]

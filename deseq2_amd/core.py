@@ -2534,3 +2534,91 @@ def unmix(x, pure, alpha=None, shift=None, power=1, format="matrix", quiet=False
         for i in range(xh.shape[1]):                                                 # diag(cor(., .)), :124-129
             cor[i] = np.corrcoef(v(xh[:, i]), v(fitted[:, i]))[0, 1]
     return {"mix": mix, "cor": cor, "fitted": _named(fitted, None, xnames)}
+
+
+# ------------------------------------------------------------------ R/plots.R:239-291, dist(t(assay(vsd)))
+PLOTPCA_INTGROUP_STOP = "the argument 'intgroup' should specify columns of colData(dds)"
+
+
+class PCAData(dict):
+    """plotPCA(returnData = TRUE): the columns of R's data frame in its order, by name -- "PC<a>", "PC<b>", "group", the
+    intgroup columns, "name" --; attrs["percentVar"] is attr(d, "percentVar")"""
+
+    def __init__(self, columns, percentVar):
+        super().__init__(columns)
+        self.attrs = {"percentVar": percentVar}
+
+
+def _transform_of(obj, what):
+    if not isinstance(obj, DESeqTransform):
+        raise TypeError("%s takes what vst(), rlog(), normTransform() or normalized_counts() return" % what)
+    return obj.engine, obj.handle
+
+
+def rowVars(obj):
+    """matrixStats::rowVars(assay(obj)) of a transform (R/plots.R:245): the n variances on the host; the matrix stays where
+    the engine keeps it (csrc/explore.hip on the device)"""
+    E, h = _transform_of(obj, "rowVars")
+    return E.row_vars(h)[1]
+
+
+def sampleDists(obj):
+    """as.matrix(dist(t(assay(obj)))), method "euclidean": the m x m sample-to-sample distances on the host, from the
+    engine's all-pairs sums over every gene (csrc/explore.hip on the device).  dist's rescaling of
+    sums with NA terms is not mirrored: a NaN in a sample gives NaN against every other sample."""
+    E, h = _transform_of(obj, "sampleDists")
+    return E.pair_sums(h, "dist")
+
+
+def pca(obj, ntop=500):
+    """prcomp(t(assay(obj)[select, ])) with select = order(rowVars, decreasing = TRUE)[seq_len(min(ntop, n))]
+    (R/plots.R:245-254): dict(select (0-based), sdev, x (m x min(m, k) scores), percentVar).  The variances, the order and
+    the m x m Gram matrix of the centred selection are the engine's; LAPACK's symmetric eigen-solver on the host turns the
+    Gram matrix into the components, on the sample side whatever k is.  The sign of a component (arbitrary in R) is fixed:
+    its score of largest magnitude is positive.  A selected row with a non-finite variance stops as prcomp does."""
+    from . import explore_host
+    E, h = _transform_of(obj, "pca")
+    if int(ntop) < 1:
+        raise ValueError("ntop should be at least 1")
+    tv = E.top_var(h, int(ntop))
+    if not np.isfinite(tv["selVar"]).all():
+        raise ValueError(explore_host.PRCOMP_STOP)
+    G = E.pair_sums(h, "gram", rows=tv["rows"], centre=tv["centre"])
+    out = {"select": tv["select"]}
+    out.update(explore_host.pca_from_gram(G, len(tv["select"])))
+    return out
+
+
+def plotPCA(obj, intgroup="condition", ntop=500, returnData=True, pcsToUse=(1, 2)):
+    """R/plots.R:239-291 with returnData = TRUE: the data frame behind the plot as a PCAData.  intgroup names entries of
+    attrs["factors"] of the transform or of the object it came from (level codes per sample); group is the factor itself,
+    or the levels pasted with ":" when more than one is given; name: attrs["colnames"] when present, else "sample1" ...
+    There is no plotting layer: returnData = False is not served."""
+    import sys
+    print("using ntop=%s top features by variance" % _rnum(ntop), file=sys.stderr)                    # :242
+    E, h = _transform_of(obj, "plotPCA")
+    pcs = [int(v) for v in np.atleast_1d(pcsToUse)]
+    if len(pcs) != 2:
+        raise ValueError("pcsToUse should name two components")
+    p = pca(obj, ntop=ntop)                                                                          # :245-254
+    intgroup = [intgroup] if isinstance(intgroup, str) else list(intgroup)
+    factors = obj.attrs.get("factors") or obj.dds.attrs.get("factors") or {}
+    if not all(g in factors for g in intgroup):                                                      # :256-258
+        raise ValueError(PLOTPCA_INTGROUP_STOP)
+    r = p["x"].shape[1]
+    if min(pcs) < 1 or max(pcs) > r:
+        raise ValueError("pcsToUse should lie within 1 .. %d" % r)
+    m = p["x"].shape[0]
+    cols = {g: np.asarray(factors[g]) for g in intgroup}                                             # :260
+    if len(intgroup) > 1:                                                                            # :263-267
+        group = np.array([":".join(str(cols[g][j]) for g in intgroup) for j in range(m)])
+    else:
+        group = cols[intgroup[0]]
+    names = obj.attrs.get("colnames") or obj.dds.attrs.get("colnames") or ["sample%d" % (j + 1) for j in range(m)]
+    d = {"PC%d" % pcs[0]: p["x"][:, pcs[0] - 1].copy(), "PC%d" % pcs[1]: p["x"][:, pcs[1] - 1].copy(), "group": group}
+    d.update(cols)
+    d["name"] = list(names)
+    out = PCAData(d, p["percentVar"][[pcs[0] - 1, pcs[1] - 1]])                                      # :270-278
+    if not returnData:
+        raise NotImplementedError("plotPCA: there is no plotting layer; returnData = True returns the data frame")
+    return out

@@ -848,6 +848,76 @@ int unmix_dev_locked(const DsqUnmixArgs *a, const DsqUnmixOut *o, void *workspac
     return DSQ_OK;
 }
 
+// sample PCA / sample distances (explore.hip): what both entries check before anything is launched
+int top_var_check(const DsqTopVarArgs *a, const DsqTopVarOut *o) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->struct_size != sizeof *a || o->struct_size != sizeof *o) return capi_fail(DSQ_ERR_ARG, "struct_size is not sizeof the block");
+    if (a->n < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
+    if (a->m < 2) return capi_fail(DSQ_ERR_ARG, "m = %d samples: a variance needs at least two", a->m);
+    if (a->ntop < 0) return capi_fail(DSQ_ERR_ARG, "ntop = %d is negative", a->ntop);
+    if (!a->x) return capi_fail(DSQ_ERR_ARG, "NULL x");
+    if (!o->rowMean || !o->rowVar || (a->ntop > 0 && !o->select)) return capi_fail(DSQ_ERR_ARG, "NULL output array");
+    return DSQ_OK;
+}
+
+int top_var_dev_locked(const DsqTopVarArgs *a, const DsqTopVarOut *o, hipStream_t st) {
+    if (int rc = top_var_check(a, o)) return rc;
+    if (a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld = %ld < m = %d", (long)a->ld, a->m);
+    if (int rc = capi_check_device()) return rc;
+    RowVarsKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.m = a->m; kp.ld = (long)a->ld; kp.x = a->x;
+    kp.rowMean = o->rowMean; kp.rowVar = o->rowVar;
+    capi_prof_begin("top_var", a->n, st);
+    DSQ_HIP(launch_row_vars(kp, st));
+    const int k = a->ntop < a->n ? a->ntop : a->n;
+    if (k > 0) {
+        void *w;
+        if (int rc = capi_ws_get(WS_SCRATCH, top_var_workspace_bytes(a->n), &w)) return rc;
+        DSQ_HIP(launch_top_var_order(o->rowVar, a->n, k, o->select, w, st));
+    }
+    capi_prof_end(st);
+    return DSQ_OK;
+}
+
+int sample_pairs_check(const DsqSamplePairsArgs *a, const DsqSamplePairsOut *o) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->struct_size != sizeof *a || o->struct_size != sizeof *o) return capi_fail(DSQ_ERR_ARG, "struct_size is not sizeof the block");
+    if (a->n < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
+    if (a->m < 2) return capi_fail(DSQ_ERR_ARG, "m = %d samples: pairs need at least two", a->m);
+    if (a->kind != DSQ_PAIRS_DIST2 && a->kind != DSQ_PAIRS_DIST && a->kind != DSQ_PAIRS_GRAM) return capi_fail(DSQ_ERR_ARG, "unknown kind %d", a->kind);
+    if (!a->x) return capi_fail(DSQ_ERR_ARG, "NULL x");
+    if (a->rows ? a->nrows < 1 : (a->nrows != 0 && a->nrows != a->n))
+        return capi_fail(DSQ_ERR_ARG, "nrows = %d: %s", a->nrows, a->rows ? "a row list has at least one entry" : "0 or n without a row list");
+    if (!o->out) return capi_fail(DSQ_ERR_ARG, "NULL output array");
+    return DSQ_OK;
+}
+
+int sample_pairs_dev_locked(const DsqSamplePairsArgs *a, const DsqSamplePairsOut *o, hipStream_t st) {
+    if (int rc = sample_pairs_check(a, o)) return rc;
+    if (a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld = %ld < m = %d", (long)a->ld, a->m);
+    if (int rc = capi_check_device()) return rc;
+    PairKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.m = a->m; kp.ld = (long)a->ld; kp.x = a->x;
+    kp.kind = a->kind == DSQ_PAIRS_GRAM ? PAIR_GRAM : PAIR_DIST2;
+    kp.root = a->kind == DSQ_PAIRS_DIST ? 1 : 0;
+    kp.R = a->rows ? a->nrows : a->n;
+    kp.rows = a->rows;
+    kp.centre = a->kind == DSQ_PAIRS_GRAM ? a->centre : nullptr;
+    PairSlices ps;
+    pair_slices(kp.R, kp.m, &ps);
+    kp.nb = ps.nb; kp.ntiles = ps.ntiles; kp.L = ps.L; kp.S = ps.S;
+    void *w;
+    if (int rc = capi_ws_get(WS_SCRATCH, pair_workspace_bytes(kp.R, kp.m), &w)) return rc;
+    kp.partial = (double *)w;
+    kp.out = o->out;
+    capi_prof_begin("sample_pairs", a->m, st);
+    DSQ_HIP(launch_pair_sums(kp, st));
+    capi_prof_end(st);
+    return DSQ_OK;
+}
+
 // the solve of estimateSizeFactors(type = "iterate") (sf_iterate.hip): what both entries check before anything is launched
 int sf_iterate_check(const DsqSfIterateArgs *a, const DsqSfIterateOut *o) {
     if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
@@ -1022,6 +1092,8 @@ DSQ_DEV(dsq_vst_rowstats_dev, DsqVstArgs, const DsqVstOut *, vst_dev_locked(a, o
 DSQ_DEV(dsq_rlog_dev, DsqRlogArgs, const DsqRlogOut *, rlog_dev_locked(a, o, st))
 DSQ_DEV(dsq_results_dev, DsqResultsArgs, const DsqResultsOut *, results_dev_locked(a, o, st))
 DSQ_DEV(dsq_contrasts_dev, DsqContrastsArgs, const DsqContrastsOut *, contrasts_dev_locked(a, o, st))
+DSQ_DEV(dsq_top_var_dev, DsqTopVarArgs, const DsqTopVarOut *, top_var_dev_locked(a, o, st))
+DSQ_DEV(dsq_sample_pairs_dev, DsqSamplePairsArgs, const DsqSamplePairsOut *, sample_pairs_dev_locked(a, o, st))
 #undef DSQ_DEV
 int dsq_linear_mu_dev(const DsqPrefitArgs *a, double mu_floor, double *mu, void *s) {
     return dev_entry(s, [&](hipStream_t st) { return linear_mu_dev_locked(a, mu_floor, mu, st); });
@@ -1057,6 +1129,14 @@ int64_t dsq_sf_iterate_workspace_bytes(int32_t n, int32_t m) {
     return (int64_t)sf_iterate_workspace_bytes(n, m);
 }
 int32_t dsq_sf_iterate_slice_genes(void) { return kSfIterSliceGenes; }
+
+int64_t dsq_sample_pairs_slice_rows(int64_t rows_summed, int32_t m) {
+    if (rows_summed < 1 || m < 1) return 0;
+    PairSlices ps;
+    pair_slices((long)rows_summed, m, &ps);
+    return (int64_t)ps.L;
+}
+int32_t dsq_row_vars_register_width(void) { return row_vars_register_width(); }
 
 int64_t dsq_size_factors_workspace_bytes(int32_t n, int32_t m) {
     if (n < 0 || m < 0) return 0;

@@ -849,6 +849,51 @@ int dsq_unmix(const DsqUnmixArgs *a, const DsqUnmixOut *o) {
     return s.finish();
 }
 
+int dsq_top_var(const DsqTopVarArgs *a, const DsqTopVarOut *o) {
+    HostCall hc;
+    DSQ_TRY(host_ready(top_var_check(a, o), DSQ_LAYOUT_R));
+    hipStream_t st = hc.st;
+    const long ld = round_ld(a->m);
+    const size_t k = a->ntop < a->n ? a->ntop : a->n;
+    DsqTopVarArgs d = *a;
+    DsqTopVarOut od = *o;
+    Stage s(st, a->n);
+    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->x, 8, a->n, a->m, ld, &d.x));
+    d.ld = ld;
+    s.out_gene_vec(&od.rowMean, o->rowMean);
+    s.out_gene_vec(&od.rowVar, o->rowVar);
+    if (k) s.out_vec(&od.select, o->select, k * 4);
+    DSQ_TRY(s.pack_out());
+    DSQ_TRY(top_var_dev_locked(&d, &od, st));
+    return s.finish();
+}
+
+int dsq_sample_pairs(const DsqSamplePairsArgs *a, const DsqSamplePairsOut *o) {
+    const auto check = [&]() -> int {
+        if (int rc = sample_pairs_check(a, o)) return rc;
+        for (int t = 0; a->rows && t < a->nrows; t++)
+            if (a->rows[t] < 0 || a->rows[t] >= a->n) return capi_fail(DSQ_ERR_ARG, "rows[%d] = %d is outside [0, %d)", t, a->rows[t], a->n);
+        return DSQ_OK;
+    };
+    HostCall hc;
+    DSQ_TRY(host_ready(check(), DSQ_LAYOUT_R));
+    hipStream_t st = hc.st;
+    const long ld = round_ld(a->m);
+    const size_t m = a->m, R = a->rows ? a->nrows : a->n;
+    DsqSamplePairsArgs d = *a;
+    DsqSamplePairsOut od = *o;
+    Stage s(st, a->n);
+    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->x, 8, a->n, a->m, ld, &d.x));
+    d.ld = ld;
+    if (a->rows) s.vec(&d.rows, a->rows, R * 4);
+    if (a->kind == DSQ_PAIRS_GRAM && a->centre) s.vec(&d.centre, a->centre, R * 8);
+    DSQ_TRY(s.pack_in());
+    s.out_vec(&od.out, o->out, m * m * 8);
+    DSQ_TRY(s.pack_out());
+    DSQ_TRY(sample_pairs_dev_locked(&d, &od, st));
+    return s.finish();
+}
+
 int dsq_sf_iterate(const DsqSfIterateArgs *a, const DsqSfIterateOut *o) {
     const auto check = [&]() -> int {
         if (int rc = sf_iterate_check(a, o)) return rc;

@@ -336,6 +336,44 @@ void radix_sort_columns(unsigned long long *keyA, unsigned long long *keyB, unsi
                         unsigned int *hist, unsigned int *const_digit, int n, int ncols, hipStream_t st);
 size_t sort_hist_entries(long n);                // 256 x the tiles of one column
 
+// sample-level exploration of a resident transform (explore.hip): x gene-major, element (g, i) at
+// [g * ld + i], read only.
+struct RowVarsKernelParams {
+    int n, m;
+    long ld;
+    const double *x;
+    double *rowMean, *rowVar;    // n each
+};
+int row_vars_register_width();                   // rows of up to this many samples are read once (else swept twice)
+hipError_t launch_row_vars(const RowVarsKernelParams &kp, hipStream_t st);
+// the first k entries of order(rowVar, decreasing = TRUE) -- ties and NaNs by ascending row, NaNs last -- into select
+size_t top_var_workspace_bytes(long n);
+hipError_t launch_top_var_order(const double *rowVar, int n, int k, int32_t *select, void *workspace, hipStream_t st);
+// The all-pairs sums over R rows of the m samples.  The summation order is a function of (R, m) alone: the rows are cut into
+// S slices of L consecutive rows (the last one shorter), L = max(kPairMinSlice, ceil(R / max(1, kPairWork / tiles))) with
+// tiles = nb (nb + 1) / 2, nb = ceil(m / kPairTile); a slice is summed in row order from +0.0, the slice partials are added in
+// slice order.  So one tile of pairs is cut into up to kPairWork slices (a small m fills the device) and the partials take
+// at most max(kPairWork, tiles) tiles of 32 KiB.
+constexpr int kPairTile = 64, kPairMinSlice = 64, kPairWork = 2048;
+enum { PAIR_DIST2 = 0, PAIR_GRAM = 1 };
+struct PairSlices { int nb; long ntiles, L, S; };
+void pair_slices(long R, int m, PairSlices *ps);
+size_t pair_workspace_bytes(long R, int m);
+struct PairKernelParams {
+    int n, m;
+    long ld;
+    const double *x;
+    int kind, root;              // PAIR_*; root: the square root of the sums (dist)
+    long R;                      // rows summed
+    const int32_t *rows;         // R row indices, or nullptr: rows 0 .. R - 1
+    const double *centre;        // R values, entry t subtracted from row t of the list (PAIR_GRAM), or nullptr
+    int nb;
+    long ntiles, L, S;           // pair_slices(R, m)
+    double *partial;             // pair_workspace_bytes(R, m)
+    double *out;                 // m x m
+};
+hipError_t launch_pair_sums(const PairKernelParams &kp, hipStream_t st);
+
 // K contrasts from one covariance pass per gene (contrasts.hip).  n x m matrices gene-major with
 // leading dimension ld, n x p / n x K matrices column-major; ncell > 0 selects the cell-collapsed Gram sums (cell_perm,
 // cell_start as in BetaKernelParams); contrasts == nullptr: the all-zero flags only.

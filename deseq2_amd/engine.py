@@ -395,6 +395,27 @@ class HostEngine:
         from . import unmix_host
         return unmix_host.unmix_fit(self.vlog, np.asarray(x, np.float64), pure, alpha=alpha, shift=shift, power=power, maxit=maxit)
 
+    def row_vars(self, x):
+        """(rowMean, rowVar) of an n x m handle (matrixStats::rowVars as documented): the two wave-order sums of
+        csrc/explore.hip stated in numpy (explore_host.py), the same bits"""
+        from . import explore_host
+        return explore_host.row_vars(np.asarray(x, np.float64))
+
+    def top_var(self, x, ntop):
+        """the first min(ntop, n) rows of order(rowVars, decreasing = TRUE) (R/plots.R:245-248).  dict(select: the 0-based
+        rows on the host, selVar: their variances on the host, rows / centre: the list and the means of the listed rows in
+        the form this engine's pair_sums takes)"""
+        from . import explore_host
+        mean, var = self.row_vars(x)
+        sel = explore_host.top_var(var, ntop)
+        return {"select": sel, "selVar": var[sel], "rows": sel, "centre": mean[sel]}
+
+    def pair_sums(self, x, kind, rows=None, centre=None):
+        """the m x m all-pairs sums over the listed rows (all rows when None) of an n x m handle on the host: kind "dist2",
+        "dist" or "gram" (rows less centre, one value per listed row), in the order of csrc/explore.hip (explore_host.py)"""
+        from . import explore_host
+        return explore_host.pair_sums(np.asarray(x, np.float64), kind, rows=rows, centre=centre)
+
     def sf_iterate_solve(self, y, mu, sf, disp, rows, Q=0.05, maxit=100):
         """the solve of one round of estimateSizeFactorsIterate (R/core.R:2600-2611): y / mu n x m handles, sf the m size
         factors mu was fitted with, disp n, rows n flags (rowSums > 0).  The iteration of csrc/sf_iterate.hip stated in numpy
@@ -869,6 +890,42 @@ class DeviceEngine:
                                  r["flag"].to(t.float64)[:, None]], dim=1)).numpy()
         return {"p": pack[:, :k].copy(), "loss": pack[:, k].copy(), "iter": pack[:, k + 1].astype(np.int32),
                 "flag": pack[:, k + 2].astype(np.int32)}
+
+    def _resident(self, x):
+        return x if isinstance(x, self.native.GeneMajor) else self.matrix(x)
+
+    def row_vars(self, x):
+        """(rowMean, rowVar) of a resident n x m float64 handle by row_vars_kernel (csrc/explore.hip, dsq_top_var_dev); the
+        two n-vectors come to the host in one copy"""
+        x = self._resident(x)
+        r = self._timed("top_var", x.n, lambda: self.native.top_var_dev(x, 0))
+        h = self._host(r["_pack"]).numpy()
+        return h[0].copy(), h[1].copy()
+
+    def top_var(self, x, ntop):
+        """the row variances and their top-ntop order on the device (dsq_top_var_dev): the means and variances stay resident;
+        the selection and the variances of the selected rows come to the host in one copy"""
+        t = self.torch
+        x = self._resident(x)
+        r = self._timed("top_var", x.n, lambda: self.native.top_var_dev(x, ntop))
+        sel = r["select"]
+        idx = sel.to(t.int64)
+        pack = self._host(t.stack([idx.to(t.float64), r["rowVar"].index_select(0, idx)])).numpy()
+        return {"select": pack[0].astype(np.int64), "selVar": pack[1].copy(), "rows": sel,
+                "centre": r["rowMean"].index_select(0, idx)}
+
+    def pair_sums(self, x, kind, rows=None, centre=None):
+        """the m x m all-pairs sums of a resident n x m float64 handle by pair_sums_kernel (csrc/explore.hip,
+        dsq_sample_pairs_dev); rows / centre: device tensors as top_var returns them, or host arrays, which go up; the m x m
+        result comes to the host"""
+        t = self.torch
+        x = self._resident(x)
+        if rows is not None and not t.is_tensor(rows):
+            rows = t.as_tensor(np.ascontiguousarray(rows, dtype=np.int32)).to(self.device)
+        if centre is not None and not t.is_tensor(centre):
+            centre = self._vec(centre)
+        out = self._timed("sample_pairs", x.m, lambda: self.native.sample_pairs_dev(x, kind, rows=rows, centre=centre))
+        return self._host(out).numpy().copy()
 
     def sf_iterate_solve(self, y, mu, sf, disp, rows, Q=0.05, maxit=100):
         """the solve of one round of estimateSizeFactorsIterate on the device (csrc/sf_iterate.hip, dsq_sf_iterate_dev) on

@@ -916,6 +916,72 @@ def unmix_dev(x, pure, alpha=None, shift=None, power=1, maxit=200, workspace=Non
     return {"p": p, "loss": loss, "iter": ints[0], "flag": ints[1]}
 
 
+def top_var(x, ntop=500):
+    """dsq_top_var: host matrix in (n x m, R layout); dict(rowMean n, rowVar n, select: the first min(ntop, n) rows of
+    order(rowVar, decreasing = TRUE), 0-based) out"""
+    x = _fcol(x)
+    if x.ndim != 2:
+        raise ValueError("x must be a matrix")
+    n, m = x.shape
+    k = max(0, min(int(ntop), n))
+    mean, var, sel = np.zeros(n), np.zeros(n), np.zeros(max(k, 1), np.int32)
+    a = L.sized(L.DsqTopVarArgs, n=n, m=m, ld=0, x=_ptr(x), ntop=int(ntop))
+    o = L.sized(L.DsqTopVarOut, rowMean=_ptr(mean), rowVar=_ptr(var), select=_ptr(sel))
+    L.check(L.lib().dsq_top_var(C.byref(a), C.byref(o)))
+    return {"rowMean": mean, "rowVar": var, "select": sel[:k].astype(np.int64)}
+
+
+def sample_pairs(x, kind, rows=None, centre=None):
+    """dsq_sample_pairs: host matrix in (n x m, R layout), kind "dist2" / "dist" / "gram", rows: 0-based row list or None
+    (every row), centre: one value per listed row (gram); the m x m matrix out"""
+    x = _fcol(x)
+    if x.ndim != 2:
+        raise ValueError("x must be a matrix")
+    n, m = x.shape
+    rows = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+    centre = None if centre is None else np.ascontiguousarray(centre, dtype=np.float64)
+    if centre is not None and centre.size != (n if rows is None else rows.size):
+        raise ValueError("centre must have one entry per listed row")
+    out = np.zeros((m, m))
+    a = L.sized(L.DsqSamplePairsArgs, n=n, m=m, ld=0, x=_ptr(x), kind=L.DSQ_PAIRS[kind], nrows=0 if rows is None else rows.size,
+                rows=_ptr(rows), centre=_ptr(centre))
+    o = L.sized(L.DsqSamplePairsOut, out=_ptr(out))
+    L.check(L.lib().dsq_sample_pairs(C.byref(a), C.byref(o)))
+    return out
+
+
+def top_var_dev(x, ntop=500):
+    """dsq_top_var_dev on a resident matrix: x a GeneMajor float64 handle.  Returns dict(rowMean, rowVar: (n,) float64
+    tensors (_pack: both as one (2, n) tensor), select: (min(ntop, n),) int32 tensor); nothing is read back."""
+    import torch
+    assert isinstance(x, GeneMajor) and x.t.dtype == torch.float64
+    dev, n = x.t.device, x.n
+    k = max(0, min(int(ntop), n))
+    pack = torch.empty((2, n), dtype=torch.float64, device=dev)
+    sel = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    a = L.sized(L.DsqTopVarArgs, n=n, m=x.m, ld=x.ld, x=_t_ptr(x.t), ntop=int(ntop))
+    o = L.sized(L.DsqTopVarOut, rowMean=_t_ptr(pack[0]), rowVar=_t_ptr(pack[1]), select=_t_ptr(sel))
+    L.check(L.lib().dsq_top_var_dev(C.byref(a), C.byref(o), _stream()))
+    return {"rowMean": pack[0], "rowVar": pack[1], "select": sel[:k], "_pack": pack}
+
+
+def sample_pairs_dev(x, kind, rows=None, centre=None):
+    """dsq_sample_pairs_dev on a resident matrix: x a GeneMajor float64 handle, rows an int32 device tensor or None, centre a
+    float64 device tensor with one entry per listed row or None.  Returns the (m, m) float64 tensor; nothing is read back."""
+    import torch
+    assert isinstance(x, GeneMajor) and x.t.dtype == torch.float64
+    if rows is not None:
+        assert rows.dtype == torch.int32 and rows.dim() == 1 and rows.is_contiguous()
+    if centre is not None:
+        assert centre.dtype == torch.float64 and centre.is_contiguous() and centre.numel() == (x.n if rows is None else rows.numel())
+    out = torch.empty((x.m, x.m), dtype=torch.float64, device=x.t.device)
+    a = L.sized(L.DsqSamplePairsArgs, n=x.n, m=x.m, ld=x.ld, x=_t_ptr(x.t), kind=L.DSQ_PAIRS[kind],
+                nrows=0 if rows is None else int(rows.numel()), rows=_t_ptr(rows), centre=_t_ptr(centre))
+    o = L.sized(L.DsqSamplePairsOut, out=_t_ptr(out))
+    L.check(L.lib().dsq_sample_pairs_dev(C.byref(a), C.byref(o), _stream()))
+    return out
+
+
 def sf_iterate_solve(counts, mu, sf, disp, rows, Q=0.05, maxit=100):
     """the solve of one round of estimateSizeFactorsIterate (R/core.R:2600-2611) through dsq_sf_iterate: host arrays in R
     layout in (counts / mu n x m, sf m, disp n, rows n flags); dict(s, sf, F, iter, evals, flag) out."""

@@ -774,6 +774,70 @@ int32_t dsq_sf_iterate_slice_genes(void);
 int dsq_sf_iterate_dev(const DsqSfIterateArgs *args, const DsqSfIterateOut *out, void *workspace, int64_t workspace_bytes, void *stream);
 int dsq_sf_iterate(const DsqSfIterateArgs *args, const DsqSfIterateOut *out);
 
+/* ---- dsq_top_var, dsq_sample_pairs: sample PCA and sample distances on a transform (R/plots.R:239-291, dist(t(assay(vsd)));
+ *      DESIGN.md section 19) -------------------------------------------------------------------------------------------
+ * x: n genes x m samples of float64 (what vst / rlog / normalized counts leave resident), m >= 2.
+ * dsq_top_var: rowMean = (wave-order sum over the samples) / m, rowVar = (wave-order sum of (a - mean) (a - mean)) / (m - 1)
+ * (matrixStats::rowVars as documented), and select = the first min(ntop, n) entries of order(rowVar, decreasing = TRUE):
+ * ties by ascending row, NaN variances after every number by ascending row.  ntop = 0: the row statistics alone (select
+ * may be NULL).
+ * dsq_sample_pairs: out (m x m, symmetric on the bits) over the rows listed (`rows`, nrows entries, repeats allowed; NULL:
+ * all n rows in order, nrows 0 or n):
+ *   DSQ_PAIRS_DIST2   out[i,j] = sum_g (x[g,i] - x[g,j]) (x[g,i] - x[g,j]), the diagonal +0
+ *   DSQ_PAIRS_DIST    its square root: as.matrix(dist(t(x))), method "euclidean" (dist's NA rescaling is not mirrored: a
+ *                     NaN in a sample gives NaN in every pair with another sample)
+ *   DSQ_PAIRS_GRAM    out[i,j] = sum_t c[t,i] c[t,j], c[t,.] = x[rows[t],.] - centre[t] (centre: one value per LISTED row,
+ *                     or NULL: nothing is subtracted)
+ * The order of every sum is part of the interface and depends on (rows summed, m) only: slices of
+ * dsq_sample_pairs_slice_rows(rows summed, m) consecutive listed rows, each added in list order from +0.0, then the slice
+ * partials in slice order.  No float atomics.
+ * _dev: device pointers, asynchronous on `stream`; x gene-major with leading dimension ld >= m (padding is not read);
+ * scratch comes from the workspace of the stream's context.  A listed row outside [0, n) is not read: its sums are NaN.
+ * dsq_top_var / dsq_sample_pairs: host pointers, x in R layout (column-major), ONE device, synchronous; a listed row
+ * outside [0, n) is DSQ_ERR_ARG.
+ * DSQ_ERR_ARG: struct_size not sizeof the block, n < 1, m < 2, ld < m (_dev), ntop < 0, an unknown kind, nrows without rows
+ * other than 0 or n, rows with nrows < 1, a NULL x or output.  All decided before a device is asked for.              */
+#define DSQ_PAIRS_DIST2 0
+#define DSQ_PAIRS_DIST 1
+#define DSQ_PAIRS_GRAM 2
+typedef struct {
+    uint32_t struct_size;      /* sizeof(DsqTopVarArgs)                                                             */
+    int32_t n, m;
+    int64_t ld;                /* _dev: leading dimension of x (>= m); dsq_top_var: ignored                          */
+    const double *x;           /* n x m                                                                             */
+    int32_t ntop;              /* >= 0; min(ntop, n) entries of select are written; plotPCA(): 500                  */
+} DsqTopVarArgs;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(DsqTopVarOut)                                                              */
+    double *rowMean;           /* n                                                                                 */
+    double *rowVar;            /* n                                                                                 */
+    int32_t *select;           /* min(ntop, n) row indices (0-based); may be NULL when ntop = 0                     */
+} DsqTopVarOut;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(DsqSamplePairsArgs)                                                        */
+    int32_t n, m;
+    int64_t ld;                /* _dev: leading dimension of x (>= m); dsq_sample_pairs: ignored                     */
+    const double *x;           /* n x m                                                                             */
+    int32_t kind;              /* DSQ_PAIRS_*                                                                       */
+    int32_t nrows;             /* entries of rows (and centre); without rows: 0 or n                                */
+    const int32_t *rows;       /* nrows row indices (0-based), or NULL: every row                                   */
+    const double *centre;      /* DSQ_PAIRS_GRAM: one value per listed row, or NULL; other kinds: ignored           */
+} DsqSamplePairsArgs;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(DsqSamplePairsOut)                                                         */
+    double *out;               /* m x m                                                                             */
+} DsqSamplePairsOut;
+
+int64_t dsq_sample_pairs_slice_rows(int64_t rows_summed, int32_t m);   /* the L of the summation order               */
+int32_t dsq_row_vars_register_width(void);   /* rows of up to this many samples are read once by the row-variance kernel */
+int dsq_top_var_dev(const DsqTopVarArgs *args, const DsqTopVarOut *out, void *stream);
+int dsq_top_var(const DsqTopVarArgs *args, const DsqTopVarOut *out);
+int dsq_sample_pairs_dev(const DsqSamplePairsArgs *args, const DsqSamplePairsOut *out, void *stream);
+int dsq_sample_pairs(const DsqSamplePairsArgs *args, const DsqSamplePairsOut *out);
+
 /* ---- dsq_results: results() for one coefficient (R/results.R:443-575, 638-740) -------------------
  * The table -- baseMean, log2FoldChange, lfcSE, stat, pvalue of design column c --, the threshold tests of :484-515 under
  * the normal distribution, pvalue NA where na_mask is set (the Cook's filter of :520-564 is the caller's: a host decision
