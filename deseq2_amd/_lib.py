@@ -304,6 +304,32 @@ class DsqSamplePairsOut(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("out", C.c_void_p)]
 
 
+class DsqCollapseArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("m", C.c_int32), ("g", C.c_int32), ("ld", C.c_int64),
+                ("y", C.c_void_p), ("members", C.c_void_p), ("offsets", C.c_void_p)]
+
+
+class DsqCollapseOut(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("ld", C.c_int64), ("out", C.c_void_p), ("status", C.c_void_p)]
+
+
+class DsqColSumsArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("m", C.c_int32), ("ld", C.c_int64), ("y", C.c_void_p)]
+
+
+class DsqColSumsOut(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sums", C.c_void_p)]
+
+
+class DsqFpmArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("m", C.c_int32), ("ld", C.c_int64), ("y", C.c_void_p),
+                ("kind", C.c_int32), ("lib", C.c_void_p), ("basepairs", C.c_void_p), ("txlen", C.c_void_p)]
+
+
+class DsqFpmOut(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("out", C.c_void_p)]
+
+
 def sized(cls, **kw):
     """an argument block that carries its own size in struct_size"""
     return cls(struct_size=C.sizeof(cls), **kw)
@@ -349,6 +375,7 @@ DSQ_VST_MAX_KNOTS = 1600
 DSQ_UNMIX_MAX_K = 16
 DSQ_SF = {"ratio": 0, "poscounts": 1}
 DSQ_PAIRS = {"dist2": 0, "dist": 1, "gram": 2}
+DSQ_FPM = {"fpm": 0, "fpkm_basepairs": 1, "fpkm_txlen": 2}
 DSQ_PH_GENE_EST, DSQ_PH_TREND, DSQ_PH_MAP_TEST, DSQ_PH_OUTLIERS, DSQ_PH_FINISH, DSQ_PH_PRIOR = 1, 2, 4, 8, 16, 32
 DSQ_PH_OUTLIERS_DETECT, DSQ_PH_OUTLIERS_REFIT = 64, 128
 DSQ_ST = {k: i for i, k in enumerate((
@@ -381,6 +408,7 @@ EXPORTED_SYMBOLS = [
     "dsq_sf_iterate", "dsq_sf_iterate_dev", "dsq_sf_iterate_workspace_bytes", "dsq_sf_iterate_slice_genes",
     "dsq_top_var", "dsq_top_var_dev", "dsq_sample_pairs", "dsq_sample_pairs_dev", "dsq_sample_pairs_slice_rows",
     "dsq_row_vars_register_width",
+    "dsq_collapse", "dsq_collapse_dev", "dsq_col_sums", "dsq_col_sums_dev", "dsq_fpm", "dsq_fpm_dev",
     "dsq_results", "dsq_results_dev", "dsq_results_workspace_bytes",
     "dsq_contrasts", "dsq_contrasts_dev", "dsq_contrasts_max_m",
     "dsq_pt", "dsq_pt_dev",
@@ -480,6 +508,12 @@ def lib():
     L.dsq_sample_pairs_slice_rows.restype = C.c_int64
     L.dsq_row_vars_register_width.argtypes = []
     L.dsq_row_vars_register_width.restype = C.c_int32
+    L.dsq_collapse.argtypes = [C.POINTER(DsqCollapseArgs), C.POINTER(DsqCollapseOut)]
+    L.dsq_collapse_dev.argtypes = [C.POINTER(DsqCollapseArgs), C.POINTER(DsqCollapseOut), C.c_void_p]
+    L.dsq_col_sums.argtypes = [C.POINTER(DsqColSumsArgs), C.POINTER(DsqColSumsOut)]
+    L.dsq_col_sums_dev.argtypes = [C.POINTER(DsqColSumsArgs), C.POINTER(DsqColSumsOut), C.c_void_p]
+    L.dsq_fpm.argtypes = [C.POINTER(DsqFpmArgs), C.POINTER(DsqFpmOut)]
+    L.dsq_fpm_dev.argtypes = [C.POINTER(DsqFpmArgs), C.POINTER(DsqFpmOut), C.c_void_p]
     L.dsq_results.argtypes = [C.POINTER(DsqResultsArgs), C.POINTER(DsqResultsOut)]
     L.dsq_results_dev.argtypes = [C.POINTER(DsqResultsArgs), C.POINTER(DsqResultsOut), C.c_void_p]
     L.dsq_results_workspace_bytes.argtypes = [C.c_int32, C.c_int32]

@@ -19,6 +19,9 @@ run there too, for any number of samples (csrc/rlog.hip).
 results() / resultsContrasts() (R/results.R) and lfcShrink(type = "normal") (R/lfcShrink.R: the Normal prior; the prior
 variance of all columns on the device, csrc/beta_prior.hip) are mirrored at the end of this file.
 
+collapseReplicates, fpm / fpkm (R/helper.R), counts() (R/methods.R) and plotCounts(returnData = TRUE) (R/plots.R) close the
+file; their O(n m) parts run in the engine (csrc/count_helpers.hip).
+
 Not mirrored (out of the hot-path scope): local/glmGamPoi dispersion fits; lfcShrink(type = "apeglm" /
 "ashr"), which delegate to packages whose source is not part of the reference tree.
 """
@@ -2621,4 +2624,211 @@ def plotPCA(obj, intgroup="condition", ntop=500, returnData=True, pcsToUse=(1, 2
     out = PCAData(d, p["percentVar"][[pcs[0] - 1, pcs[1] - 1]])                                      # :270-278
     if not returnData:
         raise NotImplementedError("plotPCA: there is no plotting layer; returnData = True returns the data frame")
+    return out
+
+
+# ------------------------------------------------------------------ R/helper.R:187-216, 291-391; R/methods.R:1-29; R/plots.R:365-411
+COLLAPSE_WARNING = ("\n\n  Warning! collapseReplicates only sums columns of the 'counts' assay.\n"
+                    "  Other assays are dropped from output, and must be manually combined,\n"
+                    "  as it is not unambiguous how to combine non-count assays.\n")
+COUNTS_REPLACED_WARNING = ("there are no assays named 'replaceCounts', using original.\n"
+                           "calling DESeq() will replace outliers if they are detected and store this assay.")
+COUNTS_NORMALIZED_STOP = "first calculate size factors, add normalizationFactors, or set normalized=FALSE"
+PLOTCOUNTS_INTGROUP_STOP = "all variables in 'intgroup' must be columns of colData"
+FPKM_NO_LENGTH_STOP = ('fpkm needs feature lengths: an n x m handle assays["avgTxLength"] or the n-vector mcols["basepairs"] '
+                       "(there are no rowRanges in this mirror)")
+
+
+def _is_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def _factor_levels(labels, levels=None):
+    """factor(labels) followed by droplevels(): (level names, code per label).  Without `levels` they are sort(unique(labels))
+    as factor() orders them: numerically when every label is a number (bool excluded), else every label is taken as
+    as.character() of itself (numbers as R prints them) and the strings sort by code point (R's sort follows the session's
+    collation; the C locale's is used here).  With `levels` (levels(groupby) of an existing factor) that order is kept and
+    the levels without a label are dropped."""
+    labels = list(labels)
+    if levels is None:
+        if all(_is_number(v) for v in labels):
+            keys = labels
+            lev = sorted(set(float(v) for v in labels))
+            names = [_rnum(v) for v in lev]
+            index = {v: c for c, v in enumerate(lev)}
+            codes = [index[float(v)] for v in keys]
+        else:
+            keys = [_rnum(v) if _is_number(v) else str(v) for v in labels]
+            names = sorted(set(keys))
+            index = {v: c for c, v in enumerate(names)}
+            codes = [index[v] for v in keys]
+        return names, np.asarray(codes, np.int64)
+    names = [_rnum(v) if _is_number(v) else str(v) for v in levels]
+    index = {v: c for c, v in enumerate(names)}
+    keys = [_rnum(v) if _is_number(v) else str(v) for v in labels]
+    if any(k not in index for k in keys):
+        raise ValueError("groupby holds a label that is not among its levels (NA in R)")
+    codes = np.asarray([index[k] for k in keys], np.int64)
+    used = sorted(set(codes.tolist()))                                               # droplevels, :198
+    remap = {c: i for i, c in enumerate(used)}
+    return [names[c] for c in used], np.asarray([remap[c] for c in codes.tolist()], np.int64)
+
+
+def collapseReplicates(dds, groupby, run=None, renameCols=True, levels=None):
+    """R/helper.R:187-216 on either engine: the object with one column per level of groupby, its counts the sums of the
+    level's columns (the engine's collapse_columns: csrc/count_helpers.hip on the device, where the matrix stays).
+    groupby: m labels; levels: see _factor_levels, which also states how mixed numeric and string labels are ordered.
+    The result is object[, colsToKeep] for the first column of each level: the rows of x, every attrs["factors"] code vector
+    and the size factors (when the object carries real ones) are subset to them; mcols and dispersionFunction are kept as R
+    keeps rowData; attrs["colnames"] are the levels (renameCols) or the kept columns' names; attrs["runsCollapsed"] pastes
+    `run` per level.  A normalization-factor matrix, weights and every entry of assays are dropped with R's warning (after
+    the length check on groupby).  An object without a size-factor vector counts as carrying the matrix: from_device
+    called without sizeFactors= holds only its nf_r and so warns, whatever that matrix was built from.  `levels` is beyond
+    R's signature: R carries them inside the factor groupby, here they come beside the labels.  R's stopifnot()s come as
+    ValueError; a level whose sum exceeds the largest integer raises ValueError naming it (R: NA from
+    mode<-, then the closing stopifnot fails)."""
+    E = dds.engine
+    groupby = list(groupby)
+    _r_stopifnot(len(groupby) == dds.m, "length(groupby) == ncol(object)")           # :199, ahead of the warning: a refused call says one thing
+    if dds.sizeFactors is None or dds.has_weights or dds.assays:                      # :190-197
+        warnings.warn(COLLAPSE_WARNING)
+    names, codes = _factor_levels(groupby, levels)                                   # :188, :198
+    g = len(names)
+    order = np.argsort(codes, kind="stable")                                         # sp <- split(seq(along = groupby), groupby), :200
+    members = order.astype(np.int32)
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(codes, minlength=g))]).astype(np.int32)
+    y, status = E.collapse_columns(dds.y, members, offsets)                          # :201-202
+    if status:
+        c = E.collapse_overflow_group(dds.y, members, offsets)
+        raise ValueError("collapseReplicates: the sum of the columns of level '%s' exceeds the largest integer (%d): "
+                         "NA in R" % (names[c if c is not None else 0], 2 ** 31 - 1))
+    keep = members[offsets[:-1]].astype(np.int64)                                    # colsToKeep, :203
+    out = DESeqDataSet.__new__(DESeqDataSet)                                         # object[, colsToKeep], :204-206
+    out.n, out.m, out.engine = dds.n, g, E
+    out.x = np.ascontiguousarray(dds.x[keep])
+    out.counts_host = None
+    out.y = y
+    out.has_weights, out.weights_h = False, None
+    out.xh = E.design(out.x)
+    out.mcols, out.assays, out.attrs = dict(dds.mcols), {}, {}
+    out.dispersionFunction = None if dds.dispersionFunction is None else dict(dds.dispersionFunction)
+    real = dds._sf_given and dds.sizeFactors is not None
+    _install_size_factors(out, np.asarray(dds.sizeFactors, np.float64)[keep] if real else np.ones(g))
+    out._sf_given = bool(real)
+    if dds.attrs.get("factors") is not None:
+        out.attrs["factors"] = type(dds.attrs["factors"])((k, np.asarray(v)[keep]) for k, v in dds.attrs["factors"].items())
+    if run is not None:                                                              # :207-210
+        run = list(run)
+        _r_stopifnot(len(groupby) == len(run), "length(groupby) == length(run)")
+        out.attrs["runsCollapsed"] = [",".join(str(run[j]) for j in members[offsets[c]:offsets[c + 1]]) for c in range(g)]
+    if renameCols:                                                                   # :211-213
+        out.attrs["colnames"] = list(names)
+    elif dds.attrs.get("colnames") is not None:
+        out.attrs["colnames"] = [dds.attrs["colnames"][j] for j in keep]
+    before = sum(int(v) for v in E.col_sums(dds.y))                                  # :214, on the engine's exact column sums
+    after = sum(int(v) for v in E.col_sums(out.y))
+    _r_stopifnot(before == after, "sum(as.numeric(assay(object))) == sum(as.numeric(assay(collapsed)))")
+    return out
+
+
+def _library_sizes(dds, robust):
+    """library.sizes of fpm (R/helper.R:385-389): colSums(k) -- the engine's exact int64 sums, each rounded once to double
+    --, or sizeFactors * exp(mean(log(colSums(k)))) in the library's log / exp with the mean as the sequential sum in sample
+    order over m (as xim_size_factors states its mean): host arithmetic over m numbers"""
+    E = dds.engine
+    cs = np.asarray(E.col_sums(dds.y), np.int64).astype(np.float64)
+    if not robust:
+        return cs
+    lg = E.vlog(cs)
+    mean = np.cumsum(lg)[-1] / cs.size
+    return np.asarray(dds.sizeFactors, np.float64) * E.vexp(np.array([mean]))[0]
+
+
+def fpm(dds, robust=True):
+    """R/helper.R:378-391 on either engine: 1e6 * sweep(k, 2, library.sizes, "/") as a DESeqTransform of kind "fpm" (the
+    matrix stays where the engine keeps it).  robust: the library sizes are sizeFactors * exp(mean(log(colSums(k)))),
+    estimated on a copy when the object has no size factors; not used when assays["avgTxLength"] is present."""
+    noAvgTxLen = "avgTxLength" not in dds.assays                                     # :380
+    work = dds
+    if robust and noAvgTxLen and not (dds._sf_given and dds.sizeFactors is not None):         # :381-383, on a copy
+        work = estimateSizeFactors(_shallow(dds))
+    lib = _library_sizes(work, bool(robust and noAvgTxLen))                          # :385-389
+    return DESeqTransform(dds, dds.engine.fpm_transform(dds.y, lib, "fpm"), "fpm")   # :390
+
+
+def fpkm(dds, robust=True):
+    """R/helper.R:291-323 on either engine, as a DESeqTransform of kind "fpkm".  assays["avgTxLength"] (an n x m engine
+    handle) takes precedence: 1e3 * fpm / avgTxLength over the plain column sums, then -- robust -- divided by the
+    median-ratio size factors of that matrix (estimateSizeFactorsForMatrix); else mcols["basepairs"]: 1e3 * sweep(fpm, 1,
+    basepairs, "/").  There are no rowRanges in this mirror: with neither, ValueError."""
+    E = dds.engine
+    if "avgTxLength" in dds.assays:                                                  # :293-302
+        lib = _library_sizes(dds, False)
+        ex = E.fpm_transform(dds.y, lib, "fpkm_txlen", txlen=dds.assays["avgTxLength"])
+        if robust:
+            sf = E.size_factors(ex, type="ratio")                                    # :296
+            ex = E.vst_transform(ex, None, "normalized", sizeFactors=sf["sizeFactors"])      # :297
+        return DESeqTransform(dds, ex, "fpkm")
+    if dds.mcols.get("basepairs") is None:                                           # :303
+        raise ValueError(FPKM_NO_LENGTH_STOP)
+    bp = np.asarray(dds.mcols["basepairs"], np.float64).reshape(-1)
+    if bp.size != dds.n:
+        raise ValueError('mcols["basepairs"] should hold one length per row')
+    work = dds
+    if robust and not (dds._sf_given and dds.sizeFactors is not None):               # fpm(object, robust), :292
+        work = estimateSizeFactors(_shallow(dds))
+    lib = _library_sizes(work, bool(robust))
+    return DESeqTransform(dds, E.fpm_transform(dds.y, lib, "fpkm_basepairs", basepairs=bp), "fpkm")    # :322
+
+
+def counts(dds, normalized=False, replaced=False):
+    """counts.DESeqDataSet (R/methods.R:1-29): a DESeqTransform over the count handle (kind "counts": assay() gives the
+    integer matrix) or, normalized, what normalized_counts returns -- of assays["replaceCounts"] when replaced and DESeq()
+    stored it, else with R's warning of the original counts."""
+    src = dds
+    if replaced:                                                                     # :7-14
+        if "replaceCounts" in dds.assays:
+            src = _shallow(dds)
+            src.mcols, src.assays, src.attrs = dds.mcols, dds.assays, dds.attrs
+            src.y = dds.assays["replaceCounts"]
+        else:
+            warnings.warn(COUNTS_REPLACED_WARNING)
+    if not normalized:                                                               # :18-19
+        return DESeqTransform(dds, src.y, "counts")
+    if dds.sizeFactors is None:                                                      # :21-22 (normalization factors)
+        return normalized_counts(src)
+    if not dds._sf_given or np.isnan(np.asarray(dds.sizeFactors, np.float64)).any():          # :23-24
+        raise ValueError(COUNTS_NORMALIZED_STOP)
+    return normalized_counts(src)                                                    # :26
+
+
+def plotCounts(dds, gene, intgroup="condition", normalized=True, transform=True, returnData=True, replaced=False, pc=None):
+    """R/plots.R:365-411 with returnData = TRUE: dict(count = counts(dds, normalized, replaced)[gene, ] + pc, then the
+    intgroup columns from attrs["factors"]).  gene: a 0-based row index; pc: 0.5 when transform else 0 unless given.  Only
+    the one row is computed (take_rows first).  There is no plotting layer: returnData = False is not served."""
+    ok = isinstance(gene, (int, np.integer)) and not isinstance(gene, (bool, np.bool_)) and 0 <= int(gene) < dds.n
+    _r_stopifnot(ok, "length(gene) == 1 & (is.numeric(gene) & (gene >= 1 & gene <= nrow(dds)))")     # :372
+    intgroup = [intgroup] if isinstance(intgroup, str) else list(intgroup)
+    factors = dds.attrs.get("factors") or {}
+    if not all(v in factors for v in intgroup):                                      # :373
+        raise ValueError(PLOTCOUNTS_INTGROUP_STOP)
+    if not returnData:
+        raise NotImplementedError("plotCounts: there is no plotting layer; returnData = True returns the data frame")
+    if pc is None:                                                                   # :381-383
+        pc = 0.5 if transform else 0
+    work = dds
+    if not dds._sf_given:                                                            # :385-387
+        work = estimateSizeFactors(_shallow(dds))
+        work.attrs, work.assays = dds.attrs, dds.assays
+    row = _shallow(work)                                                             # counts(...)[gene, ], :388
+    row.n = 1
+    E = dds.engine
+    src = work.assays["replaceCounts"] if replaced and "replaceCounts" in work.assays else work.y
+    row.y = E.take_rows(src, np.array([int(gene)]))
+    row.assays = {"replaceCounts": row.y} if replaced and "replaceCounts" in work.assays else {}
+    if work.sizeFactors is None:
+        row.nf = E.take_rows(work.nf, np.array([int(gene)]))
+    cnts = np.asarray(counts(row, normalized=normalized, replaced=replaced).assay(), np.float64).reshape(-1)
+    out = {"count": cnts + pc}                                                       # :401, :411
+    out.update((v, np.asarray(factors[v])) for v in intgroup)
     return out

@@ -918,6 +918,87 @@ int sample_pairs_dev_locked(const DsqSamplePairsArgs *a, const DsqSamplePairsOut
     return DSQ_OK;
 }
 
+// collapseReplicates / colSums / fpm / fpkm (count_helpers.hip): what both entries check before anything is launched
+int collapse_check(const DsqCollapseArgs *a, const DsqCollapseOut *o) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->struct_size != sizeof *a || o->struct_size != sizeof *o) return capi_fail(DSQ_ERR_ARG, "struct_size is not sizeof the block");
+    if (a->n < 1 || a->m < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
+    if (a->g < 1 || a->g > a->m) return capi_fail(DSQ_ERR_ARG, "g = %d groups of m = %d samples", a->g, a->m);
+    if (!a->y || !a->members || !a->offsets) return capi_fail(DSQ_ERR_ARG, "NULL counts, members or offsets");
+    if (!o->out) return capi_fail(DSQ_ERR_ARG, "NULL output array");
+    return DSQ_OK;
+}
+
+int collapse_dev_locked(const DsqCollapseArgs *a, const DsqCollapseOut *o, hipStream_t st) {
+    if (int rc = collapse_check(a, o)) return rc;
+    if (a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld = %ld < m = %d", (long)a->ld, a->m);
+    if (o->ld < a->g) return capi_fail(DSQ_ERR_ARG, "output ld = %ld < g = %d", (long)o->ld, a->g);
+    if (!o->status) return capi_fail(DSQ_ERR_ARG, "NULL status");
+    if (int rc = capi_check_device()) return rc;
+    CollapseKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.m = a->m; kp.g = a->g; kp.ld = (long)a->ld; kp.ldo = (long)o->ld;
+    kp.y = a->y; kp.members = a->members; kp.offsets = a->offsets;
+    kp.out = o->out; kp.status = o->status;
+    capi_prof_begin("collapse", a->n, st);
+    DSQ_HIP(launch_collapse(kp, st));
+    capi_prof_end(st);
+    return DSQ_OK;
+}
+
+int col_sums_check(const DsqColSumsArgs *a, const DsqColSumsOut *o) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->struct_size != sizeof *a || o->struct_size != sizeof *o) return capi_fail(DSQ_ERR_ARG, "struct_size is not sizeof the block");
+    if (a->n < 1 || a->m < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
+    if (!a->y) return capi_fail(DSQ_ERR_ARG, "NULL counts");
+    if (!o->sums) return capi_fail(DSQ_ERR_ARG, "NULL output array");
+    return DSQ_OK;
+}
+
+int col_sums_dev_locked(const DsqColSumsArgs *a, const DsqColSumsOut *o, hipStream_t st) {
+    if (int rc = col_sums_check(a, o)) return rc;
+    if (a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld = %ld < m = %d", (long)a->ld, a->m);
+    if (int rc = capi_check_device()) return rc;
+    ColSumsKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.m = a->m; kp.ld = (long)a->ld; kp.y = a->y;
+    kp.sums = (long long *)o->sums;
+    capi_prof_begin("col_sums", a->n, st);
+    DSQ_HIP(launch_col_sums(kp, st));
+    capi_prof_end(st);
+    return DSQ_OK;
+}
+
+int fpm_check(const DsqFpmArgs *a, const DsqFpmOut *o) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->struct_size != sizeof *a || o->struct_size != sizeof *o) return capi_fail(DSQ_ERR_ARG, "struct_size is not sizeof the block");
+    if (a->n < 1 || a->m < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
+    if (a->kind != DSQ_FPM && a->kind != DSQ_FPKM_BASEPAIRS && a->kind != DSQ_FPKM_TXLEN) return capi_fail(DSQ_ERR_ARG, "unknown kind %d", a->kind);
+    if (!a->y || !a->lib) return capi_fail(DSQ_ERR_ARG, "NULL counts or library sizes");
+    if (a->kind == DSQ_FPKM_BASEPAIRS && !a->basepairs) return capi_fail(DSQ_ERR_ARG, "DSQ_FPKM_BASEPAIRS: NULL basepairs");
+    if (a->kind == DSQ_FPKM_TXLEN && !a->txlen) return capi_fail(DSQ_ERR_ARG, "DSQ_FPKM_TXLEN: NULL txlen");
+    if (!o->out) return capi_fail(DSQ_ERR_ARG, "NULL output matrix");
+    return DSQ_OK;
+}
+
+int fpm_dev_locked(const DsqFpmArgs *a, const DsqFpmOut *o, hipStream_t st) {
+    if (int rc = fpm_check(a, o)) return rc;
+    if (a->ld < a->m) return capi_fail(DSQ_ERR_ARG, "ld = %ld < m = %d", (long)a->ld, a->m);
+    if (int rc = capi_check_device()) return rc;
+    FpmKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.m = a->m; kp.ld = (long)a->ld; kp.y = a->y;
+    kp.kind = a->kind;
+    kp.lib = a->lib;
+    kp.basepairs = a->kind == DSQ_FPKM_BASEPAIRS ? a->basepairs : nullptr;
+    kp.txlen = a->kind == DSQ_FPKM_TXLEN ? a->txlen : nullptr;
+    kp.out = o->out;
+    capi_prof_begin("fpm", a->n, st);
+    DSQ_HIP(launch_fpm(kp, st));
+    capi_prof_end(st);
+    return DSQ_OK;
+}
+
 // the solve of estimateSizeFactors(type = "iterate") (sf_iterate.hip): what both entries check before anything is launched
 int sf_iterate_check(const DsqSfIterateArgs *a, const DsqSfIterateOut *o) {
     if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
@@ -1094,6 +1175,9 @@ DSQ_DEV(dsq_results_dev, DsqResultsArgs, const DsqResultsOut *, results_dev_lock
 DSQ_DEV(dsq_contrasts_dev, DsqContrastsArgs, const DsqContrastsOut *, contrasts_dev_locked(a, o, st))
 DSQ_DEV(dsq_top_var_dev, DsqTopVarArgs, const DsqTopVarOut *, top_var_dev_locked(a, o, st))
 DSQ_DEV(dsq_sample_pairs_dev, DsqSamplePairsArgs, const DsqSamplePairsOut *, sample_pairs_dev_locked(a, o, st))
+DSQ_DEV(dsq_collapse_dev, DsqCollapseArgs, const DsqCollapseOut *, collapse_dev_locked(a, o, st))
+DSQ_DEV(dsq_col_sums_dev, DsqColSumsArgs, const DsqColSumsOut *, col_sums_dev_locked(a, o, st))
+DSQ_DEV(dsq_fpm_dev, DsqFpmArgs, const DsqFpmOut *, fpm_dev_locked(a, o, st))
 #undef DSQ_DEV
 int dsq_linear_mu_dev(const DsqPrefitArgs *a, double mu_floor, double *mu, void *s) {
     return dev_entry(s, [&](hipStream_t st) { return linear_mu_dev_locked(a, mu_floor, mu, st); });

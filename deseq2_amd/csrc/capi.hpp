@@ -57,6 +57,9 @@ int unmix_check(const DsqUnmixArgs *a, const DsqUnmixOut *o);
 int sf_iterate_check(const DsqSfIterateArgs *a, const DsqSfIterateOut *o);
 int top_var_check(const DsqTopVarArgs *a, const DsqTopVarOut *o);
 int sample_pairs_check(const DsqSamplePairsArgs *a, const DsqSamplePairsOut *o);
+int collapse_check(const DsqCollapseArgs *a, const DsqCollapseOut *o);
+int col_sums_check(const DsqColSumsArgs *a, const DsqColSumsOut *o);
+int fpm_check(const DsqFpmArgs *a, const DsqFpmOut *o);
 int results_check(const DsqResultsArgs *a, const DsqResultsOut *o);
 int contrasts_check(const DsqContrastsArgs *a, const DsqContrastsOut *o);
 int pt_check(const double *q, const double *df, int32_t n, int32_t K, int32_t tail, const double *out);
@@ -78,6 +81,9 @@ int unmix_dev_locked(const DsqUnmixArgs *a, const DsqUnmixOut *o, void *workspac
 int sf_iterate_dev_locked(const DsqSfIterateArgs *a, const DsqSfIterateOut *o, void *workspace, int64_t workspace_bytes, hipStream_t st);
 int top_var_dev_locked(const DsqTopVarArgs *a, const DsqTopVarOut *o, hipStream_t st);
 int sample_pairs_dev_locked(const DsqSamplePairsArgs *a, const DsqSamplePairsOut *o, hipStream_t st);
+int collapse_dev_locked(const DsqCollapseArgs *a, const DsqCollapseOut *o, hipStream_t st);
+int col_sums_dev_locked(const DsqColSumsArgs *a, const DsqColSumsOut *o, hipStream_t st);
+int fpm_dev_locked(const DsqFpmArgs *a, const DsqFpmOut *o, hipStream_t st);
 int results_dev_locked(const DsqResultsArgs *a, const DsqResultsOut *o, hipStream_t st);
 int contrasts_dev_locked(const DsqContrastsArgs *a, const DsqContrastsOut *o, hipStream_t st);
 

@@ -894,6 +894,93 @@ int dsq_sample_pairs(const DsqSamplePairsArgs *a, const DsqSamplePairsOut *o) {
     return s.finish();
 }
 
+int dsq_collapse(const DsqCollapseArgs *a, const DsqCollapseOut *o) {
+    const auto check = [&]() -> int {
+        if (int rc = collapse_check(a, o)) return rc;
+        // split(seq(along = groupby), groupby): every sample once, ascending inside a group, no empty group (droplevels)
+        if (a->offsets[0] != 0 || a->offsets[a->g] != a->m) return capi_fail(DSQ_ERR_ARG, "offsets run from %d to %d, not from 0 to m = %d", a->offsets[0], a->offsets[a->g], a->m);
+        std::vector<char> seen(a->m, 0);
+        for (int c = 0; c < a->g; c++) {
+            if (a->offsets[c + 1] <= a->offsets[c]) return capi_fail(DSQ_ERR_ARG, "group %d is empty or offsets descend", c);
+            for (int k = a->offsets[c]; k < a->offsets[c + 1]; k++) {
+                const int j = a->members[k];
+                if (j < 0 || j >= a->m || seen[j]) return capi_fail(DSQ_ERR_ARG, "members[%d] = %d is outside [0, %d) or listed twice", k, j, a->m);
+                if (k > a->offsets[c] && j < a->members[k - 1]) return capi_fail(DSQ_ERR_ARG, "members of group %d are not ascending", c);
+                seen[j] = 1;
+            }
+        }
+        return DSQ_OK;
+    };
+    HostCall hc;
+    DSQ_TRY(host_ready(check(), DSQ_LAYOUT_R));
+    hipStream_t st = hc.st;
+    const size_t n = a->n, m = a->m, g = a->g;
+    const long ld = round_ld(a->m), ldo = round_ld(a->g);
+    DsqCollapseArgs d = *a;
+    DsqCollapseOut od = *o;
+    Stage s(st, n);
+    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->y, 4, a->n, a->m, ld, &d.y));
+    d.ld = ld;
+    s.vec(&d.members, a->members, m * 4);
+    s.vec(&d.offsets, a->offsets, (g + 1) * 4);
+    DSQ_TRY(s.pack_in());
+    int32_t status = 0;
+    s.out_vec(&od.status, &status, 4, 8);
+    DSQ_TRY(s.pack_out());
+    DSQ_HIP(hipMemsetAsync(od.status, 0, 8, st));
+    void *gm;
+    DSQ_TRY(capi_ws_get(WS_MUOUT, n * ldo * 4, &gm));
+    od.out = (int32_t *)gm;
+    od.ld = ldo;
+    DSQ_TRY(collapse_dev_locked(&d, &od, st));
+    DSQ_TRY(s.flush());
+    int32_t *r;
+    DSQ_TRY(s.out_mat(WS_H_OUTMAT, &r, o->out, g));
+    DSQ_HIP(launch_transpose_gm_to_r_i32(od.out, r, a->n, a->g, ldo, st));
+    DSQ_TRY(s.finish());
+    if (o->status) *o->status = status;
+    if (status & 1) return capi_fail(DSQ_ERR_VALUE, "a group sum exceeds the largest integer (2147483647)");
+    return DSQ_OK;
+}
+
+int dsq_col_sums(const DsqColSumsArgs *a, const DsqColSumsOut *o) {
+    HostCall hc;
+    DSQ_TRY(host_ready(col_sums_check(a, o), DSQ_LAYOUT_R));
+    hipStream_t st = hc.st;
+    const long ld = round_ld(a->m);
+    DsqColSumsArgs d = *a;
+    DsqColSumsOut od = *o;
+    Stage s(st, a->n);
+    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->y, 4, a->n, a->m, ld, &d.y));
+    d.ld = ld;
+    s.out_vec(&od.sums, o->sums, (size_t)a->m * 8);
+    DSQ_TRY(s.pack_out());
+    DSQ_TRY(col_sums_dev_locked(&d, &od, st));
+    return s.finish();
+}
+
+int dsq_fpm(const DsqFpmArgs *a, const DsqFpmOut *o) {
+    HostCall hc;
+    DSQ_TRY(host_ready(fpm_check(a, o), DSQ_LAYOUT_R));
+    hipStream_t st = hc.st;
+    const size_t n = a->n, m = a->m;
+    const long ld = round_ld(a->m);
+    DsqFpmArgs d = *a;
+    DsqFpmOut od = *o;
+    Stage s(st, n);
+    stage_prefault(o->out, n * m * 8);
+    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->y, 4, a->n, a->m, ld, &d.y));
+    d.ld = ld;
+    if (a->kind == DSQ_FPKM_TXLEN) DSQ_TRY(up_gene_major(s, WS_H_NF, WS_NF, a->txlen, 8, a->n, a->m, ld, &d.txlen));
+    s.vec(&d.lib, a->lib, m * 8);                  // first in the packed buffer: 16-byte aligned, as the paired loads want
+    if (a->kind == DSQ_FPKM_BASEPAIRS) s.gene_vec(&d.basepairs, a->basepairs);
+    DSQ_TRY(s.pack_in());
+    DSQ_TRY(gm_result_slot(n, ld, &od.out));
+    DSQ_TRY(fpm_dev_locked(&d, &od, st));
+    DSQ_TRY(gm_result_down(s, od.out, o->out, a->n, a->m, ld));
+    return s.finish();
+}
+
 int dsq_sf_iterate(const DsqSfIterateArgs *a, const DsqSfIterateOut *o) {
     const auto check = [&]() -> int {
         if (int rc = sf_iterate_check(a, o)) return rc;

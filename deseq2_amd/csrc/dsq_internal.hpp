@@ -374,6 +374,38 @@ struct PairKernelParams {
 };
 hipError_t launch_pair_sums(const PairKernelParams &kp, hipStream_t st);
 
+// collapseReplicates / colSums / fpm / fpkm on the resident counts (count_helpers.hip): y int32
+// gene-major, element (i, j) at [i * ld + j], read only.
+struct CollapseKernelParams {
+    int n, m, g;
+    long ld, ldo;
+    const int32_t *y;
+    const int32_t *members;      // m sample indices, group by group
+    const int32_t *offsets;      // g + 1: group c owns members[offsets[c] .. offsets[c + 1])
+    int32_t *out;                // n x g, element (i, c) at [i * ldo + c]
+    int32_t *status;             // ORed: 1 a sum that is no int32, 2 a member or an offset outside the matrix
+};
+hipError_t launch_collapse(const CollapseKernelParams &kp, hipStream_t st);
+struct ColSumsKernelParams {
+    int n, m;
+    long ld;
+    const int32_t *y;
+    long long *sums;             // m
+};
+hipError_t launch_col_sums(const ColSumsKernelParams &kp, hipStream_t st);
+enum { FPM_FPM = 0, FPM_FPKM_BASEPAIRS = 1, FPM_FPKM_TXLEN = 2 };       // = DSQ_FPM, DSQ_FPKM_* of the public header
+struct FpmKernelParams {
+    int n, m;
+    long ld;                     // of y, txlen and out alike
+    const int32_t *y;
+    int kind;
+    const double *lib;           // m library sizes
+    const double *basepairs;     // n (FPM_FPKM_BASEPAIRS)
+    const double *txlen;         // n x m (FPM_FPKM_TXLEN)
+    double *out;                 // n x m
+};
+hipError_t launch_fpm(const FpmKernelParams &kp, hipStream_t st);
+
 // K contrasts from one covariance pass per gene (contrasts.hip).  n x m matrices gene-major with
 // leading dimension ld, n x p / n x K matrices column-major; ncell > 0 selects the cell-collapsed Gram sums (cell_perm,
 // cell_start as in BetaKernelParams); contrasts == nullptr: the all-zero flags only.

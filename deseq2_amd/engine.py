@@ -416,6 +416,45 @@ class HostEngine:
         from . import explore_host
         return explore_host.pair_sums(np.asarray(x, np.float64), kind, rows=rows, centre=centre)
 
+    # ---- collapseReplicates / colSums / fpm / fpkm (R/helper.R:187-216, 291-391): plain numpy, the host statement of
+    # csrc/count_helpers.hip (integer sums exact, every quotient and product one IEEE operation in R's order: the same bits)
+    def collapse_columns(self, y, members, offsets):
+        """the n x g count handle of group sums (group c = members[offsets[c] .. offsets[c + 1]), 0-based samples) and the
+        status: 1 when a sum is no int32 (R: NA from mode<-), the handle then being of no use"""
+        K = np.asarray(y)
+        members = np.asarray(members, np.int64)
+        cols = [K[:, members[offsets[c]:offsets[c + 1]]].sum(axis=1, dtype=np.int64) for c in range(len(offsets) - 1)]
+        S = np.stack(cols, axis=1)
+        status = int((S > np.iinfo(np.int32).max).any() or (S < np.iinfo(np.int32).min).any())
+        return self.counts(S.astype(np.int32)), status
+
+    def collapse_overflow_group(self, y, members, offsets):
+        """the first group one of whose sums is no int32 (the error path of collapse_columns), or None"""
+        K = np.asarray(y)
+        for c in range(len(offsets) - 1):
+            s = K[:, np.asarray(members[offsets[c]:offsets[c + 1]], np.int64)].sum(axis=1, dtype=np.int64)
+            if (s > np.iinfo(np.int32).max).any() or (s < np.iinfo(np.int32).min).any():
+                return c
+        return None
+
+    def col_sums(self, y):
+        """colSums of a count handle before the conversion to double: m exact int64 sums on the host"""
+        return np.asarray(y).sum(axis=0, dtype=np.int64)
+
+    def fpm_transform(self, y, lib, kind, basepairs=None, txlen=None):
+        """fpm / fpkm of a count handle (R/helper.R:390, 322, 294) for m library sizes: kind "fpm", "fpkm_basepairs"
+        (basepairs: n) or "fpkm_txlen" (txlen: an n x m handle).  Returns an n x m handle."""
+        K = np.asarray(y).astype(np.float64)
+        with np.errstate(all="ignore"):
+            f = 1e6 * (K / np.asarray(lib, np.float64)[None, :])
+            if kind == "fpkm_basepairs":
+                f = 1e3 * (f / np.asarray(basepairs, np.float64)[:, None])
+            elif kind == "fpkm_txlen":
+                f = (1e3 * f) / np.asarray(txlen, np.float64)
+            elif kind != "fpm":
+                raise ValueError("kind should be fpm, fpkm_basepairs or fpkm_txlen")
+        return np.asfortranarray(f)
+
     def sf_iterate_solve(self, y, mu, sf, disp, rows, Q=0.05, maxit=100):
         """the solve of one round of estimateSizeFactorsIterate (R/core.R:2600-2611): y / mu n x m handles, sf the m size
         factors mu was fitted with, disp n, rows n flags (rowSums > 0).  The iteration of csrc/sf_iterate.hip stated in numpy
@@ -926,6 +965,43 @@ class DeviceEngine:
             centre = self._vec(centre)
         out = self._timed("sample_pairs", x.m, lambda: self.native.sample_pairs_dev(x, kind, rows=rows, centre=centre))
         return self._host(out).numpy().copy()
+
+    # ---- collapseReplicates / colSums / fpm / fpkm on the resident counts (csrc/count_helpers.hip): no n x m matrix leaves HBM
+    def _csr_dev(self, members, offsets):
+        t = self.torch
+        return (t.as_tensor(np.ascontiguousarray(members, dtype=np.int32)).to(self.device),
+                t.as_tensor(np.ascontiguousarray(offsets, dtype=np.int32)).to(self.device))
+
+    def collapse_columns(self, y, members, offsets):
+        """the grouped column sums by collapse_kernel (dsq_collapse_dev): the m + g + 1 indices go up, the n x g count handle
+        stays resident, the status word (4 bytes) comes to the host"""
+        mt, ot = self._csr_dev(members, offsets)
+        out, status = self._timed("collapse", y.n, lambda: self.native.collapse_dev(y, mt, ot))
+        return out, int(self._host(status)[0]) & 1
+
+    def collapse_overflow_group(self, y, members, offsets):
+        """the first group one of whose sums is no int32, or None: the error path of collapse_columns, in stock tensor
+        operations on the resident counts (one flag per group comes to the host)"""
+        t = self.torch
+        for c in range(len(offsets) - 1):
+            idx = t.as_tensor(np.asarray(members[offsets[c]:offsets[c + 1]], np.int64), device=self.device)
+            s = y.view().index_select(1, idx).sum(dim=1, dtype=t.int64)
+            if bool(((s > 2 ** 31 - 1) | (s < -2 ** 31)).any()):
+                return c
+        return None
+
+    def col_sums(self, y):
+        """colSums of the resident counts by col_sums_kernel (dsq_col_sums_dev): the m int64 sums come to the host"""
+        s = self._timed("col_sums", y.n, lambda: self.native.col_sums_dev(y))
+        return self._host(s).numpy().copy()
+
+    def fpm_transform(self, y, lib, kind, basepairs=None, txlen=None):
+        """fpm / fpkm of the resident counts in one pass (fpm_kernel, dsq_fpm_dev): the m library sizes (and the n feature
+        lengths) go up, the n x m result is a handle and stays in HBM.  txlen: a resident n x m handle."""
+        bp = None if basepairs is None else self._vec(basepairs)
+        tl = None if txlen is None else self._resident(txlen)
+        libd = self._vec(lib)
+        return self._timed("fpm", y.n, lambda: self.native.fpm_dev(y, libd, kind, basepairs=bp, txlen=tl))
 
     def sf_iterate_solve(self, y, mu, sf, disp, rows, Q=0.05, maxit=100):
         """the solve of one round of estimateSizeFactorsIterate on the device (csrc/sf_iterate.hip, dsq_sf_iterate_dev) on

@@ -982,6 +982,121 @@ def sample_pairs_dev(x, kind, rows=None, centre=None):
     return out
 
 
+def _icol(y):
+    y = np.asarray(y)
+    if y.dtype.kind not in "iu" and y.dtype != np.bool_:
+        raise ValueError("counts must be an integer matrix")
+    y = np.asfortranarray(y.astype(np.int32, copy=False))
+    if y.ndim != 2:
+        raise ValueError("counts must be a matrix")
+    return y
+
+
+def _csr(members, offsets):
+    return np.ascontiguousarray(members, dtype=np.int32), np.ascontiguousarray(offsets, dtype=np.int32)
+
+
+def collapse(counts, members, offsets):
+    """dsq_collapse: host int matrix in (n x m, R layout) and the groups as a CSR pair (members: the m 0-based sample
+    indices group by group, offsets: g + 1); the n x g int32 matrix of group sums out.  A sum that is no int32 raises
+    DsqError (DSQ_ERR_VALUE)."""
+    y = _icol(counts)
+    n, m = y.shape
+    members, offsets = _csr(members, offsets)
+    g = offsets.size - 1
+    if members.size != m:
+        raise ValueError("members must list every sample once")
+    out = np.zeros((n, max(g, 0)), dtype=np.int32, order="F")
+    a = L.sized(L.DsqCollapseArgs, n=n, m=m, g=g, ld=0, y=_ptr(y), members=_ptr(members), offsets=_ptr(offsets))
+    o = L.sized(L.DsqCollapseOut, ld=0, out=_ptr(out), status=None)
+    L.check(L.lib().dsq_collapse(C.byref(a), C.byref(o)))
+    return out
+
+
+def col_sums(counts):
+    """dsq_col_sums: host int matrix in (n x m, R layout); the m column sums out, int64 (exact)"""
+    y = _icol(counts)
+    n, m = y.shape
+    sums = np.zeros(m, dtype=np.int64)
+    a = L.sized(L.DsqColSumsArgs, n=n, m=m, ld=0, y=_ptr(y))
+    o = L.sized(L.DsqColSumsOut, sums=_ptr(sums))
+    L.check(L.lib().dsq_col_sums(C.byref(a), C.byref(o)))
+    return sums
+
+
+def fpm(counts, lib, kind="fpm", basepairs=None, txlen=None):
+    """dsq_fpm: host int matrix in (n x m, R layout), lib the m library sizes, kind "fpm" / "fpkm_basepairs" (basepairs: n)
+    / "fpkm_txlen" (txlen: n x m); the n x m float64 matrix out"""
+    y = _icol(counts)
+    n, m = y.shape
+    lib = np.ascontiguousarray(lib, dtype=np.float64).reshape(-1)
+    if lib.size != m:
+        raise ValueError("lib must hold one library size per sample")
+    bp = None if basepairs is None else np.ascontiguousarray(basepairs, dtype=np.float64).reshape(-1)
+    if bp is not None and bp.size != n:
+        raise ValueError("basepairs must hold one length per gene")
+    tl = None if txlen is None else _fcol(txlen)
+    if tl is not None and tl.shape != (n, m):
+        raise ValueError("txlen must have the shape of counts")
+    out = np.zeros((n, m), order="F")
+    a = L.sized(L.DsqFpmArgs, n=n, m=m, ld=0, y=_ptr(y), kind=L.DSQ_FPM[kind], lib=_ptr(lib), basepairs=_ptr(bp), txlen=_ptr(tl))
+    o = L.sized(L.DsqFpmOut, out=_ptr(out))
+    L.check(L.lib().dsq_fpm(C.byref(a), C.byref(o)))
+    return out
+
+
+def collapse_dev(y, members, offsets):
+    """dsq_collapse_dev on resident counts: y a GeneMajor int32 handle, members / offsets int32 device tensors (m and
+    g + 1 entries).  Returns (the n x g GeneMajor int32 handle, padding columns zero; the status word as a (1,) int32
+    device tensor: bit 1 a sum that is no int32, bit 2 a member or an offset outside the matrix); nothing is read back."""
+    import torch
+    assert isinstance(y, GeneMajor) and y.t.dtype == torch.int32
+    for v in (members, offsets):
+        assert v.dtype == torch.int32 and v.dim() == 1 and v.is_contiguous()
+    g = int(offsets.numel()) - 1
+    assert int(members.numel()) == y.m
+    dev = y.t.device
+    out = GeneMajor(torch.zeros((y.n, gene_major_ld(g)), dtype=torch.int32, device=dev), g)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    a = L.sized(L.DsqCollapseArgs, n=y.n, m=y.m, g=g, ld=y.ld, y=_t_ptr(y.t), members=_t_ptr(members), offsets=_t_ptr(offsets))
+    o = L.sized(L.DsqCollapseOut, ld=out.ld, out=_t_ptr(out.t), status=_t_ptr(status))
+    L.check(L.lib().dsq_collapse_dev(C.byref(a), C.byref(o), _stream()))
+    return out, status
+
+
+def col_sums_dev(y):
+    """dsq_col_sums_dev on resident counts: y a GeneMajor int32 handle.  Returns the (m,) int64 device tensor of column
+    sums; nothing is read back."""
+    import torch
+    assert isinstance(y, GeneMajor) and y.t.dtype == torch.int32
+    sums = torch.empty(y.m, dtype=torch.int64, device=y.t.device)
+    a = L.sized(L.DsqColSumsArgs, n=y.n, m=y.m, ld=y.ld, y=_t_ptr(y.t))
+    o = L.sized(L.DsqColSumsOut, sums=_t_ptr(sums))
+    L.check(L.lib().dsq_col_sums_dev(C.byref(a), C.byref(o), _stream()))
+    return sums
+
+
+def fpm_dev(y, lib, kind="fpm", basepairs=None, txlen=None):
+    """dsq_fpm_dev on resident counts: y a GeneMajor int32 handle, lib a (m,) float64 device tensor, basepairs a (n,)
+    float64 device tensor, txlen a GeneMajor float64 handle with y's ld.  Returns the n x m GeneMajor float64 handle
+    (padding columns zero); nothing is read back."""
+    import torch
+    assert isinstance(y, GeneMajor) and y.t.dtype == torch.int32
+    assert lib.dtype == torch.float64 and lib.numel() == y.m and lib.is_contiguous()
+    if basepairs is not None:
+        assert basepairs.dtype == torch.float64 and basepairs.numel() == y.n and basepairs.is_contiguous()
+    if txlen is not None:
+        assert isinstance(txlen, GeneMajor) and txlen.t.dtype == torch.float64 and txlen.ld == y.ld and txlen.n == y.n
+    out = GeneMajor(torch.empty((y.n, y.ld), dtype=torch.float64, device=y.t.device), y.m)
+    if y.ld > y.m:
+        out.t[:, y.m:] = 0.0
+    a = L.sized(L.DsqFpmArgs, n=y.n, m=y.m, ld=y.ld, y=_t_ptr(y.t), kind=L.DSQ_FPM[kind], lib=_t_ptr(lib),
+                basepairs=_t_ptr(basepairs), txlen=None if txlen is None else _t_ptr(txlen.t))
+    o = L.sized(L.DsqFpmOut, out=_t_ptr(out.t))
+    L.check(L.lib().dsq_fpm_dev(C.byref(a), C.byref(o), _stream()))
+    return out
+
+
 def sf_iterate_solve(counts, mu, sf, disp, rows, Q=0.05, maxit=100):
     """the solve of one round of estimateSizeFactorsIterate (R/core.R:2600-2611) through dsq_sf_iterate: host arrays in R
     layout in (counts / mu n x m, sf m, disp n, rows n flags); dict(s, sf, F, iter, evals, flag) out."""

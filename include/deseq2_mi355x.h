@@ -838,6 +838,87 @@ int dsq_top_var(const DsqTopVarArgs *args, const DsqTopVarOut *out);
 int dsq_sample_pairs_dev(const DsqSamplePairsArgs *args, const DsqSamplePairsOut *out, void *stream);
 int dsq_sample_pairs(const DsqSamplePairsArgs *args, const DsqSamplePairsOut *out);
 
+/* ---- dsq_collapse, dsq_col_sums, dsq_fpm: collapseReplicates, colSums and fpm / fpkm on the count matrix
+ *      (R/helper.R:187-216, 291-391) ---------------------------------------------------------------
+ * y: n genes x m samples of int32 counts.
+ * dsq_collapse: out[i,c] = the sum over the samples of group c of y[i,.] (sapply(sp, function(i) rowSums(y[,i])) with
+ * mode "integer"), accumulated in int64.  The g groups are split(seq(along = groupby), groupby) as a CSR pair: members
+ * holds the m sample indices (0-based), group 0's in ascending order, then group 1's, ...; offsets holds g + 1 entries,
+ * offsets[0] = 0, offsets[g] = m, group c = members[offsets[c] .. offsets[c+1]).  A sum that is no int32 (R: NA from
+ * mode<-) ORs 1 into *status and leaves that element unspecified.
+ * dsq_col_sums: sums[j] = the sum over the genes of y[.,j] in int64: exact, whatever the order (integer atomics).  The
+ * double colSums() returns is (double)sums[j]: one rounding, to nearest even.
+ * dsq_fpm: one elementwise pass, every operation IEEE double in R's order and rounded once (no reciprocal, no folded
+ * constant); k = (double)y[i,j]:
+ *   DSQ_FPM             out[i,j] = 1e6 * (k / lib[j])                              R/helper.R:390
+ *   DSQ_FPKM_BASEPAIRS  out[i,j] = 1e3 * ((1e6 * (k / lib[j])) / basepairs[i])     R/helper.R:322
+ *   DSQ_FPKM_TXLEN      out[i,j] = (1e3 * (1e6 * (k / lib[j]))) / txlen[i,j]       R/helper.R:294
+ * lib: the m library sizes (colSums, or sizeFactors * exp(mean(log(colSums))): the caller's m numbers).  A zero library
+ * size gives NaN (0/0) or Inf, a NaN one NaN, as in R.
+ * _dev: device pointers, asynchronous on `stream`, nothing allocated, no host synchronisation; y gene-major with leading
+ * dimension ld >= m (padding is neither read nor written); txlen and the output of dsq_fpm_dev share y's ld; the output
+ * of dsq_collapse_dev has its own (>= g).  *status is zeroed by the caller.  members and offsets are device memory the
+ * entry cannot look at: an offset outside [0, m] is clipped, a member outside [0, m) is not read, and either ORs 2 into
+ * *status.
+ * dsq_collapse / dsq_col_sums / dsq_fpm: host pointers, matrices in R layout (column-major), ONE device, synchronous.
+ * dsq_collapse returns DSQ_ERR_VALUE when a sum is no int32 (out is then unspecified) and refuses members / offsets
+ * that are not such a CSR pair with DSQ_ERR_ARG.
+ * DSQ_ERR_ARG: struct_size not sizeof the block, n < 1, m < 1, g < 1 or g > m, ld < m or an output ld < g (_dev), an
+ * unknown kind, a NULL pointer the kind needs.  All decided before a device is asked for.                              */
+#define DSQ_FPM 0
+#define DSQ_FPKM_BASEPAIRS 1
+#define DSQ_FPKM_TXLEN 2
+typedef struct {
+    uint32_t struct_size;      /* sizeof(DsqCollapseArgs)                                                           */
+    int32_t n, m, g;           /* genes, samples, groups (1 <= g <= m)                                              */
+    int64_t ld;                /* _dev: leading dimension of y (>= m); dsq_collapse: ignored                         */
+    const int32_t *y;          /* n x m                                                                             */
+    const int32_t *members;    /* m sample indices, group by group                                                  */
+    const int32_t *offsets;    /* g + 1                                                                             */
+} DsqCollapseArgs;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(DsqCollapseOut)                                                            */
+    int64_t ld;                /* _dev: leading dimension of out (>= g); dsq_collapse: ignored                       */
+    int32_t *out;              /* n x g                                                                             */
+    int32_t *status;           /* _dev: one word, zeroed by the caller; dsq_collapse: may be NULL                   */
+} DsqCollapseOut;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(DsqColSumsArgs)                                                            */
+    int32_t n, m;
+    int64_t ld;                /* _dev: leading dimension of y (>= m); dsq_col_sums: ignored                         */
+    const int32_t *y;          /* n x m                                                                             */
+} DsqColSumsArgs;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(DsqColSumsOut)                                                             */
+    int64_t *sums;             /* m                                                                                 */
+} DsqColSumsOut;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(DsqFpmArgs)                                                                */
+    int32_t n, m;
+    int64_t ld;                /* _dev: leading dimension of y, txlen and out (>= m); dsq_fpm: ignored               */
+    const int32_t *y;          /* n x m                                                                             */
+    int32_t kind;              /* DSQ_FPM, DSQ_FPKM_BASEPAIRS, DSQ_FPKM_TXLEN                                       */
+    const double *lib;         /* m library sizes                                                                   */
+    const double *basepairs;   /* DSQ_FPKM_BASEPAIRS: n feature lengths; other kinds: ignored                       */
+    const double *txlen;       /* DSQ_FPKM_TXLEN: n x m average transcript lengths; other kinds: ignored            */
+} DsqFpmArgs;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(DsqFpmOut)                                                                 */
+    double *out;               /* n x m                                                                             */
+} DsqFpmOut;
+
+int dsq_collapse_dev(const DsqCollapseArgs *args, const DsqCollapseOut *out, void *stream);
+int dsq_collapse(const DsqCollapseArgs *args, const DsqCollapseOut *out);
+int dsq_col_sums_dev(const DsqColSumsArgs *args, const DsqColSumsOut *out, void *stream);
+int dsq_col_sums(const DsqColSumsArgs *args, const DsqColSumsOut *out);
+int dsq_fpm_dev(const DsqFpmArgs *args, const DsqFpmOut *out, void *stream);
+int dsq_fpm(const DsqFpmArgs *args, const DsqFpmOut *out);
+
 /* ---- dsq_results: results() for one coefficient (R/results.R:443-575, 638-740) -------------------
  * The table -- baseMean, log2FoldChange, lfcSE, stat, pvalue of design column c --, the threshold tests of :484-515 under
  * the normal distribution, pvalue NA where na_mask is set (the Cook's filter of :520-564 is the caller's: a host decision
