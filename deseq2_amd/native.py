@@ -1,15 +1,13 @@
-"""Python mirror of the reference's R/RcppExports.R:4,8,12 -- the three `.Call` stubs
-`fitDisp`, `fitBeta`, `fitDispGrid` -- bound to the MI355X engine instead of
-src/DESeq2.cpp.  Same argument names, same order, same return-list member names and
-types (`fitBeta$iter` is double, `fitDisp$iter` is integer; `contrast_num/denom` are
-n x 1 matrices; src/DESeq2.cpp:268-276, 458-464, 512).
-
-Two flavours:
-  fitBeta / fitDisp / fitDispGrid             numpy in, numpy out (host pointers through
-                                              dsq_fit_*; what the R shim does)
-  fitBeta_dev / fitDisp_dev / fitDispGrid_dev torch CUDA tensors in/out through
-                                              dsq_fit_*_dev on the current stream; matrices
-                                              may be R-layout or gene-major.
+"""The engine's entry points (include/deseq2_mi355x.h, bound in _lib) as Python functions: each builds the argument and
+output blocks of its entry, calls it and raises DsqError on a non-zero status.  The three `.Call` stubs of the reference's
+R/RcppExports.R:4,8,12 -- `fitDisp`, `fitBeta`, `fitDispGrid`: same argument names and order, same return-list members and
+types (`fitBeta$iter` is double, `fitDisp$iter` integer, `contrast_num/denom` n x 1 matrices; src/DESeq2.cpp:268-276,
+458-464, 512) --, the steps R runs around them (prefit moments, linear mu, log-likelihood, intercept fit, optim rows, the
+dispersion trend, the beta prior, Cook's distances, outlier replacement), DESeq() behind one call, and what surrounds an
+analysis: size factors (type "iterate" too), vst, rlog, unmix, results, contrasts, pt, sample PCA / distances,
+collapseReplicates, fpm / fpkm.  Two flavours:
+  name      numpy in, numpy out: host pointers in R layout through dsq_<entry> (what the R shim does)
+  name_dev  torch CUDA tensors in and out through dsq_<entry>_dev on the current stream, n x m matrices as GeneMajor handles
 """
 import ctypes as C
 
@@ -35,6 +33,27 @@ def _counts(y):
     if y.dtype.kind in "iu" or y.dtype == np.bool_:
         return np.asfortranarray(y.astype(np.int32, copy=False)), L.DSQ_Y_INT32
     return np.asfortranarray(y.astype(np.float64, copy=False)), L.DSQ_Y_FLOAT64
+
+
+def _need_matrix(y):
+    if y.ndim != 2:
+        raise ValueError("counts must be a matrix")
+    return y
+
+
+def _host_nf(nf, n, m):
+    """(nf, nf_is_vector) of a host `nf`: the m size factors or an n x m matrix"""
+    nf = np.asarray(nf, np.float64)
+    vec = nf.ndim == 1
+    nf = np.ascontiguousarray(nf) if vec else _fcol(nf)
+    if nf.shape != ((m,) if vec else (n, m)):
+        raise ValueError("nf must be the m size factors or an n x m matrix")
+    return nf, vec
+
+
+def _cells(cells):
+    """the cell_of / ncell pair of an argument block from the host array of design-cell ids (None: not known)"""
+    return dict(cell_of=_ptr(cells) if cells is not None else None, ncell=(int(cells.max()) + 1) if cells is not None else 0)
 
 
 def _scalar_len1(v, name):
@@ -455,8 +474,7 @@ def cooksDistance(counts, nf, mu, H, x):
     ck = np.zeros((n, m), order="F")
     mx, rd = np.zeros(n), np.zeros(n)
     args = L.DsqCooksArgs(n=n, m=m, p=np.asarray(x).shape[1], layout=L.DSQ_LAYOUT_R, ld=0, y=_ptr(y), y_type=ytype,
-                          nf=_ptr(nf), nf_is_vector=0, mu=_ptr(mu), H=_ptr(H), cell_of=_ptr(cells),
-                          ncell=int(cells.max()) + 1)
+                          nf=_ptr(nf), nf_is_vector=0, mu=_ptr(mu), H=_ptr(H), **_cells(cells))
     out = L.DsqCooksOut(cooks=_ptr(ck), maxCooks=_ptr(mx), robustDisp=_ptr(rd))
     L.check(L.lib().dsq_cooks_distance(C.byref(args), C.byref(out)))
     return {"cooks": ck, "maxCooks": mx, "robustDisp": rd}
@@ -491,9 +509,7 @@ def estimateSizeFactorsForMatrix(counts, type="ratio", geoMeans=None, controlGen
     if type not in L.DSQ_SF:
         raise ValueError("type should be 'ratio' or 'poscounts'")
     y, ytype = _counts(counts)
-    if y.ndim != 2:
-        raise ValueError("counts must be a matrix")
-    n, m = y.shape
+    n, m = _need_matrix(y).shape
     gm = None
     if geoMeans is not None:
         gm = np.ascontiguousarray(geoMeans, dtype=np.float64).reshape(-1)
@@ -535,14 +551,8 @@ def vst(counts, nf, kind="parametric", asymptDisp=None, extraPois=None, alpha=No
     dsq_vst: host arrays in R layout in, the n x m matrix out.  nf: the m size factors or an n x m matrix.  want_stats:
     also (rowMeans, row maxima) of the normalized counts."""
     y, ytype = _counts(counts)
-    if y.ndim != 2:
-        raise ValueError("counts must be a matrix")
-    n, m = y.shape
-    nf = np.asarray(nf, np.float64)
-    vec = nf.ndim == 1
-    nf = np.ascontiguousarray(nf) if vec else _fcol(nf)
-    if nf.shape != ((m,) if vec else (n, m)):
-        raise ValueError("nf must be the m size factors or an n x m matrix")
+    n, m = _need_matrix(y).shape
+    nf, vec = _host_nf(nf, n, m)
     kw, tab = _vst_args(kind, asymptDisp, extraPois, alpha, pc, table, eta, xi)
     out = np.zeros((n, m), order="F") if want_out else None
     rmean = np.zeros(n) if want_stats else None
@@ -560,14 +570,8 @@ def rlog(counts, nf, dispFit, betaPriorVar, intercept=None, tol=1e-4, maxit=100,
     (form A; None with an intercept given), iter, flag: 0 fitted, 1 row not fitted, 2 a non-finite coefficient).  nf: the
     m size factors or an n x m matrix; betaPriorVar on the log2 scale."""
     y, ytype = _counts(counts)
-    if y.ndim != 2:
-        raise ValueError("counts must be a matrix")
-    n, m = y.shape
-    nf = np.asarray(nf, np.float64)
-    vec = nf.ndim == 1
-    nf = np.ascontiguousarray(nf) if vec else _fcol(nf)
-    if nf.shape != ((m,) if vec else (n, m)):
-        raise ValueError("nf must be the m size factors or an n x m matrix")
+    n, m = _need_matrix(y).shape
+    nf, vec = _host_nf(nf, n, m)
     disp = np.ascontiguousarray(np.broadcast_to(np.asarray(dispFit, np.float64), (n,)))
     icpt = None
     if intercept is not None:
@@ -655,6 +659,21 @@ def gene_major_ld(m):
     return (m + 7) & ~7
 
 
+def _y_type(y):
+    import torch
+    return L.DSQ_Y_FLOAT64 if y.t.dtype == torch.float64 else L.DSQ_Y_INT32
+
+
+def _f64_like(y):
+    """an uninitialised GeneMajor float64 matrix of y's shape, padding columns zero (the kernel writes every sample column
+    exactly once: only the padding, which it leaves alone, is cleared)"""
+    import torch
+    out = GeneMajor(torch.empty((y.n, y.ld), dtype=torch.float64, device=y.t.device), y.m)
+    if y.ld > y.m:
+        out.t[:, y.m:] = 0.0
+    return out
+
+
 def fitBeta_dev(y, x, nf, alpha_hat, contrast, beta_mat, lambda_, weights, useWeights, tol, maxit, useQR,
                 minmu, want_hat=True, want_mu=False, mu_floor=0.0, nf_is_vector=False, cells=None):
     """All array arguments are torch CUDA tensors.  y / nf / weights: GeneMajor (y int32) --
@@ -684,9 +703,7 @@ def fitBeta_dev(y, x, nf, alpha_hat, contrast, beta_mat, lambda_, weights, useWe
                          alpha_hat=_t_ptr(alpha_hat), contrast=_t_ptr(contrast), beta_mat=_t_ptr(beta_mat),
                          lambda_=_t_ptr(lambda_), weights=_t_ptr(weights.t) if useWeights else None,
                          useWeights=int(bool(useWeights)), tol=float(tol), maxit=int(maxit),
-                         useQR=int(bool(useQR)), minmu=float(minmu),
-                         cell_of=_ptr(cells) if cells is not None else None,
-                         ncell=(int(cells.max()) + 1) if cells is not None else 0)
+                         useQR=int(bool(useQR)), minmu=float(minmu), **_cells(cells))
     o = L.DsqFitBetaOut(beta_mat=_t_ptr(out["beta_mat"]), beta_var_mat=_t_ptr(out["beta_var_mat"]),
                         iter=_t_ptr(out["iter"]), hat_diagonals=_t_ptr(hat.t) if hat else None,
                         contrast_num=_t_ptr(out["contrast_num"]), contrast_denom=_t_ptr(out["contrast_denom"]),
@@ -721,9 +738,7 @@ def fitDisp_dev(y, x, mu_hat, log_alpha, log_alpha_prior_mean, log_alpha_prior_s
                          min_log_alpha=float(min_log_alpha), kappa_0=float(kappa_0), tol=float(tol),
                          maxit=int(maxit), usePrior=int(bool(usePrior)),
                          weights=_t_ptr(weights.t) if useWeights else None, useWeights=int(bool(useWeights)),
-                         weightThreshold=float(weightThreshold), useCR=int(bool(useCR)),
-                         cell_of=_ptr(cells) if cells is not None else None,
-                         ncell=(int(cells.max()) + 1) if cells is not None else 0)
+                         weightThreshold=float(weightThreshold), useCR=int(bool(useCR)), **_cells(cells))
     o = L.DsqFitDispOut(**{k: _t_ptr(v) for k, v in out.items()})
     L.check(L.lib().dsq_fit_disp_dev(C.byref(a), C.byref(o), _stream()))
     out = {k: v for k, v in out.items() if v is not None}
@@ -744,9 +759,7 @@ def fitDispGrid_dev(y, x, mu_hat, disp_grid, log_alpha_prior_mean, log_alpha_pri
                              log_alpha_prior_mean=_t_ptr(log_alpha_prior_mean),
                              log_alpha_prior_sigmasq=float(log_alpha_prior_sigmasq), usePrior=int(bool(usePrior)),
                              weights=_t_ptr(weights.t) if useWeights else None, useWeights=int(bool(useWeights)),
-                             weightThreshold=float(weightThreshold), useCR=int(bool(useCR)),
-                             cell_of=_ptr(cells) if cells is not None else None,
-                             ncell=(int(cells.max()) + 1) if cells is not None else 0)
+                             weightThreshold=float(weightThreshold), useCR=int(bool(useCR)), **_cells(cells))
     o = L.DsqFitDispGridOut(log_alpha=_t_ptr(la))
     L.check(L.lib().dsq_fit_disp_grid_dev(C.byref(a), C.byref(o), _stream()))
     return {"log_alpha": la}
@@ -795,8 +808,8 @@ def sizeFactors_dev(y, type="ratio", geoMeans=None, control=None, normMatrix=Non
         control = torch.as_tensor(np.ascontiguousarray(control, dtype=np.int32), device=dev)
     wsb = int(L.lib().dsq_size_factors_workspace_bytes(n, m))
     ws = workspace if workspace is not None else torch.empty(wsb, dtype=torch.uint8, device=dev)
-    a = L.DsqSizeFactorArgs(n=n, m=m, layout=L.DSQ_LAYOUT_GENE_MAJOR, ld=ld, y=_t_ptr(y.t),
-                            y_type=L.DSQ_Y_FLOAT64 if y.t.dtype == torch.float64 else L.DSQ_Y_INT32, type=L.DSQ_SF[type],
+    a = L.DsqSizeFactorArgs(n=n, m=m, layout=L.DSQ_LAYOUT_GENE_MAJOR, ld=ld, y=_t_ptr(y.t), y_type=_y_type(y),
+                            type=L.DSQ_SF[type],
                             geoMeans=_t_ptr(geoMeans), control=_t_ptr(control),
                             normMatrix=_t_ptr(normMatrix.t) if normMatrix is not None else None,
                             workspace=_t_ptr(ws), workspace_bytes=int(ws.numel()))
@@ -816,8 +829,7 @@ def _vst_dev_args(y, nf):
         assert isinstance(nf, GeneMajor) and nf.ld == y.ld and nf.n == y.n
     else:
         assert nf.dtype == torch.float64 and nf.numel() == y.m and nf.is_contiguous()
-    return dict(n=y.n, m=y.m, layout=L.DSQ_LAYOUT_GENE_MAJOR, ld=y.ld, y=_t_ptr(y.t),
-                y_type=L.DSQ_Y_FLOAT64 if y.t.dtype == torch.float64 else L.DSQ_Y_INT32,
+    return dict(n=y.n, m=y.m, layout=L.DSQ_LAYOUT_GENE_MAJOR, ld=y.ld, y=_t_ptr(y.t), y_type=_y_type(y),
                 nf=_t_ptr(nf if vec else nf.t), nf_is_vector=int(vec))
 
 
@@ -826,13 +838,9 @@ def vst_dev(y, nf, kind="parametric", asymptDisp=None, extraPois=None, alpha=Non
     """dsq_vst_dev on resident counts: y GeneMajor (int32 or float64), nf the m size factors (a device tensor) or a
     GeneMajor matrix with y's ld; the spline table is a host array (5 x K).  Returns the transformed matrix as a GeneMajor
     handle (padding columns zero; `out`: a GeneMajor of y's shape to write into); nothing is read back."""
-    import torch
     kw, tab = _vst_args(kind, asymptDisp, extraPois, alpha, pc, table, eta, xi)
     if out is None:
-        # (the kernel writes every sample column exactly once: only the padding, which it leaves alone, is cleared)
-        out = GeneMajor(torch.empty((y.n, y.ld), dtype=torch.float64, device=y.t.device), y.m)
-        if y.ld > y.m:
-            out.t[:, y.m:] = 0.0
+        out = _f64_like(y)
     assert out.n == y.n and out.ld == y.ld and out.m == y.m
     a = L.DsqVstArgs(**_vst_dev_args(y, nf), **kw)
     o = L.DsqVstOut(out=_t_ptr(out.t), rowMean=None, rowMax=None, bad=_t_ptr(bad))
@@ -858,9 +866,7 @@ def rlog_dev(y, nf, dispFit, betaPriorVar, intercept=None, tol=1e-4, maxit=100, 
     import torch
     dev = y.t.device
     if out is None:
-        out = GeneMajor(torch.empty((y.n, y.ld), dtype=torch.float64, device=dev), y.m)
-        if y.ld > y.m:
-            out.t[:, y.m:] = 0.0
+        out = _f64_like(y)
     assert out.n == y.n and out.ld == y.ld and out.m == y.m
     assert dispFit.dtype == torch.float64 and dispFit.numel() == y.n and dispFit.is_contiguous()
     if intercept is not None:
@@ -986,10 +992,7 @@ def _icol(y):
     y = np.asarray(y)
     if y.dtype.kind not in "iu" and y.dtype != np.bool_:
         raise ValueError("counts must be an integer matrix")
-    y = np.asfortranarray(y.astype(np.int32, copy=False))
-    if y.ndim != 2:
-        raise ValueError("counts must be a matrix")
-    return y
+    return _need_matrix(np.asfortranarray(y.astype(np.int32, copy=False)))
 
 
 def _csr(members, offsets):
@@ -1087,9 +1090,7 @@ def fpm_dev(y, lib, kind="fpm", basepairs=None, txlen=None):
         assert basepairs.dtype == torch.float64 and basepairs.numel() == y.n and basepairs.is_contiguous()
     if txlen is not None:
         assert isinstance(txlen, GeneMajor) and txlen.t.dtype == torch.float64 and txlen.ld == y.ld and txlen.n == y.n
-    out = GeneMajor(torch.empty((y.n, y.ld), dtype=torch.float64, device=y.t.device), y.m)
-    if y.ld > y.m:
-        out.t[:, y.m:] = 0.0
+    out = _f64_like(y)
     a = L.sized(L.DsqFpmArgs, n=y.n, m=y.m, ld=y.ld, y=_t_ptr(y.t), kind=L.DSQ_FPM[kind], lib=_t_ptr(lib),
                 basepairs=_t_ptr(basepairs), txlen=None if txlen is None else _t_ptr(txlen.t))
     o = L.sized(L.DsqFpmOut, out=_t_ptr(out.t))
@@ -1229,8 +1230,7 @@ def cooksDistance_dev(y, nf, mu, H, cell_of, p, nf_is_vector=False):
     mx, rd = pack[0], pack[1]
     args = L.DsqCooksArgs(n=n, m=m, p=int(p), layout=L.DSQ_LAYOUT_GENE_MAJOR, ld=ld, y=_t_ptr(y.t),
                           y_type=L.DSQ_Y_INT32, nf=_t_ptr(nf if nf_is_vector else nf.t),
-                          nf_is_vector=int(nf_is_vector), mu=_t_ptr(mu.t), H=_t_ptr(H.t), cell_of=_ptr(cells),
-                          ncell=int(cells.max()) + 1)
+                          nf_is_vector=int(nf_is_vector), mu=_t_ptr(mu.t), H=_t_ptr(H.t), **_cells(cells))
     out = L.DsqCooksOut(cooks=_t_ptr(ck), maxCooks=_t_ptr(mx), robustDisp=_t_ptr(rd))
     L.check(L.lib().dsq_cooks_distance_dev(C.byref(args), C.byref(out), _stream()))
     return {"cooks": GeneMajor(ck, m), "maxCooks": mx, "robustDisp": rd, "_pack": pack}

@@ -1,5 +1,6 @@
 """CPU: the C-ABI library loads, exports every symbol include/deseq2_mi355x.h declares, and
-fails loudly (no CPU fallback) when no GPU is present.  No compute calls here."""
+fails loudly (no CPU fallback) when no GPU is present; the ctypes binding (deseq2_amd/_lib.py) is held whole to the header:
+every struct layout, every signature, every constant.  No compute calls here."""
 import ctypes
 import os
 import re
@@ -10,10 +11,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _header_symbols():
+def _header():
+    """include/deseq2_mi355x.h without its comments"""
     h = open(os.path.join(ROOT, "include", "deseq2_mi355x.h")).read()
-    h = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
-    return sorted(set(re.findall(r"\b(dsq_[a-z0-9_]+)\s*\(", h)))
+    return re.sub(r"/\*.*?\*/", "", h, flags=re.S)
+
+
+def _header_symbols():
+    return sorted(set(re.findall(r"\b(dsq_[a-z0-9_]+)\s*\(", _header())))
 
 
 def test_library_exports_every_declared_symbol():
@@ -27,33 +32,138 @@ def test_library_exports_every_declared_symbol():
     assert L.dsq_version() == 100
 
 
-def test_struct_layout_matches_header():
-    """ctypes mirrors of the argument blocks: sizes and the offset of every field as the C compiler lays them out"""
+# ---- deseq2_amd/_lib.py against the header: layouts, signatures, constants.  gcc and the header only, no built library ----
+def _compiled(statements):
+    """the lines a C program of these statements prints, compiled against the header"""
     import subprocess
     import tempfile
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "deseq2_mi355x.h"\n#define SZ(T, f) sizeof(((T *)0)->f)\n'
+           'int main(void){\n%s\nreturn 0; }\n' % "\n".join(statements))
+    with tempfile.TemporaryDirectory() as td:
+        c, exe = os.path.join(td, "s.c"), os.path.join(td, "s")
+        open(c, "w").write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
+        return subprocess.check_output([exe]).decode().strip().splitlines()
+
+
+def test_struct_layout_matches_header():
+    """every block the header defines has its ctypes mirror and no other exists: size, and the offset and size of every
+    field, as the C compiler lays them out; the last field mirrored ends where the block ends, so that a field missing at
+    the tail fails even where padding would hide it"""
     from deseq2_amd import _lib
-    names = ["DsqFitBetaArgs", "DsqFitBetaOut", "DsqFitDispArgs", "DsqFitDispOut", "DsqFitDispGridArgs",
-             "DsqFitDispGridOut", "DsqPrefitArgs", "DsqPrefitOut", "DsqLogLikeArgs", "DsqInterceptArgs",
-             "DsqInterceptOut", "DsqOptimArgs", "DsqOptimOut", "DsqCooksArgs", "DsqCooksOut", "DsqReplaceArgs", "DsqReplaceOut", "DsqDeseqArgs",
-             "DsqDeseqOut"]
+    names = re.findall(r"\}\s*(Dsq\w+)\s*;", _header())
+    assert len(names) >= 46 and len(set(names)) == len(names)
+    mirrors = {v.__name__ for v in vars(_lib).values() if isinstance(v, type) and issubclass(v, ctypes.Structure)
+               and v.__name__.startswith("Dsq")}
+    assert mirrors == set(names), sorted(mirrors ^ set(names))
     lines = []
     for nm in names:
         t = getattr(_lib, nm)
-        lines.append('printf("%%zu", sizeof(%s));' % nm)
+        assert t.__name__ == nm
+        lines.append('printf("%%zu %%zu", sizeof(%s), _Alignof(%s));' % (nm, nm))
         for f, _ in t._fields_:
-            lines.append('printf(" %%zu", offsetof(%s, %s));' % (nm, "lambda" if f == "lambda_" else f))
+            c = "lambda" if f == "lambda_" else f
+            lines.append('printf(" %%zu %%zu", offsetof(%s, %s), SZ(%s, %s));' % (nm, c, nm, c))
         lines.append('printf("\\n");')
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "deseq2_mi355x.h"\nint main(void){\n%s\nreturn 0; }\n' % "\n".join(lines)
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, "s.c"); exe = os.path.join(td, "s")
-        open(c, "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        out = subprocess.check_output([exe]).decode().strip().splitlines()
+    out = _compiled(lines)
+    assert len(out) == len(names)
     for nm, line in zip(names, out):
         t = getattr(_lib, nm)
-        got = list(map(int, line.split()))
-        want = [ctypes.sizeof(t)] + [getattr(t, f).offset for f, _ in t._fields_]
-        assert got == want, nm
+        size, align, *fields = map(int, line.split())
+        want = [ctypes.sizeof(t), ctypes.alignment(t)] + [v for f, _ in t._fields_ for v in (getattr(t, f).offset, getattr(t, f).size)]
+        assert [size, align] + fields == want, nm
+        end = fields[-2] + fields[-1]
+        assert -(-end // align) * align == size, "%s: fields are missing behind %s" % (nm, t._fields_[-1][0])
+
+
+def _prototypes():
+    """{name: (return type, [parameter types])} of every function the header declares, as C spells them"""
+    protos = {}
+    for ret, name, params in re.findall(r"^[ \t]*((?:const\s+)?\w+(?:\s*\*)?)\s*\b(dsq_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header(), flags=re.M):
+        assert name not in protos, name
+        params = [" ".join(q.split()) for q in params.split(",")]
+        protos[name] = (" ".join(ret.split()), [] if params == ["void"] else params)
+    return protos
+
+
+def _ctype_of(c_type, _lib, is_return=False):
+    """the ctypes type(s) that may stand for a C parameter (its name still attached) or return type"""
+    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double}
+    if "*" in c_type:
+        base = c_type[:c_type.index("*")].replace("const", "").strip()
+        if base.startswith("Dsq"):
+            return (ctypes.POINTER(getattr(_lib, base)),)
+        if is_return:
+            assert base == "char", c_type
+            return (ctypes.c_char_p,)
+        return (ctypes.c_void_p, ctypes.c_char_p)
+    base = c_type if is_return else c_type.rsplit(" ", 1)[0]          # `int32_t n` -> int32_t
+    return (scalars[base],)
+
+
+def test_signatures_match_header():
+    """the signature table names the functions the header declares, each with the prototype's parameter count, scalar widths,
+    argument blocks and return type"""
+    from deseq2_amd import _lib
+    protos = _prototypes()
+    assert sorted(protos) == _header_symbols() and len(protos) >= 83           # no prototype escaped the strict pattern
+    assert sorted(_lib.SIGNATURES) == sorted(protos)
+    assert _lib.EXPORTED_SYMBOLS == list(_lib.SIGNATURES)
+    assert {"dsq_pt_dev", "dsq_weights_prep_dev", "dsq_beta_prior_var_dev"} <= set(protos)      # the multi-line ones
+    for name, (ret, params) in protos.items():
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert argtypes is not None and len(argtypes) == len(params), name
+        assert restype in _ctype_of(ret, _lib, is_return=True), (name, ret, restype)
+        for i, (c_type, t) in enumerate(zip(params, argtypes)):
+            assert t in _ctype_of(c_type, _lib), (name, i, c_type, t)
+
+
+def _c_spelling(key):
+    """the header's spelling of a key of the Python-side families: upper case, camel humps split"""
+    s = re.sub(r"([A-Z][a-z]+)(?=\d)", r"\1_", key)       # a number behind a hump is one of its own: Abs2014 -> Abs_2014
+    return re.sub(r"(?<=[a-z])(?=[A-Z])", "_", s).upper()
+
+
+# header constants that Python deliberately does not mirror
+_NOT_MIRRORED = {"DSQ_VERSION": "the library reports it: dsq_version() is held to 100 in test_library_exports_every_declared_symbol"}
+
+
+def test_constants_match_header():
+    """from the header to Python: every DSQ_* macro and enumerator, with the value the C compiler gives it, is mirrored by
+    exactly one rule -- a module attribute of its name or a key of its family's dict -- or is exempted by name"""
+    from deseq2_amd import _lib
+    assert [_c_spelling(k) for k in ("greaterAbs2014", "two_sided", "Wald", "LRT", "dist2", "parametric_or_mean")] == [
+        "GREATER_ABS_2014", "TWO_SIDED", "WALD", "LRT", "DIST2", "PARAMETRIC_OR_MEAN"]
+    h = _header()
+    names = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(DSQ_\w+)[ \t]+\S", h, flags=re.M)
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", h):
+        names += re.findall(r"\b(DSQ_\w+)\b", body)
+    assert len(names) >= 70 and len(set(names)) == len(names)
+    out = _compiled(['printf("%%lld\\n", (long long)(%s));' % nm for nm in names])
+    header = dict(zip(names, map(int, out)))
+    assert len(out) == len(names)
+    # (prefix, dict): key k mirrors <prefix>_<_c_spelling(k)>; DSQ_FPM is the irregular family: DSQ_FPM, DSQ_FPKM_*
+    families = [("DSQ_" + f, getattr(_lib, "DSQ_" + f)) for f in ("TEST", "ALT", "PT", "VST", "SF", "PAIRS", "FIT", "ST")]
+    families.append(("DSQ", _lib.DSQ_FPM))
+    mirror = {}
+    for prefix, d in families:
+        for k, v in d.items():
+            mirror.setdefault(prefix + "_" + _c_spelling(k), []).append(v)
+    assert set(mirror) <= set(header), sorted(set(mirror) - set(header))         # no key without its constant
+    for nm in header:
+        claims = list(mirror.get(nm, []))
+        if isinstance(getattr(_lib, nm, None), int):
+            claims.append(getattr(_lib, nm))
+        if nm in _NOT_MIRRORED:
+            assert not claims, nm
+            continue
+        assert len(claims) == 1, "%s is mirrored %d times" % (nm, len(claims))
+        assert claims[0] == header[nm], (nm, claims[0], header[nm])
+    assert set(_NOT_MIRRORED) <= set(header)
+    assert header["DSQ_VERSION"] == 100
+    assert _lib.ERR_NAMES == {v: nm for nm, v in header.items() if nm.startswith("DSQ_ERR_")}
+    # every module-level DSQ_* integer is one of the header's, too
+    assert {k for k, v in vars(_lib).items() if k.startswith("DSQ_") and isinstance(v, int)} <= set(header)
 
 
 def test_no_cpu_fallback_without_gpu():

@@ -2,14 +2,10 @@
 tests/test_capi_cpu.py: every check is decided from the argument block before a device is asked for, so the codes hold with
 and without a GPU (1 = DSQ_ERR_ARG, 2 = DSQ_ERR_UNSUPPORTED)."""
 import ctypes
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
 
 
@@ -111,22 +107,3 @@ def test_max_m_follows_the_lds():
     assert v == sorted(v, reverse=True) and v[-1] >= 1024
     for p, got in zip((1, 16, 32, 64), v):
         assert 8 * (3 * p * p + got) <= 160 * 1024 < 8 * (3 * p * p + got) + 8 * (4 * p + 300)
-
-
-def test_struct_layout_matches_header():
-    from deseq2_amd import _lib
-    names = ["DsqContrastsArgs", "DsqContrastsOut"]
-    lines = []
-    for nm in names:
-        lines.append('printf("%%zu", sizeof(%s));' % nm)
-        lines += ['printf(" %%zu", offsetof(%s, %s));' % (nm, "lambda" if f == "lambda_" else f) for f, _ in getattr(_lib, nm)._fields_]
-        lines.append('printf("\\n");')
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "deseq2_mi355x.h"\nint main(void){\n%s\nreturn 0; }\n' % "\n".join(lines)
-    with tempfile.TemporaryDirectory() as td:
-        c, exe = os.path.join(td, "s.c"), os.path.join(td, "s")
-        open(c, "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        out = subprocess.check_output([exe]).decode().strip().splitlines()
-    for nm, line in zip(names, out):
-        t = getattr(_lib, nm)
-        assert list(map(int, line.split())) == [ctypes.sizeof(t)] + [getattr(t, f).offset for f, _ in t._fields_], nm

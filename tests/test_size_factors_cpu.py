@@ -1,15 +1,10 @@
 """estimateSizeFactors without a GPU: the host statement (HostEngine.size_factors, core.estimateSizeFactors) against the
-numpy specification of tests/sf_spec.py, tests/testthat/test_size_factor.R restated, the C layout of the two new argument
-blocks, and DESeq(sfType=...) on the oracle engine."""
-import ctypes
-import os
+numpy specification of tests/sf_spec.py, tests/testthat/test_size_factor.R restated, and DESeq(sfType=...) on the oracle engine."""
 
 import numpy as np
 import pytest
 
 from tests import sf_spec
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _counts(n, m, seed, zeros=0.1):
@@ -188,29 +183,9 @@ def test_control_genes_argument_forms():
         control_flags([1, 1], 5)
 
 
-def test_size_factor_struct_layout_matches_header():
-    """the ctypes mirrors of DsqSizeFactorArgs / DsqSizeFactorOut against the C compiler (as
-    test_capi_cpu.test_struct_layout_matches_header does for the other argument blocks)"""
-    import subprocess
-    import tempfile
+def test_size_factor_entries_are_exported():
+    """(the layout of DsqSizeFactorArgs / DsqSizeFactorOut: test_capi_cpu.test_struct_layout_matches_header)"""
     from deseq2_amd import _lib
-    names = ["DsqSizeFactorArgs", "DsqSizeFactorOut"]
-    lines = []
-    for nm in names:
-        t = getattr(_lib, nm)
-        lines.append('printf("%%zu", sizeof(%s));' % nm)
-        for f, _ in t._fields_:
-            lines.append('printf(" %%zu", offsetof(%s, %s));' % (nm, f))
-        lines.append('printf("\\n");')
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "deseq2_mi355x.h"\nint main(void){\n%s\nreturn 0; }\n' % "\n".join(lines)
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, "s.c"); exe = os.path.join(td, "s")
-        open(c, "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        out = subprocess.check_output([exe]).decode().strip().splitlines()
-    for nm, line in zip(names, out):
-        t = getattr(_lib, nm)
-        assert list(map(int, line.split())) == [ctypes.sizeof(t)] + [getattr(t, f).offset for f, _ in t._fields_], nm
     for s in ("dsq_size_factors", "dsq_size_factors_dev", "dsq_size_factors_workspace_bytes"):
         assert s in _lib.EXPORTED_SYMBOLS and hasattr(_lib.lib(), s)
     assert _lib.lib().dsq_size_factors_workspace_bytes(1000, 70) >= 1000 * 8 + 70 * 1024
