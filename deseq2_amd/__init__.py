@@ -12,9 +12,10 @@ from .core import pt  # noqa: F401
 from .core import unmix  # noqa: F401
 from .core import rowVars, sampleDists, pca, plotPCA, PCAData  # noqa: F401
 from .core import collapseReplicates, fpm, fpkm, counts, plotCounts  # noqa: F401
+from .core import localDispersionFit  # noqa: F401
 
 __all__ = ["fitBeta", "fitDisp", "fitDispGrid", "estimateSizeFactors", "estimateSizeFactorsForMatrix", "vst",
            "varianceStabilizingTransformation", "getVarianceStabilizedData", "normTransform", "normalized_counts",
            "DESeqTransform", "results", "resultsContrasts", "resultsNames", "DESeqResults", "p_adjust", "pvalueAdjustment", "lowess",
            "pt", "unmix", "rowVars", "sampleDists", "pca", "plotPCA", "PCAData", "collapseReplicates", "fpm", "fpkm", "counts",
-           "plotCounts"]
+           "plotCounts", "localDispersionFit"]

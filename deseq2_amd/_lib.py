@@ -140,6 +140,8 @@ DsqColSumsArgs = _struct("DsqColSumsArgs", "u struct_size; i n m; l ld; p y")
 DsqColSumsOut = _struct("DsqColSumsOut", "u struct_size; p sums")
 DsqFpmArgs = _struct("DsqFpmArgs", "u struct_size; i n m; l ld; p y; i kind; p lib basepairs txlen")
 DsqFpmOut = _struct("DsqFpmOut", "u struct_size; p out")
+DsqLocalFitArgs = _struct("DsqLocalFitArgs", "u struct_size; i n; p means disps; d minDisp; p fit_in; i n_eval; p eval_means")
+DsqLocalFitOut = _struct("DsqLocalFitOut", "u struct_size; p fit dispFit status")
 DsqResultsArgs = _struct("DsqResultsArgs", "i n p c test; p beta betaSE stat pvalue baseMean replace na_mask; d lfcThreshold;"
                          " i altHypothesis independentFiltering; p filter theta; i K; d alpha; p workspace; l workspace_bytes;"
                          " p df")
@@ -187,6 +189,7 @@ for _name, _a, _o in (("dsq_prefit_moments", DsqPrefitArgs, DsqPrefitOut), ("dsq
                       ("dsq_rlog", DsqRlogArgs, DsqRlogOut), ("dsq_top_var", DsqTopVarArgs, DsqTopVarOut),
                       ("dsq_sample_pairs", DsqSamplePairsArgs, DsqSamplePairsOut), ("dsq_collapse", DsqCollapseArgs, DsqCollapseOut),
                       ("dsq_col_sums", DsqColSumsArgs, DsqColSumsOut), ("dsq_fpm", DsqFpmArgs, DsqFpmOut),
+                      ("dsq_local_fit", DsqLocalFitArgs, DsqLocalFitOut),
                       ("dsq_results", DsqResultsArgs, DsqResultsOut), ("dsq_contrasts", DsqContrastsArgs, DsqContrastsOut)):
     _pair(_name, *_blocks(_a, _o))
 _pair("dsq_nbinom_loglike", C.POINTER(DsqLogLikeArgs), _P)
@@ -216,8 +219,9 @@ for _name in ("dsq_to_gene_major_f64", "dsq_to_gene_major_i32", "dsq_from_gene_m
     _sig(_name, _P, _P, _I32, _I32, _I64, _P)                    # src, dst, n, m, ld, stream
 _sig("dsq_counts_f64_to_gene_major_i32", _P, _P, _I32, _I32, _I64, _P, _P)
 _sig("dsq_test_math", _I, _P, _P, _P, _P, _I64)
-for _name in ("dsq_unmix_block_threads", "dsq_sf_iterate_slice_genes", "dsq_row_vars_register_width"):
+for _name in ("dsq_unmix_block_threads", "dsq_sf_iterate_slice_genes", "dsq_row_vars_register_width", "dsq_local_fit_lanes"):
     _sig(_name, res=_I32)
+_sig("dsq_local_fit_block_doubles", _I32, res=_I64)
 _sig("dsq_sample_pairs_slice_rows", _I64, _I32, res=_I64)
 _sig("dsq_contrasts_max_m", _I32, res=_I32)
 for _name in ("dsq_version", "dsq_device_count", "dsq_release_workspace", "dsq_profile_count"):

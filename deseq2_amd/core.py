@@ -700,9 +700,30 @@ def trimmed_mean_fit(dge, minDisp=1e-8, trim=0.001):
     return math.ldexp(float(mant), shift - 128)
 
 
-def estimateDispersionsFit(dds, fitType="parametric", minDisp=1e-8, engine=None):
-    """R/core.R:864-939 + `dispersionFunction<-` (R/methods.R:142-190)"""
+LOCAL_SUBSTITUTED = ("-- note: fitType='parametric', but the dispersion trend was not well captured by the\n"
+                     "   function: y = a/x + b, and a local regression fit was automatically substituted.\n"
+                     "   specify fitType='local' or 'mean' to avoid this message next time.")
+
+
+def localDispersionFit(dds_or_engine, means, disps, minDisp=1e-8):
+    """R/core.R:2194-2203: the function of the mean that fitType = "local" fits to the genes handed in -- the estimator behind
+    locfit(logDisps ~ logMeans, weights = means) at locfit's defaults, evaluated directly at every mean it is called on
+    (locfit interpolates between the vertices of a tree, so its values are not pinned).  The
+    fit and every evaluation run on the engine (the device engine's on the device).  When all disps are below 10 minDisp
+    the constant function minDisp comes back, where R returns a vector that cannot be called."""
+    E = getattr(dds_or_engine, "engine", dds_or_engine)
+    return E.local_fit(means, disps, minDisp)
+
+
+def estimateDispersionsFit(dds, fitType="parametric", minDisp=1e-8, engine=None, parametricFallback="mean"):
+    """R/core.R:864-939 + `dispersionFunction<-` (R/methods.R:142-190).  parametricFallback: what a parametric trend that
+    does not fit is answered with -- "mean" (this library's default) or "local" (the reference's substitution and its
+    message, :888-893)."""
     E = engine if engine is not None else dds.engine
+    if not callable(fitType) and fitType not in ("parametric", "local", "mean"):
+        raise ValueError("fitType should be one of 'parametric', 'local', 'mean'")
+    if parametricFallback not in ("mean", "local"):
+        raise ValueError("parametricFallback should be 'mean' or 'local'")
     dge, bm = dds.mcols["dispGeneEst"], dds.mcols["baseMean"]
     useForFit = dge > 100 * minDisp
     if useForFit.sum() == 0:
@@ -712,7 +733,12 @@ def estimateDispersionsFit(dds, fitType="parametric", minDisp=1e-8, engine=None)
             coefs = E.parametric_fit(bm[useForFit], dge[useForFit])
             fn = ("parametric", coefs)
         except RuntimeError:
-            fitType = "mean"       # the reference falls back to locfit (not available here)
+            fitType = parametricFallback
+            if fitType == "local":
+                import sys
+                print(LOCAL_SUBSTITUTED, file=sys.stderr)
+    if fitType == "local":
+        fn = ("local", localDispersionFit(E, bm[useForFit], dge[useForFit], minDisp))
     if fitType == "mean":
         fn = ("mean", trimmed_mean_fit(dge, minDisp))                                  # mean(trim = 0.001)
     if callable(fitType):
@@ -722,7 +748,7 @@ def estimateDispersionsFit(dds, fitType="parametric", minDisp=1e-8, engine=None)
         fn = ("custom", fitType(bm[useForFit], dge[useForFit]))
     if fn[0] == "parametric":
         dispFit = fn[1][0] + fn[1][1] / bm
-    elif fn[0] == "custom":
+    elif fn[0] in ("custom", "local"):
         with np.errstate(invalid="ignore", divide="ignore"):
             dispFit = np.asarray(fn[1](bm), dtype=np.float64)
     else:
@@ -795,12 +821,13 @@ def estimateDispersionsMAP(dds, outlierSD=2, dispPriorVar=None, minDisp=1e-8, ka
     return dds
 
 
-def estimateDispersions(dds, fitType="parametric", maxit=100, dispPriorVar=None, **kw):
+def estimateDispersions(dds, fitType="parametric", maxit=100, dispPriorVar=None, parametricFallback="mean", **kw):
     """R/methods.R:500-563 (maxit is handed to both dispersion searches, :520,:546).  dispPriorVar: the argument of
     estimateDispersionsMAP (R/core.R:989-994) for callers that run the three steps themselves -- the way an analysis with
-    residual df <= 3 gets its prior variance (R's estimate there needs R's RNG, :1155-1190)."""
+    residual df <= 3 gets its prior variance (R's estimate there needs R's RNG, :1155-1190).  parametricFallback: see
+    estimateDispersionsFit."""
     estimateDispersionsGeneEst(dds, maxit=maxit, **kw)
-    estimateDispersionsFit(dds, fitType=fitType)
+    estimateDispersionsFit(dds, fitType=fitType, parametricFallback=parametricFallback)
     estimateDispersionsMAP(dds, maxit=maxit, dispPriorVar=dispPriorVar, modelMatrix=kw.get("modelMatrix"))   # (R/methods.R:546)
     return dds
 
@@ -1105,7 +1132,7 @@ def _dispersion_function(dds, baseMean):
     fn = dds.dispersionFunction
     if fn["fitType"] == "parametric":
         return fn["coefficients"][0] + fn["coefficients"][1] / baseMean
-    if fn["fitType"] == "custom":
+    if fn["fitType"] in ("custom", "local"):
         return np.asarray(fn["coefficients"](baseMean), dtype=np.float64)
     return np.full(baseMean.shape, fn["coefficients"])
 
@@ -1211,7 +1238,9 @@ def cooksOutlier(dds, cooksCutoff=None):
 
 def _DESeqNZ(dds, test, fitType, reduced, minReplicatesForReplace, disp_maxit=100, **kw):
     dpv = kw.pop("dispPriorVar", None)      # (not an argument of R's DESeq(): of estimateDispersionsMAP, R/core.R:989-994)
-    estimateDispersions(dds, fitType=fitType, maxit=disp_maxit, minmu=kw.get("minmu", 0.5), dispPriorVar=dpv)      # R/core.R:393
+    fallback = kw.pop("parametricFallback", "mean")                  # (nor this one: of estimateDispersionsFit here)
+    estimateDispersions(dds, fitType=fitType, maxit=disp_maxit, minmu=kw.get("minmu", 0.5), dispPriorVar=dpv,
+                        parametricFallback=fallback)                                                                # R/core.R:393
     if test == "Wald":
         nbinomWaldTest(dds, **kw)
     elif test == "LRT":
@@ -1391,8 +1420,9 @@ def vst_subset_rows(baseMean, nsub):
 
 def getVarianceStabilizedData(dds):
     """R/vst.R:146-193: the transformation that belongs to the object's dispersion function, applied to the normalized
-    counts by the engine in one pass.  fitType "custom" (the caller's trend: what R reaches as "local") takes the spline
-    path.  Returns the n x m engine handle."""
+    counts by the engine in one pass.  fitType "local" and "custom" (the caller's trend) take the spline path of :157-183:
+    the trend is evaluated at the grid values through the function, i.e. for "local" on the engine.  Returns the n x m
+    engine handle."""
     fn = dds.dispersionFunction
     if fn is None or fn.get("fitType") is None:
         raise ValueError("call estimateDispersions before calling getVarianceStabilizedData")
@@ -1403,7 +1433,7 @@ def getVarianceStabilizedData(dds):
         return E.vst_transform(dds.y, nf, "parametric", sizeFactors=sf, asymptDisp=a, extraPois=e)
     if fn["fitType"] == "mean":
         return E.vst_transform(dds.y, nf, "mean", sizeFactors=sf, alpha=float(fn["coefficients"]))
-    if fn["fitType"] == "custom":
+    if fn["fitType"] in ("custom", "local"):
         sfa = sf if sf is not None else E.nf_col_geomeans(nf)                    # :159-165
         xim = float(np.mean(1.0 / np.asarray(sfa, np.float64)))
         rmean, rmax = E.row_stats(dds.y, nf, sizeFactors=sf)

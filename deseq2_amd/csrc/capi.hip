@@ -918,6 +918,42 @@ int sample_pairs_dev_locked(const DsqSamplePairsArgs *a, const DsqSamplePairsOut
     return DSQ_OK;
 }
 
+// the local-regression dispersion trend (local_fit.hip): what both entries check before anything is launched
+int local_fit_check(const DsqLocalFitArgs *a, const DsqLocalFitOut *o) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->struct_size != sizeof *a || o->struct_size != sizeof *o) return capi_fail(DSQ_ERR_ARG, "struct_size is not sizeof the block");
+    if (a->n < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
+    if (!o->status) return capi_fail(DSQ_ERR_ARG, "NULL status");
+    if (!(a->minDisp > 0.0)) return capi_fail(DSQ_ERR_ARG, "minDisp must be > 0");
+    if (a->n_eval < 0 || (a->eval_means ? a->n_eval < 1 : a->n_eval != 0))
+        return capi_fail(DSQ_ERR_ARG, "n_eval = %d: %s", a->n_eval, a->eval_means ? "an evaluation list has at least one entry" : "0 without eval_means");
+    if (a->fit_in) {
+        if (!a->eval_means || !o->dispFit) return capi_fail(DSQ_ERR_ARG, "fit_in: eval_means and dispFit are needed");
+    } else if (!a->means || !a->disps) return capi_fail(DSQ_ERR_ARG, "NULL means or disps");
+    if (a->eval_means && !o->dispFit) return capi_fail(DSQ_ERR_ARG, "eval_means without dispFit");
+    return DSQ_OK;
+}
+
+int local_fit_dev_locked(const DsqLocalFitArgs *a, const DsqLocalFitOut *o, hipStream_t st) {
+    if (int rc = local_fit_check(a, o)) return rc;
+    if (int rc = capi_check_device()) return rc;
+    const double *block = a->fit_in;
+    capi_prof_begin("local_fit", a->n, st);
+    if (!block) {
+        void *w, *b = o->fit;
+        if (int rc = capi_ws_get(WS_SCRATCH, local_fit_workspace_bytes(a->n), &w)) return rc;
+        if (!b)
+            if (int rc = capi_ws_get(WS_TREND, (kLocalFitHeaderDoubles + 3 * (size_t)a->n) * 8, &b)) return rc;
+        DSQ_HIP(launch_local_fit_build(a->means, a->disps, a->n, a->minDisp, (double *)b, w, st));
+        block = (const double *)b;
+    }
+    const double *q = a->eval_means ? a->eval_means : a->means;
+    const long nq = !o->dispFit ? 0 : a->eval_means ? a->n_eval : a->n;
+    DSQ_HIP(launch_local_fit_eval(block, q, nq, o->dispFit, o->status, st));
+    capi_prof_end(st);
+    return DSQ_OK;
+}
+
 // collapseReplicates / colSums / fpm / fpkm (count_helpers.hip): what both entries check before anything is launched
 int collapse_check(const DsqCollapseArgs *a, const DsqCollapseOut *o) {
     if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
@@ -1178,6 +1214,7 @@ DSQ_DEV(dsq_sample_pairs_dev, DsqSamplePairsArgs, const DsqSamplePairsOut *, sam
 DSQ_DEV(dsq_collapse_dev, DsqCollapseArgs, const DsqCollapseOut *, collapse_dev_locked(a, o, st))
 DSQ_DEV(dsq_col_sums_dev, DsqColSumsArgs, const DsqColSumsOut *, col_sums_dev_locked(a, o, st))
 DSQ_DEV(dsq_fpm_dev, DsqFpmArgs, const DsqFpmOut *, fpm_dev_locked(a, o, st))
+DSQ_DEV(dsq_local_fit_dev, DsqLocalFitArgs, const DsqLocalFitOut *, local_fit_dev_locked(a, o, st))
 #undef DSQ_DEV
 int dsq_linear_mu_dev(const DsqPrefitArgs *a, double mu_floor, double *mu, void *s) {
     return dev_entry(s, [&](hipStream_t st) { return linear_mu_dev_locked(a, mu_floor, mu, st); });
@@ -1221,6 +1258,9 @@ int64_t dsq_sample_pairs_slice_rows(int64_t rows_summed, int32_t m) {
     return (int64_t)ps.L;
 }
 int32_t dsq_row_vars_register_width(void) { return row_vars_register_width(); }
+
+int32_t dsq_local_fit_lanes(void) { return kLocalFitLanes; }
+int64_t dsq_local_fit_block_doubles(int32_t n) { return n < 1 ? 0 : kLocalFitHeaderDoubles + 3 * (int64_t)n; }
 
 int64_t dsq_size_factors_workspace_bytes(int32_t n, int32_t m) {
     if (n < 0 || m < 0) return 0;

@@ -60,6 +60,7 @@ int sample_pairs_check(const DsqSamplePairsArgs *a, const DsqSamplePairsOut *o);
 int collapse_check(const DsqCollapseArgs *a, const DsqCollapseOut *o);
 int col_sums_check(const DsqColSumsArgs *a, const DsqColSumsOut *o);
 int fpm_check(const DsqFpmArgs *a, const DsqFpmOut *o);
+int local_fit_check(const DsqLocalFitArgs *a, const DsqLocalFitOut *o);
 int results_check(const DsqResultsArgs *a, const DsqResultsOut *o);
 int contrasts_check(const DsqContrastsArgs *a, const DsqContrastsOut *o);
 int pt_check(const double *q, const double *df, int32_t n, int32_t K, int32_t tail, const double *out);
@@ -84,6 +85,7 @@ int sample_pairs_dev_locked(const DsqSamplePairsArgs *a, const DsqSamplePairsOut
 int collapse_dev_locked(const DsqCollapseArgs *a, const DsqCollapseOut *o, hipStream_t st);
 int col_sums_dev_locked(const DsqColSumsArgs *a, const DsqColSumsOut *o, hipStream_t st);
 int fpm_dev_locked(const DsqFpmArgs *a, const DsqFpmOut *o, hipStream_t st);
+int local_fit_dev_locked(const DsqLocalFitArgs *a, const DsqLocalFitOut *o, hipStream_t st);
 int results_dev_locked(const DsqResultsArgs *a, const DsqResultsOut *o, hipStream_t st);
 int contrasts_dev_locked(const DsqContrastsArgs *a, const DsqContrastsOut *o, hipStream_t st);
 

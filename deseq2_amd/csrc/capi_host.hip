@@ -894,6 +894,34 @@ int dsq_sample_pairs(const DsqSamplePairsArgs *a, const DsqSamplePairsOut *o) {
     return s.finish();
 }
 
+int dsq_local_fit(const DsqLocalFitArgs *a, const DsqLocalFitOut *o) {
+    HostCall hc;
+    DSQ_TRY(host_ready(local_fit_check(a, o), DSQ_LAYOUT_R));
+    hipStream_t st = hc.st;
+    const size_t n = a->n, blockb = (kLocalFitHeaderDoubles + 3 * n) * 8;
+    const size_t nq = !o->dispFit ? 0 : a->eval_means ? (size_t)a->n_eval : n;
+    DsqLocalFitArgs d = *a;
+    DsqLocalFitOut od = *o;
+    int32_t status[4] = {0, 0, 0, 0};
+    Stage s(st, n);
+    if (a->fit_in) s.vec(&d.fit_in, a->fit_in, blockb);
+    else {
+        s.vec(&d.means, a->means, n * 8);
+        s.vec(&d.disps, a->disps, n * 8);
+    }
+    if (a->eval_means) s.vec(&d.eval_means, a->eval_means, nq * 8);
+    DSQ_TRY(s.pack_in());
+    if (!a->fit_in) s.out_vec(&od.fit, o->fit, blockb);
+    if (nq) s.out_vec(&od.dispFit, o->dispFit, nq * 8);
+    s.out_vec(&od.status, status, sizeof status);
+    DSQ_TRY(s.pack_out());
+    DSQ_TRY(local_fit_dev_locked(&d, &od, st));
+    DSQ_TRY(s.finish());
+    memcpy(o->status, status, sizeof status);
+    if (status[0] > 0 && status[1] < 3) return capi_fail(DSQ_ERR_FIT, "local dispersion fit: fewer than 3 points in a window");
+    return DSQ_OK;
+}
+
 int dsq_collapse(const DsqCollapseArgs *a, const DsqCollapseOut *o) {
     const auto check = [&]() -> int {
         if (int rc = collapse_check(a, o)) return rc;

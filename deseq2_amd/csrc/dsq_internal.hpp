@@ -406,6 +406,18 @@ struct FpmKernelParams {
 };
 hipError_t launch_fpm(const FpmKernelParams &kp, hipStream_t st);
 
+// the local-regression dispersion trend (local_fit.hip).  The fit handle is one block of
+// kLocalFitHeaderDoubles + 3 n doubles: a header (N, k, the all-below-floor flag, n, minDisp), then x | y | w of the fit set
+// in sorted order, each n long (the first N entries written).  kLocalFitLanes: the partial sums of every moment -- partial
+// (j mod kLocalFitLanes) takes the window's points in ascending sorted index j, then the butterfly of wave_allreduce.
+constexpr int kLocalFitLanes = 64, kLocalFitHeaderDoubles = 4;
+size_t local_fit_workspace_bytes(long n);        // the sort's scratch
+hipError_t launch_local_fit_build(const double *means, const double *disps, int n, double minDisp, double *block, void *workspace,
+                                  hipStream_t st);
+// dispFit at the n_eval means q into out (out == nullptr: nothing is evaluated), then status[0..3] = N, k, singular points,
+// all-below-floor
+hipError_t launch_local_fit_eval(const double *block, const double *q, long n_eval, double *out, int32_t *status, hipStream_t st);
+
 // K contrasts from one covariance pass per gene (contrasts.hip).  n x m matrices gene-major with
 // leading dimension ld, n x p / n x K matrices column-major; ncell > 0 selects the cell-collapsed Gram sums (cell_perm,
 // cell_start as in BetaKernelParams); contrasts == nullptr: the all-zero flags only.

@@ -187,6 +187,46 @@ class ContrastColumns:
         return self._pick(self.flag_matrix, k)
 
 
+class DeviceLocalFit:
+    """The local-regression dispersion trend on the device (DeviceEngine.local_fit): the resident fit handle, N, k and the
+    all-below-floor flag.  Calling it on a host array of means evaluates on the device and returns a host array (the values
+    and the status come down in one copy); on a resident vector it returns a resident vector and nothing comes down.
+    nSingular: the singular points of the last evaluation that came to the host."""
+
+    def __init__(self, E, means, disps, minDisp=1e-8):
+        t = E.torch
+        self.E, self.minDisp = E, float(minDisp)
+        md = means if t.is_tensor(means) else E._vec(np.asarray(means, np.float64).reshape(-1))
+        dd = disps if t.is_tensor(disps) else E._vec(np.asarray(disps, np.float64).reshape(-1))
+        if md.shape != dd.shape:
+            raise ValueError("means and disps must have one entry per gene each")
+        r = E._timed("local_fit", int(md.numel()), lambda: E.native.local_fit_dev(md, dd, self.minDisp, evaluate=False))
+        self.fit = r["fit"]
+        st = E._host(r["status"]).numpy()
+        self.N, self.k, self.nSingular, self.allBelowFloor = int(st[0]), int(st[1]), 0, bool(st[3])
+        if self.N and self.k < 3:
+            raise RuntimeError(E.native.LOCAL_FIT_TOO_FEW)
+
+    def eval_dev(self, q, out=None):
+        """dispFit at the resident means q (a contiguous float64 vector): (values, status), both resident"""
+        r = self.E._timed("local_fit", int(q.numel()), lambda: self.E.native.local_fit_dev(
+            eval_means=q, fit=self.fit, minDisp=self.minDisp, out=out))
+        return r["dispFit"], r["status"]
+
+    def __call__(self, q):
+        E = self.E
+        t = E.torch
+        if t.is_tensor(q):
+            return self.eval_dev(q.contiguous())[0]
+        q = np.asarray(q, np.float64)
+        if q.size == 0:
+            return np.zeros(q.shape)
+        v, st = self.eval_dev(E._vec(np.ascontiguousarray(q).reshape(-1)))
+        h = E._host(t.cat([v, st.to(t.float64)])).numpy()
+        self.nSingular = int(h[-2])
+        return h[:-4].reshape(q.shape).copy()
+
+
 class HostEngine:
     name = "host"
 
@@ -489,6 +529,12 @@ class HostEngine:
     def parametric_fit(self, means, disps):
         """parametricDispersionFit, R/core.R:2166-2190"""
         return self.fns.parametricDispersionFit(means, disps)
+
+    def local_fit(self, means, disps, minDisp=1e-8):
+        """localDispersionFit, R/core.R:2194-2203: the function of the mean, local_fit_host.py on this
+        engine's log / exp"""
+        from . import local_fit_host
+        return local_fit_host.LocalFit(self.vlog, self.vexp, means, disps, minDisp)
 
     def mad(self, v):
         """stats::mad (R/methods.R:180)"""
@@ -1062,6 +1108,11 @@ class DeviceEngine:
     def parametric_fit(self, means, disps):
         dm, dd = self._vec(means), self._vec(disps)
         return self._timed("trend_fit", int(dm.numel()), lambda: self.native.parametricDispersionFit_dev(dm, dd))
+
+    def local_fit(self, means, disps, minDisp=1e-8):
+        """localDispersionFit on the device (csrc/local_fit.hip, dsq_local_fit_dev): means / disps host vectors, which go up,
+        or resident ones.  The fit handle stays resident; the status words (16 bytes) come to the host."""
+        return DeviceLocalFit(self, means, disps, minDisp)
 
     def mad(self, v):
         """stats::mad on the device (a sort; selecting order statistics is exact, so the value equals numpy's)"""

@@ -7,7 +7,8 @@ without a host decision -- including the rows that go to the reference's host-si
 R/fitNbinomGLMs.R:340-407), which the library re-fits by a row-listed launch of its optim kernel.  The host looks at
 the device ONCE per analysis, at the end: counters and the dispersion-trend scalars.  Results are bit-identical to core.DESeq() (tests/test_gpu_fused.py).
 
-Supported: DeviceEngine, p <= 64, fitType = "parametric" / "mean", test = "Wald" (also with betaPrior = TRUE on the standard or
+Supported: DeviceEngine, p <= 64, fitType = "parametric" / "mean" / "local" (the local regression runs on the device between
+two phases of the chain) or a trend the caller fits itself, test = "Wald" (also with betaPrior = TRUE on the standard or
 the expanded model matrix, and with useT) or "LRT" (any full-rank reduced model matrix), niter = 1, more than 3
 residual degrees of freedom.  Anything else falls back to core.DESeq() / parallel.DESeqParallel().
 """
@@ -21,9 +22,9 @@ from . import core
 
 def supported(dds, test="Wald", reduced=None, fitType="parametric", **kw):
     E = dds.engine
-    if getattr(E, "name", "") != "device" or not (fitType in ("parametric", "mean") or callable(fitType)):
+    if getattr(E, "name", "") != "device" or not (fitType in ("parametric", "mean", "local") or callable(fitType)):
         return False
-    if callable(fitType) and kw.get("betaPrior"):
+    if (callable(fitType) or fitType == "local") and kw.get("betaPrior"):
         return False
     if dds.p > L.DSQ_MAX_P or dds.m <= dds.p:
         return False
@@ -477,8 +478,25 @@ def DESeq(dds, test="Wald", fitType="parametric", reduced=None, minReplicatesFor
     run.args.fitType = L.DSQ_FIT["mean" if fitType == "mean" else "parametric_or_mean"]
     if kw.get("dispPriorVar"):
         run.args.dispPriorVar_in = float(kw["dispPriorVar"])
-    custom = None
-    if callable(fitType):
+    custom = local = None
+    if fitType == "local":
+        # the local-regression trend (R/core.R:889-893, csrc/local_fit.hip) between the gene-estimate phase and the rest of
+        # the chain, on the resident baseMean / dispGeneEst: the useForFit rows are compacted on the device, the fit handle and
+        # its values at every gene's mean stay there (dispFit_in), and only the fit's status words cross to the host.  The
+        # refit of replaced rows evaluates the kept handle at their NEW means (R/core.R:2512) between the two halves of the
+        # outlier phase, on the device as well.  Gene shards go call by call.
+        if world > 1:
+            return parallel.DESeqParallel(dds, test=test, fitType=fitType, reduced=reduced, comm_device=comm_device,
+                                          minReplicatesForReplace=minReplicatesForReplace, **kw)
+        run.launch(L.DSQ_PH_GENE_EST)
+        use = run.dispGeneEst > 100 * run.minDisp                            # (NaN on the all-zero rows: not used)
+        fit_means, fit_disps = run.baseMean[use], run.dispGeneEst[use]
+        if fit_means.numel() == 0:
+            raise RuntimeError("all gene-wise dispersion estimates are within 2 orders of magnitude from the minimum value")
+        custom = local = E.local_fit(fit_means, fit_disps, run.minDisp)
+        run._fit_in = local.eval_dev(run.baseMean)[0]
+        run.args.dispFit_in = _ptr(run._fit_in)
+    elif callable(fitType):
         # the caller's trend (core.estimateDispersionsFit: what R has after fitType = "local" or dispersionFunction<-):
         # the gene-wise estimates come up, the function is evaluated on the host, its values go down as dispFit_in.  The
         # refit of replaced rows needs the function at their NEW means (R/core.R:2512): the outlier phase then runs in its two
@@ -542,6 +560,11 @@ def DESeq(dds, test="Wald", fitType="parametric", reduced=None, minReplicatesFor
         run.lam_prior = np.ascontiguousarray((1.0 / bpv) / np.log(2) ** 2)                 # R/fitNbinomGLMs.R:311,162
         run.args.lambda_prior = run.lam_prior.ctypes.data_as(C.c_void_p)
         run.launch(L.DSQ_PH_PRIOR | L.DSQ_PH_OUTLIERS)
+    elif local is not None and run.do_replace:
+        run.launch(L.DSQ_PH_TREND | L.DSQ_PH_MAP_TEST | L.DSQ_PH_OUTLIERS_DETECT)
+        refit = (run.replace != 0) & (run.allZero == 0)                   # refitReplace, R/core.R:2496-2498
+        run._fit_in.copy_(t.where(refit, local.eval_dev(run.baseMean)[0], run._fit_in))
+        run.launch(L.DSQ_PH_OUTLIERS_REFIT)
     elif custom is not None and run.do_replace:
         run.launch(L.DSQ_PH_TREND | L.DSQ_PH_MAP_TEST | L.DSQ_PH_OUTLIERS_DETECT)
         h2 = E._host(t.stack([run.baseMean, run.replace.to(t.float64), run.allZero.to(t.float64)])).numpy()
@@ -601,7 +624,8 @@ def DESeq(dds, test="Wald", fitType="parametric", reduced=None, minReplicatesFor
             return core.DESeq(dds, test=test, fitType=fitType, reduced=reduced,
                               minReplicatesForReplace=minReplicatesForReplace, **kw)
         if custom is not None:
-            fn = {"fitType": "custom", "coefficients": custom, "varLogDispEsts": float(sc[2]), "dispPriorVar": float(sc[3])}
+            fn = {"fitType": "custom" if local is None else "local", "coefficients": custom, "varLogDispEsts": float(sc[2]),
+                  "dispPriorVar": float(sc[3])}
         elif sc[L.DSQ_SC_FIT_USED] == L.DSQ_FIT["mean"]:
             fn = {"fitType": "mean", "coefficients": float(sc[0]), "varLogDispEsts": float(sc[2]), "dispPriorVar": float(sc[3])}
         else:

@@ -342,8 +342,8 @@ def DESeq(counts, x, sizeFactors=None, test="Wald", reduced=None, normalizationF
     per-gene columns (NA = NaN; integer columns as float64 with NaN), the requested n x m assays, the dispersion
     function and the status counters.  fitType: "parametric" (a trend that does not fit is an error, DSQ_ERR_FIT: the R
     caller then takes the reference's route to locfit), "mean", or "parametric_or_mean" (the mean substituted on the device).
-    A trend the library does not fit (fitType = "local", dispersionFunction<-): geneEstOnly = True returns after
-    estimateDispersionsGeneEst; the caller evaluates its trend at res["baseMean"] and calls again with dispFit = those values
+    A trend this entry does not fit (fitType = "local": local_fit below, or R's locfit; dispersionFunction<-): geneEstOnly =
+    True returns after estimateDispersionsGeneEst; the caller evaluates its trend at res["baseMean"] and calls again with dispFit = those values
     (count outliers are then flagged but not replaced: the refit is the caller's, R/core.R:2484-2563).  dispPriorVar: the
     argument of estimateDispersionsMAP (R/core.R:989-994); required for m - p <= 3, where R's own estimate is a seeded
     Monte-Carlo match (:1155-1190) the library leaves to the caller."""
@@ -1096,6 +1096,70 @@ def fpm_dev(y, lib, kind="fpm", basepairs=None, txlen=None):
     o = L.sized(L.DsqFpmOut, out=_t_ptr(out.t))
     L.check(L.lib().dsq_fpm_dev(C.byref(a), C.byref(o), _stream()))
     return out
+
+
+LOCAL_FIT_TOO_FEW = "local dispersion fit: fewer than 3 points in a window"
+_LOCAL_FIT_STATUS = ("N", "k", "nSingular", "allBelowFloor")
+
+
+def local_fit(means=None, disps=None, minDisp=1e-8, eval_means=None, fit=None, evaluate=True):
+    """dsq_local_fit (host arrays): the local-regression trend of (means, disps), or -- fit: the block an earlier call
+    returned -- of that fit, evaluated at eval_means (None: at means; evaluate = False: the fit alone).  Returns
+    dict(dispFit or None, fit: the block, N, k, nSingular, allBelowFloor); raises RuntimeError when a window would hold
+    fewer than 3 points."""
+    st = np.zeros(4, np.int32)
+    ev = None if eval_means is None else np.ascontiguousarray(eval_means, dtype=np.float64).reshape(-1)
+    if fit is None:
+        means = np.ascontiguousarray(means, dtype=np.float64).reshape(-1)
+        disps = np.ascontiguousarray(disps, dtype=np.float64).reshape(-1)
+        if means.shape != disps.shape:
+            raise ValueError("means and disps must have one entry per gene each")
+        n = means.size
+        block = np.zeros(int(L.lib().dsq_local_fit_block_doubles(n)) if n else 0)
+    else:
+        block = np.ascontiguousarray(fit, dtype=np.float64)
+        n, means, disps = (block.size - 4) // 3, None, None
+    nq = 0 if not evaluate else ev.size if ev is not None else n
+    out = np.full(nq, np.nan) if evaluate else None
+    a = L.sized(L.DsqLocalFitArgs, n=n, means=_ptr(means), disps=_ptr(disps), minDisp=float(minDisp),
+                fit_in=_ptr(block) if fit is not None else None, n_eval=0 if ev is None else ev.size, eval_means=_ptr(ev))
+    o = L.sized(L.DsqLocalFitOut, fit=_ptr(block) if fit is None else None, dispFit=_ptr(out), status=_ptr(st))
+    try:
+        L.check(L.lib().dsq_local_fit(C.byref(a), C.byref(o)))
+    except L.DsqError as e:
+        if e.code == L.DSQ_ERR_FIT:
+            raise RuntimeError(LOCAL_FIT_TOO_FEW) from None
+        raise
+    return dict(zip(_LOCAL_FIT_STATUS, (int(v) for v in st)), dispFit=out, fit=block)
+
+
+def local_fit_dev(means=None, disps=None, minDisp=1e-8, eval_means=None, fit=None, evaluate=True, out=None):
+    """dsq_local_fit_dev on resident vectors: means / disps / eval_means (n,) float64 device tensors; fit: the block tensor an
+    earlier call returned (evaluate only).  out: where dispFit goes (default: a fresh tensor).  Returns dict(dispFit, fit,
+    status: (4,) int32 device tensor N, k, nSingular, allBelowFloor); nothing is read back."""
+    import torch
+    for v in (means, disps, eval_means, fit, out):
+        assert v is None or (v.dtype == torch.float64 and v.dim() == 1 and v.is_contiguous())
+    src = means if fit is None else fit
+    dev = src.device
+    if fit is None:
+        assert means.numel() == disps.numel()
+        n = means.numel()
+        block = torch.empty(int(L.lib().dsq_local_fit_block_doubles(n)), dtype=torch.float64, device=dev)
+    else:
+        block, n = fit, (fit.numel() - 4) // 3
+    nq = 0 if not evaluate else eval_means.numel() if eval_means is not None else n
+    if evaluate and out is None:
+        out = torch.empty(nq, dtype=torch.float64, device=dev)
+    assert not evaluate or out.numel() == nq
+    status = torch.empty(4, dtype=torch.int32, device=dev)
+    a = L.sized(L.DsqLocalFitArgs, n=n, means=_t_ptr(means if fit is None else None), disps=_t_ptr(disps if fit is None else None),
+                minDisp=float(minDisp), fit_in=_t_ptr(fit), n_eval=0 if eval_means is None else int(eval_means.numel()),
+                eval_means=_t_ptr(eval_means))
+    o = L.sized(L.DsqLocalFitOut, fit=_t_ptr(block) if fit is None else None, dispFit=_t_ptr(out) if evaluate else None,
+                status=_t_ptr(status))
+    L.check(L.lib().dsq_local_fit_dev(C.byref(a), C.byref(o), _stream()))
+    return {"dispFit": out if evaluate else None, "fit": block, "status": status}
 
 
 def sf_iterate_solve(counts, mu, sf, disp, rows, Q=0.05, maxit=100):

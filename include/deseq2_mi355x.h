@@ -452,9 +452,10 @@ enum { DSQ_ST_N_NONZERO = 0, DSQ_ST_N_GRID_GENEEST, DSQ_ST_N_TREND, DSQ_ST_TREND
        DSQ_ST_N_GRID_MAP, DSQ_ST_N_OPTIM_GENEEST, DSQ_ST_N_OPTIM_TEST, DSQ_ST_N_REPLACE, DSQ_ST_N_REFIT,
        DSQ_ST_N_GRID_GENEEST_REFIT, DSQ_ST_N_GRID_MAP_REFIT, DSQ_ST_N_OPTIM_GENEEST_REFIT, DSQ_ST_N_OPTIM_TEST_REFIT,
        DSQ_ST_COUNT = 16 };        /* (14, 15: counters of the chain's own) */
-/* estimateDispersionsFit's fitType (R/core.R:864-939).  "local" needs locfit (an R package, not in the reference's
- * tree): a caller that wants the reference's automatic substitution asks for DSQ_FIT_PARAMETRIC, gets DSQ_ERR_FIT when
- * the trend does not fit and takes its own route; DSQ_FIT_PARAMETRIC_OR_MEAN substitutes the mean on the device.   */
+/* estimateDispersionsFit's fitType (R/core.R:864-939).  "local" is no DSQ_FIT_* value: the chain sees it as a given trend
+ * (dispFit_in), which dsq_local_fit_dev below computes on the device from the gene-estimate phase's baseMean / dispGeneEst.
+ * A caller that wants the reference's automatic substitution asks for DSQ_FIT_PARAMETRIC, gets DSQ_ERR_FIT when the trend
+ * does not fit and takes that route (or its own); DSQ_FIT_PARAMETRIC_OR_MEAN substitutes the mean on the device.   */
 #define DSQ_FIT_PARAMETRIC          0
 #define DSQ_FIT_MEAN                1    /* mean(dispGeneEst[dispGeneEst > 10 minDisp], trim = 0.001), R/core.R:894-899 */
 #define DSQ_FIT_PARAMETRIC_OR_MEAN  2
@@ -518,7 +519,7 @@ typedef struct {
     int32_t p_prior, prior_expanded, prior_intercept;   /* expanded: rank-deficient start values; first column all ones */
     const double *lambda_prior;    /* HOST, p_prior: 1 / betaPriorVar / log(2)^2; read by DSQ_PH_PRIOR / _OUTLIERS */
     int32_t fitType;               /* DSQ_FIT_*: read by DSQ_PH_TREND                                             */
-    /* the caller's dispersion trend -- what R has after fitType = "local" (locfit, R/core.R:889-893) or
+    /* the caller's dispersion trend -- fitType = "local" (R/core.R:889-893: dsq_local_fit_dev evaluates it on the device) or
      * `dispersionFunction(dds) <- f` (R/methods.R:142-190) --, evaluated by the caller at the baseMean of every gene (the
      * DSQ_PH_GENE_EST phase gives baseMean and dispGeneEst): device, n values.  DSQ_PH_TREND then fits nothing and takes
      * varLogDispEsts / the prior variance from the residuals against it (against trend_fit_in, n_trend values aligned with
@@ -919,6 +920,57 @@ int dsq_col_sums(const DsqColSumsArgs *args, const DsqColSumsOut *out);
 int dsq_fpm_dev(const DsqFpmArgs *args, const DsqFpmOut *out, void *stream);
 int dsq_fpm(const DsqFpmArgs *args, const DsqFpmOut *out);
 
+/* ---- dsq_local_fit: the local-regression dispersion trend, estimateDispersionsFit(fitType = "local") (R/core.R:889-893,
+ *      localDispersionFit :2194-2203) ------------------------------------------------------------
+ * The estimator behind locfit(logDisps ~ logMeans, weights = means) with locfit's defaults: nearest-neighbour fraction 0.7,
+ * local quadratic, tricube kernel, Gaussian family, prior weights times kernel weights -- evaluated directly at every
+ * requested mean (locfit's ev = dat()).  locfit evaluates on the vertices of an adaptive tree and interpolates: agreement
+ * with its interpolated values is not claimed.
+ * means / disps: what the caller offers to the fit (R: the useForFit rows).  The fit set is the rows with
+ * 10 minDisp <= disps < Inf and 0 < means < Inf, N of them: x = log(means), y = log(disps), w = means, sorted by x, ties by
+ * row.  N = 0 (all below the floor): the trend is the constant minDisp.  k = floor(7 N / 10) points per window; k < 3 is
+ * "fewer than 3 points in a window": every value NaN, DSQ_ERR_FIT from the host entry.
+ * At a mean q, z = log(q): the k nearest x are a window [l, l + k) of the sorted set, h the k-th smallest |x - z|,
+ * t = (x - z) / h, W = w (1 - |t|^3)^3 for |t| < 1; S_r = sum W t^r (r = 0..4), T_r = sum W t^r y (r = 0..2); the value is
+ * exp(a0), a0 the intercept of the 3 x 3 normal equations by elimination without pivoting.  A window with fewer than three
+ * distinct x of positive weight, or a pivot that is not > 0, gives NaN and is counted; so does a q that is NaN, <= 0 or Inf
+ * (not counted).  log / exp: the library's pinned arithmetic.
+ * The order of the eight sums is part of the interface and depends on (l, k) only: dsq_local_fit_lanes() partial sums,
+ * partial (j mod lanes) adds the window's points in ascending sorted index j from +0.0; the partials are then added
+ * pairwise, partial i with partial i xor 1, then xor 2, 4, 8, 16, 32.  No atomics.
+ * The fit handle: out->fit, dsq_local_fit_block_doubles(n) doubles (a header, then x | y | w in sorted order).  A later call
+ * with args->fit_in pointing at it (and the same n) evaluates without fitting again: the same bits as a fresh call.
+ * Evaluation points: eval_means (n_eval of them); eval_means NULL and dispFit given: the n means themselves.  dispFit NULL:
+ * the fit is built and nothing is evaluated.
+ * status[0..3]: N, k, the number of singular evaluation points, 1 when all rows were below the floor.
+ * _dev: device pointers, asynchronous on `stream`, no host synchronisation: N and k stay on the device between the fit and
+ * the evaluation.  out->fit NULL: the block lives in the workspace of the stream's context until the next call.
+ * dsq_local_fit: host pointers, ONE device, synchronous; fit / fit_in are host copies of the block.
+ * DSQ_ERR_ARG: struct_size not sizeof the block, n < 1, a NULL status, means / disps NULL without fit_in, fit_in without
+ * eval_means and dispFit, n_eval < 0 or without eval_means, minDisp not > 0.  All decided before a device is asked for.    */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(DsqLocalFitArgs)                                                           */
+    int32_t n;                 /* rows of means / disps; with fit_in: the n its block was built with                */
+    const double *means;       /* n, or NULL with fit_in                                                            */
+    const double *disps;       /* n, or NULL with fit_in                                                            */
+    double minDisp;            /* R: 1e-8                                                                           */
+    const double *fit_in;      /* NULL: fit (means, disps); else the block of an earlier call: evaluate only        */
+    int32_t n_eval;            /* entries of eval_means (0 without)                                                 */
+    const double *eval_means;  /* n_eval means, or NULL: evaluate at `means`                                        */
+} DsqLocalFitArgs;
+
+typedef struct {
+    uint32_t struct_size;      /* sizeof(DsqLocalFitOut)                                                            */
+    double *fit;               /* dsq_local_fit_block_doubles(n), or NULL: not kept                                 */
+    double *dispFit;           /* one value per evaluation point, or NULL: fit only                                 */
+    int32_t *status;           /* 4 words                                                                           */
+} DsqLocalFitOut;
+
+int32_t dsq_local_fit_lanes(void);                  /* the partial sums of the summation order                       */
+int64_t dsq_local_fit_block_doubles(int32_t n);     /* the size of a fit handle, in doubles                           */
+int dsq_local_fit_dev(const DsqLocalFitArgs *args, const DsqLocalFitOut *out, void *stream);
+int dsq_local_fit(const DsqLocalFitArgs *args, const DsqLocalFitOut *out);
+
 /* ---- dsq_results: results() for one coefficient (R/results.R:443-575, 638-740) -------------------
  * The table -- baseMean, log2FoldChange, lfcSE, stat, pvalue of design column c --, the threshold tests of :484-515 under
  * the normal distribution, pvalue NA where na_mask is set (the Cook's filter of :520-564 is the caller's: a host decision
@@ -1097,8 +1149,8 @@ typedef struct {
                                       NULL = estimated                                                              */
     int32_t fitType;               /* DSQ_FIT_PARAMETRIC (0, the default of DESeq()), DSQ_FIT_MEAN, DSQ_FIT_PARAMETRIC_OR_MEAN;
                                       dispersionFunction[DSQ_SC_FIT_USED] says which trend the results carry          */
-    /* a trend the library does not fit -- fitType = "local" (locfit: R code, R/core.R:889-893) or `dispersionFunction<-`
-     * (R/methods.R:142-190) -- in two calls: geneEstOnly = 1 runs estimateDispersionsGeneEst only (baseMean, baseVar,
+    /* a trend this entry does not fit -- fitType = "local" (R/core.R:889-893: dsq_local_fit between the two calls, or R's own
+     * locfit) or `dispersionFunction<-` (R/methods.R:142-190) -- in two calls: geneEstOnly = 1 runs estimateDispersionsGeneEst only (baseMean, baseVar,
      * allZero, dispGeneEst, dispGeneIter come back; every other column NA); the caller fits its trend and calls again with
      * dispFit = its values at baseMean (host, n; rows that are all zero: anything).  Count outliers are then flagged by
      * Cook's distance as always, but NOT replaced: the refit needs the trend at the new means of the replaced rows, so the
