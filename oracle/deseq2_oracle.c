@@ -12,11 +12,15 @@
  * Same control flow, same counters, same break conditions, same clamps.  Each block
  * cites the reference lines it follows.
  *
- * PARITY STATUS: PINNED by the reference's own tests; the reference itself is UNBUILDABLE here.
+ * PARITY STATUS: PINNED by the reference's own tests and by its own source compiled against stand-ins.
  * src/DESeq2.cpp includes RcppArmadillo.h, R.h, Rmath.h and R_ext/Utils.h (:16,23-25): R, Rcpp,
- * RcppArmadillo and Armadillo are external libraries this image lacks, no R runs here, and a build
- * against stand-ins for them would not be the reference -- none is made, and no output of real R
- * is in the tree.  What pins this file:
+ * RcppArmadillo and Armadillo are external libraries this image lacks and no R runs here, so no
+ * output of real R is in the tree.  What pins this file:
+ *   (0) src/DESeq2.cpp itself, compiled where it lies against the stand-in headers of oracle/shim/
+ *       (oracle/Makefile `ref`): the reference's control flow executed unchanged over stand-in linear
+ *       algebra and binary128 special functions -- not R's nmath, not Armadillo's LAPACK.  Its recorded
+ *       outputs (tests/golden/reference/) and, where the library is built, live runs:
+ *       tests/test_oracle_vs_reference.py, tests/test_gpu_reference.py;
  *   (1) the reference's known-answer tests (tests/testthat/test_results.R:9,43-50;
  *       test_optim.R:30-39) and the cross-implementation properties its tests assert
  *       (test_betaFitting.R:2-47, test_dispersions.R:35-111, test_QR.R, test_weights.R:9-19)

@@ -8,9 +8,12 @@ polygamma for R's lgamma / digamma / trigamma.  Rf_dnbinom_mu is the C oracle's 
 algorithm (oracle/orc_nmath.c; held < 1 ulp-level against mpmath by tests/test_oracle_math.py) -- scipy's
 nbinom.logpmf cancels badly at small dispersions and would not do.
 
-Why it exists: the reference itself cannot be built in this image.  src/DESeq2.cpp:16,23-25 needs
+Why it exists: the reference cannot be built in this image the way R builds it.  src/DESeq2.cpp:16,23-25 needs
 RcppArmadillo.h, R.h, Rmath.h and R_ext/Utils.h -- external libraries (R, Rcpp, RcppArmadillo, Armadillo)
-that are absent -- and a build against stand-ins for them is not a reference build.  So the C oracle
+that are absent.  The build of its source against stand-in headers (oracle/shim/, oracle/Makefile `ref`) executes
+the reference's control flow, but over stand-in linear algebra and binary128 special functions: real LAPACK and
+double-precision special functions of another hand are this module's half (tests/test_oracle_vs_reference.py holds
+both restatements to that build).  So the C oracle
 (oracle/deseq2_oracle.c) is pinned by the reference's OWN tests' known answers and properties
 (tests/test_oracle_properties.py), and this module gives it an independently written
 counterpart with different linear algebra (LAPACK instead of the oracle's own LU / Householder), different

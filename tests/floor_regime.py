@@ -91,17 +91,22 @@ def rates(a, b):
                 map_rel_max=float((np.abs(a["dispMAP"] - b["dispMAP"]) / b["dispMAP"]).max()))
 
 
-def assert_visible_parity(got, ref, name):
-    """the budgets"""
+def assert_visible_parity(got, ref, name, max_dge_rel=None, max_conv_differs=None):
+    """the budgets.  max_dge_rel / max_conv_differs: a case's own count of genes in place of 0.03 n / 0.08 n, for the cases
+    tests/reference_cases.py states one for (against the reference build); every other budget is the same for all"""
     s = rates(got, ref)
+    if max_dge_rel is None:
+        max_dge_rel = 0.03 * s["n"]
+    if max_conv_differs is None:
+        max_conv_differs = 0.08 * s["n"]
     assert s["floor_start"] >= 0.25 * s["n"], "%s: only %d of %d genes start at the floor" % (name, s["floor_start"], s["n"])
     assert s["beta_iter_mismatch"] == 0, "%s: fitBeta$iter differs on %d genes" % (name, s["beta_iter_mismatch"])
     # clamped dispGeneEst: the floor genes end within rounding noise of the clamp
     assert s["dge_abs_max"] <= 1e-7, "%s: clamped dispGeneEst off by %.3g" % (name, s["dge_abs_max"])
-    assert s["dge_rel_gt_1e6"] <= 0.03 * s["n"], "%s: %d genes beyond 1e-6 relative" % (name, s["dge_rel_gt_1e6"])
+    assert s["dge_rel_gt_1e6"] <= max_dge_rel, "%s: %d genes beyond 1e-6 relative" % (name, s["dge_rel_gt_1e6"])
     # the decisions R takes on them
     assert s["refit_differs"] <= max(2, 0.005 * s["n"]), "%s: refitDisp differs on %d genes" % (name, s["refit_differs"])
-    assert s["conv_differs"] <= 0.08 * s["n"], "%s: dispGeneEstConv differs on %d genes" % (name, s["conv_differs"])
+    assert s["conv_differs"] <= max_conv_differs, "%s: dispGeneEstConv differs on %d genes" % (name, s["conv_differs"])
     assert s["map_conv_differs"] == 0, "%s: MAP dispConv differs on %d genes" % (name, s["map_conv_differs"])
     assert s["map_iter_equal"] >= 0.99 and s["map_rel_max"] <= 1e-5, "%s: MAP %r" % (name, s)
     # away from the floor the strict claim holds: iteration counts equal (bar ulp-level ties, <= 1 %)

@@ -1,9 +1,11 @@
 """CPU: the C oracle against its independently written counterpart (oracle/lapack_oracle.py).
 
-The reference (src/DESeq2.cpp) cannot be built in this image -- it needs R, Rcpp, RcppArmadillo and Armadillo, none of
-which exist here, and a build against stand-ins for them would not be the reference.  What pins the oracle to the
-reference is therefore the reference's OWN tests: tests/test_oracle_properties.py restates their known answers and
-properties.  This file adds a second line of evidence: a numpy restatement of the same three routines
+The reference (src/DESeq2.cpp) cannot be built AS R BUILDS IT in this image -- it needs R, Rcpp, RcppArmadillo and
+Armadillo, none of which exist here.  Its source does compile against stand-in headers (oracle/shim/, oracle/Makefile `ref`):
+that build is the reference's control flow over stand-in linear algebra and binary128 special functions -- not R's nmath, not
+Armadillo's LAPACK -- and tests/test_oracle_vs_reference.py holds the oracle and the restatement below to it, the half a
+second reading of the same text cannot check.  The reference's OWN tests pin the oracle too: tests/test_oracle_properties.py
+restates their known answers and properties.  This file is the other half: a numpy restatement of the same three routines
 with real LAPACK (dgeqrf / dgesv / dgetrf / dgetri through numpy.linalg -- what Armadillo itself calls), scipy's special
 functions and numpy's summation order, written from the reference's text matrix expression by matrix expression.  Two
 restatements that share no linear algebra, no lgamma / digamma and no summation order must agree on: iteration counts
@@ -222,7 +224,7 @@ def test_oracle_vs_lapack(oracle, lapack, name):
     compare(run_all(oracle, d), run_all(lapack, d), d, name)
 
 
-def test_weight_subsetting_edge_cases(oracle, lapack):
+def weight_edge_inputs():
     """src/DESeq2.cpp:39-43: rows with weight <= threshold are dropped from the Cox-Reid matrix, then the
     design columns that are left all-zero.  Every observation weighted out (a 0 x 0 matrix, det = 1), a single
     observation left, a design column that loses all its samples."""
@@ -241,7 +243,15 @@ def test_weight_subsetting_edge_cases(oracle, lapack):
     nf = np.ones((n, m))
     bargs = (y, x, nf, alpha, np.r_[1.0, 0, 0, 0], beta_init_qr(y, nf, x), np.full(p, 1e-6) / np.log(2) ** 2, w, True,
              1e-8, 100, True, 0.5)
-    ob, rb = oracle.fitBeta(*bargs), lapack.fitBeta(*bargs)
+    return y, x, nf, w, alpha, bargs
+
+
+def check_weight_subsetting_edge_cases(oracle, other):
+    """the oracle against `other` (the LAPACK restatement here, the reference build in tests/test_oracle_vs_reference.py) on
+    weight_edge_inputs()"""
+    y, x, nf, w, alpha, bargs = weight_edge_inputs()
+    n = y.shape[0]
+    ob, rb = oracle.fitBeta(*bargs), other.fitBeta(*bargs)
     np.testing.assert_array_equal(ob["iter"], rb["iter"])
     ok = rb["iter"] < 100
     np.testing.assert_allclose(ob["beta_mat"][ok], rb["beta_mat"][ok], rtol=1e-7, atol=1e-10)
@@ -249,7 +259,7 @@ def test_weight_subsetting_edge_cases(oracle, lapack):
     la = np.log(alpha)
     for prior in (False, True):
         dargs = (y, x, mu, la, la - 0.1, 0.8, np.log(1e-9), 1.0, 1e-6, 100, prior, np.maximum(w, 1e-6), True, 1e-2, True)
-        od, rd = oracle.fitDisp(*dargs), lapack.fitDisp(*dargs)
+        od, rd = oracle.fitDisp(*dargs), other.fitDisp(*dargs)
         # gene 2: the Cox-Reid matrix is singular after the subsetting (det = rounding noise in both)
         ok = np.isfinite(rd["initial_lp"]) & np.isfinite(od["initial_lp"]) & (np.arange(n) != 2)
         for k in FLAGS:
@@ -258,8 +268,11 @@ def test_weight_subsetting_edge_cases(oracle, lapack):
             np.testing.assert_allclose(od[k][ok], rd[k][ok], rtol=1e-7, atol=1e-9, err_msg="fitDisp$" + k)
 
 
-@pytest.mark.parametrize("seed", range(12))
-def test_seeded_sweep(oracle, lapack, seed):
+def test_weight_subsetting_edge_cases(oracle, lapack):
+    check_weight_subsetting_edge_cases(oracle, lapack)
+
+
+def sweep_case(seed):
     """random shapes / designs / weights / ridge / QR / CR settings"""
     rng = np.random.default_rng(9000 + seed)
     designs = ["two_group", "batch_condition", ("factor", 3), ("factor", 5), ("factor", 7), ("factor", 10)]
@@ -271,7 +284,13 @@ def test_seeded_sweep(oracle, lapack, seed):
               lam=float(10 ** rng.uniform(-6, 0)))
     if kw["weights"] and rng.uniform() < 0.5:
         kw["zero_w"] = True
-    d = _case(n, m, dz, seed=int(rng.integers(1e6)), **kw)
+    return _case(n, m, dz, seed=int(rng.integers(1e6)), **kw)
+
+
+@pytest.mark.parametrize("seed", range(12))
+def test_seeded_sweep(oracle, lapack, seed):
+    """random shapes / designs / weights / ridge / QR / CR settings"""
+    d = sweep_case(seed)
     compare(run_all(oracle, d), run_all(lapack, d), d, "sweep%d" % seed)
 
 
