@@ -10,6 +10,7 @@ from .core import (vst, varianceStabilizingTransformation, getVarianceStabilized
 from .core import results, resultsContrasts, resultsNames, DESeqResults, p_adjust, pvalueAdjustment, lowess  # noqa: F401
 from .core import pt  # noqa: F401
 from .core import unmix  # noqa: F401
+from .core import apeglm, lfcShrinkApeglm, svalue, apeglm_prior_scale  # noqa: F401
 from .core import rowVars, sampleDists, pca, plotPCA, PCAData  # noqa: F401
 from .core import collapseReplicates, fpm, fpkm, counts, plotCounts  # noqa: F401
 from .core import localDispersionFit  # noqa: F401

@@ -25,6 +25,7 @@ DSQ_MAX_P = 64
 DSQ_RESULTS_MAX_K = 4096
 DSQ_VST_MAX_KNOTS = 1600
 DSQ_UNMIX_MAX_K = 16
+DSQ_APEGLM_MAX_P = 16
 DSQ_PH_GENE_EST, DSQ_PH_TREND, DSQ_PH_MAP_TEST, DSQ_PH_OUTLIERS, DSQ_PH_FINISH, DSQ_PH_PRIOR = 1, 2, 4, 8, 16, 32
 DSQ_PH_OUTLIERS_DETECT, DSQ_PH_OUTLIERS_REFIT = 64, 128
 DSQ_SC_COEF0, DSQ_SC_COEF1, DSQ_SC_VAR_LOG_DISP, DSQ_SC_DISP_PRIOR_VAR, DSQ_SC_FIT_USED = 0, 1, 2, 3, 4
@@ -126,6 +127,9 @@ DsqVstOut = _struct("DsqVstOut", "p out rowMean rowMax bad")
 DsqRlogArgs = _struct("DsqRlogArgs", _COUNTS + "; p nf; i nf_is_vector; p dispFit; d betaPriorVar; p intercept; d tol minmu;"
                       " i maxit")
 DsqRlogOut = _struct("DsqRlogOut", "p rlog intercept iter flag bad")
+DsqApeglmArgs = _struct("DsqApeglmArgs", _DESIGN + "; p nf; i nf_is_vector; p x weights disp init; i coef; u no_shrink;"
+                        " d prior_scale prior_df no_shrink_scale; i has_threshold; d threshold tol; i maxit")
+DsqApeglmOut = _struct("DsqApeglmOut", "p map sd fsr thresh iter conv start objective bad")
 DsqUnmixArgs = _struct("DsqUnmixArgs", "i n m k; l ld; p x pure; i has_alpha has_shift; d alpha shift; i power maxit")
 DsqUnmixOut = _struct("DsqUnmixOut", "p p loss iter flag")
 DsqSfIterateArgs = _struct("DsqSfIterateArgs", "i n m; l ld; p y mu sf disp rows; d Q; i maxit")
@@ -186,7 +190,8 @@ for _name, _a, _o in (("dsq_fit_beta", DsqFitBetaArgs, DsqFitBetaOut), ("dsq_fit
 for _name, _a, _o in (("dsq_prefit_moments", DsqPrefitArgs, DsqPrefitOut), ("dsq_intercept_fit", DsqInterceptArgs, DsqInterceptOut),
                       ("dsq_cooks_distance", DsqCooksArgs, DsqCooksOut), ("dsq_replace_outliers", DsqReplaceArgs, DsqReplaceOut),
                       ("dsq_size_factors", DsqSizeFactorArgs, DsqSizeFactorOut), ("dsq_vst", DsqVstArgs, DsqVstOut),
-                      ("dsq_rlog", DsqRlogArgs, DsqRlogOut), ("dsq_top_var", DsqTopVarArgs, DsqTopVarOut),
+                      ("dsq_rlog", DsqRlogArgs, DsqRlogOut), ("dsq_apeglm", DsqApeglmArgs, DsqApeglmOut),
+                      ("dsq_top_var", DsqTopVarArgs, DsqTopVarOut),
                       ("dsq_sample_pairs", DsqSamplePairsArgs, DsqSamplePairsOut), ("dsq_collapse", DsqCollapseArgs, DsqCollapseOut),
                       ("dsq_col_sums", DsqColSumsArgs, DsqColSumsOut), ("dsq_fpm", DsqFpmArgs, DsqFpmOut),
                       ("dsq_local_fit", DsqLocalFitArgs, DsqLocalFitOut),
@@ -219,7 +224,8 @@ for _name in ("dsq_to_gene_major_f64", "dsq_to_gene_major_i32", "dsq_from_gene_m
     _sig(_name, _P, _P, _I32, _I32, _I64, _P)                    # src, dst, n, m, ld, stream
 _sig("dsq_counts_f64_to_gene_major_i32", _P, _P, _I32, _I32, _I64, _P, _P)
 _sig("dsq_test_math", _I, _P, _P, _P, _P, _I64)
-for _name in ("dsq_unmix_block_threads", "dsq_sf_iterate_slice_genes", "dsq_row_vars_register_width", "dsq_local_fit_lanes"):
+for _name in ("dsq_unmix_block_threads", "dsq_sf_iterate_slice_genes", "dsq_row_vars_register_width", "dsq_local_fit_lanes",
+              "dsq_apeglm_lds_doubles"):
     _sig(_name, res=_I32)
 _sig("dsq_local_fit_block_doubles", _I32, res=_I64)
 _sig("dsq_sample_pairs_slice_rows", _I64, _I32, res=_I64)

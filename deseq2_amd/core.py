@@ -22,8 +22,11 @@ variance of all columns on the device, csrc/beta_prior.hip, DESIGN.md section 16
 collapseReplicates, fpm / fpkm (R/helper.R), counts() (R/methods.R) and plotCounts(returnData = TRUE) (R/plots.R) close the
 file; their O(n m) parts run in the engine (csrc/count_helpers.hip).
 
-Not mirrored (out of the hot-path scope): local/glmGamPoi dispersion fits; lfcShrink(type = "apeglm" /
-"ashr"), which delegate to packages whose source is not part of the reference tree.
+lfcShrinkApeglm / apeglm / svalue serve lfcShrink(type = "apeglm") (R/lfcShrink.R:328-440): the estimator as documented, by
+the library's own iteration (csrc/apeglm.hip).
+
+Not mirrored (out of the hot-path scope): the glmGamPoi dispersion fit; lfcShrink(type = "ashr"), which
+delegates to a package whose source is not part of the reference tree.
 """
 import warnings
 
@@ -1625,6 +1628,8 @@ class DESeqResults:
     """What results() returns: the six columns baseMean, log2FoldChange, lfcSE, stat, pvalue, padj and metadata(res).  The
     columns stay where the engine made them (HBM on the device engine) until one is asked for: res["padj"]."""
     COLUMNS = ("baseMean", "log2FoldChange", "lfcSE", "stat", "pvalue", "padj")
+    coef = None                        # results(name = ): the column of the coefficient (what R reads back from the description)
+    shown = None                       # lfcShrinkApeglm: the columns R keeps (res[, 1:3] with svalue, res[, c(1:3, 5:6)])
 
     def __init__(self, tab, priorInfo=None, engine=None):
         self.tab, self.engine = tab, engine
@@ -1634,6 +1639,8 @@ class DESeqResults:
 
     @property
     def columns(self):
+        if self.shown is not None:
+            return list(self.shown)
         return [c for c in ("row",) + self.COLUMNS if c in self._set or (c in self.COLUMNS[:5])]
 
     @property
@@ -1895,8 +1902,10 @@ def results(dds, name=None, lfcThreshold=0, altHypothesis="greaterAbs", cooksCut
     else:
         raise ValueError("the argument 'name' should be a coefficient name or a column index")   # :403-405
     lfc, se, stat, pvalue = _stored_columns(dds, c, test)
-    return _results_tail(dds, lfc, se, stat, pvalue, lfcThreshold, altHypothesis, cooksCutoff, independentFiltering, alpha,
-                         filter, theta, pAdjustMethod, filterFun, tidy)
+    res = _results_tail(dds, lfc, se, stat, pvalue, lfcThreshold, altHypothesis, cooksCutoff, independentFiltering, alpha,
+                        filter, theta, pAdjustMethod, filterFun, tidy)
+    res.coef = c
+    return res
 
 
 def _results_checks(dds, lfcThreshold, altHypothesis, alpha, pAdjustMethod, test):
@@ -2343,10 +2352,11 @@ def lfcShrink(dds, coef=None, contrast=None, res=None, type="normal", lfcThresho
     Not served (NotImplementedError): type "apeglm" / "ashr", svalue, returnList, format, saveCols, parallel."""
     import sys
     from .fused import finish
-    reasons = {"svalue": "s-values belong to type = 'apeglm' / 'ashr'", "returnList": "only type = 'apeglm' / 'ashr' return a list",
+    reasons = {"svalue": "s-values belong to type = 'apeglm' / 'ashr' (see lfcShrinkApeglm)",
+               "returnList": "only type = 'apeglm' / 'ashr' return a list (see lfcShrinkApeglm)",
                "format": "only the table is served", "saveCols": "only the six result columns are served",
                "parallel": "the refit runs on one device", "BPPARAM": "see parallel",
-               "apeAdapt": "type = 'apeglm' is not served", "apeMethod": "type = 'apeglm' is not served"}
+               "apeAdapt": "type = 'apeglm' is served by lfcShrinkApeglm", "apeMethod": "type = 'apeglm' is served by lfcShrinkApeglm"}
     for k, v in not_served.items():
         if k not in reasons:
             raise TypeError("lfcShrink() got an unexpected keyword argument '%s'" % k)
@@ -2364,7 +2374,8 @@ def lfcShrink(dds, coef=None, contrast=None, res=None, type="normal", lfcThresho
         raise RuntimeError("first run DESeq() before running lfcShrink()")        # :162-166
     if type != "normal":
         raise NotImplementedError("lfcShrink(type = '%s') delegates to the %s package, whose source is not part of the reference "
-                                  "tree: nothing here could pin it.  Served: type = 'normal'" % (type, type))
+                                  "tree: nothing here could pin it.  Served: type = 'normal'%s" % (type, type,
+                                  "; the apeglm estimator is served by lfcShrinkApeglm(dds, coef, ...)" if type == "apeglm" else ""))
     if dds.attrs.get("betaPrior"):
         raise ValueError("lfcShrink() should be used downstream of DESeq() with betaPrior=FALSE (the default)")   # :170-173
     if np.ndim(lfcThreshold) != 0 or not lfcThreshold >= 0:
@@ -2474,6 +2485,231 @@ def lfcShrink(dds, coef=None, contrast=None, res=None, type="normal", lfcThresho
     out.metadata["lfcThreshold"] = lfcThreshold                                   # :497
     out.priorInfo = {"type": "normal", "package": "deseq2_amd", "betaPriorVar": betaPriorVar}   # :498-505
     return out
+
+
+# ------------------------------------------------------------------ R/lfcShrink.R:328-440, 489-528: apeglm
+APEGLM_CITATION = ("using 'apeglm' for LFC shrinkage. If used in published research, please cite:\n"
+                   "    Zhu, A., Ibrahim, J.G., Love, M.I. (2018) Heavy-tailed prior distributions for\n"
+                   "    sequence count data: removing the noise and preserving large differences.\n"
+                   "    Bioinformatics. https://doi.org/10.1093/bioinformatics/bty895")
+QNORM_975 = 1.959963984540054
+
+
+def svalue(lfsr):
+    """apeglm::svalue as R/lfcShrink.R:523-528 restates it: sort with NA last, cumulative mean, rank with ties "first".  On
+    the host, in numpy, on both engines (R's cumsum is sequential, and so is numpy.cumsum)."""
+    from . import apeglm_host
+    return apeglm_host.svalue(lfsr)
+
+
+_svalue = svalue                       # (lfcShrinkApeglm has an argument of that name)
+
+
+class _ColumnsTab:
+    """the table of a DESeqResults whose columns are host arrays"""
+
+    def __init__(self, cols):
+        self.resident = cols
+
+    def column(self, name):
+        return self.resident[name]
+
+
+def apeglm_prior_scale(mle, floor=1e-6):
+    """The adaptive scale of the apeglm prior from mle = (estimate, standard error) on the natural-log scale (n x 2), over the
+    rows where both are finite: the marginal-likelihood estimate of the variance A of a Normal prior, D_i ~ N(0, A + S_i^2)
+    (Efron and Morris), i.e. the root of sum_i (D_i^2 - S_i^2 - A) / (S_i^2 + A)^2 = 0 by the fixed point
+    A <- sum w_i (D_i^2 - S_i^2) / sum w_i, w_i = 1 / (S_i^2 + A)^2, sums by math.fsum; S = min(max(sqrt(A), floor), 1).
+    The library's own statement of the estimator: agreement with the package's routine is not pinned."""
+    from . import apeglm_host
+    mle = np.asarray(mle, np.float64)
+    if mle.ndim != 2 or mle.shape[1] != 2:
+        raise ValueError("mle is an n x 2 matrix: estimate, standard error")
+    return apeglm_host.prior_scale(mle[:, 0], mle[:, 1], floor=floor)
+
+
+def apeglm(Y, x, param, coef, mle=None, threshold=None, weights=None, offset=None, prior_control=None, init=None, engine=None):
+    """apeglm::apeglm for the negative binomial likelihood as lfcShrink calls it (R/lfcShrink.R:393-396; DESIGN.md section
+    22): Y n x m counts (a matrix or an engine handle), x the m x p design, param the n dispersions, coef the 0-based
+    coefficient, mle (n x 2, natural log: estimate and standard error of `coef`) for the adaptive prior scale, threshold on
+    the natural-log scale, weights n x m, offset n x m (natural log; None = 0).  prior_control: dict with no_shrink (list
+    of columns, [0]), prior_mean 0, prior_scale (from mle when given, else 1), prior_df (1), prior_no_shrink_mean 0,
+    prior_no_shrink_scale (15).  init: n x p second start (natural log).  Returns dict(map n x p, sd n x p, fsr n, svalue n,
+    thresh n (with a threshold), interval n x 2, diag dict(iter, conv, start, objective), prior_control).
+    The estimator is the package's as its paper and lfcShrink's documentation state it; the optimiser, the choice between two
+    modes and the prior-scale routine are the library's own, and agreement with the package's numbers is not pinned."""
+    x = np.asarray(x, np.float64)
+    p = x.shape[1]
+    pc = {"no_shrink": [0], "prior_mean": 0.0, "prior_scale": None, "prior_df": 1.0, "prior_no_shrink_mean": 0.0,
+          "prior_no_shrink_scale": 15.0}
+    for k, v in (prior_control or {}).items():
+        if k not in pc:
+            raise ValueError("prior_control has no element '%s'" % k)
+        pc[k] = v
+    if pc["prior_mean"] != 0 or pc["prior_no_shrink_mean"] != 0:
+        raise NotImplementedError("apeglm: a prior mean other than 0 is not served")
+    if not (isinstance(coef, (int, np.integer)) and 0 <= int(coef) < p):
+        raise ValueError("coef is a column of x (0-based)")
+    no_shrink = np.zeros(p, bool)
+    no_shrink[list(pc["no_shrink"])] = True
+    if no_shrink[coef]:
+        raise ValueError("coef is among the columns that are not shrunk")
+    if pc["prior_scale"] is None:
+        pc["prior_scale"] = apeglm_prior_scale(mle) if mle is not None else 1.0
+    E = engine if engine is not None else HostEngine()
+    nf = 1.0 if offset is None else E.vexp(np.asarray(offset, np.float64))
+    n = Y.shape[0] if hasattr(Y, "shape") else Y.n
+    if np.ndim(nf) == 0:
+        nf = np.ones(x.shape[0])
+    fit = E.apeglm_fit(Y, x, nf if np.ndim(nf) == 2 else None, np.broadcast_to(np.asarray(param, np.float64), (n,)), int(coef),
+                       no_shrink, float(pc["prior_scale"]), float(pc["prior_df"]), float(pc["prior_no_shrink_scale"]),
+                       weights=weights, init=init, threshold=threshold, sizeFactors=nf if np.ndim(nf) == 1 else None)
+    return _apeglm_fields(fit, int(coef), threshold, pc)
+
+
+def _apeglm_fields(fit, coef, threshold, pc):
+    mc, sc = fit["map"][:, coef], fit["sd"][:, coef]
+    out = {"map": fit["map"], "sd": fit["sd"], "fsr": fit["fsr"], "svalue": svalue(fit["fsr"]),
+           "interval": np.stack([mc - QNORM_975 * sc, mc + QNORM_975 * sc], axis=1),
+           "diag": {"iter": fit["iter"][np.arange(mc.size), np.nan_to_num(fit["start"]).astype(int)], "iter_by_start": fit["iter"],
+                    "conv": fit["conv"], "start": fit["start"], "objective": fit["objective"]},
+           "prior_control": dict(pc)}
+    if threshold is not None:
+        out["thresh"] = fit["thresh"]
+    return out
+
+
+def lfcShrinkApeglm(dds, coef, res=None, lfcThreshold=0, svalue=False, returnList=False, apeAdapt=True, quiet=False, **not_served):
+    """lfcShrink(type = "apeglm") (R/lfcShrink.R:156-219, 328-440, 489-518): MAP fold changes under a Cauchy prior with the
+    posterior SD of the Laplace approximation, per gene on the engine (csrc/apeglm.hip on the device).
+    `coef` is a name of resultsNames(dds) or a column index (0-based, as results(name = ) takes it).  Returns `res`
+    (results(dds, name = coef) when not given) with log2FoldChange = log2(e) map and lfcSE = log2(e) sd, columns
+    baseMean, log2FoldChange, lfcSE, pvalue, padj -- or, with svalue = TRUE or lfcThreshold > 0, baseMean, log2FoldChange,
+    lfcSE, svalue --, metadata["lfcThreshold"], metadata["description"] and priorInfo with prior_control; with
+    returnList, (res, fit).  The fit runs on the ORIGINAL counts with the stored dispersions, offsets from sizeFactors or
+    normalizationFactors and the weights assay as given; the second start of the search is log(2) times the stored MLE
+    coefficients.  apeAdapt = False runs with prior scale 1 and needs only dispersions (:176-180).
+    The optimiser, the choice of mode and the prior-scale routine are the library's own: agreement with the apeglm package's
+    numbers is not pinned.  Not served (NotImplementedError): apeMethod other than "nbinomCR", format, saveCols, parallel."""
+    import sys
+    from .fused import finish
+    reasons = {"format": "only the table is served", "saveCols": "only the result columns are served",
+               "parallel": "the fit runs on one device", "BPPARAM": "see parallel",
+               "apeMethod": "only the default, the negative binomial likelihood with the stored dispersions, is served"}
+    for k, v in not_served.items():
+        if k not in reasons:
+            raise TypeError("lfcShrinkApeglm() got an unexpected keyword argument '%s'" % k)
+        if not (v is None or v is False or (k == "format" and v == "DataFrame") or (k == "apeMethod" and v == "nbinomCR")):
+            raise NotImplementedError("lfcShrinkApeglm(%s = ): %s" % (k, reasons[k]))
+    if not isinstance(dds, DESeqDataSet):
+        raise TypeError('is(dds, "DESeqDataSet") is not TRUE')                    # :156
+    if res is not None and not isinstance(res, DESeqResults):
+        raise ValueError("res should be a DESeqResults object, for GRanges output use 'format'")   # :157-159
+    finish(dds)                      # (an analysis enqueued with wait = False)
+    fitted = "beta" in dds.mcols
+    if not fitted and apeAdapt:
+        raise RuntimeError("first run DESeq() before running lfcShrink()")        # :162-166
+    if dds.attrs.get("betaPrior"):
+        raise ValueError("lfcShrink() should be used downstream of DESeq() with betaPrior=FALSE (the default)")   # :170-173
+    if np.ndim(lfcThreshold) != 0 or not lfcThreshold >= 0:
+        raise ValueError("length(lfcThreshold) == 1 && lfcThreshold >= 0 is not TRUE")   # :174
+    names = resultsNames(dds) if fitted else _coef_names(dds, dds.p)             # :175-180
+    if coef is None:
+        raise ValueError("!missing(coef) is not TRUE")                            # :340
+    if isinstance(coef, str):                                                     # :182-192
+        if coef not in names:
+            raise ValueError("coef %in% resultsNamesDDS is not TRUE")
+        c = names.index(coef)
+    elif isinstance(coef, (int, np.integer)) and not isinstance(coef, bool) and 0 <= int(coef) < len(names):
+        c = int(coef)
+    else:
+        raise ValueError("coef <= length(resultsNamesDDS) is not TRUE")
+    coefAlpha = names[c]
+    # (what apeglm itself refuses: the coefficient is among the columns that are not shrunk; and what is served)
+    if c == 0:
+        raise ValueError("coef is the intercept, which is not shrunk")
+    if dds.p > 16:
+        raise NotImplementedError("lfcShrinkApeglm: %d design columns (at most 16 are served)" % dds.p)
+    if res is None and fitted:                                                    # :193-195
+        res = results(dds, name=c)
+    elif res is None:
+        # :176-180 "we can run apeglm without running nbinomWaldTest()": there are no results to start from, so the table
+        # is baseMean and NA columns, which the fit fills
+        na = np.full(dds.n, np.nan)
+        res = DESeqResults(_ColumnsTab({"baseMean": np.asarray(dds.mcols.get("baseMean", na), np.float64), "log2FoldChange": na,
+                                        "lfcSE": na, "stat": na, "pvalue": na}), {"type": "none", "package": "deseq2_amd"}, dds.engine)
+        res["padj"] = na
+        res.coef = c
+    # (:207-208 reads res$lfcSE; on the route without a Wald test the table above has none by construction, and the fit
+    # needs none with apeAdapt = FALSE, so the stop is made only where a Wald test ran)
+    if fitted and np.isnan(np.asarray(res["lfcSE"], np.float64)).all():
+        raise ValueError("lfcShrink requires standard errors, use default fitType")   # :207-208
+    if "dispersion" not in dds.mcols:
+        raise RuntimeError("type='normal' and 'apeglm' require dispersion estimates, first call estimateDispersions()")   # :211-213
+    if res.n != dds.n:
+        raise ValueError("all(rownames(dds) == rownames(res)) is not TRUE")      # :214 (the objects carry no row names)
+    if apeAdapt and res.coef != c:                                                # :342-347
+        raise ValueError("'coef' should specify same coefficient as in results 'res'")
+    if not quiet:                                                                 # :349-352
+        print(APEGLM_CITATION, file=sys.stderr)
+    E = dds.engine
+    LN2 = float.fromhex("0x1.62e42fefa39efp-1")                                  # log(2)
+    LOG2E = float.fromhex("0x1.71547652b82fep+0")                                # log2(exp(1))
+    disps = np.asarray(dds.mcols["dispersion"], np.float64)                       # :361
+    mle = None
+    if apeAdapt:                                                                  # :373-377
+        mle = LN2 * np.stack([np.asarray(res["log2FoldChange"], np.float64), np.asarray(res["lfcSE"], np.float64)], axis=1)
+    apeT = None
+    if lfcThreshold > 0:                                                          # :383-389
+        if not quiet:
+            print("computing FSOS 'false sign or small' s-values (T=%s)" % _r_round3(lfcThreshold), file=sys.stderr)
+        svalue = True
+        apeT = LN2 * lfcThreshold
+    pc = {"no_shrink": [0], "prior_mean": 0.0, "prior_scale": apeglm_prior_scale(mle) if mle is not None else 1.0,
+          "prior_df": 1.0, "prior_no_shrink_mean": 0.0, "prior_no_shrink_scale": 15.0}
+    no_shrink = np.zeros(dds.p, bool)
+    no_shrink[0] = True
+    init = LN2 * np.asarray(dds.mcols["beta"], np.float64) if fitted else None
+    # :354-372, :393-396: the original counts, offsets log(sizeFactors) or log(normalizationFactors), the weights assay
+    fit = E.apeglm_fit(dds.y, dds.x, None if dds.sizeFactors is not None else dds.nf, disps, c, no_shrink, pc["prior_scale"],
+                       pc["prior_df"], pc["prior_no_shrink_scale"], weights=dds.weights_h if dds.has_weights else None,
+                       init=init, threshold=apeT, sizeFactors=dds.sizeFactors)
+    fit = _apeglm_fields(fit, c, apeT, pc)
+    if fit["map"].shape[0] != dds.n:
+        raise RuntimeError("nrow(fit$map) == nrow(dds) is not TRUE")              # :418
+    conv = fit["diag"]["conv"]                                                    # :419-422
+    if not (conv[~np.isnan(conv)] == 0).all() and not quiet:
+        print("some rows did not converge in finding the MAP", file=sys.stderr)
+    out = DESeqResults(res.tab, None, res.engine)
+    out.metadata = dict(res.metadata)
+    out._set = dict(res._set)
+    out.coef = c
+    out["log2FoldChange"] = LOG2E * fit["map"][:, c]                              # :423
+    out["lfcSE"] = LOG2E * fit["sd"][:, c]                                        # :424
+    spaces = coefAlpha.replace("_", " ")
+    desc = {"baseMean": "mean of normalized counts for all samples",
+            "log2FoldChange": "log2 fold change (MAP): " + spaces,                 # :425
+            "lfcSE": "posterior SD: " + spaces}                                   # :426
+    if svalue:                                                                    # :427-437
+        if lfcThreshold > 0:
+            out["svalue"] = _svalue(fit["thresh"])
+            desc["svalue"] = "FSOS s-value (T=%s): %s" % (_r_round3(lfcThreshold), spaces)
+        else:
+            out["svalue"] = fit["svalue"]
+            desc["svalue"] = "s-value: " + spaces
+        out.shown = ("baseMean", "log2FoldChange", "lfcSE", "svalue")
+    else:                                                                         # :439
+        desc["pvalue"], desc["padj"] = "Wald test p-value: " + spaces, "BH adjusted p-values"
+        out.shown = ("baseMean", "log2FoldChange", "lfcSE", "pvalue", "padj")
+    out.metadata["description"] = desc
+    out.metadata["lfcThreshold"] = lfcThreshold                                   # :497
+    out.priorInfo = {"type": "apeglm", "package": "deseq2_amd", "prior_control": fit["prior_control"]}   # :498-507
+    return (out, fit) if returnList else out                                      # :514-518
+
+
+def _r_round3(v):
+    """round(v, 3) as paste0 prints it"""
+    return "%g" % round(float(v), 3)
 
 
 # ------------------------------------------------------------------ R/helper.R:70-132

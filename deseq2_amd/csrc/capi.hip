@@ -810,6 +810,52 @@ int rlog_dev_locked(const DsqRlogArgs *a, const DsqRlogOut *o, hipStream_t st) {
     return DSQ_OK;
 }
 
+// apeglm shrinkage (apeglm.hip): what both entries check before anything is launched
+int apeglm_check(const DsqApeglmArgs *a, const DsqApeglmOut *o) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->n < 1 || a->m < 1 || a->p < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
+    if (a->p > DSQ_APEGLM_MAX_P) return capi_fail(DSQ_ERR_UNSUPPORTED, "p = %d design columns: at most %d", a->p, DSQ_APEGLM_MAX_P);
+    if (!a->y || !a->nf || !a->x || !a->disp) return capi_fail(DSQ_ERR_ARG, "NULL counts, size / normalization factors, design or dispersions");
+    if (a->y_type != DSQ_Y_INT32 && a->y_type != DSQ_Y_FLOAT64) return capi_fail(DSQ_ERR_ARG, "unknown y_type %d", a->y_type);
+    if (!o->map || !o->sd || !o->fsr || !o->thresh || !o->iter || !o->conv || !o->start || !o->objective)
+        return capi_fail(DSQ_ERR_ARG, "NULL output array");
+    if (a->coef < 0 || a->coef >= a->p) return capi_fail(DSQ_ERR_ARG, "coef = %d is outside [0, %d)", a->coef, a->p);
+    if ((a->no_shrink >> a->coef) & 1u) return capi_fail(DSQ_ERR_ARG, "coef = %d is among the columns that are not shrunk", a->coef);
+    if (a->p < 32 && (a->no_shrink >> a->p)) return capi_fail(DSQ_ERR_ARG, "no_shrink names a column beyond p = %d", a->p);
+    const auto positive = [](double v) { return v > 0.0 && v - v == 0.0; };
+    if (!positive(a->prior_scale) || !positive(a->prior_df) || !positive(a->no_shrink_scale))
+        return capi_fail(DSQ_ERR_ARG, "prior_scale = %g, prior_df = %g, no_shrink_scale = %g must be positive and finite", a->prior_scale,
+                         a->prior_df, a->no_shrink_scale);
+    if (a->has_threshold && !(a->threshold >= 0.0)) return capi_fail(DSQ_ERR_ARG, "threshold = %g must not be negative", a->threshold);
+    if (a->maxit < 0 || a->tol != a->tol) return capi_fail(DSQ_ERR_ARG, "bad tol / maxit");
+    return DSQ_OK;
+}
+
+int apeglm_dev_locked(const DsqApeglmArgs *a, const DsqApeglmOut *o, hipStream_t st) {
+    if (int rc = apeglm_check(a, o)) return rc;
+    if (int rc = check_layout(a->layout, a->ld, a->m, true)) return rc;
+    if (int rc = capi_check_device()) return rc;
+    ApeglmKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.m = a->m; kp.p = a->p;
+    kp.y = a->y;
+    const bool gm = a->layout == DSQ_LAYOUT_GENE_MAJOR;
+    kp.si = gm ? (long)a->ld : 1L;  kp.sj = gm ? 1L : (long)a->n;
+    kp.nf = a->nf; kp.nf_is_vector = a->nf_is_vector ? 1 : 0;
+    kp.x = a->x; kp.weights = a->weights; kp.disp = a->disp; kp.init = a->init;
+    kp.coef = a->coef; kp.no_shrink = a->no_shrink;
+    kp.prior_scale = a->prior_scale; kp.prior_df = a->prior_df; kp.no_shrink_scale = a->no_shrink_scale;
+    kp.has_threshold = a->has_threshold ? 1 : 0; kp.threshold = a->threshold;
+    kp.tol = a->tol; kp.maxit = a->maxit;
+    kp.map = o->map; kp.sd = o->sd; kp.fsr = o->fsr; kp.thresh = o->thresh; kp.iter = o->iter; kp.conv = o->conv;
+    kp.start = o->start; kp.objective = o->objective;
+    kp.bad = a->y_type == DSQ_Y_FLOAT64 ? o->bad : nullptr;
+    capi_prof_begin("apeglm", a->n, st);
+    DSQ_HIP(launch_apeglm(kp, a->y_type == DSQ_Y_FLOAT64, st));
+    capi_prof_end(st);
+    return DSQ_OK;
+}
+
 // unmix() (unmix.hip): what both entries check before anything is launched
 int unmix_check(const DsqUnmixArgs *a, const DsqUnmixOut *o) {
     if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
@@ -1207,6 +1253,7 @@ DSQ_DEV(dsq_size_factors_dev, DsqSizeFactorArgs, const DsqSizeFactorOut *, size_
 DSQ_DEV(dsq_vst_dev, DsqVstArgs, const DsqVstOut *, vst_dev_locked(a, o, true, false, st))
 DSQ_DEV(dsq_vst_rowstats_dev, DsqVstArgs, const DsqVstOut *, vst_dev_locked(a, o, false, true, st))
 DSQ_DEV(dsq_rlog_dev, DsqRlogArgs, const DsqRlogOut *, rlog_dev_locked(a, o, st))
+DSQ_DEV(dsq_apeglm_dev, DsqApeglmArgs, const DsqApeglmOut *, apeglm_dev_locked(a, o, st))
 DSQ_DEV(dsq_results_dev, DsqResultsArgs, const DsqResultsOut *, results_dev_locked(a, o, st))
 DSQ_DEV(dsq_contrasts_dev, DsqContrastsArgs, const DsqContrastsOut *, contrasts_dev_locked(a, o, st))
 DSQ_DEV(dsq_top_var_dev, DsqTopVarArgs, const DsqTopVarOut *, top_var_dev_locked(a, o, st))
@@ -1236,6 +1283,7 @@ int dsq_parametric_dispersion_fit_dev(const double *means, const double *disps, 
 int dsq_unmix_dev(const DsqUnmixArgs *a, const DsqUnmixOut *o, void *workspace, int64_t workspace_bytes, void *s) {
     return dev_entry(s, [&](hipStream_t st) { return unmix_dev_locked(a, o, workspace, workspace_bytes, st); });
 }
+int32_t dsq_apeglm_lds_doubles(void) { return kApeXLdsDoubles; }
 int64_t dsq_unmix_workspace_bytes(int32_t n, int32_t m, int32_t k) {
     if (n < 1 || m < 1 || k < 1) return 0;
     return (int64_t)unmix_workspace_bytes(n, m);

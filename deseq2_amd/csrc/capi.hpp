@@ -53,6 +53,7 @@ int check_replace(const DsqReplaceArgs *a, const DsqReplaceOut *o);
 int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o);
 int vst_check(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats);
 int rlog_check(const DsqRlogArgs *a, const DsqRlogOut *o);
+int apeglm_check(const DsqApeglmArgs *a, const DsqApeglmOut *o);
 int unmix_check(const DsqUnmixArgs *a, const DsqUnmixOut *o);
 int sf_iterate_check(const DsqSfIterateArgs *a, const DsqSfIterateOut *o);
 int top_var_check(const DsqTopVarArgs *a, const DsqTopVarOut *o);
@@ -78,6 +79,7 @@ int replace_dev_locked(const DsqReplaceArgs *a, const DsqReplaceOut *o, hipStrea
 int size_factors_dev_locked(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o, hipStream_t st);
 int vst_dev_locked(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats, hipStream_t st);
 int rlog_dev_locked(const DsqRlogArgs *a, const DsqRlogOut *o, hipStream_t st);
+int apeglm_dev_locked(const DsqApeglmArgs *a, const DsqApeglmOut *o, hipStream_t st);
 int unmix_dev_locked(const DsqUnmixArgs *a, const DsqUnmixOut *o, void *workspace, int64_t workspace_bytes, hipStream_t st);
 int sf_iterate_dev_locked(const DsqSfIterateArgs *a, const DsqSfIterateOut *o, void *workspace, int64_t workspace_bytes, hipStream_t st);
 int top_var_dev_locked(const DsqTopVarArgs *a, const DsqTopVarOut *o, hipStream_t st);

@@ -814,6 +814,40 @@ int dsq_rlog(const DsqRlogArgs *a, const DsqRlogOut *o) {
     return DSQ_OK;
 }
 
+int dsq_apeglm(const DsqApeglmArgs *a, const DsqApeglmOut *o) {
+    HostCall hc;
+    DSQ_TRY(host_ready(apeglm_check(a, o), a ? a->layout : 0));
+    hipStream_t st = hc.st;
+    const size_t n = a->n, m = a->m, p = a->p;
+    const long ld = round_ld(a->m);
+    DsqApeglmArgs d = *a;
+    DsqApeglmOut od = *o;
+    Stage s(st, n);
+    DSQ_TRY(up_gene_major(s, WS_H_Y, WS_Y, a->y, a->y_type == DSQ_Y_INT32 ? 4 : 8, a->n, a->m, ld, &d.y));
+    d.layout = DSQ_LAYOUT_GENE_MAJOR; d.ld = ld;
+    DSQ_TRY(nf_up_gene_major(s, &d.nf, a->nf, a->nf_is_vector, a->n, a->m, ld));
+    if (a->weights) DSQ_TRY(up_gene_major(s, WS_H_W, WS_W, a->weights, 8, a->n, a->m, ld, &d.weights));
+    s.vec(&d.x, a->x, m * p * 8);
+    s.gene_vec(&d.disp, a->disp);
+    if (a->init) s.vec(&d.init, a->init, n * p * 8);
+    DSQ_TRY(s.pack_in());
+    int32_t bad = 0;
+    s.out_vec(&od.bad, &bad, 4, 8);
+    s.out_vec(&od.map, o->map, n * p * 8);
+    s.out_vec(&od.sd, o->sd, n * p * 8);
+    s.out_gene_vec(&od.fsr, o->fsr);
+    s.out_gene_vec(&od.thresh, o->thresh);
+    s.out_vec(&od.iter, o->iter, n * 2 * 8);
+    s.out_gene_vec(&od.conv, o->conv);
+    s.out_gene_vec(&od.start, o->start);
+    s.out_gene_vec(&od.objective, o->objective);
+    DSQ_TRY(s.pack_out());
+    DSQ_HIP(hipMemsetAsync(od.bad, 0, 8, st));
+    DSQ_TRY(apeglm_dev_locked(&d, &od, st));
+    DSQ_TRY(s.finish());
+    if (bad) return capi_fail(DSQ_ERR_VALUE, "count matrix holds negative, non-finite or non-integer values");
+    return DSQ_OK;
+}
 
 int dsq_unmix(const DsqUnmixArgs *a, const DsqUnmixOut *o) {
     const auto check = [&]() -> int {

@@ -269,6 +269,30 @@ struct RlogKernelParams {
 };
 hipError_t launch_rlog(const RlogKernelParams &kp, int y_f64, hipStream_t st);
 
+// apeglm shrinkage (apeglm.hip).  Element (i, j) of counts / nf matrix / weights sits at
+// [i * si + j * sj]; map / sd / init: n x p, p contiguous per gene; iter: n x 2.
+struct ApeglmKernelParams {
+    int n, m, p;
+    const void *y;
+    long si, sj;
+    const double *nf;
+    int nf_is_vector;
+    const double *x;             // m x p column-major
+    const double *weights;       // matrix or nullptr
+    const double *disp;          // n
+    const double *init;          // n x p or nullptr
+    int coef;
+    unsigned no_shrink;
+    double prior_scale, prior_df, no_shrink_scale;
+    int has_threshold;
+    double threshold, tol;
+    int maxit;
+    double *map, *sd, *fsr, *thresh, *iter, *conv, *start, *objective;
+    int32_t *bad;                // float64 counts: as VstKernelParams.bad
+};
+constexpr int kApeXLdsDoubles = 4096;     // the design is staged in LDS while m * p doubles fit here (dsq_apeglm_lds_doubles)
+hipError_t launch_apeglm(const ApeglmKernelParams &kp, int y_f64, hipStream_t st);
+
 // unmix() (unmix.hip): x gene-major (element (g, i) at [g * ld + i]), pure gene-major with k
 // contiguous doubles per gene; vx: the caller's workspace, m x n, written by the preparation kernel and read by the fit.
 struct UnmixKernelParams {

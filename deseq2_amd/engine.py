@@ -435,6 +435,21 @@ class HostEngine:
         from . import unmix_host
         return unmix_host.unmix_fit(self.vlog, np.asarray(x, np.float64), pure, alpha=alpha, shift=shift, power=power, maxit=maxit)
 
+    def apeglm_fit(self, y, x, nf, disp, coef, no_shrink, prior_scale, prior_df=1.0, no_shrink_scale=15.0, weights=None,
+                   init=None, threshold=None, tol=1e-8, maxit=100, sizeFactors=None):
+        """the apeglm posterior per gene: y / nf / weights n x m handles (or arrays), x m x p,
+        no_shrink a boolean mask of p, init n x p or None.  The iteration of csrc/apeglm.hip stated in numpy over this
+        engine's exp / log / log1p (apeglm_host.py), the same bits.  Returns dict(map n x p, sd n x p, fsr, thresh,
+        iter n x 2, conv, start, objective) on the host, NaN on the rows that are not fitted."""
+        from . import apeglm_host
+        if np.asarray(x).shape[1] > apeglm_host.MAX_P:
+            raise NotImplementedError("apeglm: %d design columns (at most %d are served)" % (np.asarray(x).shape[1], apeglm_host.MAX_P))
+        return apeglm_host.fit(self.fns.unary, np.asarray(y, np.float64), x, sizeFactors if sizeFactors is not None else nf,
+                               np.asarray(disp, np.float64), coef, no_shrink, prior_scale, prior_df, no_shrink_scale,
+                               weights=None if weights is None else np.asarray(weights, np.float64),
+                               init=None if init is None else np.asarray(init, np.float64), threshold=threshold, tol=tol,
+                               maxit=maxit)
+
     def row_vars(self, x):
         """(rowMean, rowVar) of an n x m handle (matrixStats::rowVars as documented): the two wave-order sums of
         csrc/explore.hip stated in numpy (explore_host.py), the same bits"""
@@ -975,6 +990,34 @@ class DeviceEngine:
                                  r["flag"].to(t.float64)[:, None]], dim=1)).numpy()
         return {"p": pack[:, :k].copy(), "loss": pack[:, k].copy(), "iter": pack[:, k + 1].astype(np.int32),
                 "flag": pack[:, k + 2].astype(np.int32)}
+
+    def apeglm_fit(self, y, x, nf, disp, coef, no_shrink, prior_scale, prior_df=1.0, no_shrink_scale=15.0, weights=None,
+                   init=None, threshold=None, tol=1e-8, maxit=100, sizeFactors=None):
+        """the apeglm posterior per gene on the device (csrc/apeglm.hip, dsq_apeglm_dev) on the current stream: y the
+        resident counts (or a host matrix, which goes up once), nf a resident matrix or -- with sizeFactors -- the m-vector,
+        weights a resident matrix (or host) or None.  What goes up: the design, the dispersions and init; what comes down,
+        in one copy: map, sd (n x p) and the six per-gene columns."""
+        t = self.torch
+        p = np.asarray(x).shape[1]
+        if not isinstance(y, self.native.GeneMajor):
+            y = self.counts(y) if np.issubdtype(np.asarray(y).dtype, np.integer) else self.matrix(y)
+        f = self._sf_dev(sizeFactors) if sizeFactors is not None else (nf if isinstance(nf, self.native.GeneMajor) else self.matrix(nf))
+        if weights is not None and not isinstance(weights, self.native.GeneMajor):
+            weights = self.matrix(weights)
+        bad = t.zeros(2, dtype=t.int32, device=self.device) if y.t.dtype == t.float64 else None
+        r = self._timed("apeglm", y.n, lambda: self.native.apeglm_dev(
+            y, self.design(x), f, self._vec(disp), coef, no_shrink, prior_scale, prior_df, no_shrink_scale, weights=weights,
+            init=None if init is None else self._vec(np.ascontiguousarray(init, dtype=np.float64)), threshold=threshold,
+            tol=tol, maxit=maxit, bad=bad))
+        if bad is not None and int(self._host(bad)[0]) != 0:
+            raise ValueError("count matrix holds negative, non-finite or non-integer values")
+        h = self._host(r["_pack"]).numpy()
+        out, at, n = {}, 0, y.n
+        for k, c in self.native._APEGLM_OUT:
+            c = p if c == "p" else c
+            out[k] = h[at:at + n * c].reshape((n, c) if c != 1 else (n,)).copy()
+            at += n * c
+        return out
 
     def _resident(self, x):
         return x if isinstance(x, self.native.GeneMajor) else self.matrix(x)

@@ -590,6 +590,42 @@ def rlog(counts, nf, dispFit, betaPriorVar, intercept=None, tol=1e-4, maxit=100,
     return {"rlog": out, "intercept": oi, "iter": it, "flag": flag}
 
 
+def _apeglm_form(p, coef, no_shrink, prior_scale, prior_df, no_shrink_scale, threshold, tol, maxit):
+    mask = 0
+    for k, flag in enumerate(np.asarray(no_shrink, bool).reshape(-1)):
+        mask |= int(flag) << k
+    return dict(coef=int(coef), no_shrink=mask, prior_scale=float(prior_scale), prior_df=float(prior_df),
+                no_shrink_scale=float(no_shrink_scale), has_threshold=int(threshold is not None),
+                threshold=float(threshold) if threshold is not None else 0.0, tol=float(tol), maxit=int(maxit))
+
+
+_APEGLM_OUT = (("map", "p"), ("sd", "p"), ("fsr", 1), ("thresh", 1), ("iter", 2), ("conv", 1), ("start", 1), ("objective", 1))
+
+
+def apeglm(counts, x, nf, disp, coef, no_shrink, prior_scale, prior_df=1.0, no_shrink_scale=15.0, weights=None, init=None,
+           threshold=None, tol=1e-8, maxit=100):
+    """the apeglm posterior through dsq_apeglm: host arrays in R layout in (counts n x m, x m x p, nf
+    the m size factors or an n x m matrix, weights n x m or None, init n x p or None; no_shrink a boolean mask of p);
+    dict(map n x p, sd n x p, fsr, thresh, iter n x 2, conv, start, objective) out, NaN on the rows that are not fitted."""
+    y, ytype = _counts(counts)
+    n, m = _need_matrix(y).shape
+    x = _fcol(np.asarray(x, np.float64))
+    p = x.shape[1]
+    nf, vec = _host_nf(nf, n, m)
+    disp = np.ascontiguousarray(np.broadcast_to(np.asarray(disp, np.float64), (n,)))
+    w = None if weights is None else _fcol(np.asarray(weights, np.float64))
+    b0 = None if init is None else np.ascontiguousarray(init, dtype=np.float64)
+    if (w is not None and w.shape != (n, m)) or (b0 is not None and b0.shape != (n, p)):
+        raise ValueError("weights is n x m and init n x p")
+    out = {k: np.zeros((n, p if c == "p" else c) if c != 1 else n) for k, c in _APEGLM_OUT}
+    a = L.DsqApeglmArgs(n=n, m=m, p=p, layout=L.DSQ_LAYOUT_R, ld=0, y=_ptr(y), y_type=ytype, nf=_ptr(nf), nf_is_vector=int(vec),
+                        x=_ptr(x), weights=_ptr(w), disp=_ptr(disp), init=_ptr(b0),
+                        **_apeglm_form(p, coef, no_shrink, prior_scale, prior_df, no_shrink_scale, threshold, tol, maxit))
+    o = L.DsqApeglmOut(bad=None, **{k: _ptr(v) for k, v in out.items()})
+    L.check(L.lib().dsq_apeglm(C.byref(a), C.byref(o)))
+    return out
+
+
 _FIT_ERRORS = {1: "parametric dispersion fit failed", 2: "dispersion fit did not converge"}
 
 
@@ -879,6 +915,39 @@ def rlog_dev(y, nf, dispFit, betaPriorVar, intercept=None, tol=1e-4, maxit=100, 
                      flag=_t_ptr(flag), bad=_t_ptr(bad))
     L.check(L.lib().dsq_rlog_dev(C.byref(a), C.byref(o), _stream()))
     return {"rlog": out, "intercept": pack[0] if intercept is None else None, "iter": pack[1], "flag": flag}
+
+
+def apeglm_dev(y, x, nf, disp, coef, no_shrink, prior_scale, prior_df=1.0, no_shrink_scale=15.0, weights=None, init=None,
+               threshold=None, tol=1e-8, maxit=100, bad=None):
+    """dsq_apeglm_dev on resident counts: y GeneMajor (int32 or float64), x an (m, p) host array or a device tensor holding
+    it column-major, nf the m size factors (a device tensor) or a GeneMajor matrix with y's ld, weights a GeneMajor float64
+    matrix with y's ld or None, disp a float64 device vector of n, init an (n, p) contiguous float64 device tensor or None.
+    Returns one (n, 2 p + 8) float64 device tensor `pack` and the dict of its column views (map, sd, fsr, thresh, iter,
+    conv, start, objective); nothing is read back."""
+    import torch
+    dev = y.t.device
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float64).T)).to(dev)      # (p, m) contiguous = m x p column-major
+    p = x.shape[0]
+    assert x.dtype == torch.float64 and x.is_contiguous() and x.shape[1] == y.m
+    assert disp.dtype == torch.float64 and disp.numel() == y.n and disp.is_contiguous()
+    if weights is not None:
+        assert isinstance(weights, GeneMajor) and weights.ld == y.ld and weights.n == y.n and weights.t.dtype == torch.float64
+    if init is not None:
+        assert init.dtype == torch.float64 and tuple(init.shape) == (y.n, p) and init.is_contiguous()
+    out, at = {}, 0
+    pack = torch.empty(y.n * (2 * p + 8), dtype=torch.float64, device=dev)
+    for k, c in _APEGLM_OUT:
+        c = p if c == "p" else c
+        out[k] = pack[at:at + y.n * c].view((y.n, c) if c != 1 else (y.n,))
+        at += y.n * c
+    a = L.DsqApeglmArgs(**_vst_dev_args(y, nf), p=p, x=_t_ptr(x), weights=_t_ptr(None if weights is None else weights.t),
+                        disp=_t_ptr(disp), init=_t_ptr(init),
+                        **_apeglm_form(p, coef, no_shrink, prior_scale, prior_df, no_shrink_scale, threshold, tol, maxit))
+    o = L.DsqApeglmOut(bad=_t_ptr(bad), **{k: _t_ptr(v) for k, v in out.items()})
+    L.check(L.lib().dsq_apeglm_dev(C.byref(a), C.byref(o), _stream()))
+    out["_pack"] = pack
+    return out
 
 
 def _unmix_form(alpha, shift, power, maxit):

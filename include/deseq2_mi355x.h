@@ -733,6 +733,69 @@ int32_t dsq_unmix_block_threads(void);   /* the T of the summation order: thread
 int dsq_unmix_dev(const DsqUnmixArgs *args, const DsqUnmixOut *out, void *workspace, int64_t workspace_bytes, void *stream);
 int dsq_unmix(const DsqUnmixArgs *args, const DsqUnmixOut *out);
 
+/* ---- dsq_apeglm: apeglm shrinkage, lfcShrink(type = "apeglm") (R/lfcShrink.R:328-440) ------------
+ * Per gene i, the coefficients b (natural-log scale) of a negative binomial GLM with dispersion a_i that minimise
+ *     F_i(b) = - sum_j w_ij [ y_ij eta_ij - (y_ij + 1/a_i) log1p(a_i mu_ij) ]
+ *              + sum_{k in no_shrink} b_k^2 / (2 no_shrink_scale^2)
+ *              + sum_{k not in no_shrink} ((prior_df + 1) / 2) log1p(b_k^2 / (prior_df prior_scale^2)),
+ *     eta = x b + log nf,  mu = exp(eta)
+ * (a Student t prior, Cauchy at prior_df = 1, on the shrunken coefficients), the Laplace posterior SD
+ * sd_k = sqrt((H(map)^-1)_kk) from the observed Hessian, and for the coefficient `coef`: fsr = pnorm(-|map| / sd) and, with
+ * a threshold T, thresh = P(|b| < T) under N(map, sd^2).  The package reaches the mode by its own optimiser; the library
+ * minimises the same F by its own deterministic damped Newton (Levenberg-Marquardt) iteration from two starts -- the
+ * shrunken one (shrunken coefficients 0, column 0 at log(max(weighted mean of y / nf, 0.1)) when it is unshrunken), then
+ * `init` clipped to +-30 when given -- and keeps the lower F (a tie: the first), every operation rounded once in a stated
+ * order (tests/apeglm_spec.py).  Agreement with the package's numbers is not pinned.
+ * conv: 0 an accepted undamped step with max |step| < tol, 1 maxit reached, 2 no acceptable step (or F not finite at the
+ * start: objective NaN), + 4 when the Hessian at the point returned is not positive definite (sd, fsr, thresh NaN).
+ * start: 0 the shrunken start won, 1 init.  iter: 2 per gene, the iterations from either start (0 without init).
+ * A row whose counts are all zero or whose dispersion is NaN, infinite or not positive is not fitted: NaN everywhere.
+ * map, sd, init: n x p with the p values of a gene contiguous, in both entries.  x: m x p column-major.
+ * _dev: device pointers, asynchronous on `stream`, no allocation, no host synchronisation, no workspace; padding columns
+ * m .. ld-1 of gene-major matrices are not read; a negative, non-finite or non-integer float64 count sets *bad.
+ * dsq_apeglm: host pointers in R layout, ONE device, synchronous; DSQ_ERR_VALUE for such a count matrix.
+ * DSQ_ERR_UNSUPPORTED: p > DSQ_APEGLM_MAX_P.  DSQ_ERR_ARG: coef out of range or inside no_shrink, a scale or df that is
+ * not positive and finite, a negative or NaN threshold, tol NaN, maxit < 0.  All decided before a device is asked for. */
+#define DSQ_APEGLM_MAX_P 16
+typedef struct {
+    int32_t n, m, p;
+    int32_t layout;            /* DSQ_LAYOUT_* of y / nf (matrix) / weights                                         */
+    int64_t ld;                /* leading dimension for DSQ_LAYOUT_GENE_MAJOR (>= m)                                */
+    const void *y;             /* n x m counts                                                                      */
+    int32_t y_type;            /* DSQ_Y_INT32 or DSQ_Y_FLOAT64                                                      */
+    const double *nf;          /* m size factors (nf_is_vector) or n x m normalization factors in `layout`          */
+    int32_t nf_is_vector;
+    const double *x;           /* m x p design, column-major                                                        */
+    const double *weights;     /* n x m in `layout`, >= 0, or NULL (all 1)                                          */
+    const double *disp;        /* n                                                                                 */
+    const double *init;        /* n x p (natural log), the second start, or NULL                                    */
+    int32_t coef;              /* 0-based: the coefficient fsr / thresh are formed for                              */
+    uint32_t no_shrink;        /* bit k set: column k gets Normal(0, no_shrink_scale^2); apeglm: column 0           */
+    double prior_scale;        /* S > 0                                                                             */
+    double prior_df;           /* > 0; apeglm: 1                                                                    */
+    double no_shrink_scale;    /* > 0; apeglm: 15                                                                   */
+    int32_t has_threshold;
+    double threshold;          /* natural-log scale, >= 0; read when has_threshold                                  */
+    double tol;                /* 1e-8                                                                              */
+    int32_t maxit;             /* >= 0; 100.  0 returns the start                                                   */
+} DsqApeglmArgs;
+
+typedef struct {
+    double *map;               /* n x p                                                                             */
+    double *sd;                /* n x p                                                                             */
+    double *fsr;               /* n                                                                                 */
+    double *thresh;            /* n (NaN without a threshold)                                                       */
+    double *iter;              /* n x 2                                                                             */
+    double *conv;              /* n                                                                                 */
+    double *start;             /* n                                                                                 */
+    double *objective;         /* n: F at map                                                                       */
+    int32_t *bad;              /* _dev: one device int32 the CALLER has zeroed, or NULL; dsq_apeglm: ignored        */
+} DsqApeglmOut;
+
+int32_t dsq_apeglm_lds_doubles(void);   /* the design is staged in LDS while m * p is at most this; read through L2 beyond */
+int dsq_apeglm_dev(const DsqApeglmArgs *args, const DsqApeglmOut *out, void *stream);
+int dsq_apeglm(const DsqApeglmArgs *args, const DsqApeglmOut *out);
+
 /* ---- dsq_sf_iterate: the solve of estimateSizeFactors(type = "iterate") (R/core.R:2600-2611) ------
  * One outer round of estimateSizeFactorsIterate fixes the counts k, q_ij = mu_ij / sf_j and the dispersions a_i over the
  * rows whose flag is set, and maximises over s (sum s = 0)
