@@ -31,6 +31,16 @@
  * list members) follow the reference line by line; see DESIGN.md.  Inputs are
  * borrowed and never written.  No CPU fallback exists: without a usable gfx950
  * device every call fails with DSQ_ERR_DEVICE.
+ *
+ * Memory contract of the core _dev entries (dsq_fit_beta_dev, dsq_fit_disp_dev, dsq_fit_disp_grid_dev,
+ * dsq_prefit_moments_dev, dsq_linear_mu_dev, dsq_nbinom_loglike_dev, dsq_intercept_fit_dev,
+ * dsq_parametric_dispersion_fit_dev, dsq_cooks_distance_dev, dsq_replace_outliers_dev, dsq_weights_prep_dev, dsq_xim_dev,
+ * the layout helpers, dsq_beta_prior_var_dev, dsq_deseq_dev): padding columns m .. ld-1 of gene-major inputs are not
+ * read, of gene-major outputs not written.  Outputs and workspaces need not be initialised: every element the entry
+ * defines is written before it is read, whatever the buffer held.  The two exceptions are flags the library ORs into,
+ * which the caller zeroes first: *any_negative of dsq_weights_prep_dev and *bad of dsq_counts_f64_to_gene_major_i32.
+ * Nothing outside the buffers handed over (at the sizes stated here) is written.  tests/test_gpu_entry_memory.py and tests/test_gpu_chain_memory.py hold the library
+ * to this on poisoned memory.
  */
 #ifndef DESEQ2_MI355X_H
 #define DESEQ2_MI355X_H
@@ -493,7 +503,10 @@ typedef struct {
     const double *lambda;          /* HOST: p ridge values on the natural-log scale (R/fitNbinomGLMs.R:162)      */
     double min_log_alpha;          /* log(minDisp / 10) (R/core.R:775)                                           */
     void *workspace;               /* device, dsq_deseq_workspace_bytes(...): holds the row lists and counters of
-                                      the analysis between phases -- the same buffer for all its phases           */
+                                      the analysis between phases -- the same buffer for all its phases.  It need
+                                      not be initialised: the first phase of an analysis (DSQ_PH_GENE_EST) reads
+                                      nothing of it that it has not written, so between two analyses it may hold
+                                      anything -- another analysis' vectors included                              */
     int64_t workspace_bytes;
     int32_t test;                  /* 0 Wald, 1 LRT (reduced = ~1 unless x_red is given)                         */
     /* outlier phase (all host arrays; R/core.R:2081,2101,2366-2371) */
@@ -534,7 +547,14 @@ typedef struct {
 } DsqDeseqArgs;
 
 typedef struct {
-    /* per-gene results, device, caller-allocated; rows that are all-zero come back NaN / -1 */
+    /* per-gene results, device, caller-allocated; rows that are all-zero come back NaN / -1.  None of the outputs need
+     * be initialised.  Written whole: every per-gene column (logLikeReduced under the Wald test too: NA), status,
+     * mle_beta, and the rows of mu, H and cooks over the columns 0 .. m-1 (NA in the all-zero rows).  Left as it was:
+     *   scalars        DSQ_SC_COEF0 .. DSQ_SC_FIT_USED are written, the spare entries behind them are not;
+     *   mu_hat         rows of all-zero genes (allZero = 1 after DSQ_PH_GENE_EST, weightsFail rows included) are left as
+     *                  they were;
+     *   replaceCounts  only the rows with replace != 0 are written;
+     *   all five n x ld matrices: the padding columns m .. ld-1 are not written.                                       */
     double *baseMean, *baseVar;
     int32_t *allZero;
     double *dispGeneEst;
