@@ -39,7 +39,7 @@ const Tuning &tuning() {
                        env_int("DSQ_BETA_CELLS", 1), env_int("DSQ_DISP_CELL_MINP", DSQ_DISP_CELL_MINP),
                        env_int("DSQ_OVERLAP", 1), env_int("DSQ_LPT", 1),
                        env_int("DSQ_LPT_MAXN", 16384), env_int("DSQ_LPT_KEY1", 1), env_int("DSQ_LPT_KEYD", 1), env_int("DSQ_LPT_KEYM", 2),
-                       env_int("DSQ_LPT_KEY2", 1), env_int("DSQ_OUTLIER_FIRST", 1)};
+                       env_int("DSQ_LPT_KEY2", 1), env_int("DSQ_OUTLIER_FIRST", 1), env_int("DSQ_DISP_PREDICT", -1)};
     return t;
 }
 

@@ -28,6 +28,7 @@ struct DispKernelParams {
     const double *grid;
     int ngrid;
     int ablate, force_iters; // profiling only
+    int predict;             // evaluator policy of the line search (Tuning::disp_predict) -- set by the launch (fit_disp.hip)
     int xlds;                // 1: X staged in LDS, 0: read through L1/L2
     int *work_counter;       // zeroed int: waves draw their next gene from it (nullptr: static grid-stride)
     unsigned long long padmask;   // WIDE kernels: bit c set = design column c is zero padding
@@ -555,6 +556,14 @@ struct Tuning {
                              // gene-wise IRLS's iterations; 2: list order
     int outlier_first;       // DSQ_OUTLIER_FIRST (default 1): the rows that can hold a count outlier first, their refit beside the
                              // Cook's distances of all the others (pipeline.hip, phase_outlier_first)
+    // the per-width fitDisp search (fit_disp.hip, DSQ_DISP_GAMMA)
+    int disp_predict;        // DSQ_DISP_PREDICT: 1 likelihood-only evaluations where the search is predicted to reject; 0 fused at
+                             // every proposal; 2 likelihood-only at every proposal, fused after each acceptance that continues.
+                             // Same bits under all three.  Unset (-1): 1, but 0 for the shape gated in launch_disp_p
+                             // (fit_disp.hip): unweighted rows of a two-column design with up to 100 samples, measured at C2
+                             // (100 samples; shorter rows are an extrapolation, said there).  Rule for a gate: a shape keeps
+                             // policy 0 only where a paired measurement shows policy 1 losing there
+                             // (profiles/disp_predict.md); the knob, when set, holds for every shape
 };
 const Tuning &tuning();
 

@@ -984,13 +984,26 @@ __host__ __device__ inline size_t disp_lds_doubles(int m, int p, int waves, int 
            (size_t)waves * disp_arena_doubles(p, ncell);
 }
 
-// 1: the line search evaluates the likelihood alone at a proposal and the derivative only after the Armijo test accepts
-// it (what src/DESeq2.cpp:225-246 does); 0: both in one fused evaluation per proposal.  More than half of the proposals
-// are rejected (C3: 52 % in the gene-wise fit, 61 % in the MAP fit), yet the fused form wins -- the likelihood alone and
-// the derivative alone each cost ~0.8 of the fused evaluation, they share the logarithm, the reciprocal and the Cox-Reid
-// sweep.  Measured (same bits either way): C3 3.07 ms fused vs 3.44 ms split; C4 18.8 vs 23.3 ms (profiles/r03_ablation.md)
-#ifndef DSQ_DISP_SPLIT
-#define DSQ_DISP_SPLIT 0
+// Which evaluator produces lp_try at a proposal of the line search (DispKernelParams::predict, env DSQ_DISP_PREDICT).  The
+// search reads the derivative at a proposal only when the Armijo test accepts it AND the search goes on; more than half of
+// the proposals are rejected (C3: 52 % in the gene-wise fit, 61 % in the MAP fit), in one run at the head of the search
+// (kappa_0 = 1 times a derivative of order 100 overshoots) and in short runs after it.
+//   0  lp_dlp() at every proposal: log_posterior and dlog_posterior fused, the derivative thrown away on a rejection
+//   1  lp() alone where a rejection is predicted -- the first proposal of a gene, and after a rejected proposal while
+//      kappa > DSQ_DISP_GAMMA kstar, kstar being the largest step at which the parabola through lp(a), dlp(a) and the rejected
+//      lp(a + s), s = kappa dlp, still passes the test: c = 2 (lp_try - lp - dlp s) / s^2, kstar = 2 (1 - epsilon) / -c
+//      (+inf for c >= 0; a non-finite lp_try leaves kstar alone).  After an accepted proposal: fused.  A proposal evaluated
+//      by lp() that is accepted and continues runs lp_dlp() at the same point for its derivative (under 0.5 % of them,
+//      tools/disp_search_sim.py) -- what src/DESeq2.cpp:225-246 does at every acceptance.
+//   2  lp() at every proposal, lp_dlp() after every acceptance that continues (the tests' lever for that fallback)
+// Unset, the knob means 1 but for the shape launch_disp_p keeps on 0, which runs the kernel built without the predictor.
+// The likelihood alone costs 0.82 - 0.84 of the fused evaluation -- they share the logarithm, the reciprocal and the Cox-Reid sweep
+// --, which is why 2 loses to 0 (round 3, same bits: C3 3.07 ms fused vs 3.44 ms split; C4 18.8 vs 23.3 ms,
+// profiles/r03_ablation.md) and 1 wins (profiles/disp_predict.md).  The search's statements are the same under every policy,
+// and lp() / dlp() / lp_dlp() return the same bits for the same argument, so the eight outputs do not depend on it
+// (tests/test_gpu_disp_predict.py).  The rolled wide kernel (fit_disp_wide.hip) has its own search and stays fused.
+#ifndef DSQ_DISP_GAMMA
+#define DSQ_DISP_GAMMA 1.0
 #endif
 #ifndef DSQ_DISP_MINW
 /* p <= 4: the search kernel needs 177 registers, so 3 waves per SIMD cost ten spills and pay (6.42 -> 6.15 ms
@@ -1017,7 +1030,9 @@ __host__ __device__ constexpr bool disp_global_dv() { return !STAGE && !USE_W &&
 // was ~ 10 % of fit_disp<10>
 __host__ __device__ inline size_t disp_hist_doubles(int p, int m) { return (p >= 4 && m >= 256 && m <= 2560) ? ((size_t)m + 1) / 2 : 0; }
 
-template <int P, bool USE_W, bool STAGE, int MODE>
+// PRED (MODE 0 only): the search that chooses its evaluator per proposal (policies 1 and 2 above); without it the kernel holds
+// the fused evaluator alone -- policy 0, and the code of the shapes the launch keeps on it (launch_disp_p)
+template <int P, bool USE_W, bool STAGE, int MODE, bool PRED = false>
 __global__ void __launch_bounds__(256, (disp_global_dv<USE_W, STAGE, MODE>() ? DSQ_DISP_MINW_LONG : DSQ_DISP_MINW)) fit_disp_kernel(DispKernelParams kp) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int lane = threadIdx.x & 63;
@@ -1191,16 +1206,15 @@ __global__ void __launch_bounds__(256, (disp_global_dv<USE_W, STAGE, MODE>() ? D
             const double epsilon = 1.0e-4;
             double a = kp.log_alpha_in[g];
             double dlp;
-#if DSQ_DISP_SPLIT
-            double lp = G.lp(a);
-            dlp = G.dlp(a, G.usePrior);
-#else
             double lp = G.lp_dlp(a, G.usePrior, dlp);
-#endif
             double kappa = kp.kappa_0;
             const double initial_lp = lp, initial_dlp = dlp;
             double change = -1.0;
             int it = 0, it_acc = 0;
+            // evaluator policy (see DSQ_DISP_GAMMA above): wave-uniform scalars
+            const int predict = (PRED && kp.force_iters <= 0) ? kp.predict : 0;
+            bool expect_reject = true;                  // the first proposal, then: the last proposal was rejected
+            double kstar = 0.0;                         // (kappa_0 > 0: the first proposal goes likelihood-only)
             for (int t = 0; t < kp.maxit; t++) {
                 it++;
                 double a_propose = a + kappa * dlp;
@@ -1210,14 +1224,14 @@ __global__ void __launch_bounds__(256, (disp_global_dv<USE_W, STAGE, MODE>() ? D
                 // the reference evaluates log_posterior(a + kappa*dlp) for the Armijo test and
                 // again after accepting (:225,:233): same argument, same value -> evaluated once;
                 // the derivative it asks for after accepting (:246) is at that same point too
-                // ... evaluated together with it, or (DSQ_DISP_SPLIT) only after the test accepts and the search goes on;
-                // lp() / dlp() / lp_dlp() return the same bits for the same argument
+                // ... evaluated together with it, or, where the policy sent the proposal likelihood-only, after the test
+                // accepts and the search goes on; lp() / dlp() / lp_dlp() return the same bits for the same argument
+                // (without PRED: the constant false, and the two `if (lik_only)` below fold away)
+                const bool lik_only = PRED && (predict == 2 || (predict == 1 && expect_reject && (t == 0 || uniform(kappa > DSQ_DISP_GAMMA * kstar))));
                 double dlp_try = 0.0;
-#if DSQ_DISP_SPLIT
-                const double lp_try = G.lp(a_try);
-#else
-                const double lp_try = G.lp_dlp(a_try, G.usePrior, dlp_try);
-#endif
+                double lp_try;
+                if (lik_only) lp_try = G.lp(a_try);
+                else lp_try = G.lp_dlp(a_try, G.usePrior, dlp_try);
                 double theta_kappa = -1.0 * lp_try;
                 double theta_hat_kappa = -1.0 * lp - kappa * epsilon * (dlp * dlp);
                 if (kp.force_iters > 0 && t + 1 >= kp.force_iters) break;   // profiling only
@@ -1235,17 +1249,22 @@ __global__ void __launch_bounds__(256, (disp_global_dv<USE_W, STAGE, MODE>() ? D
                     a = a_try;
                     double lpnew = lp_try;
                     change = lpnew - lp;
-                    if (uniform(change < kp.tol)) { lp = lpnew; break; }
+                    if (uniform(change < kp.tol)) { lp = lpnew; break; }        // (both exits leave dlp at the point before)
                     if (uniform(a < kp.min_log_alpha)) break;
                     lp = lpnew;
-#if DSQ_DISP_SPLIT
-                    dlp = G.dlp(a, G.usePrior);
-#else
+                    if (lik_only) (void)G.lp_dlp(a, G.usePrior, dlp_try);       // mispredicted (or policy 2): the same lp again
                     dlp = dlp_try;
-#endif
                     kappa = __builtin_fmin(kappa * 1.1, kp.kappa_0);
                     if (it_acc % 5 == 0) kappa = kappa / 2.0;
+                    expect_reject = false;
                 } else {
+                    if (PRED && predict == 1) {
+                        const double s = kappa * dlp;
+                        const double c = 2.0 * (lp_try - lp - dlp * s) / (s * s);
+                        const double ks = (c < 0.0) ? 2.0 * (1.0 - epsilon) / -c : __builtin_huge_val();
+                        if (uniform(dfinite(lp_try))) kstar = lane_read(ks, 0);
+                    }
+                    expect_reject = true;
                     kappa = kappa / 2.0;
                 }
             }
@@ -1309,19 +1328,29 @@ static hipError_t launch_disp_p(const DispKernelParams &kp, hipStream_t st) {
                         : (size_t)waves * unstaged_lds) + cell_bytes;   // unstaged: [distinct-count buffer +] WIDE arena
     DispKernelParams kq = kp;
     kq.xlds = xlds;
+    // evaluator policy of the search: the knob when it is set; unset, policy 1 but for the one shape measured to lose under
+    // it, unweighted rows of a two-column design with up to 100 samples (C2: the step 1.74 -> 1.78 ms under policy 1, per launch
+    // 0.390 / 0.383 ms in the kernel without the predictor against 0.413 / 0.400 with it; profiles/disp_predict.md).  Rows
+    // shorter than the measured 100 are taken along: what the second evaluator costs does not shrink with the row, what it
+    // saves does.  No other unweighted shape below 256 samples was measured; they take policy 1 like everything else
+    kq.predict = MODE != 0 ? 0 : tu.disp_predict >= 0 ? tu.disp_predict : (!USE_W && P == 2 && kp.m <= 100) ? 0 : 1;
+    constexpr bool CAN_PRED = MODE == 0;
+    const bool pred = CAN_PRED && kq.predict != 0;
     kq.dist_global = nullptr;
     if (kq.work_counter && MODE == 2) kq.work_counter += 1;   // the d2 pass has its own counter
-    const void *fn = stage ? (const void *)fit_disp_kernel<P, USE_W, true, MODE> : (const void *)fit_disp_kernel<P, USE_W, false, MODE>;
-    static thread_local int bpc_cache[2][8];      // [stage][waves]: the occupancy query costs ~1 ms, ask once
-    static thread_local size_t lds_cache[2][8];
+    const void *fn = pred ? (stage ? (const void *)fit_disp_kernel<P, USE_W, true, MODE, CAN_PRED> : (const void *)fit_disp_kernel<P, USE_W, false, MODE, CAN_PRED>)
+                          : (stage ? (const void *)fit_disp_kernel<P, USE_W, true, MODE> : (const void *)fit_disp_kernel<P, USE_W, false, MODE>);
+    static thread_local int bpc_cache[4][8];      // [stage + 2 pred][waves]: the occupancy query costs ~1 ms, ask once
+    static thread_local size_t lds_cache[4][8];
     DSQ_CACHE_PER_DEVICE(bpc_cache, lds_cache);
-    if (lds_cache[stage][waves] != lds) { bpc_cache[stage][waves] = 0; lds_cache[stage][waves] = lds; }
-    int bpc = bpc_cache[stage][waves];
+    const int ci = (int)stage + 2 * (int)pred;
+    if (lds_cache[ci][waves] != lds) { bpc_cache[ci][waves] = 0; lds_cache[ci][waves] = lds; }
+    int bpc = bpc_cache[ci][waves];
     if (bpc == 0) {
         if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, 64 * waves, lds) != hipSuccess || bpc < 1) bpc = 1;
-        bpc_cache[stage][waves] = bpc;
-        if (getenv("DSQ_VERBOSE")) fprintf(stderr, "[dsq] fit_disp<P=%d,mode=%d> waves=%d stage=%d lds=%zu occupancy-api blocks/CU=%d\n", P, MODE, waves, (int)stage, lds, bpc);
+        bpc_cache[ci][waves] = bpc;
+        if (getenv("DSQ_VERBOSE")) fprintf(stderr, "[dsq] fit_disp<P=%d,mode=%d> waves=%d stage=%d lds=%zu occupancy-api blocks/CU=%d predict=%d\n", P, MODE, waves, (int)stage, lds, bpc, kq.predict);
     }
     if (tu.disp_bpc > 0) bpc = tu.disp_bpc;
     const int cus = device_cu_count();
@@ -1338,7 +1367,12 @@ static hipError_t launch_disp_p(const DispKernelParams &kp, hipStream_t st) {
     unsigned long long pz[DSQ_PROF_SLOTS] = {}, ph[DSQ_PROF_SLOTS];
     (void)hipMemcpyToSymbol(HIP_SYMBOL(disp_prof), pz, sizeof(pz));
 #endif
-    if (stage)
+    if (pred) {
+        if (stage)
+            hipLaunchKernelGGL((fit_disp_kernel<P, USE_W, true, MODE, CAN_PRED>), dim3(grid), dim3(64 * waves), lds, st, kq);
+        else
+            hipLaunchKernelGGL((fit_disp_kernel<P, USE_W, false, MODE, CAN_PRED>), dim3(grid), dim3(64 * waves), lds, st, kq);
+    } else if (stage)
         hipLaunchKernelGGL((fit_disp_kernel<P, USE_W, true, MODE>), dim3(grid), dim3(64 * waves), lds, st, kq);
     else
         hipLaunchKernelGGL((fit_disp_kernel<P, USE_W, false, MODE>), dim3(grid), dim3(64 * waves), lds, st, kq);

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Static instruction mix and register budget of the SHIPPED gfx950 code objects (round 5).
 
-    python tools/isa_mix.py deseq2_amd/libdeseq2_mi355x.so 'fit_disp_kernel<4, false, true, 0>' 'fit_beta_cell_kernel<4, false>'
+    python tools/isa_mix.py deseq2_amd/libdeseq2_mi355x.so 'fit_disp_kernel<4, false, true, 0, true>' 'fit_beta_cell_kernel<4, false>'
+
+(the search kernel exists twice: `..., 0, true>` with the evaluator predictor -- what C3 runs --, `..., 0, false>` fused only)
 
 For every kernel whose demangled name contains one of the filters: vgpr / sgpr / spill counts and scratch from the code
 object's metadata, then the instruction classes of the whole kernel and of every backward-branch region (a loop: from the

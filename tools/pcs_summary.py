@@ -29,7 +29,8 @@ if did:
     print("\n== samples per kernel"); print(top.head(12).to_string())
 com = "Instruction_Comment" if "Instruction_Comment" in df.columns else None
 ins = "Instruction" if "Instruction" in df.columns else None
-for kern in ("fit_disp_kernel<4, false, true, 0>", "fit_beta_cell_kernel<4, false>"):
+# (the search kernel exists with and without the evaluator predictor -- the last template argument; C3 runs the one with it)
+for kern in ("fit_disp_kernel<4, false, true, 0, true>", "fit_disp_kernel<4, false, true, 0, false>", "fit_beta_cell_kernel<4, false>"):
     sub = df[df["kernel"] == kern] if did else df
     if not len(sub):
         continue
