@@ -614,9 +614,11 @@ int cooks_dev_locked(const DsqCooksArgs *a, const DsqCooksOut *o, hipStream_t st
     if ((rc = in.nf(a->nf, a->nf_is_vector, &kp.nf, &kp.nf_is_vector))) return rc;
     if ((rc = in.matrix(a->mu, WS_MU, &kp.mu))) return rc;
     if ((rc = in.matrix(a->H, WS_W, &kp.H))) return rc;
+    // the slot: the table, then n doubles for robustDisp when the caller wants none.  The table goes through the pinned
+    // ring (capi_upload_table): `meta` is rewritten by the next call on this thread, maybe before this copy has run
     void *v;
     rc = capi_ws_get(WS_CELLS, meta.size() * sizeof(int32_t) + (size_t)a->n * 8, &v); if (rc) return rc;
-    DSQ_HIP(hipMemcpyAsync(v, meta.data(), meta.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    rc = capi_upload_table(WS_CELLS, meta.data(), meta.size() * sizeof(int32_t), st, &v); if (rc) return rc;
     kp.perm = (int32_t *)v; kp.in3 = kp.perm + m; kp.cell_start = kp.in3 + m;
     kp.maxCooks = o->maxCooks;
     if (o->robustDisp) kp.robustDisp = o->robustDisp;
@@ -646,9 +648,8 @@ int replace_dev_locked(const DsqReplaceArgs *a, const DsqReplaceOut *o, hipStrea
     if ((rc = in.matrix(a->cooks, WS_COOKS_IN, &kp.cooks))) return rc;
     static thread_local std::vector<int32_t> flags;
     flags.assign(a->replaceable, a->replaceable + m);
-    void *v;
-    rc = capi_ws_get(WS_CELLS, (size_t)m * sizeof(int32_t), &v); if (rc) return rc;
-    DSQ_HIP(hipMemcpyAsync(v, flags.data(), (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    void *v;            // (through the pinned ring, as the cells of cooks_dev_locked: `flags` is the next call's too)
+    rc = capi_upload_table(WS_CELLS, flags.data(), (size_t)m * sizeof(int32_t), st, &v); if (rc) return rc;
     kp.replaceable = (int32_t *)v;
     kp.replace = o->replace;
     GmOut<int32_t> counts;

@@ -117,7 +117,7 @@ struct StreamCtx {
     int dev = 0;
     hipStream_t main = nullptr;
     Slot slot[DSQ_WS_COUNT];
-    PinBuf pin[kPinRing];                  // allocated on first use: only the chain's small tables go through the ring
+    PinBuf pin[kPinRing];                  // allocated on first use: only small host tables go through the ring
     int pin_next = 0;
     SideStream side;                       // created on first use
 };
@@ -150,7 +150,8 @@ int capi_ws_get(int slot, size_t bytes, void **out) {
     return DSQ_OK;
 }
 
-// Small host tables of an ASYNCHRONOUS call (the chain: design cells, outlier metadata).  Two things the plain
+// Small host tables of an ASYNCHRONOUS call (design cells, outlier metadata, replaceable flags, a spline table: the chain's
+// and the per-call entries' alike; tests/test_gpu_stream_order.py calls back to back behind a busy stream).  Two things the plain
 // hipMemcpyAsync from a thread_local pageable buffer did not give: (1) the source may be rewritten as soon as this
 // returns -- the bytes travel through a ring of PINNED buffers, each fenced by an event recorded behind its copy (a
 // buffer is reused only when its copy has run), so nothing depends on how the runtime stages pageable copies; (2) the

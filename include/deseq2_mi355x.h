@@ -41,6 +41,24 @@
  * which the caller zeroes first: *any_negative of dsq_weights_prep_dev and *bad of dsq_counts_f64_to_gene_major_i32.
  * Nothing outside the buffers handed over (at the sizes stated here) is written.  tests/test_gpu_entry_memory.py and tests/test_gpu_chain_memory.py hold the library
  * to this on poisoned memory.
+ *
+ * Stream-order contract of every _dev entry: all the work of a call -- kernels, memsets, copies, the uploads of its small
+ * host tables (design cells, `replaceable`, a spline table, contrasts' cells) -- is ordered on `stream` behind whatever the
+ * caller enqueued there before the call, and is complete, for the stream, in front of whatever the caller enqueues there
+ * after it.  So device inputs may still be in the making on `stream` when the call is issued, and inputs, outputs and a
+ * caller-provided workspace may be reused on `stream` the moment the call returns.  Where the library forks to a stream of
+ * its own (the outlier refit of dsq_deseq_dev) the fork waits for `stream` and is joined back into it before the call's
+ * last command.  Host arrays (tables, argument blocks) are read before the call returns and may be rewritten at once: a
+ * table travels through pinned buffers of the (device, stream) context, never from the caller's or the library's pageable
+ * memory at a later time.  The call does not wait for the device: it returns while `stream` is still busy.  The exceptions
+ * state it at their entry: dsq_sf_iterate_dev and dsq_beta_prior_var_dev read results back; the fit and aux entries that
+ * take `y_type` (dsq_fit_beta_dev .. dsq_replace_outliers_dev):
+ * given DSQ_Y_FLOAT64 counts they check the counts on the device and WAIT for `stream` once, at their end, to return
+ * DSQ_ERR_VALUE (int32 counts: no wait); and a workspace slot of the context that has to GROW is reallocated behind a
+ * device synchronisation (the first call of a shape on a stream, not the steady state).  Calls on different streams share
+ * nothing that is in flight.  tests/test_gpu_stream_order.py holds the library to this on a stream that is kept busy,
+ * with inputs that arrive late and buffers recycled early (tests/stream_hold.py); tests/test_stream_cases_cpu.py holds
+ * that test's cases to the conditions under which it can fail.
  */
 #ifndef DESEQ2_MI355X_H
 #define DESEQ2_MI355X_H
