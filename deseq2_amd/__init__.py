@@ -11,6 +11,7 @@ from .core import results, resultsContrasts, resultsNames, DESeqResults, p_adjus
 from .core import pt  # noqa: F401
 from .core import unmix  # noqa: F401
 from .core import apeglm, lfcShrinkApeglm, svalue, apeglm_prior_scale  # noqa: F401
+from .core import ash, lfcShrinkAshr  # noqa: F401
 from .core import rowVars, sampleDists, pca, plotPCA, PCAData  # noqa: F401
 from .core import collapseReplicates, fpm, fpkm, counts, plotCounts  # noqa: F401
 from .core import localDispersionFit  # noqa: F401

@@ -26,6 +26,7 @@ DSQ_RESULTS_MAX_K = 4096
 DSQ_VST_MAX_KNOTS = 1600
 DSQ_UNMIX_MAX_K = 16
 DSQ_APEGLM_MAX_P = 16
+DSQ_ASH_MAX_K = 64
 DSQ_PH_GENE_EST, DSQ_PH_TREND, DSQ_PH_MAP_TEST, DSQ_PH_OUTLIERS, DSQ_PH_FINISH, DSQ_PH_PRIOR = 1, 2, 4, 8, 16, 32
 DSQ_PH_OUTLIERS_DETECT, DSQ_PH_OUTLIERS_REFIT = 64, 128
 DSQ_SC_COEF0, DSQ_SC_COEF1, DSQ_SC_VAR_LOG_DISP, DSQ_SC_DISP_PRIOR_VAR, DSQ_SC_FIT_USED = 0, 1, 2, 3, 4
@@ -130,6 +131,8 @@ DsqRlogOut = _struct("DsqRlogOut", "p rlog intercept iter flag bad")
 DsqApeglmArgs = _struct("DsqApeglmArgs", _DESIGN + "; p nf; i nf_is_vector; p x weights disp init; i coef; u no_shrink;"
                         " d prior_scale prior_df no_shrink_scale; i has_threshold; d threshold tol; i maxit")
 DsqApeglmOut = _struct("DsqApeglmOut", "p map sd fsr thresh iter conv start objective bad")
+DsqAshArgs = _struct("DsqAshArgs", "i n C; l ld; p betahat sebetahat; i has_threshold; d threshold; i maxit")
+DsqAshOut = _struct("DsqAshOut", "p PosteriorMean PosteriorSD NegativeProb PositiveProb lfsr le_T gt_mT pi sd K iter flag loglik")
 DsqUnmixArgs = _struct("DsqUnmixArgs", "i n m k; l ld; p x pure; i has_alpha has_shift; d alpha shift; i power maxit")
 DsqUnmixOut = _struct("DsqUnmixOut", "p p loss iter flag")
 DsqSfIterateArgs = _struct("DsqSfIterateArgs", "i n m; l ld; p y mu sf disp rows; d Q; i maxit")
@@ -202,7 +205,8 @@ _pair("dsq_linear_mu", C.POINTER(DsqPrefitArgs), _D, _P)
 _pair("dsq_parametric_dispersion_fit", _P, _P, _I64, _P, _P)     # means, disps, n, coefs, status
 _pair("dsq_pt", _P, _P, _I32, _I32, _I32, _P, _P)                # q, df, n, K, tail, keep, out
 # ... whose device entry also takes the caller's workspace and its size
-for _name, _a, _o in (("dsq_unmix", DsqUnmixArgs, DsqUnmixOut), ("dsq_sf_iterate", DsqSfIterateArgs, DsqSfIterateOut)):
+for _name, _a, _o in (("dsq_unmix", DsqUnmixArgs, DsqUnmixOut), ("dsq_sf_iterate", DsqSfIterateArgs, DsqSfIterateOut),
+                      ("dsq_ash", DsqAshArgs, DsqAshOut)):
     _sig(_name, *_blocks(_a, _o))
     _sig(_name + "_dev", *_blocks(_a, _o), _P, _I64, _P)
 _sig("dsq_beta_prior_var", C.POINTER(DsqBetaPriorArgs), _P)
@@ -217,6 +221,7 @@ _workspace_bytes("dsq_size_factors", 2)      # n, m
 _workspace_bytes("dsq_unmix", 3)             # n, m, k
 _workspace_bytes("dsq_sf_iterate", 2)        # n, m
 _workspace_bytes("dsq_results", 2)           # n, K
+_workspace_bytes("dsq_ash", 2)               # n, C
 _workspace_bytes("dsq_beta_prior_var", 2)    # n, columns
 _sig("dsq_weights_prep_dev", _P, _P, _I32, _I32, _I32, _I64, _D, _P, _P, _P, _P, _P)
 _sig("dsq_xim_dev", _P, _I32, _I32, _I64, _P, _P, _P)
@@ -225,7 +230,7 @@ for _name in ("dsq_to_gene_major_f64", "dsq_to_gene_major_i32", "dsq_from_gene_m
 _sig("dsq_counts_f64_to_gene_major_i32", _P, _P, _I32, _I32, _I64, _P, _P)
 _sig("dsq_test_math", _I, _P, _P, _P, _P, _I64)
 for _name in ("dsq_unmix_block_threads", "dsq_sf_iterate_slice_genes", "dsq_row_vars_register_width", "dsq_local_fit_lanes",
-              "dsq_apeglm_lds_doubles"):
+              "dsq_apeglm_lds_doubles", "dsq_ash_slice_rows"):
     _sig(_name, res=_I32)
 _sig("dsq_local_fit_block_doubles", _I32, res=_I64)
 _sig("dsq_sample_pairs_slice_rows", _I64, _I32, res=_I64)

@@ -25,15 +25,18 @@ file; their O(n m) parts run in the engine (csrc/count_helpers.hip, DESIGN.md se
 lfcShrinkApeglm / apeglm / svalue serve lfcShrink(type = "apeglm") (R/lfcShrink.R:328-440): the estimator as documented, by
 the library's own iteration (csrc/apeglm.hip).
 
-Not mirrored (out of the hot-path scope): the glmGamPoi dispersion fit; lfcShrink(type = "ashr"), which
-delegates to a package whose source is not part of the reference tree.
+lfcShrinkAshr / ash serve lfcShrink(type = "ashr") (R/lfcShrink.R:442-486), for a coefficient, a contrast or a list of
+contrasts: the estimator as its paper and the call state it, by the library's own iteration (csrc/ash.hip, DESIGN.md section
+23).  The ashr package's numbers, its optimiser and its treatment of excluded rows are unpinned.
+
+Not mirrored (out of the hot-path scope): the glmGamPoi dispersion fit.
 """
 import warnings
 
 import numpy as np
 from scipy import special as sps
 
-from .engine import HostEngine, control_flags
+from .engine import HostEngine, ResultColumns, control_flags
 
 LOG2E = np.log2(np.e)
 
@@ -2375,7 +2378,8 @@ def lfcShrink(dds, coef=None, contrast=None, res=None, type="normal", lfcThresho
     if type != "normal":
         raise NotImplementedError("lfcShrink(type = '%s') delegates to the %s package, whose source is not part of the reference "
                                   "tree: nothing here could pin it.  Served: type = 'normal'%s" % (type, type,
-                                  "; the apeglm estimator is served by lfcShrinkApeglm(dds, coef, ...)" if type == "apeglm" else ""))
+                                  "; the apeglm estimator is served by lfcShrinkApeglm(dds, coef, ...)" if type == "apeglm"
+                                  else "; the ashr estimator is served by lfcShrinkAshr(dds, coef / contrast / res, ...)"))
     if dds.attrs.get("betaPrior"):
         raise ValueError("lfcShrink() should be used downstream of DESeq() with betaPrior=FALSE (the default)")   # :170-173
     if np.ndim(lfcThreshold) != 0 or not lfcThreshold >= 0:
@@ -2710,6 +2714,221 @@ def lfcShrinkApeglm(dds, coef, res=None, lfcThreshold=0, svalue=False, returnLis
 def _r_round3(v):
     """round(v, 3) as paste0 prints it"""
     return "%g" % round(float(v), 3)
+
+
+# ------------------------------------------------------------------ R/lfcShrink.R:442-486, 489-518: ashr
+ASHR_CITATION = ("using 'ashr' for LFC shrinkage. If used in published research, please cite:\n"
+                 "    Stephens, M. (2016) False discovery rates: a new deal. Biostatistics, 18:2.\n"
+                 "    https://doi.org/10.1093/biostatistics/kxw041")
+
+
+def _on_host(v):
+    """a column where an engine made it -> a float64 host array"""
+    if hasattr(v, "detach"):
+        v = v.detach().cpu().numpy()
+    return np.asarray(v, np.float64)
+
+
+def _fitted_g(fit, c):
+    K = int(fit["K"][c])
+    return {"pi": np.array(fit["pi"][c, :K]), "mean": np.zeros(K), "sd": np.array(fit["sd"][c, :K])}
+
+
+def ash(betahat, sebetahat, lfcThreshold=None, engine=None, maxit=100):
+    """ashr::ash(betahat, sebetahat, mixcompdist = "normal", method = "shrink") as lfcShrink calls it (R/lfcShrink.R:458-459;
+    DESIGN.md section 23): betahat / sebetahat two vectors of n -- or two n x C matrices of C independent columns, fitted in
+    one batch.  A row is kept when betahat is finite and sebetahat finite and positive; the others take no part in the fit
+    and come back NaN; no kept row: ValueError.  The prior is sum_k pi_k N(0, sd_k^2) on ashr's documented sqrt(2) grid,
+    no point mass, uniform prior on the weights.  Returns dict(fitted_g = dict(pi, mean (0), sd) -- a list of C with
+    matrices --, result = dict(betahat, sebetahat, NegativeProb, PositiveProb, lfsr, svalue, lfdr (0: no point mass),
+    PosteriorMean, PosteriorSD and, with lfcThreshold = T, le_T = P(beta <= T | data) and gt_mT = P(beta > -T | data), each its
+    own one-tail sum -- R forms 1 - cdf and loses the small tail, this does not), loglik, iter, flag (0 converged, 1 maxit,
+    2 no acceptable step)).
+    The estimator is the package's as its paper (Stephens 2017) and the call state it; the optimiser is the library's own
+    sequential quadratic programme.  The package's numbers, its optimiser and its treatment of excluded rows are unpinned."""
+    E = engine if engine is not None else HostEngine()
+    b, s = np.asarray(betahat, np.float64), np.asarray(sebetahat, np.float64)
+    if b.shape != s.shape or b.ndim not in (1, 2):
+        raise ValueError("betahat and sebetahat are two vectors of one length, or two n x C matrices")
+    if lfcThreshold is not None and not (np.ndim(lfcThreshold) == 0 and lfcThreshold >= 0):
+        raise ValueError("lfcThreshold is one number that is not negative")
+    fit = E.ash_fit(b, s, threshold=None if lfcThreshold is None else float(lfcThreshold), maxit=maxit)
+    C = 1 if b.ndim == 1 else b.shape[1]
+    shape = (lambda v: _on_host(v)[0]) if b.ndim == 1 else (lambda v: np.ascontiguousarray(_on_host(v).T))
+    result = {"betahat": b, "sebetahat": s}
+    for k in ("NegativeProb", "PositiveProb", "lfsr", "PosteriorMean", "PosteriorSD") + (("le_T", "gt_mT") if lfcThreshold is not None else ()):
+        result[k] = shape(fit[k])
+    lf = result["lfsr"]
+    result["svalue"] = svalue(lf) if b.ndim == 1 else np.column_stack([svalue(lf[:, c]) for c in range(C)])
+    result["lfdr"] = np.where(np.isnan(lf), np.nan, 0.0)
+    g = [_fitted_g(fit, c) for c in range(C)]
+    one = b.ndim == 1
+    return {"fitted_g": g[0] if one else g, "result": result, "loglik": float(fit["loglik"][0]) if one else np.array(fit["loglik"]),
+            "iter": int(fit["iter"][0]) if one else np.array(fit["iter"]), "flag": int(fit["flag"][0]) if one else np.array(fit["flag"])}
+
+
+def _contrast_batch(contrast):
+    """a LIST whose elements are contrasts (numeric vectors, (factor, level code, level code), lists of names), as distinct from
+    ONE contrast in list form (one or two sequences of names)"""
+    if not isinstance(contrast, list) or not contrast:
+        return None
+    if not all(isinstance(e, (list, tuple, np.ndarray)) for e in contrast):
+        return None
+    if all(all(isinstance(v, str) for v in e) for e in contrast):
+        return None
+    return list(contrast)
+
+
+def _res_handle(res, name):
+    """the column of a results table where it lies: an engine handle, or the host array it was assigned from"""
+    if name in res._set:
+        return res[name]
+    return _realize(res).resident[name]
+
+
+def lfcShrinkAshr(dds, coef=None, contrast=None, res=None, lfcThreshold=0, svalue=False, returnList=False, quiet=False,
+                  **not_served):
+    """lfcShrink(type = "ashr") (R/lfcShrink.R:156-209, 442-518): adaptive shrinkage of the log2 fold changes and their
+    standard errors of a results table -- posterior mean and posterior SD under a scale mixture of zero-mean normals fitted
+    to all rows (csrc/ash.hip on the device).  Both columns are on the log2 scale and nothing is converted.
+    `res` is results(dds, name = coef) for `coef` (a name of resultsNames(dds) or a 0-based column), resultsContrasts(dds,
+    [contrast])[0] for `contrast` (one of its three forms), or as given -- with `res`, coef and contrast are ignored.  A LIST
+    of contrasts (or of results tables) is served in one batch and returns a list, equal to one call each.
+    Returns `res` with log2FoldChange = PosteriorMean and lfcSE = PosteriorSD (engine handles until one is asked for), columns
+    baseMean, log2FoldChange, lfcSE, pvalue, padj -- or, with svalue = TRUE or lfcThreshold > 0, baseMean, log2FoldChange,
+    lfcSE, svalue (the s-values of lfsr; with lfcThreshold = T > 0 of P(beta <= T) where the posterior mean is positive and
+    P(beta > -T) elsewhere, :478-485, each tail summed on its own) --, metadata["lfcThreshold"], metadata["description"] and
+    priorInfo with fitted_g; with returnList, (res, fit), fit as core.ash returns it.  Rows whose estimate or standard error is
+    NA (all-zero genes) take no part in the fit and come back NaN.
+    The ashr package's numbers, its optimiser and its treatment of excluded rows are unpinned.  Not served
+    (NotImplementedError): format, saveCols, parallel, and the arguments R passes on to ashr::ash (mixcompdist, method,
+    pointmass, df, ...)."""
+    import sys
+    from .fused import finish
+    reasons = {"format": "only the table is served", "saveCols": "only the result columns are served",
+               "parallel": "the fit runs on one device", "BPPARAM": "see parallel",
+               "mixcompdist": "only the normal mixture is served", "method": "only method = 'shrink' is served",
+               "pointmass": "no point mass is served", "df": "only the normal likelihood is served",
+               "prior": "only the uniform prior on the weights is served", "mode": "only mode 0 is served",
+               "gridmult": "only gridmult = sqrt(2) is served", "mixsd": "only the documented grid is served",
+               "optmethod": "the optimiser is the library's own", "outputlevel": "the outputs are fixed"}
+    for k, v in not_served.items():
+        if k not in reasons:
+            raise TypeError("lfcShrinkAshr() got an unexpected keyword argument '%s'" % k)
+        if not (v is None or v is False or (k == "format" and v == "DataFrame") or (k == "mixcompdist" and v == "normal")
+                or (k == "method" and v == "shrink")):
+            raise NotImplementedError("lfcShrinkAshr(%s = ): %s" % (k, reasons[k]))
+    if not isinstance(dds, DESeqDataSet):
+        raise TypeError('is(dds, "DESeqDataSet") is not TRUE')                    # :156
+    many = isinstance(res, list) or (res is None and _contrast_batch(contrast) is not None)
+    for r in (res if isinstance(res, list) else [res]):
+        if r is not None and not isinstance(r, DESeqResults):
+            raise ValueError("res should be a DESeqResults object, for GRanges output use 'format'")   # :157-159
+    finish(dds)                      # (an analysis enqueued with wait = False)
+    if "beta" not in dds.mcols:
+        raise RuntimeError("first run DESeq() before running lfcShrink()")        # :162-166
+    if dds.attrs.get("betaPrior"):
+        raise ValueError("lfcShrink() should be used downstream of DESeq() with betaPrior=FALSE (the default)")   # :170-173
+    if np.ndim(lfcThreshold) != 0 or not lfcThreshold >= 0:
+        raise ValueError("length(lfcThreshold) == 1 && lfcThreshold >= 0 is not TRUE")   # :174
+    names = resultsNames(dds)                                                     # :175
+    c = None
+    if coef is not None:                                                          # :182-192
+        if isinstance(coef, str):
+            if coef not in names:
+                raise ValueError("coef %in% resultsNamesDDS is not TRUE")
+            c = names.index(coef)
+        elif isinstance(coef, (int, np.integer)) and not isinstance(coef, bool) and 0 <= int(coef) < len(names):
+            c = int(coef)
+        else:
+            raise ValueError("coef <= length(resultsNamesDDS) is not TRUE")
+    if res is None:                                                               # :193-204
+        if coef is not None:
+            tabs = [results(dds, name=c)]
+        elif contrast is not None:
+            tabs = resultsContrasts(dds, _contrast_batch(contrast) or [contrast])
+        else:
+            raise ValueError("one of coef or contrast required if 'res' is missing")
+    else:
+        tabs = list(res) if many else [res]
+        if not tabs:
+            raise ValueError("one of coef or contrast required if 'res' is missing")
+    E = dds.engine
+    cols = []
+    for r in tabs:
+        if r.n != dds.n:
+            raise ValueError("all(rownames(dds) == rownames(res)) is not TRUE")  # (the objects carry no row names)
+        b, s = _res_handle(r, "log2FoldChange"), _res_handle(r, "lfcSE")
+        if np.isnan(_on_host(s)).all():
+            raise ValueError("lfcShrink requires standard errors, use default fitType")   # :207-208
+        cols.append((b, s))
+    if not quiet:                                                                 # :452-454
+        print(ASHR_CITATION, file=sys.stderr)
+    T = float(lfcThreshold)
+    fit = E.ash_fit([b for b, _ in cols], [s for _, s in cols], threshold=T if T > 0 else None)   # :456-459, :480-483
+    if (np.asarray(fit["flag"]) != 0).any() and not quiet:
+        print("ash: the iteration for the mixture weights did not converge in some column", file=sys.stderr)
+    if T > 0:                                                                     # :477
+        if not quiet:
+            print("computing FSOS 'false sign or small' s-values (T=%s)" % _r_round3(lfcThreshold), file=sys.stderr)
+        svalue = True
+    outs = []
+    for j, r in enumerate(tabs):
+        tab = _realize(r)
+        resident = dict(tab.resident)
+        for k in ("log2FoldChange", "lfcSE", "pvalue"):          # (columns assigned from the host go where the others lie)
+            if k in r._set:
+                resident[k] = r._set[k]
+        resident["log2FoldChange"], resident["lfcSE"] = fit["PosteriorMean"][j], fit["PosteriorSD"][j]   # :460-461
+        out = DESeqResults(ResultColumns(resident, _on_host), None, r.engine)
+        out.metadata = dict(r.metadata)
+        out._set = {k: v for k, v in r._set.items() if k not in ("log2FoldChange", "lfcSE", "pvalue")}
+        out.coef = r.coef
+        words = r.metadata["contrast"] if "contrast" in r.metadata else (names[r.coef].replace("_", " ") if r.coef is not None else "")
+        desc = {"baseMean": "mean of normalized counts for all samples",
+                "log2FoldChange": "log2 fold change (MMSE): " + words,           # :462
+                "lfcSE": "posterior SD: " + words}                                # :463
+        if svalue:                                                                # :469-486, :490-494
+            if T > 0:
+                def sv(j=j):
+                    pm = _on_host(fit["PosteriorMean"][j])
+                    with np.errstate(invalid="ignore"):
+                        return _svalue(np.where(pm > 0, _on_host(fit["le_T"][j]), _on_host(fit["gt_mT"][j])))   # :484-485
+            else:
+                def sv(j=j):
+                    return _svalue(_on_host(fit["lfsr"][j]))                      # :472
+            out["svalue"] = _Once(sv)
+            desc["svalue"] = "s-value: " + words
+            out.shown = ("baseMean", "log2FoldChange", "lfcSE", "svalue")
+        else:                                                                     # :474
+            desc["pvalue"], desc["padj"] = "Wald test p-value: " + words, "BH adjusted p-values"
+            out.shown = ("baseMean", "log2FoldChange", "lfcSE", "pvalue", "padj")
+        out.metadata["description"] = desc
+        out.metadata["lfcThreshold"] = lfcThreshold                               # :497
+        g = _fitted_g(fit, j)
+        out.priorInfo = {"type": "ashr", "package": "deseq2_amd", "fitted_g": g}   # :498-509
+        if returnList:                                                            # :514-518
+            result = {k: _on_host(fit[k][j]) for k in ("NegativeProb", "PositiveProb", "lfsr", "PosteriorMean", "PosteriorSD")
+                      + (("le_T", "gt_mT") if T > 0 else ())}
+            result["svalue"] = _svalue(result["lfsr"])
+            result["lfdr"] = np.where(np.isnan(result["lfsr"]), np.nan, 0.0)
+            outs.append((out, {"fitted_g": g, "result": result, "loglik": float(fit["loglik"][j]), "iter": int(fit["iter"][j]),
+                               "flag": int(fit["flag"][j])}))
+        else:
+            outs.append(out)
+    return outs if many else outs[0]
+
+
+class _Once:
+    """a column made on the first request and kept"""
+
+    def __init__(self, make):
+        self.make, self.value = make, None
+
+    def __call__(self):
+        if self.value is None:
+            self.value = self.make()
+        return self.value
 
 
 # ------------------------------------------------------------------ R/helper.R:70-132

@@ -857,6 +857,40 @@ int apeglm_dev_locked(const DsqApeglmArgs *a, const DsqApeglmOut *o, hipStream_t
     return DSQ_OK;
 }
 
+// adaptive shrinkage (ash.hip): what both entries check before anything is launched
+int ash_check(const DsqAshArgs *a, const DsqAshOut *o) {
+    if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
+    if (a->n < 1 || a->C < 1) return capi_fail(DSQ_ERR_ARG, "bad dimensions");
+    if (a->ld < a->n) return capi_fail(DSQ_ERR_ARG, "ld = %lld < n = %d", (long long)a->ld, a->n);
+    if (!a->betahat || !a->sebetahat) return capi_fail(DSQ_ERR_ARG, "NULL betahat or sebetahat");
+    if (!o->PosteriorMean || !o->PosteriorSD || !o->NegativeProb || !o->PositiveProb || !o->lfsr || !o->le_T || !o->gt_mT || !o->pi ||
+        !o->sd || !o->K || !o->iter || !o->flag || !o->loglik)
+        return capi_fail(DSQ_ERR_ARG, "NULL output array");
+    if (a->has_threshold && !(a->threshold >= 0.0)) return capi_fail(DSQ_ERR_ARG, "threshold = %g must not be negative", a->threshold);
+    if (a->maxit < 0) return capi_fail(DSQ_ERR_ARG, "maxit = %d is negative", a->maxit);
+    return DSQ_OK;
+}
+
+int ash_dev_locked(const DsqAshArgs *a, const DsqAshOut *o, void *workspace, int64_t workspace_bytes, hipStream_t st) {
+    if (int rc = ash_check(a, o)) return rc;
+    const size_t need = ash_workspace_bytes(a->n, a->C);
+    if (!workspace || workspace_bytes < (int64_t)need)
+        return capi_fail(DSQ_ERR_ARG, "workspace of %lld bytes: %zu are needed (dsq_ash_workspace_bytes)", (long long)workspace_bytes, need);
+    if (int rc = capi_check_device()) return rc;
+    AshKernelParams kp;
+    memset(&kp, 0, sizeof kp);
+    kp.n = a->n; kp.C = a->C; kp.ld = (long)a->ld;
+    kp.b = a->betahat; kp.s = a->sebetahat;
+    kp.has_threshold = a->has_threshold ? 1 : 0; kp.threshold = a->threshold; kp.maxit = a->maxit;
+    kp.pm = o->PosteriorMean; kp.psd = o->PosteriorSD; kp.neg = o->NegativeProb; kp.pos = o->PositiveProb; kp.lfsr = o->lfsr;
+    kp.le_t = o->le_T; kp.gt_mt = o->gt_mT;
+    kp.pi = o->pi; kp.sd = o->sd; kp.K = o->K; kp.iter = o->iter; kp.flag = o->flag; kp.loglik = o->loglik;
+    capi_prof_begin("ash", a->n, st);
+    const int rc = launch_ash(kp, workspace, st);
+    capi_prof_end(st);
+    return rc;
+}
+
 // unmix() (unmix.hip): what both entries check before anything is launched
 int unmix_check(const DsqUnmixArgs *a, const DsqUnmixOut *o) {
     if (!a || !o) return capi_fail(DSQ_ERR_ARG, "NULL args/out");
@@ -1285,6 +1319,14 @@ int dsq_unmix_dev(const DsqUnmixArgs *a, const DsqUnmixOut *o, void *workspace, 
     return dev_entry(s, [&](hipStream_t st) { return unmix_dev_locked(a, o, workspace, workspace_bytes, st); });
 }
 int32_t dsq_apeglm_lds_doubles(void) { return kApeXLdsDoubles; }
+int dsq_ash_dev(const DsqAshArgs *a, const DsqAshOut *o, void *workspace, int64_t workspace_bytes, void *s) {
+    return dev_entry(s, [&](hipStream_t st) { return ash_dev_locked(a, o, workspace, workspace_bytes, st); });
+}
+int64_t dsq_ash_workspace_bytes(int32_t n, int32_t C) {
+    if (n < 1 || C < 1) return 0;
+    return (int64_t)ash_workspace_bytes(n, C);
+}
+int32_t dsq_ash_slice_rows(void) { return kAshSliceRows; }
 int64_t dsq_unmix_workspace_bytes(int32_t n, int32_t m, int32_t k) {
     if (n < 1 || m < 1 || k < 1) return 0;
     return (int64_t)unmix_workspace_bytes(n, m);

@@ -10,7 +10,7 @@ static inline void prof_end(hipStream_t st) { capi_prof_end(st); }
 
 enum {  // workspace slots
     WS_Y = 0, WS_NF, WS_W, WS_MU, WS_HAT, WS_MUOUT, WS_SCRATCH, WS_BAD, WS_CELLS, WS_COOKS_IN, WS_COUNTER, WS_TREND, WS_PAD_X, WS_PAD_VEC, WS_PAD_BETA,
-    WS_CELLS_BETA, WS_VST_TABLE,
+    WS_CELLS_BETA, WS_VST_TABLE, WS_ASH_TABLE,
     // host-entry staging
     WS_H_Y, WS_H_X, WS_H_NF, WS_H_W, WS_H_MU, WS_H_VEC, WS_H_OUTMAT, WS_H_OUTMAT2, WS_H_OUTVEC,
     WS_COUNT
@@ -54,6 +54,7 @@ int size_factors_check(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *o);
 int vst_check(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats);
 int rlog_check(const DsqRlogArgs *a, const DsqRlogOut *o);
 int apeglm_check(const DsqApeglmArgs *a, const DsqApeglmOut *o);
+int ash_check(const DsqAshArgs *a, const DsqAshOut *o);
 int unmix_check(const DsqUnmixArgs *a, const DsqUnmixOut *o);
 int sf_iterate_check(const DsqSfIterateArgs *a, const DsqSfIterateOut *o);
 int top_var_check(const DsqTopVarArgs *a, const DsqTopVarOut *o);
@@ -80,6 +81,7 @@ int size_factors_dev_locked(const DsqSizeFactorArgs *a, const DsqSizeFactorOut *
 int vst_dev_locked(const DsqVstArgs *a, const DsqVstOut *o, bool transform, bool stats, hipStream_t st);
 int rlog_dev_locked(const DsqRlogArgs *a, const DsqRlogOut *o, hipStream_t st);
 int apeglm_dev_locked(const DsqApeglmArgs *a, const DsqApeglmOut *o, hipStream_t st);
+int ash_dev_locked(const DsqAshArgs *a, const DsqAshOut *o, void *workspace, int64_t workspace_bytes, hipStream_t st);
 int unmix_dev_locked(const DsqUnmixArgs *a, const DsqUnmixOut *o, void *workspace, int64_t workspace_bytes, hipStream_t st);
 int sf_iterate_dev_locked(const DsqSfIterateArgs *a, const DsqSfIterateOut *o, void *workspace, int64_t workspace_bytes, hipStream_t st);
 int top_var_dev_locked(const DsqTopVarArgs *a, const DsqTopVarOut *o, hipStream_t st);

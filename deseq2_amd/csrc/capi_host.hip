@@ -1043,6 +1043,49 @@ int dsq_fpm(const DsqFpmArgs *a, const DsqFpmOut *o) {
     return s.finish();
 }
 
+int dsq_ash(const DsqAshArgs *a, const DsqAshOut *o) {
+    HostCall hc;
+    DSQ_TRY(host_ready(ash_check(a, o), DSQ_LAYOUT_R));
+    hipStream_t st = hc.st;
+    const size_t n = a->n, C = a->C, nC = n * C;
+    // what goes up: the two matrices, packed to a column stride of n; what comes down: seven n x C matrices, pi, sd, loglik
+    // and the three int32 vectors, one block
+    void *vin, *vout, *w;
+    DSQ_TRY(capi_ws_get(WS_H_VEC, 2 * nC * 8, &vin));
+    const size_t small = 2 * C * DSQ_ASH_MAX_K + C;
+    DSQ_TRY(capi_ws_get(WS_H_OUTVEC, (7 * nC + small) * 8 + 3 * C * 4, &vout));
+    double *db = (double *)vin, *ds = db + nC;
+    for (size_t c = 0; c < C; c++) {
+        DSQ_HIP(hipMemcpyAsync(db + c * n, a->betahat + c * a->ld, n * 8, hipMemcpyHostToDevice, st));
+        DSQ_HIP(hipMemcpyAsync(ds + c * n, a->sebetahat + c * a->ld, n * 8, hipMemcpyHostToDevice, st));
+    }
+    DsqAshArgs d = *a;
+    DsqAshOut od;
+    d.betahat = db; d.sebetahat = ds; d.ld = (int64_t)n;
+    double *p = (double *)vout;
+    double **rows[7] = {&od.PosteriorMean, &od.PosteriorSD, &od.NegativeProb, &od.PositiveProb, &od.lfsr, &od.le_T, &od.gt_mT};
+    double *const host_rows[7] = {o->PosteriorMean, o->PosteriorSD, o->NegativeProb, o->PositiveProb, o->lfsr, o->le_T, o->gt_mT};
+    for (int k = 0; k < 7; k++, p += nC) *rows[k] = p;
+    od.pi = p; p += C * DSQ_ASH_MAX_K;
+    od.sd = p; p += C * DSQ_ASH_MAX_K;
+    od.loglik = p; p += C;
+    od.K = (int32_t *)p; od.iter = od.K + C; od.flag = od.iter + C;
+    const size_t wsb = ash_workspace_bytes(a->n, a->C);
+    DSQ_TRY(capi_ws_get(WS_SCRATCH, wsb, &w));
+    DSQ_TRY(ash_dev_locked(&d, &od, w, (int64_t)wsb, st));
+    for (int k = 0; k < 7; k++)
+        for (size_t c = 0; c < C; c++)
+            DSQ_HIP(hipMemcpyAsync(host_rows[k] + c * a->ld, *rows[k] + c * n, n * 8, hipMemcpyDeviceToHost, st));
+    DSQ_HIP(hipMemcpyAsync(o->pi, od.pi, C * DSQ_ASH_MAX_K * 8, hipMemcpyDeviceToHost, st));
+    DSQ_HIP(hipMemcpyAsync(o->sd, od.sd, C * DSQ_ASH_MAX_K * 8, hipMemcpyDeviceToHost, st));
+    DSQ_HIP(hipMemcpyAsync(o->loglik, od.loglik, C * 8, hipMemcpyDeviceToHost, st));
+    DSQ_HIP(hipMemcpyAsync(o->K, od.K, C * 4, hipMemcpyDeviceToHost, st));
+    DSQ_HIP(hipMemcpyAsync(o->iter, od.iter, C * 4, hipMemcpyDeviceToHost, st));
+    DSQ_HIP(hipMemcpyAsync(o->flag, od.flag, C * 4, hipMemcpyDeviceToHost, st));
+    DSQ_HIP(hipStreamSynchronize(st));
+    return DSQ_OK;
+}
+
 int dsq_sf_iterate(const DsqSfIterateArgs *a, const DsqSfIterateOut *o) {
     const auto check = [&]() -> int {
         if (int rc = sf_iterate_check(a, o)) return rc;

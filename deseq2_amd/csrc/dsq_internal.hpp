@@ -294,6 +294,28 @@ struct ApeglmKernelParams {
 constexpr int kApeXLdsDoubles = 4096;     // the design is staged in LDS while m * p doubles fit here (dsq_apeglm_lds_doubles)
 hipError_t launch_apeglm(const ApeglmKernelParams &kp, int y_f64, hipStream_t st);
 
+// adaptive shrinkage (ash.hip).  b / s and the seven per-row outputs: column c at [c * ld].
+// launch_ash carves its state from the caller's workspace, runs the host loop (one record read back per evaluation and per
+// line search) and returns a DSQ_* code: a column without a kept row and a grid beyond kAshMaxK are found on the way.
+struct AshKernelParams {
+    int n, C;
+    long ld;
+    const double *b, *s;
+    int has_threshold;
+    double threshold;
+    int maxit;
+    double *pm, *psd, *neg, *pos, *lfsr, *le_t, *gt_mt;
+    double *pi, *sd;             // C x kAshMaxK
+    int32_t *K, *iter, *flag;    // C
+    double *loglik;              // C
+};
+constexpr int kAshMaxK = 64;            // DSQ_ASH_MAX_K
+constexpr int kAshSliceRows = 128;      // dsq_ash_slice_rows(): the consecutive rows of one partial sum ...
+constexpr int kAshGroupRows = 16;       // ... which adds its groups of this many rows in order
+constexpr int kAshTrials = 32;          // the step sizes 0.75^j of one line search
+size_t ash_workspace_bytes(long n, long C);
+int launch_ash(const AshKernelParams &kp, void *workspace, hipStream_t st);
+
 // unmix() (unmix.hip): x gene-major (element (g, i) at [g * ld + i]), pure gene-major with k
 // contiguous doubles per gene; vx: the caller's workspace, m x n, written by the preparation kernel and read by the fit.
 struct UnmixKernelParams {

@@ -450,6 +450,21 @@ class HostEngine:
                                init=None if init is None else np.asarray(init, np.float64), threshold=threshold, tol=tol,
                                maxit=maxit)
 
+    def ash_fit(self, betahat, sebetahat, threshold=None, maxit=100):
+        """adaptive shrinkage of C independent columns: betahat / sebetahat vectors of n or n x C
+        matrices (or this engine's columns).  The iteration of csrc/ash.hip and of its host loop stated in numpy over this
+        engine's exp / log (ash_host.py), the same bits.  Returns dict(PosteriorMean, PosteriorSD, NegativeProb,
+        PositiveProb, lfsr, le_T, gt_mT: n x C on the host, NaN on the rows that are not kept; pi, sd: C x 64; K, iter,
+        flag: C; loglik: C).  ValueError: a column without a kept row; NotImplementedError: a grid beyond 64 components."""
+        from . import ash_host
+        b, s = np.asarray(betahat, np.float64), np.asarray(sebetahat, np.float64)
+        if isinstance(betahat, (list, tuple)):          # (a list of C columns, as the device engine takes them)
+            b, s = b.T, s.T
+        out = ash_host.fit(self.fns.unary, b.reshape(b.shape[0], -1), s.reshape(s.shape[0], -1), threshold=threshold, maxit=maxit)
+        for k in ash_host.ROW_KEYS:                     # (C, n), column c contiguous: what the device engine returns
+            out[k] = np.ascontiguousarray(out[k].T)
+        return out
+
     def row_vars(self, x):
         """(rowMean, rowVar) of an n x m handle (matrixStats::rowVars as documented): the two wave-order sums of
         csrc/explore.hip stated in numpy (explore_host.py), the same bits"""
@@ -1017,6 +1032,41 @@ class DeviceEngine:
             c = p if c == "p" else c
             out[k] = h[at:at + n * c].reshape((n, c) if c != 1 else (n,)).copy()
             at += n * c
+        return out
+
+    def ash_fit(self, betahat, sebetahat, threshold=None, maxit=100):
+        """adaptive shrinkage of C independent columns on the device (csrc/ash.hip, dsq_ash_dev) on the current stream:
+        betahat / sebetahat resident columns -- a list of C device vectors of n, or one (C, n) device tensor -- or host arrays
+        (n or n x C), which go up once.  The call synchronises the stream a few dozen times (the host decides every step of
+        the iteration from a small record).  The per-row outputs stay on the device: dict of (C, n) device tensors
+        PosteriorMean, PosteriorSD, NegativeProb, PositiveProb, lfsr, le_T, gt_mT, and on the host pi, sd (C x 64), K, iter,
+        flag, loglik.  ValueError: a column without a kept row; NotImplementedError: a grid beyond 64 components."""
+        t = self.torch
+        from . import _lib
+
+        def up(v):
+            if isinstance(v, (list, tuple)):
+                return t.stack([(e if t.is_tensor(e) else self._vec(np.asarray(e, np.float64))).to(t.float64).reshape(-1)
+                                for e in v]).contiguous()
+            if t.is_tensor(v):
+                return v.to(t.float64).reshape(-1, v.shape[-1]).contiguous()
+            a = np.asarray(v, np.float64)
+            return self._vec(np.ascontiguousarray(a.reshape(a.shape[0], -1).T))
+        b, s = up(betahat), up(sebetahat)
+        try:
+            r = self._timed("ash", int(b.shape[1]), lambda: self.native.ash_dev(b, s, threshold=threshold, maxit=maxit))
+        except _lib.DsqError as e:
+            if e.code == _lib.DSQ_ERR_VALUE:
+                raise ValueError("ash: no row with a finite estimate and a finite, positive standard error") from e
+            if e.code == _lib.DSQ_ERR_UNSUPPORTED:
+                raise NotImplementedError(str(e)) from e
+            raise
+        c = b.shape[0]
+        small, ints = self._host(r["_small"]).numpy(), self._host(r["_ints"]).numpy()
+        ck = c * _lib.DSQ_ASH_MAX_K
+        out = {k: r[k] for k in self.native._ASH_ROWS}
+        out.update(pi=small[:ck].reshape(c, -1).copy(), sd=small[ck:2 * ck].reshape(c, -1).copy(), loglik=small[2 * ck:].copy(),
+                   K=ints[0].copy(), iter=ints[1].copy(), flag=ints[2].copy())
         return out
 
     def _resident(self, x):

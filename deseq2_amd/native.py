@@ -626,6 +626,32 @@ def apeglm(counts, x, nf, disp, coef, no_shrink, prior_scale, prior_df=1.0, no_s
     return out
 
 
+_ASH_ROWS = ("PosteriorMean", "PosteriorSD", "NegativeProb", "PositiveProb", "lfsr", "le_T", "gt_mT")
+
+
+def _ash_columns(betahat, sebetahat):
+    b, s = np.asarray(betahat, np.float64), np.asarray(sebetahat, np.float64)
+    if b.shape != s.shape or b.ndim not in (1, 2):
+        raise ValueError("betahat and sebetahat are two vectors of one length, or two n x C matrices")
+    return (_fcol(b.reshape(b.shape[0], -1)), _fcol(s.reshape(s.shape[0], -1)))
+
+
+def ash(betahat, sebetahat, threshold=None, maxit=100):
+    """adaptive shrinkage through dsq_ash: betahat / sebetahat host vectors of n, or n x C matrices of C
+    independent columns; dict(PosteriorMean, PosteriorSD, NegativeProb, PositiveProb, lfsr, le_T, gt_mT: n x C, NaN on the rows
+    that are not kept; pi, sd: C x DSQ_ASH_MAX_K; K, iter, flag: int32 of C; loglik: C) out."""
+    b, s = _ash_columns(betahat, sebetahat)
+    n, c = b.shape
+    out = {k: np.zeros((n, c), order="F") for k in _ASH_ROWS}
+    out.update(pi=np.zeros((c, L.DSQ_ASH_MAX_K)), sd=np.zeros((c, L.DSQ_ASH_MAX_K)), K=np.zeros(c, np.int32),
+               iter=np.zeros(c, np.int32), flag=np.zeros(c, np.int32), loglik=np.zeros(c))
+    a = L.DsqAshArgs(n=n, C=c, ld=n, betahat=_ptr(b), sebetahat=_ptr(s), has_threshold=int(threshold is not None),
+                     threshold=float(threshold) if threshold is not None else 0.0, maxit=int(maxit))
+    o = L.DsqAshOut(**{k: _ptr(v) for k, v in out.items()})
+    L.check(L.lib().dsq_ash(C.byref(a), C.byref(o)))
+    return out
+
+
 _FIT_ERRORS = {1: "parametric dispersion fit failed", 2: "dispersion fit did not converge"}
 
 
@@ -947,6 +973,34 @@ def apeglm_dev(y, x, nf, disp, coef, no_shrink, prior_scale, prior_df=1.0, no_sh
     o = L.DsqApeglmOut(bad=_t_ptr(bad), **{k: _t_ptr(v) for k, v in out.items()})
     L.check(L.lib().dsq_apeglm_dev(C.byref(a), C.byref(o), _stream()))
     out["_pack"] = pack
+    return out
+
+
+def ash_dev(betahat, sebetahat, threshold=None, maxit=100, workspace=None):
+    """dsq_ash_dev on resident columns: betahat / sebetahat float64 device tensors of shape (C, n), contiguous (column c of the
+    header's n x C at [c * n]).  The call synchronises the current stream (the host decides every step from a record read
+    back).  Returns the dict of device tensors: the seven per-row outputs (C, n) as views of `_pack` (7, C, n); pi, sd
+    (C, DSQ_ASH_MAX_K) and loglik (C) as views of `_small`; K, iter, flag (C,) int32 as views of `_ints`.  workspace: a uint8
+    device tensor of dsq_ash_workspace_bytes(n, C) bytes to reuse."""
+    import torch
+    assert betahat.dtype == torch.float64 and sebetahat.dtype == torch.float64 and betahat.dim() == 2
+    assert betahat.shape == sebetahat.shape and betahat.is_contiguous() and sebetahat.is_contiguous()
+    c, n = betahat.shape
+    dev = betahat.device
+    pack = torch.empty((7, c, n), dtype=torch.float64, device=dev)
+    small = torch.empty(c * (2 * L.DSQ_ASH_MAX_K + 1), dtype=torch.float64, device=dev)
+    ints = torch.empty((3, c), dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(int(L.lib().dsq_ash_workspace_bytes(n, c)), dtype=torch.uint8, device=dev)
+    ck = c * L.DSQ_ASH_MAX_K
+    out = {k: pack[i] for i, k in enumerate(_ASH_ROWS)}
+    out.update(pi=small[:ck].view(c, L.DSQ_ASH_MAX_K), sd=small[ck:2 * ck].view(c, L.DSQ_ASH_MAX_K), loglik=small[2 * ck:],
+               K=ints[0], iter=ints[1], flag=ints[2])
+    a = L.DsqAshArgs(n=n, C=c, ld=n, betahat=_t_ptr(betahat), sebetahat=_t_ptr(sebetahat), has_threshold=int(threshold is not None),
+                     threshold=float(threshold) if threshold is not None else 0.0, maxit=int(maxit))
+    o = L.DsqAshOut(**{k: _t_ptr(v) for k, v in out.items()})
+    L.check(L.lib().dsq_ash_dev(C.byref(a), C.byref(o), _t_ptr(workspace), int(workspace.numel()), _stream()))
+    out.update(_pack=pack, _small=small, _ints=ints)
     return out
 
 

@@ -51,7 +51,9 @@
  * last command.  Host arrays (tables, argument blocks) are read before the call returns and may be rewritten at once: a
  * table travels through pinned buffers of the (device, stream) context, never from the caller's or the library's pageable
  * memory at a later time.  The call does not wait for the device: it returns while `stream` is still busy.  The exceptions
- * state it at their entry: dsq_sf_iterate_dev and dsq_beta_prior_var_dev read results back; the fit and aux entries that
+ * state it at their entry: dsq_sf_iterate_dev, dsq_ash_dev and dsq_beta_prior_var_dev read results back (dsq_ash_dev: the
+ * host decides every step of its iteration from a small record, so the call SYNCHRONISES `stream` (a few dozen times) and
+ * the outputs are complete on return); the fit and aux entries that
  * take `y_type` (dsq_fit_beta_dev .. dsq_replace_outliers_dev):
  * given DSQ_Y_FLOAT64 counts they check the counts on the device and WAIT for `stream` once, at their end, to return
  * DSQ_ERR_VALUE (int32 counts: no wait); and a workspace slot of the context that has to GROW is reallocated behind a
@@ -833,6 +835,64 @@ typedef struct {
 int32_t dsq_apeglm_lds_doubles(void);   /* the design is staged in LDS while m * p is at most this; read through L2 beyond */
 int dsq_apeglm_dev(const DsqApeglmArgs *args, const DsqApeglmOut *out, void *stream);
 int dsq_apeglm(const DsqApeglmArgs *args, const DsqApeglmOut *out);
+
+/* ---- dsq_ash: adaptive shrinkage, lfcShrink(type = "ashr") (R/lfcShrink.R:442-486) -----------------
+ * ashr::ash(betahat, sebetahat, mixcompdist = "normal", method = "shrink") as its paper (Stephens 2017) and the call state
+ * it, for C independent columns (the K contrasts of one resultsContrasts call) of n rows each: a scale mixture of
+ * zero-mean normals sum_k pi_k N(0, sigma_k^2) without a point mass is fitted to the kept rows (betahat finite, sebetahat
+ * finite and positive) by maximum likelihood, then every kept row gets its posterior mean, posterior SD, the two sign
+ * probabilities, lfsr = the smaller of them and, with a threshold T, P(beta <= T) and P(beta > -T), each as its own one-tail
+ * sum.  Rows that are not kept take no part and come back NaN in every per-row output.  The grid is ashr's documented
+ * gridmult = sqrt(2) rule from min(sebetahat) / 10 to 2 sqrt(max(betahat^2 - sebetahat^2)) (8 times the lower end when no row
+ * has betahat^2 > sebetahat^2), K = npoint + 1 <= DSQ_ASH_MAX_K components, at least 2.  The weights minimise
+ * phi(x) = -(1/n) sum_i log (L x)_i + sum_k x_k over x >= 0 by the library's own deterministic sequential quadratic
+ * programme (active-set solve on the host, backtracking on the true phi with all step sizes of a search evaluated in one
+ * pass), from x = 1/K until min_k g_k >= -1e-8; every operation rounded once in a stated order (DESIGN.md section 23,
+ * deseq2_amd/ash_host.py, tests/ash_spec.py).  The ashr package's numbers, its optimiser and its treatment of excluded rows are
+ * unpinned.
+ * betahat, sebetahat and the seven per-row outputs: column c at [c * ld], ld >= n; rows n .. ld-1 are neither read nor written.
+ * pi, sd: C x DSQ_ASH_MAX_K, row c the weights / standard deviations of column c, zero beyond its K.
+ * flag: 0 converged, 1 maxit reached, 2 no acceptable step.  iter: the quadratic programmes solved.
+ * Every sum over the rows takes them in slices of dsq_ash_slice_rows() consecutive rows, a slice in groups of 16, in an
+ * order that depends on n and K alone; no floating-point atomics.
+ * _dev: device pointers and the caller's workspace of at least dsq_ash_workspace_bytes(n, C) bytes (else DSQ_ERR_ARG), no
+ * allocation.  The host decides every step from a record of (K+1)(K+2)/2 doubles per column, so the call SYNCHRONISES
+ * `stream` (a few dozen times) and the outputs are complete on return; it cannot be captured into a graph.
+ * dsq_ash: host pointers, ONE device, synchronous.
+ * DSQ_ERR_VALUE: a column without a kept row.  DSQ_ERR_UNSUPPORTED: a column whose grid needs more than DSQ_ASH_MAX_K
+ * components (max / min near 2^32).  DSQ_ERR_ARG: n or C < 1, ld < n, a NULL array, a negative or NaN threshold, maxit < 0:
+ * decided before a device is asked for. */
+#define DSQ_ASH_MAX_K 64
+typedef struct {
+    int32_t n, C;              /* rows, columns                                                                     */
+    int64_t ld;                /* column stride of betahat / sebetahat and of the per-row outputs (>= n)            */
+    const double *betahat;     /* n x C                                                                             */
+    const double *sebetahat;   /* n x C                                                                             */
+    int32_t has_threshold;
+    double threshold;          /* T >= 0, on the scale of betahat; read when has_threshold                          */
+    int32_t maxit;             /* >= 0; 100                                                                         */
+} DsqAshArgs;
+
+typedef struct {
+    double *PosteriorMean;     /* n x C                                                                             */
+    double *PosteriorSD;       /* n x C                                                                             */
+    double *NegativeProb;      /* n x C                                                                             */
+    double *PositiveProb;      /* n x C                                                                             */
+    double *lfsr;              /* n x C                                                                             */
+    double *le_T;              /* n x C: P(beta <= T)  (NaN without a threshold)                                    */
+    double *gt_mT;             /* n x C: P(beta > -T)  (NaN without a threshold)                                    */
+    double *pi;                /* C x DSQ_ASH_MAX_K                                                                 */
+    double *sd;                /* C x DSQ_ASH_MAX_K                                                                 */
+    int32_t *K;                /* C                                                                                 */
+    int32_t *iter;             /* C                                                                                 */
+    int32_t *flag;             /* C                                                                                 */
+    double *loglik;            /* C: sum over the kept rows of log (L pi)_i + lnorm_i                               */
+} DsqAshOut;
+
+int64_t dsq_ash_workspace_bytes(int32_t n, int32_t C);
+int32_t dsq_ash_slice_rows(void);
+int dsq_ash_dev(const DsqAshArgs *args, const DsqAshOut *out, void *workspace, int64_t workspace_bytes, void *stream);
+int dsq_ash(const DsqAshArgs *args, const DsqAshOut *out);
 
 /* ---- dsq_sf_iterate: the solve of estimateSizeFactors(type = "iterate") (R/core.R:2600-2611) ------
  * One outer round of estimateSizeFactorsIterate fixes the counts k, q_ij = mu_ij / sf_j and the dispersions a_i over the
