@@ -28,9 +28,25 @@ static inline int aux_grid_fwd(int n) {
 static constexpr int kTileS = 256;
 __host__ __device__ static inline bool aux_tiled(int m, int p) { return (size_t)m * p >= 8192 && p <= 24; }   // (tile <= 48 KB)
 
-template <int P, bool USE_W, bool TILED>
+// KEEP (the quotient yn = (double)y / nf of a sample is taken ONCE): the moments need four sums that depend on one another only
+// through wave totals -- (sum cn, sum y), then the variance about the mean; (yn Q, log(yn + 0.1) Q), then the rough
+// dispersion from mu = tu . a -- so two sweeps carry them: sweep A the first of each pair, sweep B the second.  Sweep A
+// takes the quotient and keeps it for sweep B, in kKeepRegs registers per lane (rows of up to 64 kKeepRegs samples) or in a
+// wave-private LDS slice of m doubles behind the tile (rows of up to kKeepLdsM samples, while tile and slices fit 64 KB);
+// longer rows take the four sweeps (KEEP_NONE), which divide in every one of them.  Every accumulator receives the terms it
+// always did, from the same expressions, a lane its samples j = lane, lane + 64, ... in increasing order: the same bits.
+enum { KEEP_NONE = 0, KEEP_REGS = 1, KEEP_LDS = 2 };
+static constexpr int kKeepRegs = 8;
+static constexpr int kKeepLdsM = 1024;
+static inline int aux_keep(int m, int p, bool tiled) {
+    if (m <= 64 * kKeepRegs) return KEEP_REGS;
+    const size_t lds = ((tiled ? (size_t)p * kTileS : 0) + (size_t)4 * m) * sizeof(double);
+    return (m <= kKeepLdsM && lds <= 65536) ? KEEP_LDS : KEEP_NONE;
+}
+
+template <int P, bool USE_W, bool TILED, int KEEP>
 __global__ void __launch_bounds__(256) prefit_kernel(PrefitKernelParams kp) {
-    extern __shared__ __attribute__((aligned(16))) double tile[];       // TILED: P x kTileS doubles
+    extern __shared__ __attribute__((aligned(16))) double tile[];       // TILED: P x kTileS doubles; KEEP_LDS: + m per wave
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int waves = blockDim.x >> 6;
@@ -58,7 +74,121 @@ __global__ void __launch_bounds__(256) prefit_kernel(PrefitKernelParams kp) {
             yb[b] = yg[j]; nb[b] = nfg[j];
             if constexpr (USE_W) wb[b] = wg[j];
         };
+        static_assert(kTileS == 64 * kAuxBatch, "one tile = one batch of trips");
+        auto stage = [&](const double *src, int t0) {
+            __syncthreads();                                          // (the previous tile has been consumed)
+            const int ts = (m - t0) < kTileS ? (m - t0) : kTileS;
+            for (int idx = threadIdx.x; idx < P * kTileS; idx += blockDim.x) {
+                const int c = idx / kTileS, jj = idx - c * kTileS;
+                if (jj < ts) tile[idx] = src[(size_t)c * m + t0 + jj];
+            }
+            __syncthreads();
+        };
+        (void)stage;
         double a2[2] = {0.0, 0.0};
+        double mean, av = 0.0, ae = 0.0;
+        double tu[2 * P];
+#pragma unroll
+        for (int c = 0; c < 2 * P; c++) tu[c] = 0.0;
+        if constexpr (KEEP != KEEP_NONE) {
+            // groups of kAuxBatch trips (a tile of the TILED build): group gi holds the samples kTileS gi + 64 b + lane; every
+            // wave of a block walks the same groups (m is the launch's), so the block barriers of `stage` are reached by all
+            // of them.  In registers slot kAuxBatch gi + b of yk[] is chosen by selects on the wave-uniform gi: the group loop
+            // stays ROLLED -- unrolled (the slot a constant) the build took 189 VGPRs at p = 4 and 256 + 150 accumulation
+            // registers at p = 10, two waves and one wave per SIMD: the sample indices being constants, the design's columns
+            // are invariant in the gene loop and, it seems, held in registers across it
+            constexpr int kGroups = kKeepRegs / kAuxBatch;
+            double yk[KEEP == KEEP_REGS ? kKeepRegs : 1];
+            double *ys = tile + (TILED ? P * kTileS : 0) + (size_t)wave * m;        // KEEP_LDS: a lane re-reads what it wrote itself
+            auto keep_put = [&](int gi, int b, int j, double v) {
+                if constexpr (KEEP == KEEP_REGS) {
+                    _Pragma("unroll")
+                    for (int s = 0; s < kGroups; s++) yk[kAuxBatch * s + b] = (s == gi) ? v : yk[kAuxBatch * s + b];
+                } else ys[j] = v;
+            };
+            auto keep_get = [&](int gi, int b, int j) {
+                if constexpr (KEEP == KEEP_REGS) {
+                    double v = yk[b];
+                    _Pragma("unroll")
+                    for (int s = 1; s < kGroups; s++) v = (s == gi) ? yk[kAuxBatch * s + b] : v;
+                    return v;
+                } else return ys[j];
+            };
+            if constexpr (KEEP == KEEP_REGS) {
+                _Pragma("unroll")
+                for (int s = 0; s < kKeepRegs; s++) yk[s] = 0.0;
+            }
+            auto for_groups = [&](auto &&body) {
+                _Pragma("nounroll")
+                for (int gi = 0; gi * kTileS < m; gi++) body(gi);
+            };
+            // sweep A: sum cn, sum y; yn Q and log(yn + 0.1) Q
+            for_groups([&](int gi) {
+                const int t0 = gi * kTileS;
+                if constexpr (TILED) stage(kp.q, t0);
+                _Pragma("unroll")
+                for (int b = 0; b < kAuxBatch; b++) { const int j = t0 + 64 * b + lane; if (j < m) load_row(j, b); }
+                _Pragma("unroll")
+                for (int b = 0; b < kAuxBatch; b++) {
+                    const int j = t0 + 64 * b + lane;
+                    if (j < m) {
+                        double yy = (double)yb[b];
+                        double yn = yy / nb[b];
+                        keep_put(gi, b, j, yn);
+                        double cn = yn;
+                        if constexpr (USE_W) cn = wb[b] * cn;
+                        a2[0] += cn;
+                        a2[1] += yy;
+                        double ly = dlog(yn + 0.1);
+#pragma unroll
+                        for (int c = 0; c < P; c++) {
+                            double qv;
+                            if constexpr (TILED) qv = tile[c * kTileS + 64 * b + lane];
+                            else qv = kp.q[(size_t)c * m + j];
+                            tu[c] += yn * qv;
+                            tu[P + c] += ly * qv;
+                        }
+                    }
+                }
+            });
+            wave_allreduce_many(a2, lane);
+            wave_allreduce_many(tu, lane);
+            mean = a2[0] / (double)m;
+            // sweep B: the variance about the mean; the rough dispersion from mu = tu . a
+            for_groups([&](int gi) {
+                const int t0 = gi * kTileS;
+                if constexpr (TILED) stage(kp.a, t0);
+                if constexpr (USE_W) {
+                    _Pragma("unroll")
+                    for (int b = 0; b < kAuxBatch; b++) { const int j = t0 + 64 * b + lane; if (j < m) wb[b] = wg[j]; }
+                }
+                _Pragma("unroll")
+                for (int b = 0; b < kAuxBatch; b++) {
+                    const int j = t0 + 64 * b + lane;
+                    if (j < m) {
+                        const double yn = keep_get(gi, b, j);
+                        double cn = yn;
+                        if constexpr (USE_W) cn = wb[b] * cn;
+                        double dlt = cn - mean;
+                        av += dlt * dlt;
+                        double mu;
+                        if constexpr (TILED) {
+                            mu = tu[0] * tile[64 * b + lane];
+#pragma unroll
+                            for (int c = 1; c < P; c++) mu = __builtin_fma(tu[c], tile[c * kTileS + 64 * b + lane], mu);
+                        } else {
+                            mu = tu[0] * kp.a[j];
+#pragma unroll
+                            for (int c = 1; c < P; c++) mu = __builtin_fma(tu[c], kp.a[(size_t)c * m + j], mu);
+                        }
+                        mu = __builtin_fmax(1.0, mu);
+                        double d = yn - mu;
+                        ae += (d * d - mu) / (mu * mu);
+                    }
+                }
+            });
+            wave_allreduce_pair(av, ae, lane);
+        } else {
         sweep_batched<kAuxBatch>(m, lane, load_row, [&](int, int b) {
             double yy = (double)yb[b];
             double cn = yy / nb[b];
@@ -67,8 +197,7 @@ __global__ void __launch_bounds__(256) prefit_kernel(PrefitKernelParams kp) {
             a2[1] += yy;
         });
         wave_allreduce_many(a2, lane);
-        const double mean = a2[0] / (double)m;
-        double av = 0.0;
+        mean = a2[0] / (double)m;
         sweep_batched<kAuxBatch>(m, lane, load_row, [&](int, int b) {
             double cn = (double)yb[b] / nb[b];
             if constexpr (USE_W) cn = wb[b] * cn;
@@ -76,21 +205,7 @@ __global__ void __launch_bounds__(256) prefit_kernel(PrefitKernelParams kp) {
             av += dlt * dlt;
         });
         av = wave_allreduce(av);
-        double tu[2 * P];
-#pragma unroll
-        for (int c = 0; c < 2 * P; c++) tu[c] = 0.0;
-        double ae = 0.0;
         if constexpr (TILED) {
-            static_assert(kTileS == 64 * kAuxBatch, "one tile = one batch of trips");
-            auto stage = [&](const double *src, int t0) {
-                __syncthreads();                                          // (the previous tile has been consumed)
-                const int ts = (m - t0) < kTileS ? (m - t0) : kTileS;
-                for (int idx = threadIdx.x; idx < P * kTileS; idx += blockDim.x) {
-                    const int c = idx / kTileS, jj = idx - c * kTileS;
-                    if (jj < ts) tile[idx] = src[(size_t)c * m + t0 + jj];
-                }
-                __syncthreads();
-            };
             for (int t0 = 0; t0 < m; t0 += kTileS) {
                 stage(kp.q, t0);
                 _Pragma("unroll")
@@ -152,6 +267,7 @@ __global__ void __launch_bounds__(256) prefit_kernel(PrefitKernelParams kp) {
         });
         }
         ae = wave_allreduce(ae);
+        }
         double b[P];
 #pragma unroll
         for (int c = P - 1; c >= 0; c--) {
@@ -628,19 +744,34 @@ static inline int aux_grid(int n) {
     return blocks < cap ? (blocks < 1 ? 1 : blocks) : cap;
 }
 
+template <int P, bool TILED, int KEEP>
+static hipError_t launch_prefit_pk(const PrefitKernelParams &kp, hipStream_t st) {
+    const size_t lds = ((TILED ? (size_t)P * kTileS : 0) + (KEEP == KEEP_LDS ? (size_t)4 * kp.m : 0)) * sizeof(double);
+    if (kp.useWeights) hipLaunchKernelGGL((prefit_kernel<P, true, TILED, KEEP>), dim3(aux_grid(kp.n)), dim3(256), lds, st, kp);
+    else hipLaunchKernelGGL((prefit_kernel<P, false, TILED, KEEP>), dim3(aux_grid(kp.n)), dim3(256), lds, st, kp);
+    return hipGetLastError();
+}
+// (the two-sweep builds exist for the register-resident widths, p <= DSQ_P_REG: at the wide widths, whose time is in the fits,
+//  they would triple the kernels of this translation unit for nothing that a step shows)
+template <int P, bool TILED>
+static hipError_t launch_prefit_pt(const PrefitKernelParams &kp, hipStream_t st) {
+    if constexpr (P <= DSQ_P_REG) {
+        switch (aux_keep(kp.m, P, TILED)) {
+        case KEEP_REGS:                 // (never a tiled row: m p >= 8192 at p <= 10 is m >= 820)
+            if constexpr (!TILED) return launch_prefit_pk<P, TILED, KEEP_REGS>(kp, st);
+            break;
+        case KEEP_LDS: return launch_prefit_pk<P, TILED, KEEP_LDS>(kp, st);
+        default: break;
+        }
+    }
+    return launch_prefit_pk<P, TILED, KEEP_NONE>(kp, st);
+}
 template <int P>
 static hipError_t launch_prefit_p(const PrefitKernelParams &kp, hipStream_t st) {
     if constexpr (P <= 24) {
-        if (aux_tiled(kp.m, P)) {
-            const size_t lds = (size_t)P * kTileS * sizeof(double);
-            if (kp.useWeights) hipLaunchKernelGGL((prefit_kernel<P, true, true>), dim3(aux_grid(kp.n)), dim3(256), lds, st, kp);
-            else hipLaunchKernelGGL((prefit_kernel<P, false, true>), dim3(aux_grid(kp.n)), dim3(256), lds, st, kp);
-            return hipGetLastError();
-        }
+        if (aux_tiled(kp.m, P)) return launch_prefit_pt<P, true>(kp, st);
     }
-    if (kp.useWeights) hipLaunchKernelGGL((prefit_kernel<P, true, false>), dim3(aux_grid(kp.n)), dim3(256), 0, st, kp);
-    else hipLaunchKernelGGL((prefit_kernel<P, false, false>), dim3(aux_grid(kp.n)), dim3(256), 0, st, kp);
-    return hipGetLastError();
+    return launch_prefit_pt<P, false>(kp, st);
 }
 
 hipError_t launch_prefit(const PrefitKernelParams &kp, hipStream_t st, bool *ok) {

@@ -34,64 +34,74 @@ struct Rows {                 // the genes a rule kernel covers: rows[0 .. *n_de
 DSQ_DEV int rows_count(const Rows &r) { return r.n_dev ? *r.n_dev : r.n; }
 DSQ_DEV int rows_gene(const Rows &r, int i) { return r.rows ? r.rows[i] : i; }
 
-// ---- ordered compaction by one workgroup (the trend fit sums its input in index order) -------------------------
+// ---- ordered compaction on many workgroups (the trend fit sums its input in index order) -----------------------
 // mode 0: keep = !(allZero | force_zero) -> rows; also folds force_zero into allZero
 // mode 1: keep = disp > thresh -> (means, disps) pairs (useForFit, R/core.R:870)
-__global__ void __launch_bounds__(1024) compact_kernel(int mode, int n, int32_t *allZero, const int32_t *force_zero,
-                                                       const double *mean_in, const double *disp_in, double thresh,
-                                                       int32_t *rows_out, double *mean_out, double *disp_out,
-                                                       int32_t *count_out) {
-    // tiles of 1024 consecutive elements (coalesced), kept elements ranked by wave ballots + a 16-entry prefix per tile;
-    // FOUR tiles per round (round 4: one tile per round was 49 rounds of "load, three barriers" at 50 000 genes -- 66 us of
-    // latency, twice per analysis; the loads of a round are now in flight together and the barriers are shared)
-    constexpr int NT = 4;
-    __shared__ int wcnt[NT][16];
+// Tiles of kCompactTile consecutive elements, one workgroup each, in TWO launches: the first counts the kept elements of
+// every tile (tile_cnt: one int per tile), the second adds up the counts of the tiles in front of its own -- a few dozen
+// integers at 50 000 genes --, ranks its kept elements by wave ballots and a 16-entry prefix, and writes.  No workgroup ever
+// waits for another one: the only order between them is that of the two launches.  (One workgroup walking all tiles was
+// 39 - 52 us of latency at 50 000 genes, twice per analysis, with the rest of the device idle.)
+constexpr int kCompactTile = 1024;
+struct CompactParams {
+    int mode, n;
+    int32_t *allZero;
+    const int32_t *force_zero;
+    const double *mean_in, *disp_in;
+    double thresh;
+    int32_t *tile_cnt;
+    int32_t *rows_out;
+    double *mean_out, *disp_out;
+    int32_t *count_out;
+};
+DSQ_DEV bool compact_keep(const CompactParams &c, int i) {
+    if (i >= c.n) return false;
+    if (c.mode == 0) return !(c.allZero[i] | (c.force_zero ? c.force_zero[i] : 0));
+    return c.disp_in[i] > c.thresh;
+}
+__global__ void __launch_bounds__(kCompactTile) compact_count_kernel(CompactParams c) {
+    __shared__ int wcnt[kCompactTile / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const unsigned long long mask = __ballot(compact_keep(c, blockIdx.x * kCompactTile + t));
+    if (lane == 0) wcnt[wave] = __popcll(mask);
+    __syncthreads();
+    if (t == 0) {
+        int s = 0;
+        for (int w = 0; w < kCompactTile / 64; w++) s += wcnt[w];
+        c.tile_cnt[blockIdx.x] = s;
+    }
+}
+__global__ void __launch_bounds__(kCompactTile) compact_write_kernel(CompactParams c) {
+    __shared__ int wcnt[kCompactTile / 64];
     __shared__ int base_s;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) base_s = 0;
-    __syncthreads();
-    for (int i0 = 0; i0 < n; i0 += NT * 1024) {
-        bool keep[NT];
-        double mv[NT], dv[NT];
-#pragma unroll
-        for (int q = 0; q < NT; q++) {
-            const int i = i0 + q * 1024 + t;
-            keep[q] = false; mv[q] = 0.0; dv[q] = 0.0;
-            if (i < n) {
-                if (mode == 0) {
-                    int z = allZero[i] | (force_zero ? force_zero[i] : 0);
-                    if (force_zero) allZero[i] = z ? 1 : 0;
-                    keep[q] = !z;
-                } else {
-                    dv[q] = disp_in[i]; mv[q] = mean_in[i];
-                    keep[q] = dv[q] > thresh;
-                }
-            }
-        }
-        unsigned long long mask[NT];
-#pragma unroll
-        for (int q = 0; q < NT; q++) {
-            mask[q] = __ballot(keep[q]);
-            if (lane == 0) wcnt[q][wave] = __popcll(mask[q]);
-        }
-        __syncthreads();
-        int off = base_s;
-#pragma unroll
-        for (int q = 0; q < NT; q++) {
-            int mine = off;
-            for (int w = 0; w < 16; w++) { const int c = wcnt[q][w]; if (w < wave) mine += c; off += c; }
-            mine += __popcll(mask[q] & ((1ull << lane) - 1ull));
-            if (keep[q]) {
-                const int i = i0 + q * 1024 + t;
-                if (mode == 0) rows_out[mine] = i;
-                else { mean_out[mine] = mv[q]; disp_out[mine] = dv[q]; }
-            }
-        }
-        __syncthreads();
-        if (t == 0) base_s = off;               // (every thread has computed the same running total)
-        __syncthreads();
+    const int i = blockIdx.x * kCompactTile + t;
+    const bool keep = compact_keep(c, i);
+    if (c.mode == 0 && c.force_zero && i < c.n) c.allZero[i] = keep ? 0 : 1;
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) wcnt[wave] = __popcll(mask);
+    if (wave == 0) {                                    // the kept elements of the tiles in front of this one
+        int s = 0;
+        for (int k = lane; k < (int)blockIdx.x; k += 64) s += c.tile_cnt[k];
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) base_s = s;
     }
-    if (t == 0) *count_out = base_s;
+    __syncthreads();
+    int mine = base_s, total = base_s;
+    for (int w = 0; w < kCompactTile / 64; w++) { const int k = wcnt[w]; if (w < wave) mine += k; total += k; }
+    mine += __popcll(mask & ((1ull << lane) - 1ull));
+    if (keep) {
+        if (c.mode == 0) c.rows_out[mine] = i;
+        else { c.mean_out[mine] = c.mean_in[i]; c.disp_out[mine] = c.disp_in[i]; }
+    }
+    if (t == 0 && blockIdx.x == gridDim.x - 1) *c.count_out = total;
+}
+// tile_cnt: (n + kCompactTile - 1) / kCompactTile ints of device memory that nothing else uses until both launches are done
+static hipError_t launch_compact(CompactParams c, hipStream_t st) {
+    const int tiles = c.n > 0 ? (c.n + kCompactTile - 1) / kCompactTile : 1;
+    hipLaunchKernelGGL(compact_count_kernel, dim3(tiles), dim3(kCompactTile), 0, st, c);
+    hipLaunchKernelGGL(compact_write_kernel, dim3(tiles), dim3(kCompactTile), 0, st, c);
+    return hipGetLastError();
 }
 
 // ---- the bucket key of a launch order (see "longest-expected-first order" below) --------------------------------------
@@ -1481,9 +1491,12 @@ static int phase_gene_est(Pipe &P, const Rows &nz) {
     const Rows all = {nullptr, nullptr, P.n};
     int rc = launch_prefit_rows(P, all, a->y);                                   // getBaseMeansAndVariances + moments
     if (rc) return rc;
-    hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, P.st, 0, P.n, o->allZero, a->force_zero,
-                       (const double *)nullptr, (const double *)nullptr, 0.0, P.rows_nz, (double *)nullptr,
-                       (double *)nullptr, P.counters + CNT_NZ);
+    // (the tile counts borrow the residual buffer of the prior variance, which the trend phase fills after its own compaction)
+    CompactParams c;
+    memset(&c, 0, sizeof c);
+    c.mode = 0; c.n = P.n; c.allZero = o->allZero; c.force_zero = a->force_zero;
+    c.tile_cnt = (int32_t *)P.resbuf; c.rows_out = P.rows_nz; c.count_out = P.counters + CNT_NZ;
+    DSQ_HIP(launch_compact(c, P.st));
     if (!a->nf_is_vector) {
         // momentsDispEstimate's mean(1 / colMeans(normalizationFactors)) over the rows that are not all zero
         // (R/core.R:2440-2444 on objectNZ): columns summed down the listed genes in gene order
@@ -1503,9 +1516,11 @@ static int phase_trend(Pipe &P) {
     const double *td = a->trend_mean ? a->trend_disp : o->dispGeneEst;
     const int nt = trend_count(P);
     if (!(a->phases & DSQ_PH_GENE_EST)) DSQ_HIP(hipMemsetAsync(P.counters + CNT_TREND, 0, sizeof(int32_t), st));      // (else: the status fill)
-    hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, st, 1, nt, (int32_t *)nullptr, (const int32_t *)nullptr,
-                       tm, td, 100.0 * a->minDisp, (int32_t *)nullptr, P.trend_mean_c, P.trend_disp_c,
-                       P.counters + CNT_TREND);
+    CompactParams c;
+    memset(&c, 0, sizeof c);
+    c.mode = 1; c.n = nt; c.mean_in = tm; c.disp_in = td; c.thresh = 100.0 * a->minDisp;
+    c.tile_cnt = (int32_t *)P.resbuf; c.mean_out = P.trend_mean_c; c.disp_out = P.trend_disp_c; c.count_out = P.counters + CNT_TREND;
+    DSQ_HIP(launch_compact(c, st));
     capi_prof_begin("trend_fit", nt, st);
     hipError_t e = hipSuccess;
     if (a->dispFit_in) {
